@@ -16,12 +16,19 @@ ranks) and reports it under "strong_scaling".
 (`python -m torch.distributed.run` as a child process, before this process touches a GPU), relays
 rank 0's JSON line and exits with the children's code; under torch.distributed.run it is a rank.
 
-The JSON line carries `roofline` for the kernel that takes the most time per step (live HIP-event
-timing through the library's per-kernel profiler; kernel names = template instances, so the two
-tables' partition launches are not lumped together), `cpu_baseline` (the real reference executor
-if oracle/_ref/libmidori_ref.so travelled with the snapshot, else the repo's own C restatement),
-and, at N = 1: the wide (64-bit hash) form, the other synthetic variant, cold-start figures and the
-same query end to end through query_execute().
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`,
+the workload's configuration) - nothing else.  With --full the JSON line also carries `roofline` for
+the kernel that takes the most time per step (live HIP-event timing through the library's per-kernel
+profiler; kernel names = template instances, so the two tables' partition launches are not lumped
+together), the per-step distribution, `cpu_baseline` (the real reference executor if
+oracle/_ref/libmidori_ref.so was built, else the repo's own C restatement), at N > 1 the other
+scaling form and the exchange's phases, and, at N = 1: the wide (64-bit hash) form, the other
+synthetic variants, cold-start figures and the same query end to end through query_execute().
+
+--dump-outputs DIR writes what the last timed step returned - the group keys and COUNT(*) per group,
+a fixed seeded sample of their rows when they are large, and the joined-row and group totals - as
+float64 .npy files, so that two builds can be compared output for output (the inputs are the same
+seeded tables in every run with the same arguments).
 """
 import argparse
 import json
@@ -247,7 +254,15 @@ def parse_args():
                          "that lost a peer must not hang the job")
     ap.add_argument("--force-shuffle", action="store_true",
                     help="run the multi-GPU pipeline (partition by destination + RCCL all-to-all + local join) even with one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: per-step distribution, per-kernel profile and roofline, cold start, "
+                         "exchange phases and the other scaling form (N > 1), the other forms and variants and the end-to-end query (N = 1), "
+                         "CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; --config 3)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != 3:
+        ap.error("--dump-outputs is implemented for --config 3 (the north-star query)")
     if args.config == 3 and not args.rows:
         args.rows = 100_000_000
     return args
@@ -467,6 +482,29 @@ def dist_of(ms):
     return {"steps": n, "min": v[0], "median": v[n // 2], "p90": v[min(n - 1, (9 * n) // 10)], "max": v[-1], "mean": sum(v) / n}
 
 
+DUMP_SAMPLE_ROWS = 1 << 21     # rows of a larger result that --dump-outputs writes (three float64 arrays: 48 MB)
+
+
+def dump_outputs(path, keys, counts, joined, prefix=""):
+    """--dump-outputs: what one call of the timed operator returned, as float64 arrays under `path` - group_keys / group_counts: the
+    group keys and COUNT(*) per group in the order the call returned them, every row or, past DUMP_SAMPLE_ROWS rows, a fixed seeded
+    sample of rows kept in that order (group_index: which rows); totals: [joined rows, groups, sum of every key, sum of every count]
+    over the whole result (exact: the sums are taken in int64 on the device and stay below 2^53 at the benchmark's sizes)."""
+    os.makedirs(path, exist_ok=True)
+    g = int(keys.numel())
+    if g > DUMP_SAMPLE_ROWS:
+        idx = np.sort(np.random.default_rng(12345).choice(g, DUMP_SAMPLE_ROWS, replace=False))
+    else:
+        idx = np.arange(g)
+    sel = torch.from_numpy(idx).to(keys.device)
+    arrays = {"group_index": idx,
+              "group_keys": keys.index_select(0, sel).cpu().numpy(),
+              "group_counts": counts.index_select(0, sel).cpu().numpy(),
+              "totals": np.array([int(joined), g, int(keys.sum().item()), int(counts.to(torch.int64).sum().item())])}
+    for name, v in arrays.items():
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -586,24 +624,26 @@ def main():
             rng.append((-int(t[0].item()), int(t[1].item())))
         dx.set_key_ranges(rng[0], rng[1])
 
-    def measure(n_rank, steps, warmup, cold=None):
-        """warmup + timed loop over fresh tables of n_rank rows per rank -> dict (max over ranks, totals over ranks)"""
+    def measure(n_rank, steps, warmup, cold=None, dump=False):
+        """warmup + timed loop over fresh tables of n_rank rows per rank -> dict (max over ranks, totals over ranks); dump: write what
+        the last timed step returned (--dump-outputs); --full: the per-step distribution too"""
         a, b, total, mod = make_tables(n_rank)
         out = make_out(n_rank)
         w32 = wire_format(a, b)
         pipe = dx
         promise_ranges(a, b, w32)
+        last = {}
 
         def step():
             if pipe is None and args.unordered:
                 k, c, j = dev.join_group_count_unordered(a, None, b, None, out=out)
-                return k.numel(), j
-            if pipe is None:
+            elif pipe is None:
                 # (MDB_KEYS_MAY_ALIAS, as query_execute() calls the operator: when every left row is a group - variant U - the group keys ARE the
                 # left key column and are not copied; the headline's variant D is not such a join: everything is written)
                 k, c, f, j = dev.join_group_count(a, None, b, None, out=out, want_first=False, alias=True)
-                return k.numel(), j
-            k, c, j = pipe.join_group_count(a, None, b, None, out=out)
+            else:
+                k, c, j = pipe.join_group_count(a, None, b, None, out=out)
+            last["result"] = (k, c, j)
             return k.numel(), j
 
         if cold is not None:
@@ -634,21 +674,26 @@ def main():
         dt = time.perf_counter() - t0
         c1 = dev.counters()
         beat("timed steps done")
-        # how the steps are distributed: the same number of steps again, each between two synchronisations of its own (`value` stays the mean
-        # of the contract's loop above: one clock around all K steps)
-        each = []
-        for _ in range(steps):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            step()
-            torch.cuda.synchronize()
-            each.append((time.perf_counter() - t1) * 1e3)
-        c2 = dev.counters()
-        step_dist = dict(dist_of(each), retries_in_timed_steps=c1["retries"] - c0["retries"], samples_in_timed_steps=c1["samples"] - c0["samples"],
-                         arena_grows_in_timed_steps=c1["arena_grows"] - c0["arena_grows"], alloc_misses_in_timed_steps=c1["alloc_misses"] - c0["alloc_misses"],
-                         retries_in_distribution_steps=c2["retries"] - c1["retries"],
-                         note="min / median / p90 / max over the same number of steps run right after the timed loop, each between its own "
-                              "synchronisations (wall clock, this rank); *_in_timed_steps: mdb_dev_counters() read before and after the timed loop")
+        if dump:
+            k, c, jj = last["result"]
+            dump_outputs(args.dump_outputs, k, c, jj, f"rank{rank}_" if world > 1 else "")
+        step_dist = None
+        if args.full:
+            # how the steps are distributed: the same number of steps again, each between two synchronisations of its own (`value` stays the
+            # mean of the contract's loop above: one clock around all K steps)
+            each = []
+            for _ in range(steps):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                step()
+                torch.cuda.synchronize()
+                each.append((time.perf_counter() - t1) * 1e3)
+            c2 = dev.counters()
+            step_dist = dict(dist_of(each), retries_in_timed_steps=c1["retries"] - c0["retries"], samples_in_timed_steps=c1["samples"] - c0["samples"],
+                             arena_grows_in_timed_steps=c1["arena_grows"] - c0["arena_grows"], alloc_misses_in_timed_steps=c1["alloc_misses"] - c0["alloc_misses"],
+                             retries_in_distribution_steps=c2["retries"] - c1["retries"],
+                             note="min / median / p90 / max over the same number of steps run right after the timed loop, each between its own "
+                                  "synchronisations (wall clock, this rank); *_in_timed_steps: mdb_dev_counters() read before and after the timed loop")
         red = torch.tensor([dt, float(j), float(g)], dtype=torch.float64, device=dev.device)
         if use_dist:
             tmax = red[:1].clone()
@@ -657,81 +702,84 @@ def main():
             red[0] = tmax[0]
         dt, joined, groups = float(red[0].item()), int(red[1].item()), int(red[2].item())
         return {"a": a, "b": b, "out": out, "pipe": pipe, "step": step, "wire32": w32, "mod": mod, "n": n_rank, "total_rows": total,
-                "dt": dt, "ms_per_step": dt / steps * 1e3, "value": joined / (dt / steps), "joined": joined, "groups": groups, "step_ms": step_dist}
+                "dt": dt, "ms_per_step": dt / steps * 1e3, "value": joined / (dt / steps), "joined": joined, "groups": groups, "step_ms": step_dist,
+                "retries": c1["retries"] - c0["retries"]}
 
     cold = {}
     n_weak = args.rows
     n_strong = max(args.rows // world, 1)
     n = n_strong if (args.scaling == "strong" and world > 1) else n_weak
-    m = measure(n, args.steps, args.warmup, cold)
+    m = measure(n, args.steps, args.warmup, cold if args.full else None, dump=bool(args.dump_outputs))
     cold["context_and_first_query_ms"] = (time.perf_counter() - t_ctx) * 1e3
     a, b, out, step, pipeline = m["a"], m["b"], m["out"], m["step"], m["pipe"]
     dt, joined_total, groups_total, total_rows, mod_b, wire32 = m["dt"], m["joined"], m["groups"], m["total_rows"], m["mod"], m["wire32"]
     ms_per_step, value = m["ms_per_step"], m["value"]
 
-    # ---- per-kernel profile (outside the timed region): live HIP events around every launch, on the launch stream
-    dev.prof_enable(True)
-    dev.prof_reset()
-    prof_steps = 3
-    for _ in range(prof_steps):
-        step()
-    prof = dev.prof_read()
-    prof_syms = {k: dev.prof_symbols(k) for k in prof}     # rocprofv3's names of what ran under each profiler name
-    dev.prof_enable(False)
-    # the sharded operator, per rank: where a call's time goes (first level / the wire as far as it is not hidden / receiver) and
-    # what the plan puts on ONE xGMI link per call, next to what that link can carry (MI355X: 7 links x ~153 GB/s per GPU, point to
-    # point - an all-to-all's block for a peer crosses the one link to that peer)
-    exchange = None
-    beat("per-kernel profile done")
-    if use_dist:
-        dx.set_phase_timing(True)
-        ph = []
-        for _ in range(3):
+    # everything beside the headline runs with --full only (a plain run: set-up, warm-up, the timed steps, the line)
+    if args.full:
+        # ---- per-kernel profile (outside the timed region): live HIP events around every launch, on the launch stream
+        dev.prof_enable(True)
+        dev.prof_reset()
+        prof_steps = 3
+        for _ in range(prof_steps):
             step()
-            ph.append(dx.last_phases())
-        dx.set_phase_timing(False)
-        mine = {k: sorted(p[k] for p in ph)[1] for k in ph[0]}      # median of three
-        plan = dx.last_plan() if dx.last_fused() else None
-        per_rank = [None] * world
-        if world > 1:
-            dist.all_gather_object(per_rank, {"rank": rank, "phases_ms": mine})
-        else:
-            per_rank = [{"rank": 0, "phases_ms": mine}]
-        XGMI_LINK_GBS = 153.0
-        exchange = {"path": "first-level regions on the wire" if plan else "keys by destination",
-                    "plan": plan, "per_rank": per_rank,
-                    "phases_note": "HIP events on the operator's and the transfer stream: first_level_ms = this rank's partition passes; "
-                                   "wire_wait_ms = how long after them the last block arrived (what of the transfer is NOT hidden behind the passes); "
-                                   "receiver_ms = region descriptors, the receiver's own level if any, leaves; device_ms = all of it"}
-        if plan:
-            bpp = plan["bytes_per_peer"]
-            exchange["per_link"] = {"bytes_per_peer_per_call": bpp, "peers": world - 1, "xgmi_link_GBs": XGMI_LINK_GBS,
-                                    "predicted_link_ms": bpp / (XGMI_LINK_GBS * 1e9) * 1e3 if world > 1 else 0.0,
-                                    "note": "bytes one rank sends to ONE peer per call (fixed-size blocks, slack included, + region counters) / one "
-                                            "link's rate: the floor of wire time when every peer is one hop away and the links run in parallel; "
-                                            "compare with first_level_ms (the transfer of table x overlaps the pass over table x + 1) and wire_wait_ms"}
-    # practical HBM ceiling of this box: device-to-device copy of one key column (read + write)
-    copy_gbs = None
-    try:
-        src = a
-        dst = torch.empty_like(a)
-        for _ in range(2):
-            dst.copy_(src)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbs = 5 * 2 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del dst
-    except Exception:
-        pass
+        prof = dev.prof_read()
+        prof_syms = {k: dev.prof_symbols(k) for k in prof}     # rocprofv3's names of what ran under each profiler name
+        dev.prof_enable(False)
+        # the sharded operator, per rank: where a call's time goes (first level / the wire as far as it is not hidden / receiver) and
+        # what the plan puts on ONE xGMI link per call, next to what that link can carry (MI355X: 7 links x ~153 GB/s per GPU, point to
+        # point - an all-to-all's block for a peer crosses the one link to that peer)
+        exchange = None
+        beat("per-kernel profile done")
+        if use_dist:
+            dx.set_phase_timing(True)
+            ph = []
+            for _ in range(3):
+                step()
+                ph.append(dx.last_phases())
+            dx.set_phase_timing(False)
+            mine = {k: sorted(p[k] for p in ph)[1] for k in ph[0]}      # median of three
+            plan = dx.last_plan() if dx.last_fused() else None
+            per_rank = [None] * world
+            if world > 1:
+                dist.all_gather_object(per_rank, {"rank": rank, "phases_ms": mine})
+            else:
+                per_rank = [{"rank": 0, "phases_ms": mine}]
+            XGMI_LINK_GBS = 153.0
+            exchange = {"path": "first-level regions on the wire" if plan else "keys by destination",
+                        "plan": plan, "per_rank": per_rank,
+                        "phases_note": "HIP events on the operator's and the transfer stream: first_level_ms = this rank's partition passes; "
+                                       "wire_wait_ms = how long after them the last block arrived (what of the transfer is NOT hidden behind the passes); "
+                                       "receiver_ms = region descriptors, the receiver's own level if any, leaves; device_ms = all of it"}
+            if plan:
+                bpp = plan["bytes_per_peer"]
+                exchange["per_link"] = {"bytes_per_peer_per_call": bpp, "peers": world - 1, "xgmi_link_GBs": XGMI_LINK_GBS,
+                                        "predicted_link_ms": bpp / (XGMI_LINK_GBS * 1e9) * 1e3 if world > 1 else 0.0,
+                                        "note": "bytes one rank sends to ONE peer per call (fixed-size blocks, slack included, + region counters) / one "
+                                                "link's rate: the floor of wire time when every peer is one hop away and the links run in parallel; "
+                                                "compare with first_level_ms (the transfer of table x overlaps the pass over table x + 1) and wire_wait_ms"}
+        # practical HBM ceiling of this box: device-to-device copy of one key column (read + write)
+        copy_gbs = None
+        try:
+            src = a
+            dst = torch.empty_like(a)
+            for _ in range(2):
+                dst.copy_(src)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbs = 5 * 2 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del dst
+        except Exception:
+            pass
 
     # the other scaling form, same process group, same kernels (N > 1 only)
     other = None
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         n_other = n_weak if n == n_strong else n_strong
         if n_other != n:
             mo = measure(n_other, max(3, args.steps // 2), 1)
@@ -759,6 +807,45 @@ def main():
             verified_dist = bool(sum(p[2] for p in parts) == ej and np.array_equal(gk[o1], ek[o2]) and np.array_equal(gc[o1], ec[o2]))
 
     if rank == 0:
+        # whole-pipeline view: the bytes any correct algorithm must move once (SURVEY 8d)
+        algo_bytes = 8 * 2 * total_rows + 16 * groups_total
+        scaling_name = "strong" if (n == n_strong and world > 1) else "weak"
+        line = {
+            "metric": METRIC,
+            "value": value, "unit": "joined rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling_name, "vs_baseline": None,
+            "dtype": "int64", "data": "synthetic",
+            "retries_in_timed_steps": m["retries"], "last_plan": dev.last_plan(),
+            "config": {"workload": f"A JOIN B ON id_a=id_b GROUP BY id_a COUNT(*), {n} rows/table/GPU x {world} GPU = {total_rows} rows/table "
+                                   f"({scaling_name} scaling), variant {args.variant} "
+                                   + {"D": "(B keys 16x duplicated, in the lowest sixteenth of A's key range)", "U": "(unique keys both sides)",
+                                      "S": "(B keys 16x duplicated, spread over A's whole key range)"}[args.variant],
+                       "key_form": ["wide (64-bit hashes)", "narrow (keys within one 2^32-wide window, verified on the device: 32-bit hashes)",
+                                    "compact narrow (keys within the sampled 2^k-wide window, verified on the device: k-bit hashes, "
+                                    "direct-address leaf tables)"][dev.last_join_form()],
+                       "left_table_pruning": {"min_max": bool(dev.last_join_filter()[1]), "bitmap": int(dev.last_join_filter()[0])},
+                       "partition_levels": dev.last_join_levels(),
+                       "rows_per_table_per_gpu": n, "rows_per_table_total": total_rows, "joined_rows": joined_total, "groups": groups_total,
+                       "result": "(group key, COUNT(*)) per group - the statement's two result columns, what query_execute() asks the operator for",
+                       "operator_flags": "MDB_ORDER_FIRST | MDB_KEYS_MAY_ALIAS, as query_execute() calls the operator (group keys that would be an exact copy "
+                                         "of the left key column - every left row a group: variant U - are not written; variant D and S: everything is written)",
+                       "group_keys_are_left_column": bool(dev.last_plan().get("keys_are_left_column")) if not use_dist else False,
+                       "order": "unspecified (--unordered: mdb_dev_join_group_count without MDB_ORDER_FIRST)" if (args.unordered and not use_dist) else
+                                "reference first-occurrence order" if not use_dist else "per rank, unspecified (leaf order; first occurrence in the "
+                                "received stream on the key-by-destination path)",
+                       "parallelism": f"hash-partition x{world}, exchange behind the C-ABI (mdb_dist_join_group_count: RCCL all-to-all per table)"
+                                      + (" (forced shuffle)" if args.force_shuffle and world == 1 else "")
+                                      + ((", first-level partition regions on the wire (each table partitioned once; the receiver joins the "
+                                          "regions of all ranks: mdb_dev_shard.hip)" if dx.last_fused() else
+                                          (", 4-byte keys on the wire" if wire32 else ", 8-byte keys on the wire")) if use_dist else ""),
+                       "rccl_ranks_seen": ("test transport" if host_wire else ranks_seen) if use_dist else None,
+                       "transport": ("host memory through a gloo process group, all ranks on GPU 0 (--transport test: exercises this file's "
+                                     "N > 1 code; the wire's timings mean nothing)" if host_wire else "RCCL") if use_dist else None,
+                       "pruned_before_shuffle": bool(dx.last_pruned()) if use_dist else None},
+            "pipeline": {"algorithmic_bytes": algo_bytes, "achieved_GBs": algo_bytes / (dt / args.steps) / 1e9,
+                         "frac_of_peak": algo_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS / max(world, 1)},
+        }
+    if rank == 0 and args.full:
         narrow = dev.last_join_narrow()
         pruned = dev.last_join_filter()[1]
         levels = 1 if (dev.last_join_levels() == 1 and os.environ.get("MDB_WORDS16", "1") != "0") else 2
@@ -802,46 +889,7 @@ def main():
         # dominant kernel = the one instance that takes the most time per step (one table per partition launch)
         dom_name = max(kern, key=lambda k: kern[k]["ms_per_step"]) if kern else None
         roof = roof_of(dom_name) if dom_name else None
-        # whole-pipeline view: the bytes any correct algorithm must move once (SURVEY 8d)
-        algo_bytes = 8 * 2 * total_rows + 16 * groups_total
-        scaling_name = "strong" if (n == n_strong and world > 1) else "weak"
-        line = {
-            "metric": METRIC,
-            "value": value, "unit": "joined rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling_name, "vs_baseline": None,
-            "dtype": "int64", "data": "synthetic",
-            "step_ms": m["step_ms"], "retries_in_timed_steps": m["step_ms"]["retries_in_timed_steps"], "last_plan": dev.last_plan(),
-            "config": {"workload": f"A JOIN B ON id_a=id_b GROUP BY id_a COUNT(*), {n} rows/table/GPU x {world} GPU = {total_rows} rows/table "
-                                   f"({scaling_name} scaling), variant {args.variant} "
-                                   + {"D": "(B keys 16x duplicated, in the lowest sixteenth of A's key range)", "U": "(unique keys both sides)",
-                                      "S": "(B keys 16x duplicated, spread over A's whole key range)"}[args.variant],
-                       "key_form": ["wide (64-bit hashes)", "narrow (keys within one 2^32-wide window, verified on the device: 32-bit hashes)",
-                                    "compact narrow (keys within the sampled 2^k-wide window, verified on the device: k-bit hashes, "
-                                    "direct-address leaf tables)"][dev.last_join_form()],
-                       "left_table_pruning": {"min_max": bool(dev.last_join_filter()[1]), "bitmap": int(dev.last_join_filter()[0])},
-                       "partition_levels": dev.last_join_levels(),
-                       "rows_per_table_per_gpu": n, "rows_per_table_total": total_rows, "joined_rows": joined_total, "groups": groups_total,
-                       "result": "(group key, COUNT(*)) per group - the statement's two result columns, what query_execute() asks the operator for",
-                       "operator_flags": "MDB_ORDER_FIRST | MDB_KEYS_MAY_ALIAS, as query_execute() calls the operator (group keys that would be an exact copy "
-                                         "of the left key column - every left row a group: variant U - are not written; variant D and S: everything is written)",
-                       "group_keys_are_left_column": bool(dev.last_plan().get("keys_are_left_column")) if not use_dist else False,
-                       "order": "unspecified (--unordered: mdb_dev_join_group_count without MDB_ORDER_FIRST)" if (args.unordered and not use_dist) else
-                                "reference first-occurrence order" if not use_dist else "per rank, unspecified (leaf order; first occurrence in the "
-                                "received stream on the key-by-destination path)",
-                       "parallelism": f"hash-partition x{world}, exchange behind the C-ABI (mdb_dist_join_group_count: RCCL all-to-all per table)"
-                                      + (" (forced shuffle)" if args.force_shuffle and world == 1 else "")
-                                      + ((", first-level partition regions on the wire (each table partitioned once; the receiver joins the "
-                                          "regions of all ranks: mdb_dev_shard.hip)" if dx.last_fused() else
-                                          (", 4-byte keys on the wire" if wire32 else ", 8-byte keys on the wire")) if use_dist else ""),
-                       "rccl_ranks_seen": ("test transport" if host_wire else ranks_seen) if use_dist else None,
-                       "transport": ("host memory through a gloo process group, all ranks on GPU 0 (--transport test: exercises this file's "
-                                     "N > 1 code; the wire's timings mean nothing)" if host_wire else "RCCL") if use_dist else None,
-                       "pruned_before_shuffle": bool(dx.last_pruned()) if use_dist else None},
-            "roofline": roof,
-            "pipeline": {"algorithmic_bytes": algo_bytes, "achieved_GBs": algo_bytes / (dt / args.steps) / 1e9,
-                         "frac_of_peak": algo_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS / max(world, 1)},
-            "kernels": kern,
-        }
+        line.update(step_ms=m["step_ms"], roofline=roof, kernels=kern)
         if n == 100_000_000 and world == 1:
             line["pipeline"]["traffic"] = pmc_step_traffic(kern, pmc_variant, algo_bytes)
         if exchange is not None:
@@ -1034,6 +1082,7 @@ def main():
                 line["cpu_hash"] = cpu_hash_yardstick(a, b, gpu_result)
             except Exception as e:  # pragma: no cover
                 line["cpu_hash"] = {"error": str(e)}
+    if rank == 0:
         if args.verify and n <= 20_000_000 and world == 1:
             from oracle import cpu, np_oracle as orc
             eb = orc.gen_keys(n, 0, n, 43, mod_b) * (16 if args.variant == "S" else 1)

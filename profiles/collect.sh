@@ -22,7 +22,7 @@ passes() {	# $1 = output directory, $2... = program and arguments
 	rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR \
 		--output-format csv -d "$OUT/lds" -- "$@" > "$OUT/lds.log" 2>&1
 }
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
+ARGS="--steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary"
 for V in D U S; do
 	SUF=""; [ "$V" != "D" ] && SUF="_$V"
 	passes "$R/gpurun_out/prof_$TAG$SUF" python3 "$R/bench.py" $ARGS --variant $V

@@ -79,3 +79,49 @@ def raw_cell(v):
     if isinstance(v, float):
         return int(np.array([v], dtype=np.float64).view(np.int64)[0])
     return int(v)
+
+
+# ---- the reference's answers to inputs the tests generate themselves (tests/golden/live_reference.json) ----------------------
+# A test that used to need the reference library at run time (oracle/_ref, built only where the reference sources lie) compares
+# with the answer recorded here; where oracle/_ref is built it also recomputes that answer live, which must agree.  Record new
+# entries with oracle/_ref built (and MDB_REFERENCE_TREE naming the reference's source tree for its header layouts):
+#   MDB_RECORD_GOLDEN=1 python -m pytest tests/<file>::<test>
+
+LIVE = "live_reference.json"
+
+
+def _plain(x):
+    if isinstance(x, dict):
+        return {str(k): _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return [_plain(v) for v in x.tolist()]
+    if isinstance(x, np.integer):
+        return int(x)
+    if isinstance(x, np.floating):
+        return float(x)
+    return x
+
+
+def digest(obj):
+    """sha256 of a result (names, rows, anything JSON can hold; numpy scalars as Python numbers) in one canonical text form"""
+    import hashlib
+    return hashlib.sha256(json.dumps(_plain(obj), sort_keys=True).encode()).hexdigest()
+
+
+def reference_answer(key, live=None):
+    """The stored answer under `key` (plain JSON data, often a digest()).  `live`: None where oracle/_ref is not built, else a function
+    that computes the same answer through the reference now."""
+    path = os.path.join(GOLDEN, LIVE)
+    stored = load(LIVE) if os.path.exists(path) else {}
+    if live is not None:
+        got = live()
+        if os.environ.get("MDB_RECORD_GOLDEN") == "1":
+            stored[key] = got
+            with open(path, "w") as f:
+                json.dump(stored, f, indent=1, sort_keys=True)
+                f.write("\n")
+        assert stored.get(key) == got, f"the live reference disagrees with the stored answer {key!r}"
+    assert key in stored, f"no stored reference answer {key!r} in tests/golden/{LIVE}"
+    return stored[key]

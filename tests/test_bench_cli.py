@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -52,9 +54,9 @@ def _one_line(p):
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 8])
 def test_north_star_bench_at_world_n_through_the_test_transport(world):
-    one = _one_line(_bench(["--rows", "400000", "--steps", "2", "--warmup", "1", "--no-secondary", "--no-cpu-baseline"]))
+    one = _one_line(_bench(["--rows", "400000", "--steps", "2", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"]))
     line = _one_line(_bench(["--gpus", str(world), "--transport", "test", "--rows", "400000", "--steps", "2", "--warmup", "1", "--verify",
-                             "--no-cpu-baseline", "--peer-timeout", "240"]))
+                             "--full", "--no-cpu-baseline", "--peer-timeout", "240"]))
     missing = (set(one) - {"exchange_preview"}) - set(line)
     assert not missing and CORE_KEYS <= set(line), missing
     assert line["n_gpus"] == world and line["scaling"] == "weak" and line["value"] > 0
@@ -99,3 +101,38 @@ def test_a_rank_that_loses_a_peer_exits_non_zero(fault):
     assert p.returncode != 0, p.stdout[-1000:]
     assert time.time() - t0 < 400
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"value"' in ln and '"value": null' not in ln]
+
+
+def test_dump_outputs_is_refused_for_the_other_configs():
+    """--dump-outputs covers the north-star query; asked for with another configuration the command line is refused before
+    anything touches a GPU"""
+    p = _bench(["--config", "4", "--dump-outputs", "unused_dir"], timeout=120)
+    assert p.returncode == 2 and "--dump-outputs" in p.stderr, p.stderr[-2000:]
+
+
+HEADLINE_KEYS = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"}
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_identical_outputs(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline alone (what --full adds is absent); --dump-outputs writes what
+    the last timed step returned as float64 arrays, the same in two runs with the same arguments, and they are the oracle's result."""
+    from oracle import cpu, np_oracle as orc
+    n = 300000
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        line = _one_line(_bench(["--rows", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]))
+        assert HEADLINE_KEYS <= set(line), HEADLINE_KEYS - set(line)
+        assert not {"roofline", "kernels", "step_ms", "cpu_baseline", "cold_start", "wide_form", "end_to_end"} & set(line)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "int64"
+        arrays = {f.name[:-4]: np.load(str(f)) for f in sorted(d.iterdir())}
+        assert set(arrays) == {"group_index", "group_keys", "group_counts", "totals"}
+        assert all(v.dtype == np.float64 for v in arrays.values())
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    ek, ec, _, ej = cpu.hash_join_group_count(orc.gen_keys(n, 0, n, 42, 0), None, orc.gen_keys(n, 0, n, 43, n // 16), None, 4)
+    a = dumps[0]
+    assert np.array_equal(a["group_index"], np.arange(len(ek)))
+    assert np.array_equal(a["group_keys"], ek.astype(np.float64)) and np.array_equal(a["group_counts"], ec.astype(np.float64))
+    assert a["totals"].tolist() == [ej, len(ek), float(ek.sum()), float(ec.sum())]
