@@ -45,7 +45,6 @@ struct bg_sort_args {
 	uint32_t *words;	/* [nbands * bstride]: band b, digit d: words[b * bstride + d * cap ...] */
 	uint32_t *cur;		/* [nbands * D]: cur[b * D + d] = words of digit d in band b (more than cap: the region overflowed) */
 	uint32_t cap, bstride, nfull /* full tiles */, ntiles;
-	uint32_t ablate;	/* measurement only (MDB_BG_ABLATE): 1 no cursor atomics, 2 no words written, 4 words written in tile order (no walk) */
 	uint32_t *status;
 	struct mdb_bg_comp comp;	/* k_bg_band_sort<., true>: the key is the composite value of these columns (keys, base unused) */
 };
@@ -201,9 +200,9 @@ __global__ __launch_bounds__(BG_THREADS) void k_bg_band_sort(bg_sort_args a)
 		s1 = s0 + c0;
 		r0 = ex >> 16;
 		if (mine) {
-			if (c0 && !(a.ablate & 1u))
+			if (c0)
 				g0 = atomicAdd(&a.cur[(size_t)band * D + 2u * threadIdx.x], c0);
-			if (c1 && !(a.ablate & 1u))
+			if (c1)
 				g1 = atomicAdd(&a.cur[(size_t)band * D + 2u * threadIdx.x + 1u], c1);
 			s_cnt[threadIdx.x] = s0 | (s1 << 16);
 			if (c0)
@@ -260,11 +259,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bg_band_sort(bg_sort_args a)
 			const uint64_t m = (uint64_t)s_bits[j0 >> 5] | ((uint64_t)s_bits[(j0 >> 5) + 1u] << 32);
 			const uint32_t rank = before + (uint32_t)__popcll(m & le) - 1u;
 			before += (uint32_t)__popcll(m);
-			if (j < cnt && !(a.ablate & 2u)) {
-				if (a.ablate & 4u) {
-					dst[j] = s_stage[j];
-					continue;
-				}
+			if (j < cnt) {
 				const uint32_t o = s_dst[rank];
 				if (o != BG_OVF)
 					dst[o + j] = s_stage[j];
@@ -500,7 +495,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 				return 1;
 	}
 	if (kbits < 18u || kbits > 14u + BG_MAX_DBITS || n < ((uint64_t)1 << 21) || n >= 0xF0000000ull || ((uintptr_t)keys & 15u) ||
-	    (mdb_knob("MDB_GROUP_BANDED") && mdb_knob("MDB_GROUP_BANDED")[0] == '0'))
+	    mdb_knob_off("MDB_GROUP_BANDED"))
 		return 1;
 	/* the regions overflowed on this very column last time (a hot key): not tried again for a while */
 	if (ctx->ex_keys == keys && ctx->ex_nl == n && ctx->ex_nr == 0 && ctx->ex_uses < GC_HINT_USES)
@@ -522,7 +517,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	size_t need = mdb_align_up((size_t)nbands * bstride * 4 + 64) + mdb_align_up((size_t)D * nbands * 4) + mdb_align_up(most * 8) +
 		      order_records_arena_bytes(most, n, row_bits, sb1, sb2) + 16384;
 	/* (nearly unique keys need nearly as many key values as rows: a window with fewer cannot hold them - no pilot) */
-	const bool dense_ok = !comp && n >= ((uint64_t)1 << 22) && values >= n - n / 16 && !(mdb_knob("MDB_GROUP_DENSE") && mdb_knob("MDB_GROUP_DENSE")[0] == '0');
+	const bool dense_ok = !comp && n >= ((uint64_t)1 << 22) && values >= n - n / 16 && !mdb_knob_off("MDB_GROUP_DENSE");
 	if (dense_ok)
 		need += mdb_dense_arena_bytes(n) + mdb_align_up((n / 8 + 4096) * 8);
 	if (ctx->explain) {	/* (mdb_dev_explain_group_count: the band sort serves - nothing is launched; nearly unique keys: a pilot decides) */
@@ -558,7 +553,6 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	sa.nfull = nfull;
 	sa.ntiles = ntiles;
 	sa.status = ctx->d_status;
-	sa.ablate = mdb_knob("MDB_BG_ABLATE") ? (uint32_t)atoi(mdb_knob("MDB_BG_ABLATE")) : 0u;
 	if (comp)
 		sa.comp = *comp;
 	const size_t lds_sort = ((size_t)(D >> 1) + D + BG_TILE / 32u + BG_TILE) * 4;
@@ -640,7 +634,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 			MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 32, hipMemcpyDeviceToHost, ctx->stream));
 			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 			const uint32_t dstatus = ps[0], dgroups = ps[1], n_exc = ps[5];
-			if (mdb_knob("MDB_DEBUG_GROUP"))
+			if (mdb_knob_set("MDB_DEBUG_GROUP"))
 				fprintf(stderr, "group_count (band sort, dense): pilot %llu of %llu rows not first; %u groups, %u rows not first, %u exceptions, status %u\n",
 					(unsigned long long)pilot_dups, (unsigned long long)pilot_rows, dgroups, ps[4], n_exc, dstatus);
 			if (!(dstatus & (16384u | 128u | 2u)) && (uint64_t)dgroups + ps[4] == n) {
@@ -666,7 +660,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	const uint32_t *hs = reinterpret_cast<const uint32_t *>(&h[1]);
 	const uint32_t status = hs[0], groups = hs[1], list_len = hs[2];
-	if (mdb_knob("MDB_DEBUG_GROUP"))
+	if (mdb_knob_set("MDB_DEBUG_GROUP"))
 		fprintf(stderr, "group_count (band sort): window 2^%u at %lld, %u digits, %u bands, %u words per region: status %u, %u groups\n", kbits,
 			(long long)win_lo, D, nbands, rcap, status, groups);
 	if (status & 128u) {

@@ -803,9 +803,8 @@ static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const
  * reads that each move a 128-byte line (PMC: 1.87 GB read for 0.32 GB algorithmic, 0.22 of the 0.58 ms), after a 4-byte scatter
  * of the partners (0.34 GB written for 0.04).  Here up to two payload cells of the right table travel through its ONE partition
  * level beside the word (k_part_scatter<pf_key_cf_pay>: read in row order, written in region order - both sequential), the
- * leaf's LDS table holds the right row's PLACE in the digit's regions instead of its row id, and a left row that finds its
- * partner copies the cells from there (the digit's regions: lines the workgroup has just streamed) to out[left row id] - the one
- * scattered access left, an 8-byte store per cell.  When every left row found a partner (referential integrity: counted, not
+ * leaf's LDS table holds the right rows' cells, and a left row that finds its partner copies its cell from there to
+ * out[left row id] - the one scattered access left, an 8-byte store per cell.  When every left row found a partner (referential integrity: counted, not
  * assumed) the outputs ARE the joined rows' payload columns in left-row order, no row ids exist and nothing is compacted;
  * otherwise the call says "not served" and the pairs path answers.  (reference: _join_nested_loop_tbl2tbl + cpy_cols/merge_rows,
  * executor_select.c:1076-1149, 340-438) */
@@ -836,130 +835,11 @@ __device__ static inline void pp_locate(const uint32_t *pstart, uint32_t nsub, u
 	*i = 2u * (p - pstart[s]);
 }
 
-template <typename E /* table entry: the partner's place among the digit's regions + 1 (uint16_t when nsub * cap_r < 2^16: 64 KiB of LDS at
-		       * 2^15 entries, two workgroups per CU - the phases of one overlap the other's) */>
-__global__ __launch_bounds__(PW_THREADS) void k_leaf_pairs_payload(pp_args a, uint32_t rem, uint32_t shift)
-{
-	extern __shared__ __attribute__((aligned(16))) uint32_t pp_lds[];
-	E *const tab = reinterpret_cast<E *>(pp_lds);
-	__shared__ unsigned long long s_red[PW_THREADS / 64];
-	__shared__ uint32_t s_cnt[2][PP_MAX_SUB], s_pstart[2][PP_MAX_SUB + 1];
-	const uint32_t T = 1u << rem, mask = T - 1u, leaf = blockIdx.x;
-	for (uint32_t s = threadIdx.x; s < T * sizeof(E) / 4u; s += PW_THREADS)
-		pp_lds[s] = 0u;
-	if (threadIdx.x < 2u * PP_MAX_SUB) {
-		const uint32_t side = threadIdx.x / PP_MAX_SUB, sub = threadIdx.x % PP_MAX_SUB;
-		uint32_t c = 0;
-		if (sub < a.nsub) {
-			c = side ? a.cnt_r[sub * a.nleaves + leaf] : a.cnt_l[sub * a.nleaves + leaf];
-			const uint32_t cap = side ? a.cap_r : a.cap_l;
-			c = c < cap ? c : cap;
-		}
-		s_cnt[side][sub] = c;
-	}
-	__syncthreads();
-	if (threadIdx.x < 2u) {
-		uint32_t run = 0;
-		for (uint32_t k = 0; k < PP_MAX_SUB; k++) {
-			s_pstart[threadIdx.x][k] = run;
-			run += (s_cnt[threadIdx.x][k] + 1u) >> 1;
-		}
-		s_pstart[threadIdx.x][PP_MAX_SUB] = run;
-	}
-	__syncthreads();
-	/* ---- the right table: every row's place into the table */
-	uint32_t rows_r = 0;
-	for (uint32_t k = 0; k < a.nsub; k++)
-		rows_r += s_cnt[1][k];
-	{
-		const uint32_t P = s_pstart[1][PP_MAX_SUB];
-		for (uint32_t p0 = 0; p0 < P; p0 += PW_THREADS * PW_UNROLL) {	/* uniform trip count */
-			ulonglong2 v[PW_UNROLL];
-			uint32_t place[PW_UNROLL], left_in_sub[PW_UNROLL];
-#pragma unroll
-			for (int u = 0; u < PW_UNROLL; u++) {
-				const uint32_t p = p0 + (uint32_t)u * PW_THREADS + threadIdx.x, pc = p < P ? p : P - 1u;
-				uint32_t sub, i;
-				pp_locate(s_pstart[1], a.nsub, pc, &sub, &i);
-				v[u] = *reinterpret_cast<const ulonglong2 *>(a.hv_r + (size_t)(leaf * a.nsub + sub) * a.cap_r + i);
-				place[u] = sub * a.cap_r + i + 1u;
-				left_in_sub[u] = p < P ? s_cnt[1][sub] - i : 0u;	/* rows of the chunk that exist: 0, 1 or 2+ */
-			}
-#pragma unroll
-			for (int u = 0; u < PW_UNROLL; u++) {
-				if (left_in_sub[u] >= 1u)
-					tab[((uint32_t)(v[u].x >> 32) >> shift) & mask] = (E)place[u];
-				if (left_in_sub[u] >= 2u)
-					tab[((uint32_t)(v[u].y >> 32) >> shift) & mask] = (E)(place[u] + 1u);
-			}
-		}
-	}
-	__syncthreads();
-	unsigned long long occupied = 0;
-	for (uint32_t s = threadIdx.x; s < T; s += PW_THREADS)
-		occupied += tab[s] != 0;
-	occupied = lw_block_sum(occupied, s_red);
-	if (occupied != rows_r) {	/* a right key occurs twice */
-		if (threadIdx.x == 0)
-			mdb_raise(a.status, 32u);
-		return;
-	}
-	/* ---- the left table: partner's place -> its cells -> out[left row id] */
-	const size_t base_r = (size_t)leaf * a.nsub * a.cap_r;
-	unsigned long long pairs = 0;
-	{
-		const uint32_t P = s_pstart[0][PP_MAX_SUB];
-		for (uint32_t p0 = 0; p0 < P; p0 += PW_THREADS * PW_UNROLL) {
-			ulonglong2 v[PW_UNROLL];
-			uint32_t have[PW_UNROLL];
-#pragma unroll
-			for (int u = 0; u < PW_UNROLL; u++) {
-				const uint32_t p = p0 + (uint32_t)u * PW_THREADS + threadIdx.x, pc = p < P ? p : P - 1u;
-				uint32_t sub, i;
-				pp_locate(s_pstart[0], a.nsub, pc, &sub, &i);
-				v[u] = *reinterpret_cast<const ulonglong2 *>(a.hv_l + (size_t)(leaf * a.nsub + sub) * a.cap_l + i);
-				have[u] = p < P ? s_cnt[0][sub] - i : 0u;
-			}
-			/* the partners' places first, then their cells (loads in flight together; a row without partner reads the digit's first
-			 * cell: a load behind a per-row test is waited for before the next one is issued), then the stores */
-			uint32_t e[2 * PW_UNROLL];
-			uint64_t cell[2][2 * PW_UNROLL];
-#pragma unroll
-			for (int u = 0; u < PW_UNROLL; u++) {
-				e[2 * u] = have[u] >= 1u ? (uint32_t)tab[((uint32_t)(v[u].x >> 32) >> shift) & mask] : 0u;
-				e[2 * u + 1] = have[u] >= 2u ? (uint32_t)tab[((uint32_t)(v[u].y >> 32) >> shift) & mask] : 0u;
-			}
-#pragma unroll
-			for (int q = 0; q < 2 * PW_UNROLL; q++)
-				cell[0][q] = a.pay_r[0][base_r + (e[q] ? e[q] - 1u : 0u)];
-			if (a.npay > 1u) {	/* (uniform) */
-#pragma unroll
-				for (int q = 0; q < 2 * PW_UNROLL; q++)
-					cell[1][q] = a.pay_r[1][base_r + (e[q] ? e[q] - 1u : 0u)];
-			}
-#pragma unroll
-			for (int q = 0; q < 2 * PW_UNROLL; q++)
-				if (e[q]) {
-					const uint32_t lrid = (uint32_t)((q & 1) ? v[q >> 1].y : v[q >> 1].x);
-					if (lrid >= a.n_l)
-						continue;
-					a.out[0][lrid] = cell[0][q];
-					if (a.npay > 1u)
-						a.out[1][lrid] = cell[1][q];
-					pairs++;
-				}
-		}
-	}
-	pairs = lw_block_sum(pairs, s_red);
-	if (threadIdx.x == 0 && pairs)
-		atomicAdd(a.joined, pairs);
-}
-
 /* ONE payload column: the cells themselves sit in the LDS table (8 bytes per key value, 2^14 of them: 128 KiB) - a right row drops
  * its cell at its key's slot, a left row picks it up: no global lookup at all, the only scattered access left is the store to
  * out[left row id].  A digit of 2^15 key values (windows of 2^24) is joined in two passes over its words, one per half of the
- * slots - the second pass reads what the first has just pulled through the L2.  (The variant above looks the cells up in the digit's
- * regions: 10^7 scattered 8-byte loads fetch 32-byte sectors that leave the 4 MiB L2 before their other cells are asked for -
+ * slots - the second pass reads what the first has just pulled through the L2.  (Looking the cells up in the digit's regions
+ * instead, through a table of the right rows' places: 10^7 scattered 8-byte loads fetch 32-byte sectors that leave the 4 MiB L2 before their other cells are asked for -
  * PMC: 0.98 GB fetched for 0.24 GB - and cost 0.08 ms of its 0.30.)  Duplicate right keys are seen by the occupancy bitmap. */
 #define PC_SLOT_BITS 14u
 __global__ __launch_bounds__(PW_THREADS) void k_leaf_pairs_cell(pp_args a, uint32_t rem, uint32_t shift)
@@ -1188,7 +1068,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		return MIDORIDB_OK;
 	};
 	if (n_l == 0 || n_r == 0 || n_l >= 0xFFFFFFFFull || n_r >= 0xFFFFFFFFull || n_l + n_r < (1ull << 20) || ld_disabled() ||
-	    (mdb_knob("MDB_JOIN_PAYLOAD") && mdb_knob("MDB_JOIN_PAYLOAD")[0] == '0'))
+	    mdb_knob_off("MDB_JOIN_PAYLOAD"))
 		return 1;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
 	if (ctx->jp_bad_l == keys_l && ctx->jp_bad_nl == n_l && ctx->jp_bad_r == keys_r && ctx->jp_bad_nr == n_r && ++ctx->jp_bad_skips < 32)
@@ -1201,7 +1081,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	if (rc)
 		return rc;
 	const bool remembered = ctx->guess_remembered;
-	if (mdb_knob("MDB_DEBUG_PAYLOAD"))
+	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 		fprintf(stderr, "join_payload: narrow %d window 2^%u at %lld (attempt %d, remembered %d)\n", (int)narrow, win.kbits, (long long)win.lo, attempt, (int)remembered);
 	if (!narrow || !win.kbits)
 		return 1;
@@ -1223,7 +1103,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		const uint32_t status = (uint32_t)h[1];
 		const uint64_t J = h[2];
-		if (mdb_knob("MDB_DEBUG_PAYLOAD"))
+		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 			fprintf(stderr, "join_payload (row order): k %u status %u J %llu of %llu left rows\n", kbits, status, (unsigned long long)J,
 				(unsigned long long)n_l);
 		if (status == 0 && J == (uint64_t)npay * n_l) {
@@ -1308,7 +1188,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		const uint32_t status = (uint32_t)h[1];
 		const uint64_t J = h[2];
-		if (mdb_knob("MDB_DEBUG_PAYLOAD"))
+		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 			fprintf(stderr, "join_payload (two levels): k %u b2 %d rem %u status %u J %llu of %llu left rows\n", kbits, b2, rem, status, (unsigned long long)J,
 				(unsigned long long)n_l);
 		if (status == 0 && J == n_l) {
@@ -1380,9 +1260,9 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	a.status = ctx->d_status;
 	if (pl.nsub > PP_MAX_SUB)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: %u sub-regions per digit", pl.nsub);
-	if (!(mdb_knob("MDB_PP_CELL") && mdb_knob("MDB_PP_CELL")[0] == '0')) {
+	{
 		/* the cells IN the leaf's LDS table: one scattered access per joined row.  Two carried columns: the kernel once per column
-		 * (round 5: 0.51 -> 2 x 0.22 ms at 10^7 rows - the region-lookup leaf pays two scattered accesses per row and cell pair); the second
+		 * (round 5: 0.51 -> 2 x 0.22 ms at 10^7 rows - the region-lookup leaf paid two scattered accesses per row and cell pair); the second
 		 * launch counts its pairs into a word nobody reads */
 		const uint32_t lowbits = rem < PC_SLOT_BITS ? rem : PC_SLOT_BITS;
 		const size_t lds = ((size_t)8 << lowbits) + ((size_t)1 << lowbits) / 8 + 64;
@@ -1396,14 +1276,6 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 				ac.joined = (unsigned long long *)(ctx->d_status + 6);
 			MDB_LAUNCH_LDS(ctx, "leaf_pairs_payload", k_leaf_pairs_cell, pl.nleaves, PW_THREADS, lds, ac, rem, shift);
 		}
-	} else if ((uint64_t)pr.nsub * pr.leaf_cap < 0xFFFFull && !(mdb_knob("MDB_PP_E16") && mdb_knob("MDB_PP_E16")[0] == '0')) {
-		const size_t lds = (size_t)2 << rem;
-		MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leaf_pairs_payload<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		MDB_LAUNCH_LDS(ctx, "leaf_pairs_payload", k_leaf_pairs_payload<uint16_t>, pl.nleaves, PW_THREADS, lds, a, rem, shift);
-	} else {
-		const size_t lds = (size_t)4 << rem;
-		MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leaf_pairs_payload<uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		MDB_LAUNCH_LDS(ctx, "leaf_pairs_payload", k_leaf_pairs_payload<uint32_t>, pl.nleaves, PW_THREADS, lds, a, rem, shift);
 	}
 	uint64_t *h = ctx->h_pinned;
 	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
@@ -1461,8 +1333,8 @@ extern "C" int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_
 				return -MIDORIDB_ERROR;
 		streams += right[t].npay;
 	}
-	if (streams > 4 || key_min > key_max || n_l == 0 || ld_disabled() || (mdb_knob("MDB_JOIN_PAYLOAD") && mdb_knob("MDB_JOIN_PAYLOAD")[0] == '0') ||
-	    (mdb_knob("MDB_JOIN_PAYLOAD_MULTI") && mdb_knob("MDB_JOIN_PAYLOAD_MULTI")[0] == '0'))
+	if (streams > 4 || key_min > key_max || n_l == 0 || ld_disabled() || mdb_knob_off("MDB_JOIN_PAYLOAD") ||
+	    mdb_knob_off("MDB_JOIN_PAYLOAD_MULTI"))
 		return 1;
 	const uint64_t span = (uint64_t)key_max - (uint64_t)key_min;
 	if (span >= ((uint64_t)1 << 27))
@@ -1505,7 +1377,7 @@ extern "C" int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	const uint32_t status = (uint32_t)h[1];
 	const uint64_t J = h[2];
-	if (mdb_knob("MDB_DEBUG_PAYLOAD"))
+	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 		fprintf(stderr, "join_payload_multi (row order): %d tables, %d columns, k %u status %u J %llu of %llu x %d\n", nright, streams, kbits, status,
 			(unsigned long long)J, (unsigned long long)n_l, streams);
 	if (status == 0 && J == (uint64_t)streams * n_l) {
@@ -1652,7 +1524,7 @@ static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	 * it off).  What it cannot do - a key outside the window after all, a first-level region overflow - goes the usual way */
 	if (narrow && win.kbits >= 9u + PW_MIN_REM && win.kbits <= 9u + PW_MAX_REM && n_l <= PW_MAX_LEFT && n_l + n_r >= (1ull << 20) &&
 	    !(ctx->pw_bad_keys == keys_r && ctx->pw_bad_n == n_r) && !ld_disabled() &&
-	    !(mdb_knob("MDB_ONE_LEVEL") && mdb_knob("MDB_ONE_LEVEL")[0] == '0')) {
+	    !mdb_knob_off("MDB_ONE_LEVEL")) {
 		urc = join_pairs_unique_wide(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, win.kbits, win.lo, out_l, out_r, out_count);
 		if (urc <= 0 || urc == 3)
 			return urc;

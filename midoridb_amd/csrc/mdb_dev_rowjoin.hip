@@ -274,8 +274,6 @@ struct rj_leaf_args {
 	const uint32_t *words_l;
 	const uint32_t *offT_l;
 	uint32_t ntiles, tstride, dbits, sbits /* key values per digit: 2^sbits <= 2^14 */;
-	uint32_t ablate;	/* measurement only (MDB_RJ_ABLATE): 1 no build, 2 no probe, 4 no cell stores, 8 no right cells read */
-	unsigned long long *trace;	/* measurement only (MDB_RJ_TRACE): workgroup 8's wave 0 leaves wall_clock64() stamps at its phase boundaries */
 	unsigned long long *joined;	/* += (left row, stream) pairs served: nstreams x the left rows when every row found its partner in every table */
 	uint32_t *status;
 };
@@ -300,8 +298,7 @@ __device__ static inline uint32_t rj_digit_of_block(uint32_t b, uint32_t D)
 template <int LPP, int UNITS, bool PER_SWEEP = false /* the lane-derived terms are worked out again in every sweep (callers whose own state leaves them no registers: kept across the
 							  * sweeps they are spilled and reloaded BETWEEN the loads of a batch, behind s_waitcnt vmcnt(0) - each such load waits for the one before) */,
 	  typename FL, typename FU, typename FD>
-__device__ static inline void rj_for_pieces(const uint32_t *offT, uint32_t tstride, uint32_t ntiles, uint32_t d, FL load, FU use, FD done /* after the `use`s of a batch */,
-					    bool skip_slow = false /* measurement only: pieces are cut off after LPP words */)
+__device__ static inline void rj_for_pieces(const uint32_t *offT, uint32_t tstride, uint32_t ntiles, uint32_t d, FL load, FU use, FD done /* after the `use`s of a batch */)
 {
 	constexpr int RJ_G = LPP >= 32 ? 1 : LPP == 16 ? 2 : 4;	/* tile groups per sweep: 16 (LPP 4), 32 or 64 pieces' steps per lane and sweep */
 	static_assert(LPP >= 4 && LPP <= 64 && (RJ_G * LPP) % UNITS == 0, "units per sweep");
@@ -348,13 +345,13 @@ __device__ static inline void rj_for_pieces(const uint32_t *offT, uint32_t tstri
 					use(u, idx[u]);
 			done();
 		}
-		if (!skip_slow && __any(longest > (uint32_t)LPP)) {
+		if (__any(longest > (uint32_t)LPP)) {
 			/* pieces longer than LPP words (one in 50 at an average of LPP / 2, more than a third at an average of LPP: nearly every sweep
 			 * has some).  Tier by tier - words [tier x LPP, (tier + 1) x LPP) of the pieces that have them -, ALL tile groups together
 			 * (round 6): per group the owners of such pieces are a ballot; lane group q takes the q-th of them - found by clearing q bits of
 			 * the mask, no LDS -, one crossbar read for its offsets word, and the groups' loads go out before the first is used: a round trip
 			 * per 64 / LPP pieces and group where walking the 32 steps again, one dependent load at a time, cost a fifth of the leaf
-			 * (profiles/r06/rj_ablate.txt: 1.39 ms with, 1.08 without the long pieces; 1.24 with this) */
+			 * (profiles/r06/ measured 1.39 ms with, 1.08 without the long pieces; 1.24 with this) */
 			constexpr int NQ = 64 / LPP;
 			static_assert(RJ_G <= UNITS, "a load slot per tile group");
 #pragma unroll 1
@@ -404,9 +401,9 @@ __device__ static inline void rj_for_pieces(const uint32_t *offT, uint32_t tstri
 }
 
 template <int LPP, int UNITS, bool PER_SWEEP = false, typename FL, typename FU>
-__device__ static inline void rj_for_pieces(const uint32_t *offT, uint32_t tstride, uint32_t ntiles, uint32_t d, FL load, FU use, bool skip_slow = false)
+__device__ static inline void rj_for_pieces(const uint32_t *offT, uint32_t tstride, uint32_t ntiles, uint32_t d, FL load, FU use)
 {
-	rj_for_pieces<LPP, UNITS, PER_SWEEP>(offT, tstride, ntiles, d, load, use, [] {}, skip_slow);
+	rj_for_pieces<LPP, UNITS, PER_SWEEP>(offT, tstride, ntiles, d, load, use, [] {});
 }
 
 /* The same for pieces of 32 words and more (windows of up to 2^24 values: 1024 digits and fewer): the whole wave walks one piece after
@@ -462,13 +459,6 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_leaf(rj_leaf_args a)
 	if (threadIdx.x == 0)
 		s_dup = 0u;
 	constexpr int LP = LPP == 64 ? 32 : LPP;	/* (lanes per piece of the piece walker; LPP 64: the build walks whole-wave pieces) */
-	uint32_t tr_n = 0;
-	const bool tracing = a.trace && blockIdx.x == 8u && threadIdx.x == 0;
-#define RJ_STAMP()                                              \
-	do {                                                    \
-		if (tracing && tr_n < 60u)                      \
-			a.trace[tr_n++] = wall_clock64();       \
-	} while (0)
 #pragma unroll 1
 	for (uint32_t dl = blockIdx.x >> 3; dl < (D >> 3); dl += per) {
 	const uint32_t d = xcd * (D >> 3) + dl;
@@ -479,37 +469,31 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_leaf(rj_leaf_args a)
 		if (!first)
 			rj_barrier();	/* (the last round's lookups are done) */
 		first = false;
-		RJ_STAMP();	/* 0: round begins */
 		for (uint32_t w = threadIdx.x; w < ((1u << a.sbits) + 31u) / 32u; w += blockDim.x)
-			s_occ[w] = (a.ablate & 1u) ? 0xFFFFFFFFu : 0u;
+			s_occ[w] = 0u;
 		rj_barrier();
-		RJ_STAMP();	/* 1: table cleared */
 		/* build: the digit's right rows - their cells dropped at their slots.  A right key twice: two rows, one bit - the bits set are
 		 * counted against the rows put once the table stands (no atomic that has to come back with the old word), the difference kept
 		 * until the workgroup leaves: what a call with such a table wrote is not used */
 		{
-			if (!(a.ablate & 1u)) {
-				constexpr int UB = 8;	/* (16 measured: 8 spills, 1.26 against 1.24 ms) */
-				rj_rec rv[UB] = {};	/* (defined here on every path: not carried around the loops as "whatever they held") */
-				const rj_rec *const recs = a.recs[s];
-				auto put = [&](const rj_rec &r) {
-					const uint32_t slot = r.word >> RJ_TILE_BITS;
-					atomicOr(&s_occ[slot >> 5], 1u << (slot & 31u));
-					unset++;
-					rj_cell[slot] = (a.ablate & 8u) ? 0ull : ((uint64_t)r.hi << 32 | r.lo);
-				};
-				auto ld = [&](int u, uint32_t idx) { rv[u] = recs[idx]; };
-				auto us = [&](int u, uint32_t) { put(rv[u]); };
-				if (LPP == 64)
-					rj_for_long_pieces<UB>(a.offT_r[s], a.tstride_r[s], a.ntiles_r[s], d, ld, us);
-				else
-					rj_for_pieces<LP, UB, (LPP != 8)>(a.offT_r[s], a.tstride_r[s], a.ntiles_r[s], d, ld, us, (a.ablate & 16u) != 0);
-			}
+			constexpr int UB = 8;	/* (16 measured: 8 spills, 1.26 against 1.24 ms) */
+			rj_rec rv[UB] = {};	/* (defined here on every path: not carried around the loops as "whatever they held") */
+			const rj_rec *const recs = a.recs[s];
+			auto put = [&](const rj_rec &r) {
+				const uint32_t slot = r.word >> RJ_TILE_BITS;
+				atomicOr(&s_occ[slot >> 5], 1u << (slot & 31u));
+				unset++;
+				rj_cell[slot] = (uint64_t)r.hi << 32 | r.lo;
+			};
+			auto ld = [&](int u, uint32_t idx) { rv[u] = recs[idx]; };
+			auto us = [&](int u, uint32_t) { put(rv[u]); };
+			if (LPP == 64)
+				rj_for_long_pieces<UB>(a.offT_r[s], a.tstride_r[s], a.ntiles_r[s], d, ld, us);
+			else
+				rj_for_pieces<LP, UB, (LPP != 8)>(a.offT_r[s], a.tstride_r[s], a.ntiles_r[s], d, ld, us);
 		}
-		RJ_STAMP();	/* 2: this wave's share of the build done */
 		rj_barrier();
-		RJ_STAMP();	/* 3: every wave's */
-		for (uint32_t w = threadIdx.x; w < ((1u << a.sbits) + 31u) / 32u && !(a.ablate & 1u); w += blockDim.x)
+		for (uint32_t w = threadIdx.x; w < ((1u << a.sbits) + 31u) / 32u; w += blockDim.x)
 			unset -= (uint32_t)__popc(s_occ[w]);
 		/* probe: every left row of the digit picks its partner's cell up and leaves it at its word's place */
 		{
@@ -519,29 +503,21 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_leaf(rj_leaf_args a)
 			auto take = [&](uint32_t word, uint32_t idx) {
 				const uint32_t slot = word >> RJ_TILE_BITS;
 				if ((s_occ[slot >> 5] >> (slot & 31u)) & 1u) {
-					if (!(a.ablate & 4u))
-						cells_al[idx] = rj_cell[slot];
+					cells_al[idx] = rj_cell[slot];
 					pairs++;
 				} else {
 					miss = 1u;
 				}
 			};
-			auto ld = [&](int u, uint32_t idx) { w[u] = (a.ablate & 2u) ? 0u : a.words_l[idx]; };
-			auto us = [&](int u, uint32_t idx) {
-				if (a.ablate & 2u)
-					pairs++;
-				else
-					take(w[u], idx);
-			};
+			auto ld = [&](int u, uint32_t idx) { w[u] = a.words_l[idx]; };
+			auto us = [&](int u, uint32_t idx) { take(w[u], idx); };
 			if (LONG)
 				rj_for_long_pieces<UP>(a.offT_l, a.tstride, a.ntiles, d, ld, us);
 			else
-				rj_for_pieces<LPP, UP, (LPP != 8)>(a.offT_l, a.tstride, a.ntiles, d, ld, us, (a.ablate & 16u) != 0);
+				rj_for_pieces<LPP, UP, (LPP != 8)>(a.offT_l, a.tstride, a.ntiles, d, ld, us);
 		}
-		RJ_STAMP();	/* 4: this wave's share of the probe done */
 	}
 	}
-#undef RJ_STAMP
 	if (miss)
 		mdb_raise(a.status, 4u);	/* a left row without partner */
 	{
@@ -639,11 +615,7 @@ static size_t rj_tiles(uint64_t n) { return (size_t)((n + RJ_TILE - 1) / RJ_TILE
 uint32_t mdb_rowjoin_dbits(uint32_t kbits)
 {
 	uint32_t d = kbits > 8u + 3u ? kbits - 8u : 3u;
-	d = d > RJ_MAX_DBITS ? RJ_MAX_DBITS : d;
-	const char *knob = mdb_knob("MDB_RJ_DBITS");	/* (measurement: fewer digits, longer pieces - never fewer than the leaf's table allows) */
-	if (knob && atoi(knob) >= 3 && (uint32_t)atoi(knob) < d && kbits - (uint32_t)atoi(knob) <= RJ_SLOT_BITS)
-		d = (uint32_t)atoi(knob);
-	return d;
+	return d > RJ_MAX_DBITS ? RJ_MAX_DBITS : d;
 }
 
 bool mdb_rowjoin_serves(uint64_t n_l, uint64_t n_r, uint32_t kbits, const void *keys_l, const void *null_l, const void *keys_r, const void *null_r,
@@ -654,10 +626,11 @@ bool mdb_rowjoin_serves(uint64_t n_l, uint64_t n_r, uint32_t kbits, const void *
 	/* MDB_ROWJOIN: 0 never, 2 whenever the form applies; default: left tables of 2^24 rows and more - up to there a result column
 	 * (128 MB) stays in the Infinity Cache and the older forms' scattered 8-byte stores land in it (10^7 x 10^7 rows: 0.44 ms against
 	 * 0.56 here; 10^8 x 10^8: 6.0 ms against 2.9) */
-	const char *knob = mdb_knob("MDB_ROWJOIN");
-	if (knob && knob[0] == '0')
+	char knob[2];
+	mdb_knob_str("MDB_ROWJOIN", knob, sizeof(knob));
+	if (knob[0] == '0')
 		return false;
-	if (n_l < ((uint64_t)1 << 24) && !(knob && knob[0] == '2'))
+	if (n_l < ((uint64_t)1 << 24) && knob[0] != '2')
 		return false;
 	if (kbits < 15u || kbits > RJ_SLOT_BITS + RJ_MAX_DBITS)	/* 8 ... 8192 digits (windows of up to 2^27 values) */
 		return false;
@@ -810,7 +783,7 @@ int mdb_rowjoin_run_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l,
 	const int lpp = dbits >= 13 ? 8 : dbits == 12 ? 16 : dbits == 11 ? 32 : dbits == 10 ? 64 : 0;
 	/* as many workgroups as the device holds at a time (a multiple of 8: the XCDs), each walking its share of its XCD's digits */
 	uint32_t leaf_grid = D;
-	if (!(mdb_knob("MDB_RJ_PERSIST") && mdb_knob("MDB_RJ_PERSIST")[0] == '0')) {
+	if (!mdb_knob_off("MDB_RJ_PERSIST")) {
 		const uint32_t per_cu = (uint32_t)(((size_t)160 << 10) / (lds_leaf + 1024)), by_threads = 2048u / leaf_threads;
 		const uint32_t held = ((uint32_t)ctx->num_cus * (per_cu < by_threads ? (per_cu ? per_cu : 1u) : by_threads)) & ~7u;
 		if (held >= 8u && held < D)
@@ -822,14 +795,8 @@ int mdb_rowjoin_run_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l,
 	la.tstride = tstride_l;
 	la.dbits = dbits;
 	la.sbits = sbits;
-	la.ablate = mdb_knob("MDB_RJ_ABLATE") ? (uint32_t)atoi(mdb_knob("MDB_RJ_ABLATE")) : 0u;
 	la.joined = (unsigned long long *)(ctx->d_status + 2);
 	la.status = ctx->d_status;
-	if (mdb_knob("MDB_RJ_TRACE")) {
-		la.trace = (unsigned long long *)mdb_arena_take(ctx, 64 * 8);
-		if (la.trace)
-			MDB_HIP(ctx, hipMemsetAsync(la.trace, 0, 64 * 8, ctx->stream));
-	}
 #define RJ_LAUNCH_LEAF(L, LONG)                                                                                                                   \
 	do {                                                                                                                                      \
 		MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rj_leaf<L, LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_leaf)); \
@@ -846,15 +813,6 @@ int mdb_rowjoin_run_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l,
 	else
 		RJ_LAUNCH_LEAF(64, true);
 #undef RJ_LAUNCH_LEAF
-	if (la.trace) {		/* measurement only */
-		unsigned long long h[64];
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		MDB_HIP(ctx, hipMemcpy(h, la.trace, sizeof(h), hipMemcpyDeviceToHost));
-		fprintf(stderr, "rowjoin_leaf trace (workgroup 8, wave 0; 10 ns ticks since the first stamp; 0 round begins, 1 table cleared, 2 own build done, 3 all built, 4 own probe done):\n");
-		for (int i = 0; i < 60 && h[i]; i++)
-			fprintf(stderr, "%s%llu", i % 5 ? " " : i ? "\n  " : "  ", h[i] - h[0]);
-		fprintf(stderr, "\n");
-	}
 	pa.words_l = words;
 	pa.ncols = la.nstreams;
 	pa.n = n_l;
@@ -1137,8 +1095,8 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 	 * 2^13 values on - the parity tests; =0: never).  At 10^8 rows (profiles/r05/group_forms.json): 2.5 x 10^7 groups spread over 2^27
 	 * values 1.20 ms against the partitioned path's 1.83; 10^8 unique keys 2.20 against 2.06 - the leaf's walk over 3052 tiles' pieces of
 	 * four words is bound by requests, and every row leaves it as a group record */
-	const char *const knob = mdb_knob("MDB_GROUP_TILED");
-	const bool on = knob ? knob[0] == '1' : (kbits >= 26u && n >= ((uint64_t)1 << 24));	/* (measured at 10^8 rows only: large tables) */
+	char knob[2];
+	const bool on = mdb_knob_str("MDB_GROUP_TILED", knob, sizeof(knob)) ? knob[0] == '1' : (kbits >= 26u && n >= ((uint64_t)1 << 24));	/* (measured at 10^8 rows only: large tables) */
 	if (!on || kbits < 13u || kbits > 14u + RJ_MAX_DBITS || n >= 0xF0000000ull || ((uintptr_t)keys & 15u) || n < ((uint64_t)1 << 21))
 		return 1;
 	const uint32_t dbits = rg_group_dbits(kbits), sbits = kbits - dbits, D = 1u << dbits;
@@ -1160,14 +1118,13 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 	const size_t ostride = (size_t)D + 8u;
 	const uint64_t values = (uint64_t)1 << kbits, most = (n < values ? n : values) + 1024;	/* groups: at most the rows, at most the window's key values */
 	uint32_t rg_n = 0;
-	const bool ranged = order_ranges_apply(n, row_bits, most < ((uint64_t)1 << 23) ? most : ((uint64_t)1 << 22), &rg_n) && values <= ((uint64_t)1 << 23) &&
-			    !(mdb_knob("MDB_ORDER_RANGES") && mdb_knob("MDB_ORDER_RANGES")[0] == '0');
+	const bool ranged = order_ranges_apply(n, row_bits, most < ((uint64_t)1 << 23) ? most : ((uint64_t)1 << 22), &rg_n) && values <= ((uint64_t)1 << 23);
 	size_t need = mdb_align_up((size_t)ntiles * RJ_STRIDE * 4 + 64) + 3 * mdb_align_up(((size_t)ntiles + 64) * ostride * 2) + mdb_align_up(most * 8) +
 		      order_records_arena_bytes(most, n, row_bits, sb1, sb2) + 16384;
 	if (ranged)
 		need += mdb_align_up((size_t)rg_n * ORDER_RANGE_CAP * 8) + mdb_align_up((size_t)rg_n * 4);
 	/* (nearly unique keys need nearly as many key values as rows: a window with fewer cannot hold them - no pilot) */
-	const bool dense_ok = n >= ((uint64_t)1 << 22) && values >= n - n / 16 && !(mdb_knob("MDB_GROUP_DENSE") && mdb_knob("MDB_GROUP_DENSE")[0] == '0');
+	const bool dense_ok = n >= ((uint64_t)1 << 22) && values >= n - n / 16 && !mdb_knob_off("MDB_GROUP_DENSE");
 	if (dense_ok)
 		need += mdb_dense_arena_bytes(n) + mdb_align_up((n / 8 + 4096) * 8);
 	int rc = mdb_arena_begin(ctx, need);
@@ -1255,7 +1212,7 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 			MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 32, hipMemcpyDeviceToHost, ctx->stream));
 			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 			const uint32_t dstatus = ps[0], groups = ps[1], n_exc = ps[5];
-			if (mdb_knob("MDB_DEBUG_GROUP"))
+			if (mdb_knob_set("MDB_DEBUG_GROUP"))
 				fprintf(stderr, "group_count (tile sort, dense): pilot %llu of %llu rows not first; %u groups, %u rows not first, %u exceptions, status %u\n",
 					(unsigned long long)pilot_dups, (unsigned long long)pilot_rows, groups, ps[4], n_exc, dstatus);
 			if (!(dstatus & 16384u) && (uint64_t)groups + ps[4] == n) {

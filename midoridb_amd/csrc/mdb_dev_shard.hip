@@ -59,8 +59,7 @@ int mdb_shard_plan_make(uint32_t world, uint32_t rank, uint32_t ntab, const uint
 			return 1;
 	/* windows of 2^24 .. 2^27 values, two tables: 4096 first-level digits (k_shard_scatter_wide) leave at most 15 key bits below the
 	 * digit - one level, no second pass over either table (variant U: 2^27 values, 1.42 -> 1.0 ms) */
-	const bool wide = ntab == 2 && k > SH_D_BITS + SH_ONE_LEVEL_MAX_REM && k <= SHW_D_BITS + SHW_MAX_REM &&
-			  !(mdb_knob("MDB_SHARD_WIDE") && mdb_knob("MDB_SHARD_WIDE")[0] == '0');
+	const bool wide = ntab == 2 && k > SH_D_BITS + SH_ONE_LEVEL_MAX_REM && k <= SHW_D_BITS + SHW_MAX_REM;
 	p->dbits = wide ? SHW_D_BITS : SH_D_BITS;
 	p->world = world;
 	p->ntab = ntab;
@@ -78,12 +77,7 @@ int mdb_shard_plan_make(uint32_t world, uint32_t rank, uint32_t ntab, const uint
 		p->b2 = 0;
 		p->rem = below;
 	} else {
-		uint32_t leaf_rem = ntab > 2 ? SH_LEAF_REM - 1u : SH_LEAF_REM;
-		{
-			const char *e = mdb_knob("MDB_SHARD_REM");	/* (measurements) */
-			if (e && atoi(e) >= 8 && atoi(e) <= (int)SH_ONE_LEVEL_MAX_REM)
-				leaf_rem = (uint32_t)atoi(e);
-		}
+		const uint32_t leaf_rem = ntab > 2 ? SH_LEAF_REM - 1u : SH_LEAF_REM;
 		int b2 = below > leaf_rem ? (int)(below - leaf_rem) : 2;
 		if (b2 > MDB_MAX_RADIX_BITS)
 			return 1;	/* (windows beyond 2^30 values) */
@@ -790,8 +784,7 @@ int mdb_shard_join(mdb_dev_ctx *ctx, const mdb_shard_plan *p, const void *const 
 			return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "sharded join: wide fan-out plan with %u segments per leaf, %u tables", regs_per_digit, p->ntab);
 		/* two tables: 16-bit counters (half the LDS: two workgroups per CU at 2^14 values per digit; a count beyond 65 535 is
 		 * reported and answered by another path) */
-		if (p->dbits == SHW_D_BITS || (p->ntab == 2 && regs_per_digit <= SHW_MAX_SEG && p->rem >= 1u &&
-					       !(mdb_knob("MDB_SHARD_LEAF_U16") && mdb_knob("MDB_SHARD_LEAF_U16")[0] == '0'))) {
+		if (p->dbits == SHW_D_BITS || (p->ntab == 2 && regs_per_digit <= SHW_MAX_SEG && p->rem >= 1u)) {
 			const size_t lds16 = (size_t)4 << p->rem;
 			MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_shard_leaf_wide<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
 			MDB_LAUNCH_LDS(ctx, "shard_leaf_wide", (k_shard_leaf_wide<1024>), p->Dp, 1024, lds16, a);
@@ -801,9 +794,9 @@ int mdb_shard_join(mdb_dev_ctx *ctx, const mdb_shard_plan *p, const void *const 
 		MDB_LAUNCH_LDS(ctx, "shard_leaf", (k_shard_leaf<1024, uint16_t>), p->Dp, 1024, lds, a);
 		return MIDORIDB_OK;
 	}
-	/* two levels: the receiver's own level over the regions of all ranks, then its leaves */
+	/* two levels: the receiver's own level over the regions of all ranks, then its leaves (of at most 2^SH_LEAF_REM key values: their
+	 * words fit 2 bytes) */
 	const uint32_t nleaves = p->Dp << p->b2;
-	const bool leaf16 = p->rem <= 16u && !(mdb_knob("MDB_SHARD_LEAF16") && mdb_knob("MDB_SHARD_LEAF16")[0] == '0');
 	for (uint32_t x = 0; x < p->ntab; x++) {
 		if (arrived && arrived[x])
 			MDB_HIP(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)arrived[x], 0));
@@ -821,7 +814,7 @@ int mdb_shard_join(mdb_dev_ctx *ctx, const mdb_shard_plan *p, const void *const 
 			   tiles, max_tiles);
 		/* (a leaf's key bits fit 16: its words are written - and read by the leaf kernel - as 2 bytes) */
 		int rc = mdb_partition_words_level(ctx, reinterpret_cast<const uint32_t *>(recv[x]), tiles, max_tiles, p->b2,
-						   32u - p->dbits - (uint32_t)p->b2, leaves, cursor, nleaves, p->leaf_cap[x], leaf16 ? 32u - p->kbits : 0u);
+						   32u - p->dbits - (uint32_t)p->b2, leaves, cursor, nleaves, p->leaf_cap[x], 32u - p->kbits);
 		if (rc)
 			return rc;
 		a.words[x] = leaves;
@@ -830,16 +823,11 @@ int mdb_shard_join(mdb_dev_ctx *ctx, const mdb_shard_plan *p, const void *const 
 		a.cap[x] = p->leaf_cap[x];
 	}
 	a.nseg = 1;
-	if (leaf16 && p->rem > 10u) {
+	if (p->rem > 10u) {
 		MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_shard_leaf<1024, uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		MDB_LAUNCH_LDS(ctx, "shard_leaf", (k_shard_leaf<1024, uint16_t>), nleaves, 1024, lds, a);
-	} else if (leaf16) {
-		MDB_LAUNCH_LDS(ctx, "shard_leaf", (k_shard_leaf<512, uint16_t>), nleaves, 512, lds, a);
-	} else if (p->rem > 10u) {
-		MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_shard_leaf<1024, uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		MDB_LAUNCH_LDS(ctx, "shard_leaf", (k_shard_leaf<1024, uint32_t>), nleaves, 1024, lds, a);
 	} else {
-		MDB_LAUNCH_LDS(ctx, "shard_leaf", (k_shard_leaf<512, uint32_t>), nleaves, 512, lds, a);
+		MDB_LAUNCH_LDS(ctx, "shard_leaf", (k_shard_leaf<512, uint16_t>), nleaves, 512, lds, a);
 	}
 	return MIDORIDB_OK;
 }

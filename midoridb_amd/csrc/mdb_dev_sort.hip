@@ -234,10 +234,11 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_ranges(sort_pack_args a, 
 #define SORT_RANGE_SAMPLE_ROWS ((uint64_t)1 << 17)
 static bool sort_ranges_sampled(uint64_t n)	/* MDB_SORT_RANGE_SAMPLE: 0 never, 2 from 2^18 rows on (tests) */
 {
-	const char *knob = mdb_knob("MDB_SORT_RANGE_SAMPLE");
-	if (knob && knob[0] == '0')
+	char knob[2];
+	mdb_knob_str("MDB_SORT_RANGE_SAMPLE", knob, sizeof(knob));
+	if (knob[0] == '0')
 		return false;
-	return n >= ((knob && knob[0] == '2') ? SORT_RANGE_SAMPLE_ROWS * 2 : SORT_RANGE_SAMPLE_MIN);
+	return n >= (knob[0] == '2' ? SORT_RANGE_SAMPLE_ROWS * 2 : SORT_RANGE_SAMPLE_MIN);
 }
 static int sort_pack_ranges(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, unsigned long long *mm /* 12 words */,
 			    sort_pack_args *pa, uint32_t *total, uint32_t limit, uint64_t *vmax, bool sampled = false)
@@ -1065,8 +1066,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_group_records(const uint32_t *
 static int group_multi_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_first,
 			      int64_t *out_count, uint64_t cap, uint64_t *out_groups)
 {
-	const char *knob = mdb_knob("MDB_GROUP_MULTI_PACKED");
-	if ((knob && knob[0] == '0') || nkeys > SORT_PACK_MAX_KEYS)
+	if (mdb_knob_off("MDB_GROUP_MULTI_PACKED") || nkeys > SORT_PACK_MAX_KEYS)
 		return 1;
 	for (int c = 0; c < nkeys; c++)
 		if (keys[c].type != MDB_T_INT64 && keys[c].type != MDB_T_DOUBLE)
@@ -1087,8 +1087,7 @@ static int group_multi_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys,
 	 * written and read back (0.45 ms per 10^8 rows and two columns).  A row outside the sampled ranges, a hot combination that overflows
 	 * a region: the composite column below.  MDB_GROUP_MULTI_FUSED=0: never. */
 	{
-		const char *fk = mdb_knob("MDB_GROUP_MULTI_FUSED");
-		bool plain = !(fk && fk[0] == '0') && n >= ((uint64_t)1 << 18);	/* (the band sort: from 2^21 rows on - it says so itself) */
+		bool plain = !mdb_knob_off("MDB_GROUP_MULTI_FUSED") && n >= ((uint64_t)1 << 18);	/* (the band sort: from 2^21 rows on - it says so itself) */
 		for (int c = 0; c < nkeys; c++)
 			plain = plain && !keys[c].rid && !((uintptr_t)keys[c].values & 15u);
 		if (plain) {

@@ -392,8 +392,7 @@ static int payload_columns(struct exec *x, int t, int key_col, int *pc)
  * a range that went stale wider only makes the rule not apply.  MDB_JOIN_ELIMINATION=0: never. */
 static bool join_is_total_by_catalog(struct exec *x, const struct mdb_expr *kl, const struct mdb_expr *kr)
 {
-	const char *knob = mdb_knob("MDB_JOIN_ELIMINATION");
-	if (x->cat->dist || (knob && knob[0] == '0') || !kl || !kr || kl->kind != MDB_EX_FIELD || kr->kind != MDB_EX_FIELD || kl->tbl_idx < 0 || kr->tbl_idx < 0 ||
+	if (x->cat->dist || mdb_knob_off("MDB_JOIN_ELIMINATION") || !kl || !kr || kl->kind != MDB_EX_FIELD || kr->kind != MDB_EX_FIELD || kl->tbl_idx < 0 || kr->tbl_idx < 0 ||
 	    kl->type == MDB_CT_DOUBLE || kr->type == MDB_CT_DOUBLE || kl->type != kr->type || x->orig_tab[kr->tbl_idx])
 		return false;
 	/* (the stream's key may be named through a table that was itself joined this way: its key column is an earlier table's) */
@@ -444,8 +443,9 @@ static int join_with_payload_multi(struct exec *x, int t, const struct mdb_expr 
 	const struct mdb_expr *keys[4];
 	int tabs[4], pcs[4][2], nt = 0, streams = 0;
 	int64_t lo, hi;
-	const char *rowjoin = mdb_knob("MDB_ROWJOIN");	/* ("2": the row-order form for tables of any size - tests) */
-	if ((x->n < ((uint64_t)1 << 24) && !(rowjoin && rowjoin[0] == '2')) || nl || nr || x->orig_tab[t] || kl->kind != MDB_EX_FIELD || kl->tbl_idx < 0 || x->orig_tab[kl->tbl_idx])
+	char rowjoin[2];	/* ("2": the row-order form for tables of any size - tests) */
+	mdb_knob_str("MDB_ROWJOIN", rowjoin, sizeof(rowjoin));
+	if ((x->n < ((uint64_t)1 << 24) && rowjoin[0] != '2') || nl || nr || x->orig_tab[t] || kl->kind != MDB_EX_FIELD || kl->tbl_idx < 0 || x->orig_tab[kl->tbl_idx])
 		return 1;
 	{
 		struct mdb_table *lt = s->tabs[kl->tbl_idx].t;
@@ -1722,7 +1722,7 @@ grouped:
 				 * of the buffer instead of copying it (0.04 ms per 10^7-row column, 0.3 per 10^8) - result columns are read-only, rows
 				 * appended later lie behind the result's, and an UPDATE copies a column that has other holders before it writes */
 				if (!own && !shared && mdb_dev_alloc_size(x.dev, src) >= bytes &&
-				    !(mdb_knob("MDB_RESULT_ALIAS") && mdb_knob("MDB_RESULT_ALIAS")[0] == '0')) {
+				    !mdb_knob_off("MDB_RESULT_ALIAS")) {
 					bool stmt_buf = false;
 					for (int i = 0; i < x.bufs.n; i++)
 						stmt_buf = stmt_buf || x.bufs.p[i] == src;

@@ -236,8 +236,7 @@ int mdb_table_add_column(struct mdb_table *t, const char *name, int type)
 static void mdb_ask_huge_pages(void *p, size_t bytes)
 {
 	const uintptr_t a = ((uintptr_t)p + ((size_t)2 << 20) - 1) & ~(uintptr_t)(((size_t)2 << 20) - 1), e = ((uintptr_t)p + bytes) & ~(uintptr_t)(((size_t)2 << 20) - 1);
-	const char *knob = mdb_knob("MDB_INGEST_THP");
-	if (bytes < ((size_t)8 << 20) || e <= a || (knob && knob[0] == '0'))
+	if (bytes < ((size_t)8 << 20) || e <= a || mdb_knob_off("MDB_INGEST_THP"))
 		return;
 	(void)madvise((void *)a, (size_t)(e - a), MADV_HUGEPAGE);	/* (advice: a kernel without THP says EINVAL, nothing depends on it) */
 }
@@ -447,9 +446,9 @@ int mdb_table_bulk_copy(struct mdb_catalog *cat, struct mdb_table *t, int ncols,
 {
 	*mirrored = false;
 	int nthreads = (int)sysconf(_SC_NPROCESSORS_ONLN);
-	const char *env = mdb_knob("MDB_INGEST_THREADS");
-	if (env && atoi(env) > 0)
-		nthreads = atoi(env);
+	const long long env = mdb_knob_int("MDB_INGEST_THREADS", 0);
+	if (env > 0)
+		nthreads = env < INGEST_MAX_THREADS ? (int)env : INGEST_MAX_THREADS;
 	nthreads = nthreads < 1 ? 1 : nthreads > INGEST_MAX_THREADS ? INGEST_MAX_THREADS : nthreads;
 	/* the device mirror can follow when it is current (the new rows fit or it is rebuilt) - and no column has a NULL bitmap up there */
 	char err[256];

@@ -27,7 +27,7 @@ def load_library():
 
 
 def _follow_environment(lib):
-    """The library reads its MDB_* knobs once per process and keeps them (mdb_knob, mdb_dev_core.hip); tests and same-process A/B scripts flip
+    """The library reads its MDB_* knobs once per process and keeps them (midoridb_amd/csrc/mdb_knob.c); tests and same-process A/B scripts flip
     knobs through os.environ / monkeypatch while the process runs: every change of an MDB_* variable made through Python drops what the
     library has kept (mdb_dev_reload_knobs)."""
     lib.mdb_dev_reload_knobs.restype = None

@@ -1,5 +1,4 @@
-"""mdb_dev_join_group_count_multi at 10^8 unique keys per table (BASELINE configs[4] shape on one GPU): per-kernel times.
-MDB_LD_REM=<bits> sizes the direct-address leaves."""
+"""mdb_dev_join_group_count_multi at 10^8 unique keys per table (BASELINE configs[4] shape on one GPU): per-kernel times."""
 import os
 import sys
 import time

@@ -414,3 +414,57 @@ def test_bulk_ingest_in_chunks_by_several_threads_without_a_device(monkeypatch):
             db.append_columns("T", [rng.integers(0, 9, 3 * n + 7), rng.standard_normal(3 * n + 7)])      # several chunks, ragged tail
             db.append_columns("T", [np.arange(5), np.zeros(5)], nulls=[np.array([0, 1, 0, 0, 1], dtype=np.uint8), None])
             db.append_columns("T", [rng.integers(0, 9, n), rng.standard_normal(n)])                      # behind rows with NULL flags
+
+
+def test_knob_reader_values_reload_and_threads(monkeypatch):
+    """mdb_knob.c, the library's one reader of its MDB_* knobs: values and copies, never a pointer into what it keeps; a change made
+    through os.environ is seen after the reload the binding makes; readers racing reloads finish cleanly (the sanitizer run covers
+    this file)"""
+    import threading
+    lib = _lib()
+    for f, res, args in (("mdb_knob_set", ctypes.c_int, [ctypes.c_char_p]), ("mdb_knob_off", ctypes.c_int, [ctypes.c_char_p]),
+                         ("mdb_knob_int", ctypes.c_longlong, [ctypes.c_char_p, ctypes.c_longlong]),
+                         ("mdb_knob_str", ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t])):
+        getattr(lib, f).restype, getattr(lib, f).argtypes = res, args
+    name = b"MDB_TEST_KNOB_READER"
+
+    def string(cap):
+        buf = ctypes.create_string_buffer(b"\xff" * cap, cap)
+        return lib.mdb_knob_str(name, buf, cap), buf.value
+
+    monkeypatch.delenv(name.decode(), raising=False)
+    assert (lib.mdb_knob_set(name), lib.mdb_knob_off(name), lib.mdb_knob_int(name, 7)) == (0, 0, 7)
+    assert string(8) == (0, b"")
+    monkeypatch.setenv(name.decode(), "042x")
+    assert (lib.mdb_knob_set(name), lib.mdb_knob_off(name), lib.mdb_knob_int(name, 7)) == (1, 1, 42)
+    assert string(16) == (1, b"042x") and string(3) == (1, b"04") and string(1) == (1, b"")
+    monkeypatch.setenv(name.decode(), "2")
+    assert (lib.mdb_knob_set(name), lib.mdb_knob_off(name), lib.mdb_knob_int(name, 7)) == (1, 0, 2)
+    assert string(2) == (1, b"2")
+    monkeypatch.setenv(name.decode(), "")
+    assert (lib.mdb_knob_set(name), lib.mdb_knob_off(name), lib.mdb_knob_int(name, 7)) == (1, 0, 0)
+    monkeypatch.setenv(name.decode(), "0123456789")
+    # the environment stays as it is while the threads run (getenv against a concurrent setenv is not safe in C); one thread drops the
+    # kept values over and over while the others read them back
+    stop, bad = threading.Event(), []
+
+    def reader():
+        for _ in range(20000):
+            if (lib.mdb_knob_off(name), lib.mdb_knob_int(name, -1), string(64)) != (1, 123456789, (1, b"0123456789")):
+                bad.append(1)
+                return
+
+    def reloader():
+        while not stop.is_set():
+            lib.mdb_dev_reload_knobs()
+
+    r = threading.Thread(target=reloader)
+    r.start()
+    readers = [threading.Thread(target=reader) for _ in range(4)]
+    for t in readers:
+        t.start()
+    for t in readers:
+        t.join()
+    stop.set()
+    r.join()
+    assert not bad
