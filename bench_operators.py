@@ -88,7 +88,7 @@ def main():
         # the projection as the executor plans it (mdb_exec.c, projection pass 1): B's join key holds A's value in every joined
         # tuple, so both key columns of SELECT * are ONE gather of A's column through the left row ids (ascending: near-sequential
         # reads); the payload columns are gathered through their own row ids; one launch
-        # ... and when every left row found exactly one partner (mdb_dev_last_pairs_identity: the primary-key join) the left row ids
+        # ... and when every left row found exactly one partner (last_plan()["pairs_identity"]: the primary-key join) the left row ids
         # are 0, 1, 2 ...: A's columns are read as they stand
         lid = None if dev.last_pairs_identity() else l
         dev.gather_cols([(a_id, None, lid), (a_f, None, lid), (b_f, None, r)], j)

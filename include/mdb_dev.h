@@ -65,33 +65,13 @@ int mdb_dev_set_overlap(mdb_dev_ctx *ctx, int on);
  * mode 0: never; 1 (default): when a sample of both key columns fits, tables of 2^20 rows or more; 2: always try
  * (the plain int32 window, no sampling). */
 int mdb_dev_set_narrow_keys(mdb_dev_ctx *ctx, int mode);
-/* 1 when the last completed join / GROUP BY operator of this context ran in the narrow form (for byte accounting) */
-int mdb_dev_last_join_narrow(mdb_dev_ctx *ctx);
 /* Pruning of the left table in the compact narrow form (unsplit calls): the right table is partitioned first.
  * Min-max pruning: its first partition level records the exact range of its keys and the left table's first level drops
  * every row outside (MDB_MINMAX_PRUNE=0 turns it off).  Semi-join filter: when the key sample says that the right table
  * has less than a quarter of the left table's rows without covering a small part of its range, its hashed keys also
  * become a bitmap and the left table's second level drops the rows whose bit is clear (MDB_SEMIJOIN=0 turns it off).
  * Both are exact in effect (a row is only dropped when no right row can have its key): results are identical, only the
- * bytes moved change.
- * -> of the last completed join / GROUP BY operator: bit 8 = min-max pruning ran; low byte = 0 without the bitmap, else 1 +
- * log2(adjacent hashed values per bitmap bit); bit 9 = the tables were partitioned ONCE (key windows of 2^15 ... 2^23
- * values: one 9-bit level, direct-address leaf tables of 2^(k - 9) entries with 16-bit row counts; MDB_ONE_LEVEL=0 turns it
- * off; a key with 2^16 or more rows sends the operator back to two levels; joins with up to 31 right and 15 left rows per key keep 4 bytes
- * per key value in the leaf - two workgroups per CU -, others take the 16-bit counts on the same partitioned tables); bit 10 = several right tables were counted in one
- * pass (mdb_dev_join_group_count_multi did not chain two-table operators); bit 11 = the operator ran without MDB_ORDER_FIRST
- * (any group order); bit 12 = the ordered operator took ONE 4096-digit pass per table (key windows of 2^24 ... 2^27 values, from
- * 2^24 rows in all, at most 2^27 left rows, no min-max pruning to be had: the left table's rows travel as 4-byte words that name
- * their place in a 32 768-row tile, one workgroup joins a digit of up to 2^15 key values; MDB_WIDE12=0 turns it off,
- * MDB_WIDE12_MIN=<rows> moves the threshold; more than 31 right or 15 left rows of one key send the operator back to two levels); bit 13 = the
- * one-level join wrote its group records straight into the ordering kernel's ranges of 2^16 row ids (from the second call over the same columns
- * on, when the remembered group count is small enough) - the ordering kernel is then launched right behind the
- * leaf kernel, before the host has seen the group count, its writes bounded by `cap`: one sync per call. */
-int mdb_dev_last_join_filter(mdb_dev_ctx *ctx);
-/* 1 when the last mdb_dev_join_pairs() matched EVERY left row with exactly one right row (unique right keys, no left row
- * without a partner - the primary-key join of BASELINE configs[1]): out_l is then 0, 1, 2 ... and the left table's columns
- * of the joined stream are its columns as they stand - a caller need not gather them through out_l. */
-int mdb_dev_last_pairs_identity(mdb_dev_ctx *ctx);
+ * bytes moved change.  Which form ran: mdb_dev_last_plan(). */
 
 /* ---- catalog statistics instead of key samples (round 5).  A caller that KNOWS its key columns - query_execute() keeps the smallest /
  * largest value of every column as rows are ingested (csrc/mdb_store.c) - hands that to the operators: between
@@ -119,17 +99,26 @@ struct mdb_dev_col_stats {
 #define MDB_COL_DISTINCT 1ull
 int mdb_dev_call_stats(mdb_dev_ctx *ctx, const void *keys_l, const struct mdb_dev_col_stats *l, const void *keys_r, const struct mdb_dev_col_stats *r);
 
-/* What the last join / GROUP BY operator of this context did (for tests, EXPLAIN-like output and byte accounting) */
+/* What the last join / GROUP BY operator of this context did (for tests, EXPLAIN-like output and byte accounting).  Every operator
+ * call starts from zeros: a field a form does not report stays 0. */
 struct mdb_dev_plan_info {
-	uint32_t key_form;	/* 0: 64-bit hashes; 1: 32-bit hashes of a 2^32-wide window; 2: k-bit hashes of a compact window, direct-address leaves */
+	uint32_t key_form;	/* 0: 64-bit hashes; 1: 32-bit hashes of a 2^32-wide window (the narrow form); 2: k-bit hashes of a compact window,
+				 * direct-address leaves (MDB_DIRECT_LEAF=0 turns it off) */
 	uint32_t key_bits;	/* key_form 2: the window holds 2^key_bits values */
-	uint32_t levels;	/* partition levels of the final attempt (1 or 2) */
-	uint32_t digits;	/* first-level digits: 512, or 4096 (one 4096-digit pass per table) */
+	uint32_t levels;	/* partition levels of the final attempt (1 or 2).  1: key windows of 2^15 ... 2^23 values, one 9-bit level, direct-address
+				 * leaf tables of 2^(k - 9) entries with 16-bit row counts (MDB_ONE_LEVEL=0 turns it off); joins with up to 31 right and
+				 * 15 left rows per key keep 4 bytes per key value in the leaf; a key with 2^16 or more rows sends the operator back to 2 */
+	uint32_t digits;	/* first-level digits: 512, or 4096: the ordered operator took ONE 4096-digit pass per table (key windows of 2^24 ...
+				 * 2^27 values, from 2^24 rows in all, at most 2^27 left rows, no min-max pruning to be had: the left rows travel as
+				 * 4-byte words that name their place in a 32 768-row tile; MDB_WIDE12=0 turns it off, MDB_WIDE12_MIN=<rows> moves
+				 * the threshold; more than 31 right or 15 left rows of one key send the operator back to two levels) */
 	uint32_t minmax_pruned;	/* the left table's first level dropped the rows outside the right table's key range */
 	uint32_t semijoin;	/* 0, or 1 + log2(values per bit of the right table's key bitmap) */
-	uint32_t any_order;	/* ran without row ids and ordering */
-	uint32_t ranged_order;	/* group records written straight into the ordering kernel's ranges */
-	uint32_t multi_one_pass;	/* several right tables counted in one pass */
+	uint32_t any_order;	/* ran without row ids and ordering (no MDB_ORDER_FIRST, no first rows wanted) */
+	uint32_t ranged_order;	/* the one-level join wrote its group records straight into the ordering kernel's ranges of 2^16 row ids (from the
+				 * second call over the same columns on, or by the caller's statistics, when the group count is small enough): the
+				 * ordering kernel runs right behind the leaf kernel, its writes bounded by `cap` - one sync per call */
+	uint32_t multi_one_pass;	/* several right tables counted in one pass (mdb_dev_join_group_count_multi did not chain two-table operators) */
 	uint32_t retries;	/* times the operator was redone (0: the first plan held) */
 	uint32_t samples;	/* key-sample kernels (each with a host synchronisation) the call launched */
 	uint32_t from_stats;	/* 1: windows and ranges came from mdb_dev_call_stats() */
@@ -146,6 +135,9 @@ struct mdb_dev_plan_info {
 				 * caller's statistics (MDB_COL_DISTINCT on both key columns, the right one holding every value of its range) */
 	uint32_t payload_tables;	/* right tables the last payload join served in ONE call: 1 mdb_dev_join_payload, 2 ... mdb_dev_join_payload_multi (the left
 				 * table sorted once, one leaf launch, one placement pass); 0 not served */
+	uint32_t pairs_identity;	/* mdb_dev_join_pairs matched EVERY left row with exactly one right row (unique right keys, no left row without a
+				 * partner - the primary-key join of BASELINE configs[1]): out_l is 0, 1, 2 ... and the left table's columns of the joined
+				 * stream are its columns as they stand - a caller need not gather them through out_l */
 };
 int mdb_dev_last_plan(mdb_dev_ctx *ctx, struct mdb_dev_plan_info *out);
 /* The MDB_* environment knobs are read once per process and kept: a process that changes one while it runs calls this. */
@@ -499,7 +491,7 @@ int mdb_dev_group_count_keys(mdb_dev_ctx *ctx, const int64_t *keys, const uint64
  * With MDB_ORDER_FIRST the groups are in the reference's order (first occurrence in
  * L-major join order).  Without it - and without out_first - the order is unspecified and the operator may
  * skip everything that order costs: no row id travels through the partition levels and no ordering sort runs
- * (10^8 x 10^8 unique keys: 1.2 ms instead of 2.6; bit 11 of mdb_dev_last_join_filter() says this form ran).  *out_groups = G, *out_joined = number of joined rows
+ * (10^8 x 10^8 unique keys: 1.2 ms instead of 2.6; mdb_dev_last_plan().any_order says this form ran).  *out_groups = G, *out_joined = number of joined rows
  * (sum of counts).  Synchronous: G, J and the overflow flags come back before the groups are ordered
  * (the ordering sort is sized by G), completion after it.  Size limit per call: about 7*10^8 left rows
  * (beyond that the tables must be sharded, see mdb_dev_partition_by_dest).

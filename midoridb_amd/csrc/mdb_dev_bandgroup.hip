@@ -488,7 +488,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 {
 	*outside = false;
 	if (comp) {
-		if (comp->nkeys < 1 || comp->nkeys > MDB_BG_COMP_MAX || ctx->explain)
+		if (comp->nkeys < 1 || comp->nkeys > MDB_BG_COMP_MAX || ctx->explaining)
 			return 1;
 		for (int c = 0; c < comp->nkeys; c++)
 			if ((uintptr_t)comp->values[c] & 15u)
@@ -520,14 +520,16 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	const bool dense_ok = !comp && n >= ((uint64_t)1 << 22) && values >= n - n / 16 && !mdb_knob_off("MDB_GROUP_DENSE");
 	if (dense_ok)
 		need += mdb_dense_arena_bytes(n) + mdb_align_up((n / 8 + 4096) * 8);
-	if (ctx->explain) {	/* (mdb_dev_explain_group_count: the band sort serves - nothing is launched; nearly unique keys: a pilot decides) */
-		ctx->explain->group_form = 1;
-		ctx->explain->key_form = 2;
-		ctx->explain->key_bits = kbits;
-		ctx->explain->from_stats = ctx->explain_as_sample ? 0u : ctx->pl_from_stats;
-		ctx->explain->samples = ctx->explain_as_sample ? 1u : 0u;
-		ctx->explain->groups_as_bits = dense_ok ? 1u : 0u;
+	auto served = [&](uint32_t as_bits) {	/* the form that answered, in the plan record */
+		ctx->plan.group_form = 1;
+		ctx->plan.key_form = 2;
+		ctx->plan.key_bits = kbits;
+		ctx->plan.groups_as_bits = as_bits;
 		return MIDORIDB_OK;
+	};
+	if (ctx->explaining) {	/* (mdb_dev_explain_group_count: the band sort serves - nothing is launched; nearly unique keys: a pilot decides) */
+		mdb_explain_sampled(ctx);
+		return served(dense_ok ? 1u : 0u);
 	}
 	int rc = mdb_arena_begin(ctx, need);
 	if (rc)
@@ -644,10 +646,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 					return rc;
 				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 				*out_groups = dgroups;
-				ctx->pl_key_bits = kbits;
-				ctx->pl_group_form = 1;
-				ctx->pl_bits = 1;
-				return MIDORIDB_OK;
+				return served(1);
 			}
 			/* (the exception list overflowed, or the table's flags ask for another path: the record form says which) */
 			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
@@ -685,7 +684,5 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	if (rc)
 		return rc;
 	*out_groups = groups;
-	ctx->pl_key_bits = kbits;
-	ctx->pl_group_form = 1;
-	return MIDORIDB_OK;
+	return served(0);
 }

@@ -102,28 +102,24 @@ struct mdb_dev_ctx : mdb_col_memo {
 	hipStream_t aux_stream;		/* second stream: the two tables of a join are partitioned concurrently */
 	hipEvent_t ev_fork, ev_join;
 	bool overlap;			/* false: everything on the main stream (isolated per-kernel timing) */
-	int last_semijoin;		/* ... and dropped left rows through the right table's key bitmap (0 no; else 1 + log2 values per bit) */
-	int last_narrow;		/* the last join / GROUP BY operator ran in the narrow form */
-	bool last_left_dups_known, last_left_dups;	/* ... through leaf kernels that tell whether a key with partners has several LEFT rows, and whether one has */
-	int last_pairs_identity;	/* the last mdb_dev_join_pairs: every left row joined exactly one right row - its left vector is 0, 1, 2 ... */
+	bool last_left_dups_known, last_left_dups;	/* the last join ran through leaf kernels that tell whether a key with partners has several LEFT rows, and whether one has */
 	int narrow_mode;		/* 32-bit hashes for int32-range join keys: 0 never, 1 sampled + verified (default), 2 always try */
 	int unordered_no_counts;	/* set by mdb_dev_join_keys around its call of the any-order operator: group keys only, no COUNT column */
-	/* the caller's MDB_KEYS_MAY_ALIAS / MDB_COUNTS_OPTIONAL of the current join + GROUP BY call, and what became of them (mdb_dev_last_plan) */
+	/* the caller's MDB_KEYS_MAY_ALIAS / MDB_COUNTS_OPTIONAL of the current join + GROUP BY call (what became of them: plan) */
 	bool key_alias_ok, counts_optional;
-	uint32_t pl_keys_left, pl_counts_one, pl_payload_tables;
 	void *pending_op;		/* state of a begun-but-unfinished split operator (mdb_dev_join.hip) */
 	bool guess_remembered;		/* the last narrow-form decision came from the memo, not from a sample of the data */
 	/* mdb_dev_call_stats(): the caller's statistics of the key columns of the calls that follow */
 	bool cs_on, cs_has_r;
 	const void *cs_kl, *cs_kr;
 	struct mdb_dev_col_stats cs_l, cs_r;
-	/* mdb_dev_last_plan(): what the current / last operator did beyond the last_* words */
-	uint32_t pl_retries, pl_samples, pl_from_stats, pl_key_bits, pl_payload_form, pl_group_form, pl_bits, pl_small_form;
-	int pl_depth;			/* operators that call operators: the outermost one's entry clears the counters (mdb_plan_scope) */
+	/* mdb_dev_last_plan() / mdb_dev_explain_*(): what the current / last operator did - every operator writes its facts here */
+	struct mdb_dev_plan_info plan;
+	int pl_depth;			/* operators that call operators: the outermost one's entry clears the plan (mdb_plan_scope) */
 	/* mdb_dev_counters(): running totals since the context was created (what a slow call paid for) */
 	uint64_t ct_calls, ct_retries, ct_samples, ct_arena_grows, ct_alloc_misses;
 	/* mdb_dev_explain_*(): the operator's own decision code runs and stops in front of its first launch (a context without a device) */
-	struct mdb_dev_plan_info *explain;
+	bool explaining;
 	bool explain_as_sample;		/* ... as if the statistics were what a key sample found: the forms only a catalog's promise opens are not taken */
 	mdb_memo_key memo_key;		/* the key-column pair the live mdb_col_memo belongs to */
 	std::vector<std::pair<mdb_memo_key, mdb_col_memo>> memo_lru;	/* the other pairs' sets, most recently used last */
@@ -158,23 +154,32 @@ extern "C" int mdb_knob_off(const char *name);
 extern "C" long long mdb_knob_int(const char *name, long long dflt);
 extern "C" int mdb_knob_str(const char *name, char *buf, size_t cap);
 
-/* first statement of every public join / GROUP BY operator: what mdb_dev_last_plan() counts starts at the OUTERMOST operator's entry */
+/* first statement of every public join / GROUP BY operator: what mdb_dev_last_plan() reports starts at the OUTERMOST operator's entry */
 struct mdb_plan_scope {
 	mdb_dev_ctx *c;
 	explicit mdb_plan_scope(mdb_dev_ctx *ctx) : c(ctx)
 	{
 		if (c && c->pl_depth++ == 0)
-			c->pl_retries = c->pl_samples = c->pl_from_stats = c->pl_key_bits = c->pl_payload_form = c->pl_group_form = c->pl_bits = c->pl_small_form = c->pl_keys_left = c->pl_counts_one = c->pl_payload_tables = 0;
+			memset(&c->plan, 0, sizeof(c->plan));
 	}
 	~mdb_plan_scope()
 	{
 		if (c && --c->pl_depth == 0) {
 			c->ct_calls++;
-			c->ct_retries += c->pl_retries;
-			c->ct_samples += c->pl_samples;
+			c->ct_retries += c->plan.retries;
+			c->ct_samples += c->plan.samples;
 		}
 	}
 };
+
+/* mdb_dev_explain_* with as_sample: the statistics stand for what a raw caller's first key sample found */
+static inline void mdb_explain_sampled(mdb_dev_ctx *ctx)
+{
+	if (ctx->explain_as_sample) {
+		ctx->plan.from_stats = 0;
+		ctx->plan.samples = 1;
+	}
+}
 
 /* make the live memo the one of the key-column pair (kl, nl, kr, nr) - kr = NULL for a one-column operator (GROUP BY): the set
  * of the pair used before is put aside, the pair's own set (or an empty one) comes back (mdb_dev_core.hip) */

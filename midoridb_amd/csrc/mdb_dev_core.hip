@@ -77,8 +77,6 @@ extern "C" int mdb_dev_ctx_create(int device, void *stream, mdb_dev_ctx **out)
 	ctx->pending_op = NULL;
 	ctx->cache_bytes = 0;
 	ctx->narrow_mode = 1;
-	ctx->last_narrow = 0;
-	ctx->last_semijoin = 0;
 	memo_reset(*ctx);
 	ctx->memo_key = mdb_memo_key{ NULL, NULL, 0, 0 };
 	{
@@ -174,21 +172,6 @@ extern "C" int mdb_dev_set_overlap(mdb_dev_ctx *ctx, int on)
 	return MIDORIDB_OK;
 }
 
-extern "C" int mdb_dev_last_join_narrow(mdb_dev_ctx *ctx)
-{
-	return ctx->last_narrow;
-}
-
-extern "C" int mdb_dev_last_pairs_identity(mdb_dev_ctx *ctx)
-{
-	return ctx ? ctx->last_pairs_identity : 0;
-}
-
-extern "C" int mdb_dev_last_join_filter(mdb_dev_ctx *ctx)
-{
-	return ctx->last_semijoin;
-}
-
 extern "C" int mdb_dev_call_stats(mdb_dev_ctx *ctx, const void *keys_l, const struct mdb_dev_col_stats *l, const void *keys_r, const struct mdb_dev_col_stats *r)
 {
 	if (!ctx)
@@ -215,27 +198,7 @@ extern "C" int mdb_dev_last_plan(mdb_dev_ctx *ctx, struct mdb_dev_plan_info *out
 {
 	if (!ctx || !out)
 		return -MIDORIDB_ERROR;
-	memset(out, 0, sizeof(*out));
-	const int f = ctx->last_semijoin;
-	out->key_form = (uint32_t)ctx->last_narrow;
-	out->key_bits = ctx->last_narrow == 2 ? ctx->pl_key_bits : 0u;
-	out->levels = (f & 0x1200) ? 1u : 2u;
-	out->digits = (f & 0x1000) ? 4096u : 512u;
-	out->minmax_pruned = (f & 0x100) ? 1u : 0u;
-	out->semijoin = (uint32_t)(f & 0xFF);
-	out->any_order = (f & 0x800) ? 1u : 0u;
-	out->ranged_order = (f & 0x2000) ? 1u : 0u;
-	out->multi_one_pass = (f & 0x400) ? 1u : 0u;
-	out->retries = ctx->pl_retries;
-	out->samples = ctx->pl_samples;
-	out->from_stats = ctx->pl_from_stats;
-	out->payload_form = ctx->pl_payload_form;
-	out->group_form = ctx->pl_group_form;
-	out->groups_as_bits = ctx->pl_bits;
-	out->small_form = ctx->pl_small_form;
-	out->keys_are_left_column = ctx->pl_keys_left;
-	out->counts_all_one = ctx->pl_counts_one;
-	out->payload_tables = ctx->pl_payload_tables;
+	*out = ctx->plan;
 	return MIDORIDB_OK;
 }
 

@@ -191,7 +191,7 @@ __global__ void k_group_direct_counts(int64_t *out_count, uint64_t G, const unsi
 int mdb_group_count_direct_comp(mdb_dev_ctx *ctx, const struct mdb_bg_comp *comp, uint64_t n, uint32_t bits, uint32_t *out_first, int64_t *out_count,
 				uint64_t cap, uint64_t *out_groups)
 {
-	if (bits > 14u || n < GD_MIN_ROWS || n >= 0xFFFFFFFFull || comp->nkeys < 1 || comp->nkeys > MDB_BG_COMP_MAX || ctx->explain)
+	if (bits > 14u || n < GD_MIN_ROWS || n >= 0xFFFFFFFFull || comp->nkeys < 1 || comp->nkeys > MDB_BG_COMP_MAX || ctx->explaining)
 		return 1;
 	for (int c = 0; c < comp->nkeys; c++)
 		if ((uintptr_t)comp->values[c] & 15u)
@@ -258,7 +258,7 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 			    const uint64_t *null_r, uint64_t n_r, bool null_group, int64_t *out_key, uint32_t *out_first, int64_t *out_count,
 			    uint64_t cap, uint64_t *out_groups, uint64_t *out_joined)
 {
-	if (n + (keys_r ? n_r : 0) < GD_MIN_ROWS || n >= 0xFFFFFFFFull || ((uintptr_t)keys & 15) || ((!out_first || !out_count) && !ctx->explain))
+	if (n + (keys_r ? n_r : 0) < GD_MIN_ROWS || n >= 0xFFFFFFFFull || ((uintptr_t)keys & 15) || ((!out_first || !out_count) && !ctx->explaining))
 		return 1;
 	if (keys_r && (n_r >= 0xFFFFFFFFull || ((uintptr_t)keys_r & 15) || n_r == 0))
 		return 1;
@@ -284,9 +284,8 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	const size_t order_bytes = mdb_order_records_arena_bytes(GD_TABLE_MAX + 1, n, &kbits);
 	if (!order_bytes)
 		return 1;
-	if (ctx->explain) {	/* (mdb_dev_explain_*: per-workgroup LDS tables over a window of at most 4096 values - nothing is launched) */
-		ctx->explain->small_form = 2;
-		ctx->explain->from_stats = ctx->pl_from_stats;
+	if (ctx->explaining) {	/* (mdb_dev_explain_*: per-workgroup LDS tables over a window of at most 4096 values - nothing is launched) */
+		ctx->plan.small_form = 2;	/* (from_stats as the run reports it: as_sample does not apply to this form's plan - tests/golden/plans.json) */
 		return MIDORIDB_OK;
 	}
 	rc = mdb_arena_begin(ctx, order_bytes + 6 * mdb_align_up((GD_TABLE_MAX + 1) * 8) + 8192);
@@ -344,6 +343,7 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 		ctx->sr_valid = 0;	/* the sample missed a value outside its range: not to be reused */
 	if (h32[0] & 1024u)
 		return 1;	/* a value outside the window: the partitioned path */
+	ctx->plan.small_form = 2;
 	const uint64_t G = h32[1];
 	const uint64_t joined = (uint64_t)h32[2] | ((uint64_t)h32[3] << 32);
 	if (G > cap)

@@ -1472,8 +1472,8 @@ static int gc_begin(mdb_dev_ctx *ctx, gc_state *st)
 	}
 	if (st->wide12 && st->nextra <= 1)	/* (the groups as one bit per left row + exceptions, mdb_dev_dense.hip) */
 		need += mdb_dense_arena_bytes(st->n_l) + mdb_align_up((st->n_l / 8 + 4096) * 8);
-	if (ctx->explain) {	/* (mdb_dev_explain_*: the plan is made - no arena, no launch) */
-		ctx->explain->arena_mib = (uint32_t)((need + (1u << 20) - 1) >> 20);
+	if (ctx->explaining) {	/* (mdb_dev_explain_*: the plan is made - no arena, no launch) */
+		ctx->plan.arena_mib = (uint32_t)((need + (1u << 20) - 1) >> 20);
 		return GC_EXPLAINED;
 	}
 	int rc = mdb_arena_begin(ctx, need);
@@ -1538,22 +1538,43 @@ static bool gc_bits_possible(const gc_state *st, bool records, bool has_r, uint6
 	       !mdb_knob_off("MDB_JOIN_BITS");
 }
 
-/* mdb_dev_explain_join_group_count: the plan gc_begin has just made, as mdb_dev_last_plan would report it after the run */
-static void gc_explain_fill(mdb_dev_ctx *ctx, const gc_state *st, const int64_t *keys_r, uint64_t n_r, uint64_t cap)
+/* the shape of the plan gc_begin made, in the plan record: written at the end of gc_finish and by gc_explain_fill */
+static void gc_plan_note(mdb_dev_ctx *ctx, const gc_state *st)
 {
-	struct mdb_dev_plan_info *o = ctx->explain;
-	uint32_t kbits = 0, rg_n = 0;
-	int sb1 = 0, sb2 = 0;
-	const bool records = st->want_records && order_bits(st->n_l, &kbits, &sb1, &sb2);
-	o->key_form = st->narrow ? (st->key_bits ? 2u : 1u) : 0u;
-	o->key_bits = st->narrow ? st->key_bits : 0u;
+	struct mdb_dev_plan_info *o = &ctx->plan;
+	o->key_form = st->direct ? 2u : (st->narrow ? 1u : 0u);
+	o->key_bits = st->direct ? st->key_bits : 0u;
 	o->levels = (st->one_level || st->wide12) ? 1u : 2u;
 	o->digits = st->wide12 ? 4096u : 512u;
 	o->minmax_pruned = (st->defer_l || st->defer_l64) ? 1u : 0u;
 	o->semijoin = st->semijoin;
 	o->multi_one_pass = st->nextra ? 1u : 0u;
-	o->from_stats = ctx->explain_as_sample ? 0u : ctx->pl_from_stats;
-	o->samples = ctx->explain_as_sample ? 1u : 0u;
+}
+
+/* ... and of the forms gc_begin does not plan (the single-workgroup and the any-order operators): every shape field, so that none is left over from an operator these follow */
+static void gc_plan_shape(mdb_dev_ctx *ctx, uint32_t key_form, uint32_t levels, uint32_t minmax_pruned, uint32_t any_order)
+{
+	struct mdb_dev_plan_info *o = &ctx->plan;
+	o->key_form = key_form;
+	o->key_bits = 0;
+	o->levels = levels;
+	o->digits = 512;
+	o->minmax_pruned = minmax_pruned;
+	o->semijoin = 0;
+	o->any_order = any_order;
+	o->ranged_order = 0;
+	o->multi_one_pass = 0;
+}
+
+/* mdb_dev_explain_join_group_count: the plan gc_begin has just made, as mdb_dev_last_plan would report it after the run */
+static void gc_explain_fill(mdb_dev_ctx *ctx, const gc_state *st, const int64_t *keys_r, uint64_t n_r, uint64_t cap)
+{
+	struct mdb_dev_plan_info *o = &ctx->plan;
+	uint32_t kbits = 0, rg_n = 0;
+	int sb1 = 0, sb2 = 0;
+	const bool records = st->want_records && order_bits(st->n_l, &kbits, &sb1, &sb2);
+	gc_plan_note(ctx, st);
+	mdb_explain_sampled(ctx);
 	const bool w16 = st->one_level && st->has_r && !mdb_knob_off("MDB_WORDS16");
 	const bool leaf4 = st->one_level && st->has_r && w16 && records && !st->null_group && st->n_l <= (1ull << 27) && st->key_bits >= (uint32_t)st->b1 + 10u;
 	o->ranged_order = leaf4 && gc_ranged_by_stats(ctx, st->keys_l, keys_r, st->n_l, n_r, kbits, &rg_n) ? 1u : 0u;
@@ -1890,7 +1911,7 @@ static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const int64_t *keys_r, cons
 			a.dn_exc = (unsigned long long *)mdb_arena_take(ctx, (size_t)a.dn_exc_cap * 8);
 			if (!a.dn_exc)
 				return -MIDORIDB_INTERNAL;
-			ctx->pl_bits = by_stats ? 3u : by_pilot ? 1u : 2u;
+			ctx->plan.groups_as_bits = by_stats ? 3u : by_pilot ? 1u : 2u;
 		}
 	}
 	{
@@ -2117,7 +2138,7 @@ static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const int64_t *keys_r, cons
 					(unsigned long long)G, dn_cleared, (unsigned long long)n_l, dn_exceptions, status);
 			if ((status & 131072u) || (uint64_t)G + dn_cleared != n_l) {	/* (more groups of COUNT != 1 than last time: the record form) */
 				ctx->dn_distrust = 32;
-				ctx->pl_bits = 0;
+				ctx->plan.groups_as_bits = 0;
 				return GC_RETRY_NODENSE;
 			}
 			/* every left row a group: the group keys ARE the left key column, in its order - a caller that said so (MDB_KEYS_MAY_ALIAS) reads
@@ -2125,8 +2146,8 @@ static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const int64_t *keys_r, cons
 			 * column either (mdb_dev_last_plan says which) */
 			const bool alias = ctx->key_alias_ok && !st->keys32 && out_key && G == n_l;
 			const bool ones = ctx->counts_optional && dn_exceptions == 0;
-			ctx->pl_keys_left = alias ? 1u : 0u;
-			ctx->pl_counts_one = ones ? 1u : 0u;
+			ctx->plan.keys_are_left_column = alias ? 1u : 0u;
+			ctx->plan.counts_all_one = ones ? 1u : 0u;
 			rc = mdb_dense_emit(ctx, dn_bits, n_l, a.dn_exc, dn_exceptions, out_first, ones ? NULL : out_count, keys_l, st->keys32, alias ? NULL : out_key);
 			if (!rc)
 				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2177,11 +2198,11 @@ static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const int64_t *keys_r, cons
 		ctx->lg_joined = joined;
 		ctx->lg_valid = true;
 	}
-	ctx->last_narrow = st->direct ? 2 : (st->narrow ? 1 : 0);
 	ctx->last_left_dups_known = st->direct && has_r && !(status & 64u);	/* (the hot-key kernels and the hashed leaves do not say) */
 	ctx->last_left_dups = (status & GC_ST_LEFT_DUPS) != 0;
-	ctx->last_semijoin = (int)st->semijoin | ((st->defer_l || st->defer_l64) ? 0x100 : 0) | (st->one_level ? 0x200 : 0) | (st->nextra ? 0x400 : 0) |
-			     (st->wide12 ? 0x1000 : 0) | (ranged ? 0x2000 : 0);
+	gc_plan_note(ctx, st);
+	ctx->plan.any_order = 0;
+	ctx->plan.ranged_order = ranged ? 1u : 0u;
 	return MIDORIDB_OK;
 }
 
@@ -2315,7 +2336,7 @@ int gc_sample_range(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 		ctx->sr_hi = *hi;
 		ctx->sr_valid = 1;
 		ctx->sr_uses = 0;
-		ctx->pl_from_stats = 1;
+		ctx->plan.from_stats = 1;
 		return MIDORIDB_OK;
 	}
 	if (!fresh && ctx->sr_valid && ctx->sr_kl == keys_l && ctx->sr_nl == n_l && ctx->sr_kr == keys_r && ctx->sr_nr == n_r &&
@@ -2331,7 +2352,7 @@ int gc_sample_range(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 		h[i + 1] = INT64_MIN;
 	}
 	MDB_HIP(ctx, hipMemcpyAsync(mm, h, 48, hipMemcpyHostToDevice, ctx->stream));
-	ctx->pl_samples++;
+	ctx->plan.samples++;
 	if (keys32) {
 		MDB_LAUNCH(ctx, "key_sample", k_key_sample<int32_t>, GC_NARROW_SAMPLE / 256, 256, reinterpret_cast<const int32_t *>(keys_l), null_l, n_l,
 			   reinterpret_cast<const int32_t *>(keys_r), null_r, n_r, mm);
@@ -2607,8 +2628,7 @@ static int group_count_common(mdb_dev_ctx *ctx, const int64_t *keys_l, const uin
 		win.fast1 = false;
 	}
 	for (int attempt = 0; attempt < 6; attempt++) {
-		ctx->pl_retries = (uint32_t)attempt;
-		ctx->pl_key_bits = narrow ? win.kbits : 0u;
+		ctx->plan.retries = (uint32_t)attempt;
 		rc = group_count_run(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, has_r, null_group, fast, records, no_build_r, narrow,
 				     base, win, keys32, out_key, out_count, out_first, cap, out_groups, out_joined);
 		if ((rc == GC_RETRY_PLAIN || rc == GC_RETRY_WIDE) && ctx->guess_remembered && ctx->narrow_mode == 1 && !keys32) {
@@ -2779,13 +2799,11 @@ int tiny_group_count(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nu
 			    const uint64_t *null_r, uint64_t n_r, bool has_r, bool null_group, int64_t *out_key, int64_t *out_count,
 			    uint32_t *out_first, uint64_t cap, uint64_t *out_groups, uint64_t *out_joined)
 {
-	if (n_l == 0 || n_l > TINY_ROWS || (has_r && (n_r == 0 || n_r > TINY_ROWS)) || (!out_count && !ctx->explain))
+	if (n_l == 0 || n_l > TINY_ROWS || (has_r && (n_r == 0 || n_r > TINY_ROWS)) || (!out_count && !ctx->explaining))
 		return 1;
-	if (ctx->explain) {
-		ctx->explain->small_form = 1;
+	ctx->plan.small_form = 1;
+	if (ctx->explaining)
 		return MIDORIDB_OK;
-	}
-	ctx->pl_small_form = 1;
 	tiny_args a;
 	memset(&a, 0, sizeof(a));
 	a.keys_l = keys_l;
@@ -2814,8 +2832,7 @@ int tiny_group_count(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nu
 	*out_groups = h[1];
 	if (out_joined)
 		*out_joined = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
-	ctx->last_narrow = 0;
-	ctx->last_semijoin = 0;
+	gc_plan_shape(ctx, 0, 2, 0, 0);
 	return 0;
 }
 
@@ -2894,8 +2911,7 @@ again: {
 	*out_groups = h[1];
 	if (out_joined)
 		*out_joined = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
-	ctx->last_narrow = 2;
-	ctx->last_semijoin = 0x100 | 0x800 | (plan.b2 ? 0 : 0x200);
+	gc_plan_shape(ctx, 2, plan.b2 ? 2 : 1, 1, 1);
 	return 0;
 }
 
@@ -3153,7 +3169,7 @@ extern "C" int mdb_dev_join_group_count_multi(mdb_dev_ctx *ctx, const int64_t *k
 						 out_joined, n_right - 1, keys_r + 1, null_r ? null_r + 1 : NULL, n_r + 1);
 		if (urc <= 0) {
 			if (urc == 0)
-				ctx->last_semijoin |= 0x400;
+				ctx->plan.multi_one_pass = 1;
 			return urc;
 		}
 		*out_groups = 0;
@@ -3177,11 +3193,9 @@ extern "C" int mdb_dev_join_group_count_multi(mdb_dev_ctx *ctx, const int64_t *k
 	}
 	if (rc != GC_NOT_SERVED)
 		return rc;
-	if (ctx->explain) {	/* (mdb_dev_explain_*: the chain of two-table operators - its first step's plan, multi_one_pass 0) */
+	if (ctx->explaining) {	/* (mdb_dev_explain_*: the chain of two-table operators - its first step's plan, multi_one_pass 0) */
 		uint64_t g0 = 0, j0 = 0;
-		rc = mdb_dev_join_group_count(ctx, keys_l, null_l, n_l, keys_r[0], null_r ? null_r[0] : NULL, n_r[0], flags, NULL, NULL, NULL, n_l ? n_l : 1, &g0, &j0);
-		ctx->explain->multi_one_pass = 0;
-		return rc;
+		return mdb_dev_join_group_count(ctx, keys_l, null_l, n_l, keys_r[0], null_r ? null_r[0] : NULL, n_r[0], flags, NULL, NULL, NULL, n_l ? n_l : 1, &g0, &j0);
 	}
 	/* ---- the chain: groups of (L, R0), then (those group keys, R1) ..., counts multiplied */
 	*out_groups = 0;
@@ -3298,17 +3312,14 @@ extern "C" int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const 
 	 * 12 bytes per row.  (The one form that TRUSTS a statistic: verifying it is the scan that measured it.) */
 	if (ctx->cs_on && !ctx->explain_as_sample && ctx->cs_kl == keys && !ctx->cs_has_r && (ctx->cs_l.flags & MDB_COL_DISTINCT) && !nullbits && n && n <= cap &&
 	    n < 0xFFFFFFFFull && !mdb_knob_off("MDB_GROUP_IDENTITY")) {
-		if (ctx->explain) {
-			ctx->explain->group_form = 3;
-			ctx->explain->from_stats = 1;
-			return MIDORIDB_OK;
+		if (!ctx->explaining) {
+			int rc = mdb_group_identity(ctx, n, out_first, out_count);
+			if (rc)
+				return rc;
+			*out_groups = n;
 		}
-		int rc = mdb_group_identity(ctx, n, out_first, out_count);
-		if (rc)
-			return rc;
-		ctx->pl_from_stats = 1;
-		ctx->pl_group_form = 3;
-		*out_groups = n;
+		ctx->plan.from_stats = 1;
+		ctx->plan.group_form = 3;
 		return MIDORIDB_OK;
 	}
 	mdb_memo_switch(ctx, keys, n, NULL, 0);
@@ -3337,7 +3348,7 @@ extern "C" int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const 
 			uint32_t kb = 0;
 			int64_t wlo = 0;
 			if (lo <= hi)
-				gc_compact_window(lo, hi, &kb, &wlo, ctx->pl_from_stats != 0);
+				gc_compact_window(lo, hi, &kb, &wlo, ctx->plan.from_stats != 0);
 			if (!kb)
 				break;
 			bool outside = false;
@@ -3365,13 +3376,13 @@ extern "C" int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const 
 /* ------------------------------------------------------------------ plans as data (include/mdb_dev.h: mdb_dev_explain_*)
  *
  * A context without a device - only what the decision code reads (CU count, key-form mode, an empty memo) - gets the caller's statistics
- * under two made-up column addresses, ctx->explain points at the answer, and the operator's ENTRY POINT is called: every path it takes
- * stops where it would launch (tiny_group_count, group_direct_try, group_count_run behind gc_begin). */
+ * under two made-up column addresses, ctx->explaining is set, and the operator's ENTRY POINT is called: every path it takes stops where
+ * it would launch (tiny_group_count, group_direct_try, group_count_run behind gc_begin).  The plan record it leaves is the answer. */
 #define EXPLAIN_KL ((const int64_t *)0x1000)
 #define EXPLAIN_KR ((const int64_t *)0x2000)
 #define EXPLAIN_KX ((const int64_t *)0x3000)
 
-static mdb_dev_ctx *explain_ctx(const struct mdb_dev_explain_request *rq, struct mdb_dev_plan_info *out, bool has_r)
+static mdb_dev_ctx *explain_ctx(const struct mdb_dev_explain_request *rq, bool has_r)
 {
 	mdb_dev_ctx *ctx = new (std::nothrow) mdb_dev_ctx();
 	if (!ctx)
@@ -3382,8 +3393,7 @@ static mdb_dev_ctx *explain_ctx(const struct mdb_dev_explain_request *rq, struct
 	ctx->num_cus = rq->num_cus ? (int)rq->num_cus : 256;
 	ctx->narrow_mode = 1;
 	ctx->err[0] = 0;
-	memset(out, 0, sizeof(*out));
-	ctx->explain = out;
+	ctx->explaining = true;
 	ctx->explain_as_sample = rq->as_sample != 0;
 	ctx->cs_on = true;
 	ctx->cs_kl = EXPLAIN_KL;
@@ -3400,7 +3410,7 @@ extern "C" int mdb_dev_explain_join_group_count(const struct mdb_dev_explain_req
 {
 	if (!rq || !out || rq->further_tables > 2)
 		return -MIDORIDB_ERROR;
-	mdb_dev_ctx *ctx = explain_ctx(rq, out, true);
+	mdb_dev_ctx *ctx = explain_ctx(rq, true);
 	if (!ctx)
 		return -MIDORIDB_NOMEM;
 	const uint64_t n_l = rq->left.rows, n_r = rq->right.rows;
@@ -3418,6 +3428,7 @@ extern "C" int mdb_dev_explain_join_group_count(const struct mdb_dev_explain_req
 	}
 	if (rc && mdb_knob_set("MDB_DEBUG_EXPLAIN"))
 		fprintf(stderr, "mdb_dev_explain_join_group_count: %d (%s)\n", rc, ctx->err);
+	*out = ctx->plan;
 	delete ctx;
 	return rc;
 }
@@ -3426,7 +3437,7 @@ extern "C" int mdb_dev_explain_join_payload(const struct mdb_dev_explain_request
 {
 	if (!rq || !out || cells < 1 || cells > 2)
 		return -MIDORIDB_ERROR;
-	mdb_dev_ctx *ctx = explain_ctx(rq, out, true);
+	mdb_dev_ctx *ctx = explain_ctx(rq, true);
 	if (!ctx)
 		return -MIDORIDB_NOMEM;
 	const void *pay[2] = { (const void *)0x5000, (const void *)0x6000 };
@@ -3448,6 +3459,7 @@ extern "C" int mdb_dev_explain_join_payload(const struct mdb_dev_explain_request
 		int mrc = rq->left_nulls_bitmap ? 1 : mdb_dev_join_payload_multi(ctx, EXPLAIN_KL, NULL, rq->left.rows, rt, (int)nrt, lo, hi);
 		if (mrc == 1)
 			mrc = MIDORIDB_OK;	/* (not served: payload_form 0 - the caller joins table by table) */
+		*out = ctx->plan;
 		delete ctx;
 		return mrc;
 	}
@@ -3455,6 +3467,7 @@ extern "C" int mdb_dev_explain_join_payload(const struct mdb_dev_explain_request
 				      cells, dst);
 	if (rc == 1)
 		rc = MIDORIDB_OK;	/* (not served: payload_form 0 - mdb_dev_join_pairs and a gather answer) */
+	*out = ctx->plan;
 	delete ctx;
 	return rc;
 }
@@ -3463,12 +3476,13 @@ extern "C" int mdb_dev_explain_group_count(const struct mdb_dev_explain_request 
 {
 	if (!rq || !out)
 		return -MIDORIDB_ERROR;
-	mdb_dev_ctx *ctx = explain_ctx(rq, out, false);
+	mdb_dev_ctx *ctx = explain_ctx(rq, false);
 	if (!ctx)
 		return -MIDORIDB_NOMEM;
 	uint64_t groups = 0;
 	const int rc = mdb_dev_group_count(ctx, EXPLAIN_KL, rq->left_nulls_bitmap ? (const uint64_t *)0x4000 : NULL, rq->left.rows, MDB_ORDER_FIRST, NULL, NULL,
 					   rq->left.rows, &groups);
+	*out = ctx->plan;
 	delete ctx;
 	return rc;
 }

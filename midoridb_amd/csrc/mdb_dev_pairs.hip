@@ -1055,17 +1055,19 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	for (int c = 0; c < npay; c++)
 		if (!pay_in[c] || !out[c])
 			return -MIDORIDB_ERROR;
-	auto explained = [&](uint32_t form, uint32_t kbits, uint32_t levels, size_t arena) {	/* (mdb_dev_explain_join_payload: nothing is launched) */
-		ctx->explain->payload_form = form;
-		ctx->explain->payload_tables = form ? 1u : 0u;
-		ctx->explain->key_form = 2;
-		ctx->explain->key_bits = kbits;
-		ctx->explain->levels = levels;
-		ctx->explain->digits = 512;
-		ctx->explain->from_stats = ctx->explain_as_sample ? 0u : ctx->pl_from_stats;
-		ctx->explain->samples = ctx->explain_as_sample ? 1u : 0u;
-		ctx->explain->arena_mib = (uint32_t)((arena + (1u << 20) - 1) >> 20);
+	auto served = [&](uint32_t form, uint32_t kbits, uint32_t levels) {	/* the form that answered, in the plan record */
+		ctx->plan.payload_form = form;
+		ctx->plan.payload_tables = 1;
+		ctx->plan.key_form = 2;
+		ctx->plan.key_bits = kbits;
+		ctx->plan.levels = levels;
+		ctx->plan.digits = 512;
 		return MIDORIDB_OK;
+	};
+	auto explained = [&](uint32_t form, uint32_t kbits, uint32_t levels, size_t arena) {	/* (mdb_dev_explain_join_payload: nothing is launched) */
+		mdb_explain_sampled(ctx);
+		ctx->plan.arena_mib = (uint32_t)((arena + (1u << 20) - 1) >> 20);
+		return served(form, kbits, levels);
 	};
 	if (n_l == 0 || n_r == 0 || n_l >= 0xFFFFFFFFull || n_r >= 0xFFFFFFFFull || n_l + n_r < (1ull << 20) || ld_disabled() ||
 	    mdb_knob_off("MDB_JOIN_PAYLOAD"))
@@ -1089,7 +1091,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	 * row (mdb_dev_rowjoin.hip): windows of up to 2^27 values, NULL-free 16-byte-aligned columns */
 	if (mdb_rowjoin_serves(n_l, n_r, win.kbits, keys_l, null_l, keys_r, null_r, pay_in, out, npay)) {
 		const uint32_t kbits = win.kbits;
-		if (ctx->explain)
+		if (ctx->explaining)
 			return explained(3, kbits, 1, mdb_rowjoin_arena_bytes(n_l, n_r, kbits, npay) + 8192);
 		rc = mdb_arena_begin(ctx, mdb_rowjoin_arena_bytes(n_l, n_r, kbits, npay) + 8192);
 		if (rc)
@@ -1106,11 +1108,8 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 			fprintf(stderr, "join_payload (row order): k %u status %u J %llu of %llu left rows\n", kbits, status, (unsigned long long)J,
 				(unsigned long long)n_l);
-		if (status == 0 && J == (uint64_t)npay * n_l) {
-			ctx->pl_payload_form = 3;
-			ctx->pl_payload_tables = 1;
-			return MIDORIDB_OK;
-		}
+		if (status == 0 && J == (uint64_t)npay * n_l)
+			return served(3, kbits, 1);
 		if ((status & 128u) && remembered && attempt == 0) {
 			ctx->nh_result = -1;
 			ctx->sr_valid = 0;
@@ -1137,7 +1136,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		const uint32_t rem = kbits - (uint32_t)(b1 + b2);
 		if (b2 < 1 || b2 > MDB_MAX_RADIX_BITS || n_l >= 0xF0000000ull || n_r >= 0xF0000000ull)
 			return 1;
-		if (ctx->explain)
+		if (ctx->explaining)
 			return explained(2, kbits, 2, mdb_partition_arena_bytes(n_l, b1, b2, false, true) + mdb_partition_arena_bytes(n_r, b1, b2, false, true, npay) + 8192);
 		rc = mdb_arena_begin(ctx, mdb_partition_arena_bytes(n_l, b1, b2, false, true) + mdb_partition_arena_bytes(n_r, b1, b2, false, true, npay) + 8192);
 		if (rc)
@@ -1191,11 +1190,8 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 			fprintf(stderr, "join_payload (two levels): k %u b2 %d rem %u status %u J %llu of %llu left rows\n", kbits, b2, rem, status, (unsigned long long)J,
 				(unsigned long long)n_l);
-		if (status == 0 && J == n_l) {
-			ctx->pl_payload_form = 2;
-			ctx->pl_payload_tables = 1;
-			return MIDORIDB_OK;
-		}
+		if (status == 0 && J == n_l)
+			return served(2, kbits, 2);
 		if ((status & 128u) && remembered && attempt == 0) {
 			ctx->nh_result = -1;
 			ctx->sr_valid = 0;
@@ -1216,7 +1212,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	const int b1 = 9;
 	/* (a dimension table of a few thousand keys: the window may be wider than its keys need) */
 	const uint32_t kbits = win.kbits < 9u + PW_MIN_REM ? 9u + PW_MIN_REM : win.kbits, rem = kbits - (uint32_t)b1, shift = 32u - kbits;
-	if (ctx->explain)
+	if (ctx->explaining)
 		return explained(1, kbits, 1, mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1, false, npay) + 8192);
 	rc = mdb_arena_begin(ctx, mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1, false, npay) + 8192);
 	if (rc)
@@ -1282,11 +1278,8 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	const uint32_t status = (uint32_t)h[1];
 	const uint64_t J = h[2];
-	if (status == 0 && J == n_l) {
-		ctx->pl_payload_form = 1;
-		ctx->pl_payload_tables = 1;
-		return MIDORIDB_OK;
-	}
+	if (status == 0 && J == n_l)
+		return served(1, kbits, 1);
 	if ((status & 128u) && remembered && attempt == 0) {
 		/* a REMEMBERED window proved wrong: the buffers hold other data than when it was learned (a caller's allocator handed the
 		 * same addresses out again) - forget, look at the data itself, once more */
@@ -1354,16 +1347,19 @@ extern "C" int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_
 		}
 	}
 	const size_t arena = mdb_rowjoin_arena_bytes_multi(n_l, rt, nright, kbits) + 8192;
-	if (ctx->explain) {
-		ctx->explain->payload_form = 3;
-		ctx->explain->payload_tables = (uint32_t)nright;
-		ctx->explain->key_form = 2;
-		ctx->explain->key_bits = kbits;
-		ctx->explain->levels = 1;
-		ctx->explain->digits = 1u << mdb_rowjoin_dbits(kbits);
-		ctx->explain->from_stats = 1;
-		ctx->explain->arena_mib = (uint32_t)((arena + (1u << 20) - 1) >> 20);
+	auto served = [&]() {	/* the form that answered, in the plan record (the window: the caller's key range) */
+		ctx->plan.payload_form = 3;
+		ctx->plan.payload_tables = (uint32_t)nright;
+		ctx->plan.key_form = 2;
+		ctx->plan.key_bits = kbits;
+		ctx->plan.levels = 1;
+		ctx->plan.digits = 1u << mdb_rowjoin_dbits(kbits);
+		ctx->plan.from_stats = 1;
 		return MIDORIDB_OK;
+	};
+	if (ctx->explaining) {
+		ctx->plan.arena_mib = (uint32_t)((arena + (1u << 20) - 1) >> 20);
+		return served();
 	}
 	int rc = mdb_arena_begin(ctx, arena);
 	if (rc)
@@ -1380,13 +1376,8 @@ extern "C" int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_
 	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 		fprintf(stderr, "join_payload_multi (row order): %d tables, %d columns, k %u status %u J %llu of %llu x %d\n", nright, streams, kbits, status,
 			(unsigned long long)J, (unsigned long long)n_l, streams);
-	if (status == 0 && J == (uint64_t)streams * n_l) {
-		ctx->pl_payload_form = 3;
-		ctx->pl_payload_tables = (uint32_t)nright;
-		ctx->pl_key_bits = kbits;
-		ctx->pl_from_stats = 1;
-		return MIDORIDB_OK;
-	}
+	if (status == 0 && J == (uint64_t)streams * n_l)
+		return served();
 	return 1;
 }
 
@@ -1628,7 +1619,6 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	mdb_plan_scope plan_scope(ctx);
 	*out_l = *out_r = NULL;
 	*out_count = 0;
-	ctx->last_pairs_identity = 0;
 	if (n_l == 0 || n_r == 0)
 		return MIDORIDB_OK;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
@@ -1677,7 +1667,7 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 			*out_r = ur;
 			*out_count = uj;
 			/* (unique right keys: a left row has at most one partner; as many pairs as left rows, in left-row order: 0, 1, 2 ...) */
-			ctx->last_pairs_identity = right_unique && uj == n_l;
+			ctx->plan.pairs_identity = right_unique && uj == n_l;
 			return MIDORIDB_OK;
 		}
 		/* duplicates on both sides, or a table / region overflowed: general path below */
@@ -1885,7 +1875,7 @@ extern "C" int mdb_dev_join_keys_ordered(mdb_dev_ctx *ctx, const int64_t *keys_l
 					  n_l, &G, &J);
 	ctx->key_alias_ok = was_a;
 	ctx->counts_optional = was_o;
-	const bool keys_left = !rc && ctx->pl_keys_left != 0, counts_one = !rc && ctx->pl_counts_one != 0;
+	const bool keys_left = !rc && ctx->plan.keys_are_left_column != 0, counts_one = !rc && ctx->plan.counts_all_one != 0;
 	if (keys_left && J == G) {
 		(void)mdb_dev_free(ctx, gk);
 		(void)mdb_dev_free(ctx, gc);

@@ -1106,13 +1106,16 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 	int sb1 = 0, sb2 = 0;
 	if (!order_bits(n, &row_bits, &sb1, &sb2))
 		return 1;
-	if (ctx->explain) {	/* (mdb_dev_explain_group_count: the tile sort serves - nothing is launched) */
-		ctx->explain->group_form = 2;
-		ctx->explain->key_form = 2;
-		ctx->explain->key_bits = kbits;
-		ctx->explain->from_stats = ctx->explain_as_sample ? 0u : ctx->pl_from_stats;
-		ctx->explain->samples = ctx->explain_as_sample ? 1u : 0u;
+	auto served = [&](uint32_t as_bits) {	/* the form that answered, in the plan record */
+		ctx->plan.group_form = 2;
+		ctx->plan.key_form = 2;
+		ctx->plan.key_bits = kbits;
+		ctx->plan.groups_as_bits = as_bits;
 		return MIDORIDB_OK;
+	};
+	if (ctx->explaining) {	/* (mdb_dev_explain_group_count: the tile sort serves - nothing is launched) */
+		mdb_explain_sampled(ctx);
+		return served(0);
 	}
 	const uint32_t ntiles = (uint32_t)rj_tiles(n);
 	const size_t ostride = (size_t)D + 8u;
@@ -1222,10 +1225,7 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 					return rc;
 				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 				*out_groups = groups;
-				ctx->pl_key_bits = kbits;
-				ctx->pl_group_form = 2;
-				ctx->pl_bits = 1;
-				return MIDORIDB_OK;
+				return served(1);
 			}
 			/* (the exception list overflowed - the pilot's digits were not typical: the record form below) */
 			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 8 * sizeof(uint32_t), ctx->stream));
@@ -1294,9 +1294,7 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 		if (rc)
 			return rc;
 		*out_groups = groups;
-		ctx->pl_key_bits = kbits;
-		ctx->pl_group_form = 2;
-		return MIDORIDB_OK;
+		return served(0);
 	}
 	return 1;
 }

@@ -725,7 +725,8 @@ int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, 
 	}
 	/* compose the stream: earlier tables through pl, the new table = pr - unless pl is 0, 1, 2 ... (every row of the stream joined
 	 * exactly one right row: a primary-key join): the earlier tables' row ids then stand as they are, nothing is gathered */
-	if (key >= 0 && J == x->n && pl && mdb_dev_last_pairs_identity(x->dev))
+	struct mdb_dev_plan_info pi;
+	if (key >= 0 && J == x->n && pl && mdb_dev_last_plan(x->dev, &pi) == 0 && pi.pairs_identity)
 		x->n = J;
 	else if ((rc = stream_select(x, t, pl, J)))
 		return rc;

@@ -62,7 +62,8 @@ COL_DISTINCT = 1     # MDB_COL_DISTINCT
 class PlanInfo(ctypes.Structure):
     """struct mdb_dev_plan_info: what the last join / GROUP BY operator did"""
     _fields_ = [(k, ctypes.c_uint32) for k in ("key_form", "key_bits", "levels", "digits", "minmax_pruned", "semijoin", "any_order", "ranged_order",
-                                                "multi_one_pass", "retries", "samples", "from_stats", "payload_form", "group_form", "arena_mib", "small_form", "keys_are_left_column", "counts_all_one", "groups_as_bits", "payload_tables")]
+                                                "multi_one_pass", "retries", "samples", "from_stats", "payload_form", "group_form", "arena_mib", "small_form", "keys_are_left_column", "counts_all_one", "groups_as_bits", "payload_tables",
+                                                "pairs_identity")]
 
 
 class ExplainRequest(ctypes.Structure):
@@ -98,7 +99,7 @@ def explain(op, left, right=None, further_rows=(), as_sample=False, left_nulls_b
         rc = fn(byref(rq), byref(info))
     if rc != 0:
         raise RuntimeError(f"mdb_dev_explain_{op} failed ({rc})")
-    return {k: int(getattr(info, k)) for k, _ in PlanInfo._fields_}
+    return {k: int(getattr(info, k)) for k, _ in PlanInfo._fields_ if k != "pairs_identity"}    # (a fact of a run's output, not of a plan)
 
 
 class Counters(ctypes.Structure):
@@ -138,8 +139,6 @@ def _bind(lib):
         "mdb_dev_reserve": ([P, c_size_t], c_int),
         "mdb_dev_set_overlap": ([P, c_int], c_int),
         "mdb_dev_set_narrow_keys": ([P, c_int], c_int),
-        "mdb_dev_last_join_narrow": ([P], c_int),
-        "mdb_dev_last_join_filter": ([P], c_int),
         "mdb_dev_counters": ([P, POINTER(Counters)], c_int),
         "mdb_dev_explain_join_group_count": ([POINTER(ExplainRequest), POINTER(PlanInfo)], c_int),
         "mdb_dev_explain_group_count": ([POINTER(ExplainRequest), POINTER(PlanInfo)], c_int),
@@ -147,7 +146,6 @@ def _bind(lib):
         "mdb_dev_distinct_scan": ([P, P, P, c_uint64, c_int64, c_uint64, P, POINTER(c_int)], c_int),
         "mdb_dev_call_stats": ([P, P, POINTER(ColStats), P, POINTER(ColStats)], c_int),
         "mdb_dev_last_plan": ([P, POINTER(PlanInfo)], c_int),
-        "mdb_dev_last_pairs_identity": ([P], c_int),
         "mdb_dev_arena_bytes": ([P], c_size_t),
         "mdb_dev_alloc": ([P, c_size_t, POINTER(P)], c_int),
         "mdb_dev_free": ([P, P], c_int),
@@ -210,7 +208,7 @@ def _bind(lib):
 
 DEV_SYMBOLS = [
     "mdb_dev_ctx_create", "mdb_dev_ctx_destroy", "mdb_dev_ctx_set_stream", "mdb_dev_last_error", "mdb_dev_sync",
-    "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_last_join_narrow", "mdb_dev_last_join_filter", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_last_pairs_identity", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
+    "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
     "mdb_dev_host_alloc", "mdb_dev_host_free", "mdb_dev_h2d", "mdb_dev_d2h", "mdb_dev_prof_enable", "mdb_dev_prof_reset", "mdb_dev_prof_read", "mdb_dev_prof_symbols", "mdb_dev_filter",
     "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
@@ -346,44 +344,45 @@ class DeviceCtx:
         self._chk(self.lib.mdb_dev_call_stats(self.h, _ptr(keys_l) if sl is not None else None, byref(sl) if sl is not None else None,
                                               _ptr(keys_r) if sr is not None else None, byref(sr) if sr is not None else None), "call_stats")
 
+    # ---- single facts of last_plan()
     def last_join_narrow(self):
-        return bool(self.lib.mdb_dev_last_join_narrow(self.h))
+        return self.last_plan()["key_form"] != 0
 
     def last_join_form(self):
         """0 wide (64-bit hashes), 1 narrow (32-bit hashes of a 2^32-wide window), 2 compact narrow (k-bit hashes of the
         sampled window, direct-address leaves)"""
-        return int(self.lib.mdb_dev_last_join_narrow(self.h))
+        return self.last_plan()["key_form"]
 
     def last_join_filter(self):
         """(bitmap, minmax): bitmap = 0 when the last join did not filter the left table through the right table's key bitmap,
         else 1 + log2(values per bit); minmax = whether the left table's first level pruned by the right table's key range"""
-        v = int(self.lib.mdb_dev_last_join_filter(self.h))
-        return v & 0xFF, bool(v & 0x100)
+        p = self.last_plan()
+        return p["semijoin"], bool(p["minmax_pruned"])
 
     def last_join_multi(self):
         """the last join_group_count_multi counted all its right tables in one pass (no chain of two-table operators)"""
-        return bool(self.lib.mdb_dev_last_join_filter(self.h) & 0x400)
+        return bool(self.last_plan()["multi_one_pass"])
 
     def last_pairs_identity(self):
         """the last join_pairs matched every left row with exactly one right row: its left vector is 0, 1, 2 ..."""
-        return bool(self.lib.mdb_dev_last_pairs_identity(self.h))
+        return bool(self.last_plan()["pairs_identity"])
 
     def last_join_unordered(self):
         """the last join_group_count ran without row ids and ordering (flags without MDB_ORDER_FIRST, no first rows wanted)"""
-        return bool(self.lib.mdb_dev_last_join_filter(self.h) & 0x800)
+        return bool(self.last_plan()["any_order"])
 
     def last_join_one_pass_4096(self):
         """the last ordered join_group_count took ONE 4096-digit pass per table (key windows of 2^24 ... 2^27 values: 4-byte row words
         for the left table, leaves of up to 2^15 values shared by two workgroups)"""
-        return bool(self.lib.mdb_dev_last_join_filter(self.h) & 0x1000)
+        return self.last_plan()["digits"] == 4096
 
     def last_join_ranged_order(self):
         """the last one-level join wrote its group records straight into the ordering kernel's row-id ranges (no record list, no sort levels)"""
-        return bool(self.lib.mdb_dev_last_join_filter(self.h) & 0x2000)
+        return bool(self.last_plan()["ranged_order"])
 
     def last_join_levels(self):
         """partition levels of the last join / GROUP BY operator's final attempt: 1 (wide direct-address leaves) or 2"""
-        return 1 if int(self.lib.mdb_dev_last_join_filter(self.h)) & 0x1200 else 2
+        return self.last_plan()["levels"]
 
     def set_narrow_keys(self, mode):
         """32-bit hashes for int32-range join keys: 0 never, 1 sampled and verified (default), 2 always try."""

@@ -44,7 +44,7 @@ for seed in range(cases):
             np.array_equal(f.cpu().numpy().view(np.uint32).astype(np.int64), ef)
         if not ok:
             bad += 1
-            print("MISMATCH", seed, shape, n_l, n_r, off, round_, dev.last_join_form(), hex(int(dev.lib.mdb_dev_last_join_filter(dev.h))), flush=True)
+            print("MISMATCH", seed, shape, n_l, n_r, off, round_, dev.last_plan(), flush=True)
     # single-table GROUP BY of the right table's column (duplicates: the band sort up to 2^25 key values, the tile sort at 2^26 / 2^27, the
     # partitioned path beyond), checked on the device: first rows ascending, COUNT and first row of every key
     for round_ in range(2):
@@ -60,7 +60,7 @@ for seed in range(cases):
             bad += 1
             print("GROUP BY MISMATCH", seed, shape, n_r, off, round_, dev.last_plan(), flush=True)
         del gf, gc, fi, keys, uk, uc, o, first
-    print(f"case {seed}: shape {shape}, {n_l} x {n_r} rows, {len(ek)} groups, form {dev.last_join_form()}, flags {hex(int(dev.lib.mdb_dev_last_join_filter(dev.h)))}", flush=True)
+    print(f"case {seed}: shape {shape}, {n_l} x {n_r} rows, {len(ek)} groups, plan {dev.last_plan()}", flush=True)
     del dl, dr, k, c, f
     torch.cuda.empty_cache()
 print(f"{cases} cases, {bad} mismatches, {time.time() - t0:.1f} s")

@@ -2838,7 +2838,7 @@ def test_any_order_operators_random_shapes(dev, seed):
 
 
 def test_join_pairs_reports_an_identity_left_vector(dev):
-    """mdb_dev_last_pairs_identity: unique right keys and a partner for every left row (the primary-key join of BASELINE configs[1])
+    """mdb_dev_last_plan().pairs_identity: unique right keys and a partner for every left row (the primary-key join of BASELINE configs[1])
     -> the left vector is 0, 1, 2 ... and says so; one left row without a partner, or a right key twice, and it does not."""
     rng = np.random.default_rng(5)
     n = 700_000
@@ -2950,6 +2950,70 @@ def test_call_stats_replace_the_key_sample_and_the_plan_says_so(dev, variant):
     a3, b3 = a.clone(), b.clone()
     dev.join_group_count(a3, None, b3, None)
     assert dev.last_plan()["from_stats"] == 0      # (sampled - or remembered by address, when the allocator handed out a buffer seen before)
+
+
+# what the run and mdb_dev_explain_* must agree on.  Not compared: any_order (both ordered here), ranged_order and groups_as_bits (explain
+# predicts them - the run's answer may rest on what earlier calls over the columns delivered), retries / samples / from_stats (counters of
+# the run), arena_mib (explain only), keys_are_left_column / counts_all_one / pairs_identity (what the run's output turned out to be)
+EXPLAINED_FIELDS = ("key_form", "key_bits", "levels", "digits", "minmax_pruned", "semijoin", "multi_one_pass", "payload_form", "payload_tables",
+                    "group_form", "small_form")
+
+
+@pytest.mark.parametrize("shape", ["D", "U", "S", "group_band_sort", "payload_row_order"])
+def test_explain_names_the_plan_the_run_reports(shape, monkeypatch):
+    """one plan record, written once per fact: the operator run with the caller's exact statistics (mdb_dev_call_stats) and
+    mdb_dev_explain_* handed the same statistics and the device's CU count (no launch) report the same form.  A context of its own:
+    explain's remembers nothing, and what another test's calls left remembered by column address must not steer this run"""
+    dev = D.DeviceCtx(0)
+    try:
+        _explain_and_run(dev, shape, monkeypatch)
+    finally:
+        dev.close()
+
+
+def _explain_and_run(dev, shape, monkeypatch):
+    n = 3_000_000
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def stats(col):
+        lo, hi = dev.key_range(col)
+        distinct = dev.distinct(col, key_range=(lo, hi))
+        return (lo, hi, D.COL_DISTINCT if distinct else 0), {"min": lo, "max": hi, "rows": col.numel(), "distinct": distinct}
+
+    a = dev.gen_keys(n, 0, n, 42, 0)
+    if shape == "group_band_sort":
+        a = dev.to_dev(np.random.default_rng(11).integers(0, 1 << 21, n).astype(np.int64))
+        sa, ea = stats(a)
+        dev.call_stats(a, sa)
+        try:
+            dev.group_count(a, None)
+            run = dev.last_plan()
+        finally:
+            dev.call_stats()
+        assert run["group_form"] == 1, run
+        plan = D.explain("group_count", left=ea, num_cus=cus, lib=dev.lib)
+    else:
+        b = dev.gen_keys(n, 0, n, 43, 0 if shape in ("U", "payload_row_order") else n // 16)
+        if shape == "S":
+            b.mul_(16)
+        (sa, ea), (sb, eb) = stats(a), stats(b)
+        if shape == "payload_row_order":
+            monkeypatch.setenv("MDB_ROWJOIN", "2")      # (row order for tables below 2^24 rows too)
+        dev.call_stats(a, sa, b, sb)
+        try:
+            if shape == "payload_row_order":
+                got = dev.join_payload(a, None, b, None, [b * 3 + 1])
+                assert got is not None and torch.equal(got[0], a * 3 + 1)
+            else:
+                dev.join_group_count(a, None, b, None)
+            run = dev.last_plan()
+        finally:
+            dev.call_stats()
+        op = "join_payload" if shape == "payload_row_order" else "join_group_count"
+        plan = D.explain(op, left=ea, right=eb, num_cus=cus, lib=dev.lib)
+        assert run["payload_form"] == (3 if shape == "payload_row_order" else 0), run
+    assert run["from_stats"] == 1 and run["retries"] == 0, run
+    assert {k: run[k] for k in EXPLAINED_FIELDS} == {k: plan[k] for k in EXPLAINED_FIELDS}, (shape, run, plan)
 
 
 def test_call_stats_that_do_not_hold_cost_a_retry_never_a_result(dev):
