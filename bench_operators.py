@@ -40,14 +40,79 @@ def timed(dev, fn, reps=5, warmup=2):
     return ms, {k: round(v[1], 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:8]}, out
 
 
+def outer_join_rows(dev, res):
+    """outer_complete_1e8 (mdb_dev_outer_complete beside the device-to-device copy of the bytes it must move, the project's
+    yardstick, alternating in one run) and left_join_pairs_1e8 (the LEFT JOIN statement against the same statement with JOIN)"""
+    n = 100_000_000
+    i = torch.arange(n, dtype=torch.int32, device=dev.device)
+    pp = i[(i & 3) != 3].contiguous()       # 0.75 * 10^8 pairs over as many distinct positions; every fourth position has no pair
+    del i
+    po = torch.arange(pp.numel(), dtype=torch.int32, device=dev.device)
+    J, U = pp.numel(), n // 4
+    src = torch.empty((8 * J + 8 * (J + U)) // 8, dtype=torch.int64, device=dev.device)
+    dst = torch.empty_like(src)
+    copy_ms, oc_ms = [], []
+    kern = {}
+    for rep in range(4):                    # (the first turn warms both up and is dropped)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dst.copy_(src)
+        torch.cuda.synchronize()
+        copy_ms.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        op, oo = dev.outer_complete(pp, po, n)
+        torch.cuda.synchronize()
+        oc_ms.append((time.perf_counter() - t0) * 1e3)
+        assert op.numel() == J + U
+        del op, oo
+    dev.prof_enable(True)
+    dev.prof_reset()
+    dev.outer_complete(pp, po, n)
+    kern = {k: round(v[1], 4) for k, v in sorted(dev.prof_read().items(), key=lambda kv: -kv[1][1])[:8]}
+    dev.prof_enable(False)
+    ms, cms = min(oc_ms[1:]), min(copy_ms[1:])
+    res["outer_complete_1e8"] = {"n_p": n, "pairs": J, "unmatched": U, "ms": ms, "ms_all": oc_ms[1:], "copy_ms": cms, "copy_ms_all": copy_ms[1:],
+                                 "times_the_copy": ms / cms, "algorithmic_bytes": 8 * J + 8 * (J + U), "kernels_ms": kern,
+                                 "note": "copy_ms: torch device-to-device copy that reads 8 J + 8 (J + U) bytes and writes as many, same run"}
+    del pp, po, src, dst
+    torch.cuda.empty_cache()
+    from midoridb_amd.query import DB
+    with DB() as db:
+        db.execute("CREATE TABLE A (id_a INT);")
+        db.execute("CREATE TABLE B (id_b INT);")
+        db.generate("A", n, 42)
+        db.generate("B", n, 43, [3 * n // 4])   # B's keys lie in [0, 0.75 n): a quarter of A has no partner
+        db.results_on_device(True)
+        t = {"JOIN": [], "LEFT JOIN": []}
+        rows = {}
+        for rep in range(3):
+            for kind in t:
+                r = db.query_device(f"SELECT A.id_a, B.id_b FROM A {kind} B ON A.id_a = B.id_b;", copy=False)
+                t[kind].append(db.last_call_ms)
+                rows[kind] = r[3]
+        inner, left = min(t["JOIN"][1:]), min(t["LEFT JOIN"][1:])
+        res["left_join_pairs_1e8"] = {"rows_per_table": n, "inner_rows": rows["JOIN"], "left_rows": rows["LEFT JOIN"], "inner_call_ms": inner,
+                                      "left_call_ms": left, "difference_ms": left - inner, "inner_call_ms_all": t["JOIN"][1:],
+                                      "left_call_ms_all": t["LEFT JOIN"][1:],
+                                      "note": "query_execute() with results kept on the device; the statements alternate"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04", "operators.json"))
     ap.add_argument("--configs1", action="store_true", help="only the two BASELINE configs[0..1] shapes (scan_filter_1e8, join_payload_1e7): "
                                                              "what profiles/collect.sh runs under rocprofv3")
+    ap.add_argument("--outer", action="store_true", help="only the outer join's rows (outer_complete_1e8, left_join_pairs_1e8)")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.outer:
+        outer_join_rows(dev, res)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps({k: {kk: vv for kk, vv in d.items() if kk != "kernels_ms"} for k, d in res.items()}, indent=1))
+        return
 
     # ---- scan + WHERE (config 1 shape at 10^8 rows): SELECT v FROM T WHERE v > N/2 ; v = permutation
     n = 100_000_000
@@ -334,6 +399,8 @@ def main():
                     "(2 columns x G x 8 B over PCIe); call_ms = wall time of the C call (query_execute) alone; python_wall_ms adds "
                     "the binding's copy of the result columns into numpy arrays (not part of the C API)"}
 
+    torch.cuda.empty_cache()
+    outer_join_rows(dev, res)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

@@ -23,6 +23,19 @@
  * A "tuple stream" of length n is the device analogue of the reference's early
  * materialisation table: tuple k of a joined stream refers to base rows through
  * row-id vectors (uint32_t[n], one per FROM table); rid == NULL means identity.
+ *
+ * MDB_NO_ROW in a row-id vector: tuple k has NO row of that table (the NULL-supplied side of an
+ * outer join).  Every operator that reads a column through a row-id vector - mdb_dev_gather64,
+ * mdb_dev_gather_cols, mdb_dev_double_join_keys, the predicate programs' mdb_col_binding.rid, mdb_sort_key.rid
+ * (ORDER BY, top-k, DISTINCT, GROUP BY over several columns) - reads such a cell as value 0 with its
+ * NULL bit set, whether or not the column itself has a NULL bitmap; mdb_dev_gather32 composes
+ * "no row" to "no row".  Where an operator WRITES NULL bits (the gathers), the caller passes a
+ * destination bitmap for a vector that may hold MDB_NO_ROW also when the source column has none:
+ * without one the cell is 0 and nothing says that it is NULL.
+ * A table of 2^32 - 1 rows or more cannot be read through such a vector.  The catalog itself admits
+ * rows without a bound (mdb_store.c appends to 64-bit counts; 32-bit row ids are the device layer's);
+ * the executor refuses an outer join over a table that large (join_next_table) and
+ * mdb_dev_outer_complete refuses the positions.
  */
 #ifndef MDB_DEV_H
 #define MDB_DEV_H
@@ -36,6 +49,8 @@ extern "C" {
 #endif
 
 typedef struct mdb_dev_ctx mdb_dev_ctx;
+
+#define MDB_NO_ROW 0xFFFFFFFFu	/* in a row-id vector: this tuple has no row of the table (see above) */
 
 /* ------------------------------------------------------------------ context */
 
@@ -291,7 +306,7 @@ int mdb_dev_filter_project(mdb_dev_ctx *ctx, const struct mdb_pred_insn *prog, i
  * column re-pack of proc_select_clause()/table_rem_column() (:1369-1433,
  * src/primitive/column.c:146-243): late materialisation of one output column.
  * dst[k] = src[idx ? idx[k] : k], NULL bits carried.  dst_nullbits may be NULL when
- * src_nullbits is NULL. */
+ * src_nullbits is NULL and idx holds no MDB_NO_ROW (such a cell is 0, NULL bit set). */
 int mdb_dev_gather64(mdb_dev_ctx *ctx, const void *src, const uint64_t *src_nullbits,
 		     const uint32_t *idx, uint64_t n, void *dst, uint64_t *dst_nullbits);
 /* The projection of a whole result in ONE launch: column c of the output is dst[c][k] = src[c][rid[c] ? rid[c][k] : k]
@@ -306,7 +321,7 @@ struct mdb_gather_col {
 	const uint64_t *src_nullbits;	/* or NULL */
 	const uint32_t *rid;		/* row-id vector of the column's table in the tuple stream, or NULL = identity */
 	void *dst;			/* n 8-byte values */
-	uint64_t *dst_nullbits;		/* (n + 63) / 64 words; required when src_nullbits != NULL */
+	uint64_t *dst_nullbits;		/* (n + 63) / 64 words; required when src_nullbits != NULL or rid may hold MDB_NO_ROW */
 };
 int mdb_dev_gather_cols(mdb_dev_ctx *ctx, const struct mdb_gather_col *cols, int ncols, uint64_t n);
 
@@ -317,7 +332,7 @@ int mdb_dev_gather_cols(mdb_dev_ctx *ctx, const struct mdb_gather_col *cols, int
  * (n + 63) / 64 words. */
 int mdb_dev_double_join_keys(mdb_dev_ctx *ctx, const double *src, const uint64_t *src_nullbits, const uint32_t *idx, uint64_t n,
 			     int64_t *dst, uint64_t *dst_nullbits);
-/* dst[k] = src[idx[k]] for uint32 row-id vectors (composition of tuple streams). */
+/* dst[k] = src[idx[k]] for uint32 row-id vectors (composition of tuple streams); MDB_NO_ROW where idx[k] is MDB_NO_ROW. */
 int mdb_dev_gather32(mdb_dev_ctx *ctx, const uint32_t *src, const uint32_t *idx, uint64_t n, uint32_t *dst);
 /* out[i] = table[cells[i]] (0 for a cell outside [0, table_n)): 8-byte ids translated through a device table - how VARCHAR cells
  * (ids of one process's string dictionary, reference src/primitive/column.c:255-293 keeps heap pointers) become ids every rank agrees
@@ -446,6 +461,20 @@ int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, const ui
 /* Cross join (FROM A, B  ==  JOIN ... ON 1=1, reference optimiser_select.c:395-464):
  * all n_l * n_r pairs in (l, r) order, into caller buffers of that capacity. */
 int mdb_dev_cross_pairs(mdb_dev_ctx *ctx, uint64_t n_l, uint64_t n_r, uint32_t *out_l, uint32_t *out_r);
+
+/* ------------------------------------------------------------------ LEFT / RIGHT OUTER JOIN: outer completion
+ *
+ * The grammar accepts LEFT [OUTER] JOIN and RIGHT [OUTER] JOIN (reference src/parser/midorisql.y:229-233); the reference's
+ * executor stops at BUG_ON(join_node->join_type != AST_SEL_JOIN_INNER) (executor_select.c:1094, :1169).  Here the pair
+ * operators above find the matches and this pass adds what SQL keeps besides: pairs_p[0..J) = ascending positions on the
+ * PRESERVED side (out_l of mdb_dev_join_pairs, also after a filter has thinned the pairs), pairs_o their partners.  Output,
+ * device arrays allocated by the call (mdb_dev_free): the J pairs in their order and, for every position i in [0, n_p) that
+ * occurs in no pair, the entry (i, MDB_NO_ROW) at its place in ascending out_p order.  *out_count = J + U, U the unmatched
+ * positions: U == 0 and J == n_p means out_p is 0, 1, 2 ... .  J == 0 with pairs_p == pairs_o == NULL is valid (every position
+ * unmatched).  Positions that are not ascending or not below n_p fail the call; n_p, J and J + U stay below 2^32 - 1.
+ * Streaming: 12 J bytes read, 8 (J + U) written, 9 bytes of bookkeeping per 64 positions; no atomics, no sort.  Synchronises. */
+int mdb_dev_outer_complete(mdb_dev_ctx *ctx, const uint32_t *pairs_p, const uint32_t *pairs_o, uint64_t J, uint64_t n_p,
+			   uint32_t **out_p, uint32_t **out_o, uint64_t *out_count);
 
 /* ------------------------------------------------------------------ GROUP BY key + COUNT(*)
  *

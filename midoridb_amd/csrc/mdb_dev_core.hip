@@ -930,14 +930,14 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather64(const uint64_t *__r
 			row[r] = idx[base + (uint64_t)r * STREAM_THREADS + threadIdx.x];
 #pragma unroll
 		for (int r = 0; r < STREAM_ROUNDS; r++)
-			v[r] = src[row[r]];
+			v[r] = row[r] == MDB_NO_ROW ? 0ull : src[row[r]];	/* (no row of this table here: 0, NULL) */
 #pragma unroll
 		for (int r = 0; r < STREAM_ROUNDS; r++)
 			dst[base + (uint64_t)r * STREAM_THREADS + threadIdx.x] = v[r];
 		if (dst_null) {
 #pragma unroll
 			for (int r = 0; r < STREAM_ROUNDS; r++) {
-				const uint64_t m = __ballot(src_null && mdb_bit_is_set(src_null, row[r]));
+				const uint64_t m = __ballot(row[r] == MDB_NO_ROW || (src_null && mdb_bit_is_set(src_null, row[r])));
 				if (mdb_lane() == 0)
 					dst_null[(base + (uint64_t)r * STREAM_THREADS + threadIdx.x) >> 6] = m;
 			}
@@ -953,9 +953,13 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather64(const uint64_t *__r
 		bool isnull = false;
 		if (in) {
 			row = idx ? (uint64_t)idx[k] : k;
-			v = src[row];
-			if (src_null)
-				isnull = mdb_bit_is_set(src_null, row);
+			if (idx && row == MDB_NO_ROW) {
+				isnull = true;
+			} else {
+				v = src[row];
+				if (src_null)
+					isnull = mdb_bit_is_set(src_null, row);
+			}
 			dst[k] = v;
 		}
 		if (dst_null) {
@@ -978,7 +982,7 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather32(const uint32_t *__r
 			row[r] = idx[base + (uint64_t)r * STREAM_THREADS + threadIdx.x];
 #pragma unroll
 		for (int r = 0; r < STREAM_ROUNDS; r++)
-			v[r] = src[row[r]];
+			v[r] = row[r] == MDB_NO_ROW ? MDB_NO_ROW : src[row[r]];
 #pragma unroll
 		for (int r = 0; r < STREAM_ROUNDS; r++)
 			dst[base + (uint64_t)r * STREAM_THREADS + threadIdx.x] = v[r];
@@ -987,8 +991,10 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather32(const uint32_t *__r
 #pragma unroll
 	for (int r = 0; r < STREAM_ROUNDS; r++) {
 		const uint64_t k = base + (uint64_t)r * STREAM_THREADS + threadIdx.x;
-		if (k < n)
-			dst[k] = src[idx[k]];
+		if (k < n) {
+			const uint32_t row = idx[k];
+			dst[k] = row == MDB_NO_ROW ? MDB_NO_ROW : src[row];
+		}
 	}
 }
 
@@ -1067,14 +1073,18 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather_cols(gather_cols_args
 		for (int c = 0; c < a.ncols; c++) {
 			const uint32_t slot = a.slot[c];
 			uint64_t v[GC_ROUNDS], src_row[GC_ROUNDS];
+			bool absent[GC_ROUNDS];		/* no row of the column's table at this tuple (MDB_NO_ROW): 0, NULL */
 #pragma unroll
 			for (int r = 0; r < GC_ROUNDS; r++) {
 				src_row[r] = base + (uint64_t)r * STREAM_THREADS + threadIdx.x;
+				absent[r] = false;
 #pragma unroll
 				for (int t = 0; t < NR; t++)
-					if (slot == (uint32_t)t)
+					if (slot == (uint32_t)t) {
 						src_row[r] = row[r][t];
-				v[r] = a.src[c][src_row[r]];
+						absent[r] = row[r][t] == MDB_NO_ROW;
+					}
+				v[r] = absent[r] ? 0ull : a.src[c][src_row[r]];
 			}
 #pragma unroll
 			for (int r = 0; r < GC_ROUNDS; r++)
@@ -1082,7 +1092,7 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather_cols(gather_cols_args
 			if (a.dst_null[c]) {
 #pragma unroll
 				for (int r = 0; r < GC_ROUNDS; r++) {
-					const bool isnull = a.src_null[c] && mdb_bit_is_set(a.src_null[c], src_row[r]);
+					const bool isnull = absent[r] || (a.src_null[c] && mdb_bit_is_set(a.src_null[c], src_row[r]));
 					const uint64_t m = __ballot(isnull);
 					if (mdb_lane() == 0)
 						a.dst_null[c][(base + (uint64_t)r * STREAM_THREADS + threadIdx.x) >> 6] = m;
@@ -1102,16 +1112,18 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_gather_cols(gather_cols_args
 			row[t] = (in && t < a.nrids) ? a.rid[t][k] : 0u;
 		for (int c = 0; c < a.ncols; c++) {
 			uint64_t src_row = k;
+			bool absent = false;
 			if (a.slot[c] != 0xFF) {
 #pragma unroll
 				for (int t = 0; t < MDB_GATHER_MAX_RIDS; t++)	/* (a compile-time index keeps row[] in registers) */
 					if (a.slot[c] == t)
 						src_row = row[t];
+				absent = src_row == MDB_NO_ROW;
 			}
-			bool isnull = false;
+			bool isnull = absent;
 			if (in) {
-				a.dst[c][k] = a.src[c][src_row];
-				if (a.src_null[c])
+				a.dst[c][k] = absent ? 0ull : a.src[c][src_row];
+				if (!absent && a.src_null[c])
 					isnull = mdb_bit_is_set(a.src_null[c], src_row);
 			}
 			if (a.dst_null[c]) {
@@ -1186,8 +1198,11 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_double_join_keys(const uint6
 		bool drop = false;
 		if (in) {
 			const uint64_t row = idx ? (uint64_t)idx[k] : k;
-			uint64_t v = src[row];
-			if (src_null)
+			const bool absent = idx && row == MDB_NO_ROW;
+			uint64_t v = absent ? 0ull : src[row];
+			if (absent)
+				drop = true;
+			else if (src_null)
 				drop = mdb_bit_is_set(src_null, row);
 			if ((v << 1) == 0)
 				v = 0;					/* -0.0 -> +0.0 */

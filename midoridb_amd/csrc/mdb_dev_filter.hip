@@ -36,6 +36,8 @@ struct pred_args {
 __device__ static inline bool pred_load(const mdb_col_binding &c, uint64_t k, uint64_t *v)
 {
 	const uint64_t row = c.rid ? (uint64_t)c.rid[k] : k;
+	if (c.rid && row == MDB_NO_ROW)		/* no row of this table at tuple k: the cell is NULL */
+		return false;
 	if (c.nullbits && mdb_bit_is_set(c.nullbits, row))
 		return false;
 	*v = reinterpret_cast<const uint64_t *>(c.values)[row];

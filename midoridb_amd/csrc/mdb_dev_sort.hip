@@ -701,7 +701,7 @@ static int sort_check(mdb_dev_ctx *ctx, const char *what, int nkeys, uint64_t n)
 	return MIDORIDB_OK;
 }
 
-extern "C" int mdb_dev_sort_perm(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *perm_out)
+static int sort_perm_keys(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *perm_out)
 {
 	int rc = sort_check(ctx, "sort_perm", nkeys, n);
 	if (rc || n == 0)
@@ -776,7 +776,7 @@ static int topk_rec(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys
 		sk.values = vals;
 		sk.nullbits = nullwords;
 		sk.rid = NULL;
-		rc = mdb_dev_sort_perm(ctx, &sk, 1, s, sperm);
+		rc = sort_perm_keys(ctx, &sk, 1, s, sperm);
 		if (rc)
 			goto out;
 		MDB_LAUNCH(ctx, "topk_pick", k_topk_pick, 1, 1, sperm, (uint32_t)rank, vals, nullwords, picked);
@@ -870,7 +870,7 @@ static int topk_rec(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys
 	if (!done) {
 		if ((rc = mdb_cached_alloc(ctx, n * 4, (void **)&full)))
 			goto out;
-		if ((rc = mdb_dev_sort_perm(ctx, keys, nkeys, n, full)))
+		if ((rc = sort_perm_keys(ctx, keys, nkeys, n, full)))
 			goto out;
 		if (hipMemcpyAsync(perm_out, full, k * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
 		    hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -891,7 +891,7 @@ out:
 	return rc;
 }
 
-extern "C" int mdb_dev_topk_perm(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint64_t k, uint32_t *perm_out,
+static int topk_perm_keys(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint64_t k, uint32_t *perm_out,
 				 uint64_t *out_candidates)
 {
 	int rc = sort_check(ctx, "topk_perm", nkeys, n);
@@ -955,7 +955,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_distinct_heads_vkey(const uint
 static int group_multi_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_first,
 			      int64_t *out_count, uint64_t cap, uint64_t *out_groups);
 
-extern "C" int mdb_dev_distinct_sel(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_sel,
+static int distinct_sel_keys(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_sel,
 				    uint64_t *out_count)
 {
 	*out_count = 0;
@@ -1158,7 +1158,7 @@ static int group_multi_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys,
 	return rc;
 }
 
-extern "C" int mdb_dev_group_count_multi(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_first,
+static int group_count_multi_keys(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_first,
 					 int64_t *out_count, uint64_t cap, uint64_t *out_groups)
 {
 	*out_groups = 0;
@@ -1217,4 +1217,121 @@ extern "C" int mdb_dev_group_count_multi(mdb_dev_ctx *ctx, const struct mdb_sort
 		return rc;
 	*out_groups = G;
 	return MIDORIDB_OK;
+}
+
+/* ------------------------------------------------------------------ MDB_NO_ROW in a key's row-id vector
+ *
+ * A tuple without a row of the key's table (the NULL-supplied side of an outer join) sorts, groups and compares as a NULL cell.
+ * The methods above decide by `nullbits != NULL` whether a column can hold NULLs at all (the packed word's flag bit, the NULL
+ * pass), so a key read through a vector that holds MDB_NO_ROW is given to them as what it means: the column gathered through
+ * the vector with its NULL bits (mdb_dev_gather64 writes 0 / NULL for "no row"), row ids gone.  Whether a vector holds one is
+ * looked up (4 bytes per row, once per distinct vector, one read-back); streams without one take the methods as they were. */
+__global__ __launch_bounds__(SORT_THREADS) void k_any_no_row(const uint32_t *__restrict__ rid, uint64_t n, uint32_t *__restrict__ flag)
+{
+	bool any = false;
+	for (uint64_t k = (uint64_t)blockIdx.x * SORT_THREADS + threadIdx.x; k < n; k += (uint64_t)gridDim.x * SORT_THREADS)
+		any = any || rid[k] == MDB_NO_ROW;
+	if (__ballot(any) && mdb_lane() == 0)
+		mdb_raise(flag, 1u);
+}
+
+struct resolved_keys {
+	struct mdb_sort_key key[MDB_SORT_MAX_KEYS];
+	void *buf[2 * MDB_SORT_MAX_KEYS];
+	int nbuf;
+};
+
+static void resolved_keys_free(mdb_dev_ctx *ctx, resolved_keys *rk)
+{
+	for (int i = 0; i < rk->nbuf; i++)
+		(void)mdb_cached_free(ctx, rk->buf[i]);
+	rk->nbuf = 0;
+}
+
+static int resolve_absent_keys(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, resolved_keys *rk)
+{
+	rk->nbuf = 0;
+	if (nkeys < 1 || nkeys > MDB_SORT_MAX_KEYS || n == 0 || n >= 0xFFFFFFFFull)
+		return MIDORIDB_OK;	/* (the operator's own checks answer) */
+	bool any_rid = false;
+	for (int c = 0; c < nkeys; c++) {
+		rk->key[c] = keys[c];
+		any_rid = any_rid || keys[c].rid;
+	}
+	if (!any_rid)
+		return MIDORIDB_OK;
+	uint32_t *flags = NULL, h[MDB_SORT_MAX_KEYS];
+	int rc = mdb_cached_alloc(ctx, sizeof(h), (void **)&flags);
+	if (rc)
+		return rc;
+	rc = [&]() -> int {
+		MDB_HIP(ctx, hipMemsetAsync(flags, 0, sizeof(h), ctx->stream));
+		const uint32_t grid = (uint32_t)(((n + SORT_THREADS - 1) / SORT_THREADS) < 2048 ? ((n + SORT_THREADS - 1) / SORT_THREADS) : 2048);
+		for (int c = 0; c < nkeys; c++) {
+			int first = 0;
+			while (keys[first].rid != keys[c].rid)
+				first++;
+			if (keys[c].rid && first == c)
+				MDB_LAUNCH(ctx, "no_row_lookup", k_any_no_row, grid, SORT_THREADS, keys[c].rid, n, flags + c);
+		}
+		MDB_HIP(ctx, hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		return MIDORIDB_OK;
+	}();
+	(void)mdb_cached_free(ctx, flags);
+	for (int c = 0; c < nkeys && !rc; c++) {
+		int first = 0;
+		while (keys[first].rid != keys[c].rid)
+			first++;
+		if (!keys[c].rid || !h[first])
+			continue;
+		void *v = NULL, *nb = NULL;
+		if ((rc = mdb_cached_alloc(ctx, n * 8, &v)))
+			break;
+		rk->buf[rk->nbuf++] = v;
+		if ((rc = mdb_cached_alloc(ctx, ((n + 63) / 64) * 8, &nb)))
+			break;
+		rk->buf[rk->nbuf++] = nb;
+		if ((rc = mdb_dev_gather64(ctx, keys[c].values, keys[c].nullbits, keys[c].rid, n, v, (uint64_t *)nb)))
+			break;
+		rk->key[c].values = v;
+		rk->key[c].nullbits = (const uint64_t *)nb;
+		rk->key[c].rid = NULL;
+	}
+	if (rc)
+		resolved_keys_free(ctx, rk);
+	return rc;
+}
+
+#define WITH_RESOLVED_KEYS(call)                                        \
+	resolved_keys rk;                                               \
+	int rc = resolve_absent_keys(ctx, keys, nkeys, n, &rk);         \
+	if (rc)                                                         \
+		return rc;                                              \
+	const struct mdb_sort_key *use = rk.nbuf ? rk.key : keys;       \
+	rc = (call);                                                    \
+	resolved_keys_free(ctx, &rk);                                   \
+	return rc
+
+extern "C" int mdb_dev_sort_perm(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *perm_out)
+{
+	WITH_RESOLVED_KEYS(sort_perm_keys(ctx, use, nkeys, n, perm_out));
+}
+
+extern "C" int mdb_dev_topk_perm(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint64_t k, uint32_t *perm_out,
+				 uint64_t *out_candidates)
+{
+	WITH_RESOLVED_KEYS(topk_perm_keys(ctx, use, nkeys, n, k, perm_out, out_candidates));
+}
+
+extern "C" int mdb_dev_distinct_sel(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_sel,
+				    uint64_t *out_count)
+{
+	WITH_RESOLVED_KEYS(distinct_sel_keys(ctx, use, nkeys, n, out_sel, out_count));
+}
+
+extern "C" int mdb_dev_group_count_multi(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_first,
+					 int64_t *out_count, uint64_t cap, uint64_t *out_groups)
+{
+	WITH_RESOLVED_KEYS(group_count_multi_keys(ctx, use, nkeys, n, out_first, out_count, cap, out_groups));
 }

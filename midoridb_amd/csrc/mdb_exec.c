@@ -131,8 +131,9 @@ int stream_column(struct exec *x, const struct mdb_expr *f, const int64_t **vals
 	*nulls = col->d_nullbits;
 	if (x->rid[f->tbl_idx] && x->n) {
 		int64_t *v = dalloc(x, x->n * 8);
-		uint64_t *nb = col->d_nullbits ? dalloc(x, ((x->n + 63) / 64) * 8) : NULL;
-		if (!v || (col->d_nullbits && !nb))
+		const bool want_nb = col->d_nullbits || x->may_be_absent[f->tbl_idx];	/* ("no row" cells are NULL cells) */
+		uint64_t *nb = want_nb ? dalloc(x, ((x->n + 63) / 64) * 8) : NULL;
+		if (!v || (want_nb && !nb))
 			return dev_fail(x, "allocating a key column");
 		if (mdb_dev_gather64(x->dev, col->d_data, col->d_nullbits, x->rid[f->tbl_idx], x->n, v, nb))
 			return dev_fail(x, "gathering a key column");
@@ -190,7 +191,10 @@ uint64_t expr_tables(const struct mdb_expr *e)
 /* WHERE push-down: the reference filters AFTER the joins (proc_where_clause :1435-1463), which for inner joins gives
  * the same rows as filtering a table first whenever a conjunct reads only that table.  Splits the top-level
  * AND-conjuncts of the WHERE clause: push[t][..] = table t's own conjuncts (constants go with table 0),
- * residual[..] = conjuncts that read several tables and stay above the joins.  false = too many to split. */
+ * residual[..] = conjuncts that read several tables and stay above the joins.  false = too many to split.
+ * Outer joins: WHERE runs after the join, and a table that some join NULL-supplies (T of S LEFT JOIN T; every table of S in S RIGHT
+ * JOIN T) has rows in the stream that are not rows of the table - its conjuncts stay above the joins too (they see the NULL cells);
+ * a table that every join preserves keeps its push-down (a row the filter drops would be dropped after the joins with all its pairs). */
 
 bool where_split(const struct mdb_select *s, struct where_split *w)
 {
@@ -204,10 +208,17 @@ bool where_split(const struct mdb_select *s, struct where_split *w)
 	collect_conjuncts(s->where, all, &n, 64);
 	if (n > 64)
 		return false;
+	uint64_t null_supplied = 0;
+	for (int t = 1; t < s->ntabs; t++) {
+		if (mdb_join_is_left(s->join_type[t]))
+			null_supplied |= 1ull << t;
+		else if (mdb_join_is_right(s->join_type[t]))
+			null_supplied |= (1ull << t) - 1;
+	}
 	for (int i = 0; i < n; i++) {
 		const uint64_t m = expr_tables(all[i]);
 		int t = 0;
-		if (m & (m - 1)) {
+		if ((m & (m - 1)) || ((m ? m : 1ull) & null_supplied)) {	/* (a constant goes with table 0) */
 			w->residual[w->nresidual++] = all[i];
 			continue;
 		}
@@ -299,6 +310,8 @@ void op_stats_begin(struct exec *x, const struct mdb_expr *fl, const void *pl, c
 	const struct mdb_expr *f[2] = { fl, fr };
 	memset(st, 0, sizeof(st));
 	if (x->cat->dist || !fl || !pl || (fr && !pr))
+		return;
+	if (x->has_outer)	/* (a stream that repeats or NULL-extends rows: the columns' statistics promise nothing about it) */
 		return;
 	for (int i = 0; i < (fr ? 2 : 1); i++) {
 		if (f[i]->kind != MDB_EX_FIELD || f[i]->tbl_idx < 0 || x->orig_tab[f[i]->tbl_idx])
@@ -457,6 +470,8 @@ static int join_with_payload_multi(struct exec *x, int t, const struct mdb_expr 
 		const struct mdb_expr *k2 = kr;
 		if (t2 > t) {
 			const struct mdb_expr *on = s->on[t2], *mine = NULL, *other = NULL;
+			if (s->join_type[t2] != 1)
+				break;
 			if (!on || on->kind != MDB_EX_CMP || on->op != MDB_CMP_EQ || on->kids[0]->kind != MDB_EX_FIELD || on->kids[1]->kind != MDB_EX_FIELD)
 				break;
 			if (on->kids[0]->tbl_idx == t2 && on->kids[1]->tbl_idx < t2) {
@@ -554,6 +569,170 @@ int join_with_payload(struct exec *x, int t, const struct mdb_expr *kr, const in
 	return payload_shadow(x, t, kr->col_idx, vl, pc, np, out);
 }
 
+/* S LEFT / RIGHT [OUTER] JOIN T ON c (S = the stream of the tables joined so far, T = table t).  SQL's meaning, in the emission order of
+ * the inner join: the pairs for which the WHOLE ON expression is true, and every row of the PRESERVED side (LEFT: S, RIGHT: T) without
+ * such a pair once, the other side's tables at MDB_NO_ROW (their cells read as NULL); rows come preserved-side-major.  None of the inner
+ * join's shortcuts apply (join elimination, carried payload cells, "the right key IS the left key": it is NULL where there is no row).
+ * Order of work: T filtered by its pushed WHERE conjuncts (where_split pushes them only when every join preserves T) and, for LEFT, by
+ * the ON conjuncts that read T alone (they decide matching, and T is not preserved: a T row that fails them matches nothing) ->
+ * the pair operator, preserved side on the left -> the other ON conjuncts on the pairs, seen as a stream for the length of one filter
+ * (a conjunct over the preserved side alone makes rows unmatched, it drops none) -> mdb_dev_outer_complete -> the stream composed. */
+static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, int npconj)
+{
+	struct mdb_select *s = x->s;
+	struct mdb_table *rt = s->tabs[t].t;
+	const bool left = mdb_join_is_left(s->join_type[t]);
+	struct mdb_expr *conj[32];
+	const struct mdb_expr *tconj[PUSH_MAX + 32], *resid[32];
+	int nconj = 0, key = -1, ntconj = 0, nresid = 0;
+	const struct mdb_expr *kl = NULL, *kr = NULL;
+	uint32_t *ps = NULL, *pt = NULL;	/* the pairs: positions in S, positions in (filtered) T */
+	uint64_t J = 0;
+	int rc;
+
+	if (rt->nrows >= MDB_NO_ROW || x->n >= MDB_NO_ROW) {
+		snprintf(x->err, x->errlen, "execution phase: an outer join over 2^32 - 1 rows or more cannot be addressed\n");
+		return -MIDORIDB_ERROR;
+	}
+	if (s->on[t]) {
+		collect_conjuncts(s->on[t], conj, &nconj, 32);
+		if (nconj > 32) {	/* too many conjuncts: the whole ON is one residual predicate */
+			nconj = 0;
+			resid[nresid++] = s->on[t];
+		}
+	}
+	for (int i = 0; i < npconj; i++)
+		tconj[ntconj++] = pconj[i];
+	for (int i = 0; i < nconj; i++) {
+		struct mdb_expr *c = conj[i];
+		if (key < 0 && c->kind == MDB_EX_CMP && c->op == MDB_CMP_EQ && c->kids[0]->kind == MDB_EX_FIELD && c->kids[1]->kind == MDB_EX_FIELD) {
+			struct mdb_expr *a = c->kids[0], *b = c->kids[1];
+			if (a->tbl_idx < t && b->tbl_idx == t) {
+				kl = a;
+				kr = b;
+				key = i;
+				continue;
+			} else if (b->tbl_idx < t && a->tbl_idx == t) {
+				kl = b;
+				kr = a;
+				key = i;
+				continue;
+			}
+		}
+		if (left && expr_tables(c) == 1ull << t)
+			tconj[ntconj++] = c;
+		else
+			resid[nresid++] = c;
+	}
+	const uint32_t *rsel = NULL;
+	uint64_t r_rows = rt->nrows;
+	if ((rc = table_filter(x, t, tconj, ntconj, &rsel, &r_rows)))
+		return rc;
+	const uint64_t n_s = x->n, n_p = left ? n_s : r_rows;
+	if (key >= 0 && n_s && r_rows) {
+		const int64_t *vl;
+		const uint64_t *nl, *nr;
+		const void *vr;
+		if (kl->type == MDB_CT_DOUBLE) {
+			const void *dl;
+			if ((rc = double_join_keys(x, &s->tabs[kl->tbl_idx].t->cols[kl->col_idx], x->rid[kl->tbl_idx], n_s, &dl, &nl)) ||
+			    (rc = double_join_keys(x, &rt->cols[kr->col_idx], rsel, r_rows, &vr, &nr)))
+				return rc;
+			vl = dl;
+		} else if ((rc = stream_column(x, kl, &vl, &nl)) || (rc = table_column(x, t, kr, rsel, r_rows, &vr, &nr))) {
+			return rc;
+		}
+		if (left ? mdb_dev_join_pairs(x->dev, vl, nl, n_s, vr, nr, r_rows, &ps, &pt, &J)
+			 : mdb_dev_join_pairs(x->dev, vr, nr, r_rows, vl, nl, n_s, &pt, &ps, &J))
+			return dev_fail(x, "hash join");
+		if ((ps && track(x, ps)) || (pt && track(x, pt)))
+			return -MIDORIDB_NOMEM;
+	} else if (key < 0) {
+		/* no equi-join key (ON 1=1, ON a < b): all pairs, preserved side major, then the ON predicate */
+		if (n_s * r_rows > (1ull << 28)) {
+			snprintf(x->err, x->errlen, "execution phase: cross join of %llu x %llu rows is too large (no equi-join key in the ON clause)\n",
+				 (unsigned long long)n_s, (unsigned long long)r_rows);
+			return -MIDORIDB_ERROR;
+		}
+		J = n_s * r_rows;
+		if (J) {
+			ps = dalloc(x, J * 4);
+			pt = dalloc(x, J * 4);
+			if (!ps || !pt)
+				return dev_fail(x, "allocating join pairs");
+			if (left ? mdb_dev_cross_pairs(x->dev, n_s, r_rows, ps, pt) : mdb_dev_cross_pairs(x->dev, r_rows, n_s, pt, ps))
+				return dev_fail(x, "cross join");
+		}
+	}
+	if (J && nresid) {
+		/* the pairs as a stream, for the length of the filter: the earlier tables through ps, T through pt */
+		uint32_t *saved[MDB_MAX_TABS];
+		struct pred_prog p;
+		uint32_t *sel, *ps2, *pt2;
+		uint64_t m = 0;
+		memcpy(saved, x->rid, sizeof(saved));
+		rc = stream_select(x, t, ps, J);
+		if (!rc && rsel) {
+			uint32_t *mapped = dalloc(x, J * 4);
+			if (!mapped || mdb_dev_gather32(x->dev, rsel, pt, J, mapped))
+				rc = dev_fail(x, "re-mapping row ids");
+			x->rid[t] = mapped;
+		} else {
+			x->rid[t] = pt;
+		}
+		memset(&p, 0, sizeof(p));
+		for (int i = 0; i < nresid && !rc; i++)
+			if (pred_compile(x, &p, resid[i]) || (i && pred_emit(&p, MDB_P_AND, 0, 0, 0, 0, 0))) {
+				snprintf(x->err, x->errlen, "execution phase: predicate too large for the device program (max %d steps, %d columns)\n",
+					 MDB_PRED_MAX_INSNS, MDB_PRED_MAX_SLOTS);
+				rc = -MIDORIDB_ERROR;
+			}
+		sel = rc ? NULL : dalloc(x, J * 4);
+		if (!rc && (!sel || mdb_dev_filter(x->dev, p.insn, p.n, p.cols, p.ncols, J, sel, &m)))
+			rc = dev_fail(x, "filter");
+		memcpy(x->rid, saved, sizeof(saved));
+		x->n = n_s;
+		if (rc)
+			return rc;
+		if (m < J) {
+			ps2 = dalloc(x, (m ? m : 1) * 4);
+			pt2 = dalloc(x, (m ? m : 1) * 4);
+			if (!ps2 || !pt2 || (m && (mdb_dev_gather32(x->dev, ps, sel, m, ps2) || mdb_dev_gather32(x->dev, pt, sel, m, pt2))))
+				return dev_fail(x, "thinning the join pairs");
+			ps = ps2;
+			pt = pt2;
+			J = m;
+		}
+	}
+	/* the preserved side's rows without partner, at their places */
+	uint32_t *cp = NULL, *co = NULL;
+	uint64_t total = 0;
+	if (mdb_dev_outer_complete(x->dev, J ? (left ? ps : pt) : NULL, J ? (left ? pt : ps) : NULL, J, n_p, &cp, &co, &total))
+		return dev_fail(x, "outer completion");
+	if ((cp && track(x, cp)) || (co && track(x, co)))
+		return -MIDORIDB_NOMEM;
+	const bool identity = total == J && J == n_p;	/* every preserved row exactly one pair: cp is 0, 1, 2 ... */
+	uint32_t *cs = left ? cp : co, *ct = left ? co : cp;
+	if (left && identity)
+		x->n = total;	/* (the earlier tables' row ids stand as they are) */
+	else if ((rc = stream_select(x, t, cs, total)))
+		return rc;
+	if (rsel && total) {
+		uint32_t *mapped = dalloc(x, total * 4);
+		if (!mapped || mdb_dev_gather32(x->dev, rsel, ct, total, mapped))
+			return dev_fail(x, "re-mapping row ids");
+		ct = mapped;
+	} else if (!left && identity) {
+		ct = NULL;
+	}
+	x->rid[t] = ct;
+	if (total > J)
+		for (int u = left ? t : 0; u < (left ? t + 1 : t); u++)
+			x->may_be_absent[u] = true;
+	x->joined_rows = total;
+	return MIDORIDB_OK;
+}
+
 int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, int npconj)
 {
 	struct mdb_select *s = x->s;
@@ -567,6 +746,8 @@ int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, 
 
 	if (x->joined_ahead[t])		/* (joined together with an earlier table on the same key: join_with_payload_multi) */
 		return MIDORIDB_OK;
+	if (s->join_type[t] != 1)
+		return outer_join_next_table(x, t, pconj, npconj);
 	if (s->on[t]) {
 		collect_conjuncts(s->on[t], conj, &nconj, 32);
 		if (nconj > 32)
@@ -931,6 +1112,8 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	x.s = s;
 	x.err = err;
 	x.errlen = errlen;
+	for (int t = 1; t < s->ntabs; t++)
+		x.has_outer = x.has_outer || s->join_type[t] != 1;
 	mark_needed_all(&x);	/* (which columns the statement reads: the sharded exchange and the join that carries payload cells ask) */
 
 	/* ---- result column set in the reference's order (R3): COUNT(*) first if selected, then every column
@@ -993,7 +1176,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	bool only_count = has_count && !s->ngroup && !s->select_all;
 	for (int i = 0; i < s->nsel; i++)
 		only_count = only_count && s->sel[i]->kind == MDB_EX_COUNT;
-	fused = s->ntabs <= PUSH_TABS ? fused_chain(s, fkeys, only_count) : -1;
+	fused = s->ntabs <= PUSH_TABS && !x.has_outer ? fused_chain(s, fkeys, only_count) : -1;	/* (the fused operator is an inner join) */
 	if (fused >= 0 && !cat->dist && split_ok) {
 		/* join elimination: when the catalog says every right table of the chain is a complete primary key over the first table's key range,
 		 * the fused join + GROUP BY operator has nothing to find out - the general plan drops those joins (join_next_table) and groups the
@@ -1007,7 +1190,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	/* the join of two key columns, nothing else selected: in the reference's order it is tried as a primary-key join first (the keys with
 	 * partners in the left table's row order; large tables only: the attempt runs the ordered join + GROUP BY operator), and left to the
 	 * materialising join below when a key has several rows on a side */
-	bool keys_only = keys_only_join(s, cat, has_count, key_tbl, key_col, src, ncols, kj);
+	bool keys_only = !x.has_outer && keys_only_join(s, cat, has_count, key_tbl, key_col, src, ncols, kj);
 	int64_t *keys_ordered = NULL;
 	uint64_t keys_ordered_rows = 0;
 	if (keys_only && !cat->groups_any_order) {
@@ -1422,7 +1605,7 @@ exchange_rows:
 			 * ids or an ordering sort - the stream becomes what the fused plan's is (S4: only the group key and COUNT(*) can be
 			 * named from here on) */
 			if (cat->groups_any_order && !cat->dist && !x.fused && x.n && s->group[0]->kind == MDB_EX_FIELD && s->group[0]->type != MDB_CT_DOUBLE &&
-			    !s->select_all && !s->distinct &&
+			    !s->select_all && !s->distinct && !x.may_be_absent[s->group[0]->tbl_idx] &&
 			    s->tabs[s->group[0]->tbl_idx].t->cols[s->group[0]->col_idx].null_count == 0) {
 				int64_t *gk = dalloc(&x, x.n * 8), *gc = dalloc(&x, x.n * 8);
 				uint64_t Gk = 0;
@@ -1625,10 +1808,15 @@ grouped:
 				d_nulls[c] = aliased ? NULL : from->d_nullbits;
 				continue;
 			}
+			const void *src_vals = from->d_data;
+			if (!src_vals && !(src_vals = dalloc(&x, 8))) {	/* (an empty table under an outer join: every tuple is at "no row", no cell is read) */
+				rc = dev_fail(&x, "projection gather");
+				break;
+			}
 			{
 				/* the same column through the same row ids twice (SELECT * after an equi-join: both key columns): gathered once */
 				int g = 0;
-				while (g < ngl && !(gl[g].src == from->d_data && gl[g].rid == rid && gl[g].src_nullbits == src_nb))
+				while (g < ngl && !(gl[g].src == src_vals && gl[g].rid == rid && gl[g].src_nullbits == src_nb))
 					g++;
 				if (g < ngl) {
 					d_vals[c] = gl[g].dst;
@@ -1652,12 +1840,13 @@ grouped:
 					seen_rid[nrid++] = rid;
 			}
 			int64_t *v = dalloc(&x, out_rows * 8);
-			uint64_t *nb = src_nb ? dalloc(&x, ((out_rows + 63) / 64) * 8) : NULL;
-			if (!v || (src_nb && !nb)) {
+			const bool want_nb = src_nb || x.may_be_absent[from_tbl];	/* (a tuple without a row of the table: its cells are NULL) */
+			uint64_t *nb = want_nb ? dalloc(&x, ((out_rows + 63) / 64) * 8) : NULL;
+			if (!v || (want_nb && !nb)) {
 				rc = dev_fail(&x, "projection gather");
 				break;
 			}
-			gl[ngl].src = from->d_data;
+			gl[ngl].src = src_vals;
 			gl[ngl].src_nullbits = src_nb;
 			gl[ngl].rid = rid;
 			gl[ngl].dst = v;

@@ -53,6 +53,10 @@ struct exec {
 	const struct where_split *ws;		/* the WHERE conjuncts pushed down to single tables (general plan; NULL: none are) */
 	int joins_eliminated;			/* tables that were not joined at all: the catalog said every row of the stream has exactly one partner (join_next_table) */
 	bool joined_ahead[MDB_MAX_TABS];	/* table t was joined together with an earlier table on the same key (join_with_payload_multi) */
+	/* LEFT / RIGHT OUTER JOIN: rid[t] may hold MDB_NO_ROW (table t is the NULL-supplied side of a join that left rows without partner) -
+	 * every column of t read through rid[t] needs a NULL bitmap of its own, whether or not the column has one */
+	bool may_be_absent[MDB_MAX_TABS];
+	bool has_outer;				/* some join of the statement is an outer join: no plan that assumes inner semantics */
 };
 
 struct pred_prog {
@@ -71,6 +75,10 @@ struct where_split {
 	const struct mdb_expr *residual[64];
 	int nresidual;
 };
+
+/* join types as the parser numbers them (mdb_sql.c: LEFT 2, RIGHT 4, + 6 with OUTER; the reference's grammar, midorisql.y:229-233) */
+static inline bool mdb_join_is_left(int jt) { return jt == 2 || jt == 8; }
+static inline bool mdb_join_is_right(int jt) { return jt == 4 || jt == 10; }
 
 extern __thread const struct mdb_strdict *stmt_dict;	/* the statement's string dictionary (VARCHAR literals) */
 

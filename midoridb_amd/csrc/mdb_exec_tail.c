@@ -17,7 +17,7 @@ int select_tail(struct exec *x, int has_count)
 		return rc;
 	if (s->distinct && x->n > 1) {
 		struct mdb_sort_key keys[MDB_SORT_MAX_KEYS];
-		int nk = 0;
+		int nk = 0, tbl0 = 0;
 		uint32_t *sel;
 		uint64_t m = 0;
 		for (int t = 0; t < s->ntabs; t++)
@@ -39,6 +39,8 @@ int select_tail(struct exec *x, int has_count)
 				bind_operand(x, &f, &keys[nk].values, &keys[nk].nullbits, &keys[nk].rid);
 				keys[nk].type = s->tabs[t].t->cols[c].type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
 				keys[nk].desc = 0;
+				if (!nk)
+					tbl0 = t;
 				nk++;
 			}
 		sel = dalloc(x, x->n * 4);
@@ -54,8 +56,9 @@ int select_tail(struct exec *x, int has_count)
 				return dev_fail(x, "allocating the DISTINCT selection");
 			if (keys[0].rid) {
 				int64_t *v = dalloc(x, x->n * 8);
-				uint64_t *nb = kn ? dalloc(x, ((x->n + 63) / 64 + 1) * 8) : NULL;
-				if (!v || (kn && !nb) || mdb_dev_gather64(x->dev, kv, kn, keys[0].rid, x->n, v, nb))
+				const bool want_nb = kn || (!x->fused && x->may_be_absent[tbl0]);	/* ("no row" cells are NULL cells) */
+				uint64_t *nb = want_nb ? dalloc(x, ((x->n + 63) / 64 + 1) * 8) : NULL;
+				if (!v || (want_nb && !nb) || mdb_dev_gather64(x->dev, kv, kn, keys[0].rid, x->n, v, nb))
 					return dev_fail(x, "gathering the DISTINCT column");
 				kv = v;
 				kn = nb;

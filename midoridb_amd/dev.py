@@ -175,6 +175,7 @@ def _bind(lib):
         "mdb_dev_distinct_sel": ([P, POINTER(SortKey), c_int, c_uint64, P, POINTER(c_uint64)], c_int),
         "mdb_dev_group_count_multi": ([P, POINTER(SortKey), c_int, c_uint64, P, P, c_uint64, POINTER(c_uint64)], c_int),
         "mdb_dev_join_pairs": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
+        "mdb_dev_outer_complete": ([P, P, P, c_uint64, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys_ordered": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64), POINTER(c_int)], c_int),
         "mdb_dev_join_payload": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), c_int, POINTER(P)], c_int),
@@ -210,11 +211,14 @@ DEV_SYMBOLS = [
     "mdb_dev_ctx_create", "mdb_dev_ctx_destroy", "mdb_dev_ctx_set_stream", "mdb_dev_last_error", "mdb_dev_sync",
     "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
     "mdb_dev_host_alloc", "mdb_dev_host_free", "mdb_dev_h2d", "mdb_dev_d2h", "mdb_dev_prof_enable", "mdb_dev_prof_reset", "mdb_dev_prof_read", "mdb_dev_prof_symbols", "mdb_dev_filter",
-    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
+    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_outer_complete", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
 ]
+
+
+NO_ROW = 0xFFFFFFFF     # MDB_NO_ROW (include/mdb_dev.h): "no row of this table" in a row-id vector; -1 in an int32 tensor
 
 
 def pack_nullbits(nulls):
@@ -573,6 +577,18 @@ class DeviceCtx:
         # tensors over the library's own buffers (no copy); they go back to its allocator when the tensors are collected
         return self._adopt(pl, J, torch.int32), self._adopt(pr, J, torch.int32)
 
+    def outer_complete(self, pairs_p, pairs_o, n_p):
+        """LEFT / RIGHT OUTER JOIN's completion: the pairs (ascending preserved-side positions, partner positions; None, None for no
+        pairs) plus (i, NO_ROW) for every i in [0, n_p) that no pair names, in ascending order of the preserved position ->
+        (out_p, out_o) int32 tensors over the library's buffers (NO_ROW reads as -1)."""
+        J = 0 if pairs_p is None else pairs_p.numel()
+        pp, po, cnt = c_void_p(), c_void_p(), c_uint64()
+        self._chk(self.lib.mdb_dev_outer_complete(self.h, _ptr(pairs_p) if J else None, _ptr(pairs_o) if J else None, J, n_p,
+                                                  byref(pp), byref(po), byref(cnt)), "outer_complete")
+        if not cnt.value:
+            return (torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.int32, device=self.device))
+        return self._adopt(pp, cnt.value, torch.int32), self._adopt(po, cnt.value, torch.int32)
+
     def join_keys(self, keys_l, null_l, keys_r, null_r):
         """the join's key column alone, every key once per joined row, in unspecified order (mdb_dev_join_keys)"""
         pk, cnt = c_void_p(), c_uint64()
@@ -657,22 +673,23 @@ class DeviceCtx:
         self._chk(self.lib.mdb_dev_filter(self.h, insns, len(prog), binds, len(cols), n, _ptr(sel), byref(cnt)), "filter")
         return sel[:cnt.value]
 
-    def gather64(self, src, src_null, idx, n):
+    def gather64(self, src, src_null, idx, n, dst_nulls=False):
+        """dst_nulls: write NULL bits also for a source without a bitmap (idx may hold NO_ROW)"""
         dst = torch.empty(max(n, 1), dtype=src.dtype, device=self.device)
         dnull = None
-        if src_null is not None:
+        if src_null is not None or dst_nulls:
             dnull = torch.zeros((n + 63) // 64 or 1, dtype=torch.int64, device=self.device)
         self._chk(self.lib.mdb_dev_gather64(self.h, _ptr(src), _ptr(src_null), _ptr(idx), n, _ptr(dst), _ptr(dnull)), "gather64")
         return dst[:n], dnull
 
-    def gather_cols(self, cols, n):
+    def gather_cols(self, cols, n, dst_nulls=False):
         """Whole-result projection in one launch: cols = [(src, src_nullbits or None, rid or None), ...] ->
-        [(values[n], nullbits words or None), ...]."""
+        [(values[n], nullbits words or None), ...].  dst_nulls: NULL bits for every column (a rid may hold NO_ROW)."""
         arr = (GatherCol * len(cols))()
         outs = []
         for i, (src, nb, rid) in enumerate(cols):
             dst = torch.empty(max(n, 1), dtype=src.dtype, device=self.device)
-            dnull = torch.zeros((n + 63) // 64 or 1, dtype=torch.int64, device=self.device) if nb is not None else None
+            dnull = torch.zeros((n + 63) // 64 or 1, dtype=torch.int64, device=self.device) if (nb is not None or dst_nulls) else None
             arr[i] = GatherCol(src.data_ptr(), nb.data_ptr() if nb is not None else None, rid.data_ptr() if rid is not None else None,
                                dst.data_ptr(), dnull.data_ptr() if dnull is not None else None)
             outs.append((dst[:n], dnull))
