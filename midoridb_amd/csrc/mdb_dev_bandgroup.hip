@@ -183,7 +183,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bg_band_sort(bg_sort_args a)
 	}
 	}
 	if (bad)
-		mdb_raise(a.status, 128u);
+		mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);
 	__syncthreads();
 	/* starts of the D digits inside the tile (thread t: digits 2 t, 2 t + 1), and room in the band's regions: one global atomic per digit
 	 * that occurs - issued here, looked at behind the sort pass (a round trip to the L2 that nothing waits for) */
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bg_band_sort(bg_sort_args a)
 		const uint32_t d0 = 2u * threadIdx.x;
 		const bool o0 = g0 + c0 > a.cap, o1 = g1 + c1 > a.cap;
 		if (o0 || o1)
-			mdb_raise(a.status, 2u);
+			mdb_raise(a.status, MDB_ST_REGION_FULL);
 		if (c0)
 			s_dst[r0] = o0 ? BG_OVF : d0 * a.cap + g0 - s0;
 		if (c1)
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(1024, 8 /* waves per SIMD: two workgroups per CU */
 			ebase += s_sum[3][w];
 		if (ebase + nexc > a.exc_cap) {
 			if (lane == 0)
-				mdb_raise(a.status, 16384u);	/* (more keys with several rows than the list holds: the record form) */
+				mdb_raise(a.status, RJ_ST_EXC_FULL);	/* (more keys with several rows than the list holds: the record form) */
 			return;
 		}
 		for (uint32_t i0 = wave * 64u; i0 < S; i0 += blockDim.x) {
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(1024, 8 /* waves per SIMD: two workgroups per CU */
 		cmax = c > cmax ? c : cmax;
 	}
 	if (cmax >> (32u - a.row_bits))		/* (a COUNT that does not fit beside its row id in 32 bits: the ordering sort keeps 8-byte records) */
-		mdb_raise(a.status, 512u);
+		mdb_raise(a.status, RJ_ST_COUNT_NOT_REC32);
 	/* groups of the waves before this one */
 	uint32_t wsum = mine;
 #pragma unroll
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(1024, 8 /* waves per SIMD: two workgroups per CU */
 		if (total) {
 			nb = atomicAdd(a.rec_count, total);
 			if (nb + total > a.rec_cap) {
-				mdb_raise(a.status, 8u);	/* (sized for every key value of the window and every row: cannot happen) */
+				mdb_raise(a.status, MDB_ST_LIST_FULL);	/* (sized for every key value of the window and every row: cannot happen) */
 				nb = 0xFFFFFFFFu;
 			} else {
 				atomicAdd(a.groups, total);
@@ -589,8 +589,8 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	la.row_bits = row_bits;
 	la.rec = rec;
 	la.rec_cap = (uint32_t)(most > 0xFFFFFFFFull ? 0xFFFFFFFFull : most);
-	la.groups = ctx->d_status + 1;
-	la.rec_count = ctx->d_status + 2;
+	la.groups = ctx->d_status + RJ_STW_GROUPS;
+	la.rec_count = ctx->d_status + RJ_STW_LIST_LEN;
 	la.status = ctx->d_status;
 	const size_t lds_leaf = (size_t)8 << sbits;
 	const uint32_t threads = 1024u;
@@ -612,16 +612,16 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	/* Nearly unique keys?  The pilot - the same leaf over 64 digits, counters only - counts the rows that are not the first of their key:
 	 * one in 16 at most, and the groups leave as one bit per row + exceptions (mdb_dev_dense.hip), no record per group, no sort */
 	if (dense_ok) {
-		la.dense_cnt = ctx->d_status + 4;
+		la.dense_cnt = ctx->d_status + RJ_STW_DENSE;
 		la.dense_bits = NULL;
 		la.exc = NULL;
 		BG_LAUNCH_ANY(true, D < 64u ? D : 64u, "group_band_leaf_dense");
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 32, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, sizeof(rj_readback), hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t *ps = reinterpret_cast<const uint32_t *>(&h[1]);
-		const uint64_t pilot_dups = ps[4], pilot_rows = ps[6];
-		const bool bad_table = (ps[0] & (128u | 2u)) != 0;	/* (a key outside the window, a region that overflowed: dealt with below, on the full run's flags) */
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
+		const rj_readback *ps = reinterpret_cast<const rj_readback *>(&h[MDB_HP_STATUS]);
+		const uint64_t pilot_dups = ps->not_first, pilot_rows = ps->rows_seen;
+		const bool bad_table = (ps->flags & (MDB_ST_KEY_OUTSIDE | MDB_ST_REGION_FULL)) != 0;	/* (a key outside the window, a region that overflowed: dealt with below, on the full run's flags) */
+		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + RJ_STW_GROUPS, 0, sizeof(rj_readback) - 4 * RJ_STW_GROUPS, ctx->stream));
 		if (!bad_table && pilot_rows && pilot_dups * 16u <= pilot_rows) {
 			unsigned long long *bits = NULL;
 			const uint64_t exc_cap = n / 8 + 4096;
@@ -633,13 +633,13 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 				return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "GROUP BY over a band-sorted column: %s", ctx->err);
 			la.exc_cap = (uint32_t)exc_cap;
 			BG_LAUNCH_ANY(true, D, "group_band_leaf_dense");
-			MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 32, hipMemcpyDeviceToHost, ctx->stream));
+			MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, sizeof(rj_readback), hipMemcpyDeviceToHost, ctx->stream));
 			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			const uint32_t dstatus = ps[0], dgroups = ps[1], n_exc = ps[5];
+			const uint32_t dstatus = ps->flags, dgroups = ps->groups, n_exc = ps->exceptions;
 			if (mdb_knob_set("MDB_DEBUG_GROUP"))
 				fprintf(stderr, "group_count (band sort, dense): pilot %llu of %llu rows not first; %u groups, %u rows not first, %u exceptions, status %u\n",
-					(unsigned long long)pilot_dups, (unsigned long long)pilot_rows, dgroups, ps[4], n_exc, dstatus);
-			if (!(dstatus & (16384u | 128u | 2u)) && (uint64_t)dgroups + ps[4] == n) {
+					(unsigned long long)pilot_dups, (unsigned long long)pilot_rows, dgroups, ps->not_first, n_exc, dstatus);
+			if (!(dstatus & (RJ_ST_EXC_FULL | MDB_ST_KEY_OUTSIDE | MDB_ST_REGION_FULL)) && (uint64_t)dgroups + ps->not_first == n) {
 				if (dgroups > cap)
 					return mdb_set_err(ctx, -MIDORIDB_ERROR, "GROUP BY: %u groups, room for %llu", dgroups, (unsigned long long)cap);
 				if ((rc = mdb_dense_emit(ctx, bits, n, la.exc, n_exc, out_first, out_count)))
@@ -649,37 +649,37 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 				return served(1);
 			}
 			/* (the exception list overflowed, or the table's flags ask for another path: the record form says which) */
-			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
+			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + RJ_STW_GROUPS, 0, sizeof(rj_readback) - 4 * RJ_STW_GROUPS, ctx->stream));
 		}
 	}
 	BG_LAUNCH_ANY(false, D, "group_band_leaf");
 #undef BG_LAUNCH_ANY
 #undef BG_LAUNCH_LEAF
-	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, offsetof(rj_readback, not_first), hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t *hs = reinterpret_cast<const uint32_t *>(&h[1]);
-	const uint32_t status = hs[0], groups = hs[1], list_len = hs[2];
+	const rj_readback *hs = reinterpret_cast<const rj_readback *>(&h[MDB_HP_STATUS]);
+	const uint32_t status = hs->flags, groups = hs->groups, list_len = hs->list_len;
 	if (mdb_knob_set("MDB_DEBUG_GROUP"))
 		fprintf(stderr, "group_count (band sort): window 2^%u at %lld, %u digits, %u bands, %u words per region: status %u, %u groups\n", kbits,
 			(long long)win_lo, D, nbands, rcap, status, groups);
-	if (status & 128u) {
+	if (status & MDB_ST_KEY_OUTSIDE) {
 		*outside = true;
 		return 1;
 	}
-	if (status & 2u) {	/* a region overflowed: the caller's other forms; remembered for this column */
+	if (status & MDB_ST_REGION_FULL) {	/* a region overflowed: the caller's other forms; remembered for this column */
 		ctx->ex_keys = keys;
 		ctx->ex_nl = n;
 		ctx->ex_nr = 0;
 		ctx->ex_uses = 0;
 		return 1;
 	}
-	if (status & 8u)
+	if (status & MDB_ST_LIST_FULL)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "GROUP BY over a band-sorted column: the record list overflowed");
-	if (status & 512u)
+	if (status & RJ_ST_COUNT_NOT_REC32)
 		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));	/* (the ordering kernels raise flags of their own there) */
 	if (groups > cap)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "GROUP BY: %u groups, room for %llu", groups, (unsigned long long)cap);
-	const bool rec32 = !(status & 512u) && row_bits < 32u;
+	const bool rec32 = !(status & RJ_ST_COUNT_NOT_REC32) && row_bits < 32u;
 	rc = groups ? order_records(ctx, rec, list_len, n, row_bits, sb1, sb2, out_first, out_count, NULL, NULL, NULL, false, rec32, 0, 0, 0, false, groups) : MIDORIDB_OK;
 	if (rc)
 		return rc;

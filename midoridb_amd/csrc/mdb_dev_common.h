@@ -208,6 +208,45 @@ void *mdb_arena_take(mdb_dev_ctx *ctx, size_t bytes);
 #define MDB_ZERO_BLK_WORDS (2u * MDB_ZERO_BLK_SLOT + 2048u)
 static inline size_t mdb_align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+/* ---- ctx->d_status: how every device operator reports to the host.  Word 0 holds flag bits (mdb_raise), the words behind it
+ * counters and scratch values that each operator names for itself.  The flags below cross the translation units: the partition,
+ * scatter and ordering kernels raise them, every operator reads them, and they mean the same wherever they appear.  What an
+ * operator adds of its own has that operator's prefix (GC_ST_, PJ_ST_, RJ_ST_, SORT_ST_ ...) and a static_assert next to it
+ * that none of its flags shares a bit with another or with these. */
+#define MDB_ST_REGION_FULL 2u	/* a fixed-capacity region (histogram-free partition level, scatter pass, ordering range) overflowed: redo with the exact layout */
+#define MDB_ST_LIST_FULL 8u	/* an output list sized by the caller is exhausted */
+#define MDB_ST_KEY_OUTSIDE 128u	/* a key outside the window / the int32 range the caller's form assumes */
+#define MDB_FLAG_SET 1u		/* a scratch word of its own used as ONE boolean (not word 0): "seen" */
+#define MDB_STW_FLAGS 0		/* index of the flag word */
+#define MDB_STW_UTIL 12		/* [12..15] scratch of the stand-alone utilities (mdb_dev_combine_counts, mdb_dev_key_range, the distinct scan): no operator is running */
+
+/* every flag one bit, no bit twice */
+template <size_t N> constexpr bool mdb_flags_distinct(const uint32_t (&f)[N])
+{
+	uint64_t sum = 0;
+	uint32_t any = 0;
+	for (size_t i = 0; i < N; i++) {
+		if (!f[i] || (f[i] & (f[i] - 1u)))
+			return false;
+		sum += f[i];
+		any |= f[i];
+	}
+	return sum == any;
+}
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE }), "common status flags share a bit");
+
+/* ---- ctx->h_pinned (1024 8-byte words): the staging slots that may be in use at the same time, by 8-byte word.  A read-back stays
+ * valid until the next copy into the same slot; host-to-device sources must stay untouched until the stream has passed them. */
+#define MDB_HP_COUNT 0		/* one count read back on its own (or an operator's whole read-back when nothing else is in flight) */
+#define MDB_HP_STATUS 1		/* [1..7] up to 56 bytes of d_status from word 0 on (struct gc_readback and its kin) */
+#define MDB_HP_SORT_FLAGS 8	/* the ordering sort's look at the flag word while [1..7] are still being read */
+#define MDB_HP_HOT 9		/* the hot-key path's number of hot leaves */
+#define MDB_HP_SORT_OUTSIDE 12	/* the ORDER BY pack's count of keys outside the sampled range */
+#define MDB_HP_PART_TILES 15	/* the pruned left pass's number of second-level tiles (read inside the operator, before its status) */
+#define MDB_HP_SEND_SHARD 256	/* host -> device: the sharded operator's pruning range (two 4-byte words) */
+#define MDB_HP_SEND_RANGE 260	/* host -> device: the fused operator's key window as a pruning range; the sharded operator's "a peer failed" flag word */
+#define MDB_HP_SEND_FLAGS 264	/* host -> device: the fused operator's flag word with the retried bits taken out (the window may still be on its way) */
+
 /* run the following launches on the auxiliary stream (after everything queued so far on the main
  * stream), and come back; between the two calls ctx->stream IS the auxiliary stream */
 int mdb_aux_begin(mdb_dev_ctx *ctx, hipStream_t *saved_main);

@@ -1319,7 +1319,7 @@ extern "C" int mdb_dev_combine_counts(mdb_dev_ctx *ctx, const int64_t *cnt1, con
 	*out_sum = 0;
 	if (n == 0)
 		return MIDORIDB_OK;
-	unsigned long long *d_sum = (unsigned long long *)(ctx->d_status + 12);
+	unsigned long long *d_sum = (unsigned long long *)(ctx->d_status + MDB_STW_UTIL);
 	MDB_HIP(ctx, hipMemsetAsync(d_sum, 0, 8, ctx->stream));
 	MDB_LAUNCH(ctx, "combine_counts", k_combine_counts, stream_grid(n), STREAM_THREADS, cnt1, first1, idx, cnt2, n, out_cnt, out_first, d_sum);
 	uint64_t *h = ctx->h_pinned;
@@ -1366,7 +1366,7 @@ extern "C" int mdb_dev_key_range(mdb_dev_ctx *ctx, const int64_t *keys, const ui
 	*out_max = -0x7FFFFFFFFFFFFFFFll - 1;
 	if (n == 0)
 		return MIDORIDB_OK;
-	long long *mm = (long long *)(ctx->d_status + 12);	/* two 8-byte words of the status block */
+	long long *mm = (long long *)(ctx->d_status + MDB_STW_UTIL);	/* two 8-byte words of the status block */
 	long long *h = (long long *)ctx->h_pinned;
 	h[0] = *out_min;
 	h[1] = *out_max;
@@ -1397,7 +1397,7 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_distinct_scan(const int64_t 
 		twice |= (atomicOr(&seen[b >> 5], m) & m) != 0u;
 	}
 	if (__ballot(twice) && mdb_lane() == 0)
-		mdb_raise(flag, 1u);
+		mdb_raise(flag, MDB_FLAG_SET);
 }
 
 extern "C" int mdb_dev_distinct_scan(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, int64_t window_lo, uint64_t window_bits,
@@ -1406,7 +1406,7 @@ extern "C" int mdb_dev_distinct_scan(mdb_dev_ctx *ctx, const int64_t *keys, cons
 	*out_twice = 0;
 	if (n == 0)
 		return MIDORIDB_OK;
-	uint32_t *flag = ctx->d_status + 12;
+	uint32_t *flag = ctx->d_status + MDB_STW_UTIL;
 	MDB_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
 	const uint64_t blocks = (n + STREAM_THREADS * STREAM_ROUNDS - 1) / (STREAM_THREADS * STREAM_ROUNDS);
 	MDB_LAUNCH(ctx, "distinct_scan", k_distinct_scan, (uint32_t)(blocks < 8192 ? blocks : 8192), STREAM_THREADS, keys, nullbits, n, window_lo, window_bits,

@@ -19,6 +19,10 @@
  * and the hashed leaves) get a window of 1.25 x the span in a table of up to GD_TABLE_MAX entries - 128 KiB of dynamic LDS,
  * one workgroup per CU. */
 #define GD_RANGE 8192u		/* entries of the LDS table for spans up to GD_RANGE / 2 (two workgroups per CU), replicated per lane group */
+/* flags of the two fast paths in word 0 of ctx->d_status (each path reads only its own) */
+#define GD_ST_VALUE_OUTSIDE 1024u	/* small value range: a value outside the sampled window / its field of the composite key */
+#define GH_ST_TABLE_FULL 2048u	/* few distinct values: more of them than the table holds */
+static_assert(mdb_flags_distinct({ GD_ST_VALUE_OUTSIDE, GH_ST_TABLE_FULL }), "GROUP BY fast paths: two status flags share a bit");
 #define GD_TABLE_MAX 16384u	/* entries of a workgroup's LDS table (8 bytes each) */
 #define GD_SPAN_MAX 13000u
 #define GD_THREADS 1024
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_direct(gd_args a)
 		}
 	}
 	if (__ballot(bad) && mdb_lane() == 0)
-		mdb_raise(a.status, 1024u);
+		mdb_raise(a.status, GD_ST_VALUE_OUTSIDE);
 	__syncthreads();
 	const uint32_t copies = a.copy_mask + 1;
 	for (uint32_t off = threadIdx.x; off < a.range; off += GD_THREADS) {
@@ -220,7 +224,7 @@ int mdb_group_count_direct_comp(mdb_dev_ctx *ctx, const struct mdb_bg_comp *comp
 	unsigned long long *rec = (unsigned long long *)mdb_arena_take(ctx, (GD_TABLE_MAX + 1) * 8);
 	if (!a.g_cnt || !a.g_first || !rec)
 		return -MIDORIDB_INTERNAL;
-	uint32_t *rec_n = ctx->d_status + 1;
+	uint32_t *rec_n = ctx->d_status + GC_STW_LIST_LEN;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(a.g_cnt, 0, (GD_TABLE_MAX + 1) * 8, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(a.g_first, 0xFF, (GD_TABLE_MAX + 1) * 4, ctx->stream));
@@ -230,13 +234,13 @@ int mdb_group_count_direct_comp(mdb_dev_ctx *ctx, const struct mdb_bg_comp *comp
 	const uint64_t chunks = (n + 2 * GD_THREADS - 1) / (2 * GD_THREADS);
 	MDB_LAUNCH_LDS(ctx, "group_direct_columns", k_group_direct<true>, (uint32_t)(chunks < resident ? chunks : resident), GD_THREADS, lds, a);
 	MDB_LAUNCH(ctx, "group_direct_emit", k_group_direct_emit, (range + 1 + 255) / 256, 256, a, (const unsigned long long *)NULL, kbits, rec, rec_n,
-		   (unsigned long long *)(ctx->d_status + 2));
+		   (unsigned long long *)(ctx->d_status + GC_STW_JOINED));
 	uint32_t *h32 = (uint32_t *)ctx->h_pinned;
 	MDB_HIP(ctx, hipMemcpyAsync(h32, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h32[0] & 1024u)
+	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
 		return 1;	/* a value outside its field */
-	const uint64_t G = h32[1];
+	const uint64_t G = h32[GC_STW_LIST_LEN];
 	if (G > cap)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)cap,
 				   (unsigned long long)G);
@@ -310,8 +314,8 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	uint32_t *g_first_r = keys_r ? (uint32_t *)mdb_arena_take(ctx, (GD_TABLE_MAX + 1) * 4) : NULL;
 	if (!a.g_cnt || !a.g_first || !rec || (keys_r && (!g_cnt_r || !g_first_r)))
 		return -MIDORIDB_INTERNAL;
-	uint32_t *rec_n = ctx->d_status + 1;
-	unsigned long long *d_joined = (unsigned long long *)(ctx->d_status + 2);
+	uint32_t *rec_n = ctx->d_status + GC_STW_LIST_LEN;
+	unsigned long long *d_joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(a.g_cnt, 0, (GD_TABLE_MAX + 1) * 8, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(a.g_first, 0xFF, (GD_TABLE_MAX + 1) * 4, ctx->stream));
@@ -339,13 +343,13 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	uint32_t *h32 = (uint32_t *)ctx->h_pinned;
 	MDB_HIP(ctx, hipMemcpyAsync(h32, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h32[0] & 1024u)
+	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
 		ctx->sr_valid = 0;	/* the sample missed a value outside its range: not to be reused */
-	if (h32[0] & 1024u)
+	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
 		return 1;	/* a value outside the window: the partitioned path */
 	ctx->plan.small_form = 2;
-	const uint64_t G = h32[1];
-	const uint64_t joined = (uint64_t)h32[2] | ((uint64_t)h32[3] << 32);
+	const uint64_t G = h32[GC_STW_LIST_LEN];
+	const uint64_t joined = (uint64_t)h32[GC_STW_JOINED] | ((uint64_t)h32[GC_STW_JOINED + 1] << 32);
 	if (G > cap)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)cap,
 				   (unsigned long long)G);
@@ -535,7 +539,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_hashed(gh_args a)
 	__syncthreads();
 	if (s_bad) {
 		if (threadIdx.x == 0)
-			mdb_raise(a.status, 2048u);
+			mdb_raise(a.status, GH_ST_TABLE_FULL);
 		return;
 	}
 	/* merge into the global table */
@@ -556,7 +560,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_hashed(gh_args a)
 				if (old == 0ull || old == hv)
 					break;
 				if (++probe >= GH_GSLOTS) {
-					mdb_raise(a.status, 2048u);
+					mdb_raise(a.status, GH_ST_TABLE_FULL);
 					g = 0xFFFFFFFFu;
 					break;
 				}
@@ -591,7 +595,7 @@ int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	if (ctx->gh_keys == keys && ctx->gh_n == n && ++ctx->gh_uses < GC_HINT_USES) {
 		distinct = ctx->gh_distinct;
 	} else {
-		uint32_t *d = ctx->d_status + 9;
+		uint32_t *d = ctx->d_status + GC_STW_LAST_FIRST;	/* (free before the operator starts) */
 		MDB_LAUNCH(ctx, "key_sample_distinct", k_key_sample_distinct, 1, 1024, keys, nullbits, n, d);
 		uint32_t *h = (uint32_t *)ctx->h_pinned;
 		MDB_HIP(ctx, hipMemcpyAsync(h, d, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -624,7 +628,7 @@ int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	unsigned long long *rec = (unsigned long long *)mdb_arena_take(ctx, (GH_GSLOTS + 2) * 8);
 	if (!a.g_key || !a.g_cnt || !a.g_first || !rec)
 		return -MIDORIDB_INTERNAL;
-	uint32_t *rec_n = ctx->d_status + 1;
+	uint32_t *rec_n = ctx->d_status + GC_STW_LIST_LEN;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 8, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(a.g_key, 0, GH_GSLOTS * 8, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(a.g_cnt, 0, (GH_GSLOTS + 2) * 8, ctx->stream));
@@ -636,11 +640,11 @@ int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	uint32_t *h32 = (uint32_t *)ctx->h_pinned;
 	MDB_HIP(ctx, hipMemcpyAsync(h32, ctx->d_status, 8, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h32[0] & 2048u) {
+	if (h32[MDB_STW_FLAGS] & GH_ST_TABLE_FULL) {
 		ctx->gh_distinct = 0xFFFFFFFFu;	/* the sample was wrong about this column: not tried again while it is remembered */
 		return 1;
 	}
-	const uint64_t G = h32[1];
+	const uint64_t G = h32[GC_STW_LIST_LEN];
 	if (G > cap)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)cap,
 				   (unsigned long long)G);

@@ -58,11 +58,11 @@ size_t mdb_partition_arena_bytes(uint64_t n, int bits1, int bits2, bool want_rid
 /* Partition one key column into 2^(bits1+bits2) leaves by the top bits of fmix64(key), dropping
  * NULL keys.  stable = keep input order inside every leaf (slower ballot ranking; requires want_rid),
  * otherwise the order inside a leaf is unspecified.  fast = skip the second level's histogram pass: every
- * leaf gets a fixed-capacity region and runs are placed with atomic cursors; if a leaf overflows, bit 1 of
- * ctx->d_status[0] is set and the caller must redo the operator with fast = false.  All temporaries and
+ * leaf gets a fixed-capacity region and runs are placed with atomic cursors; if a leaf overflows, MDB_ST_REGION_FULL
+ * is raised and the caller must redo the operator with fast = false.  All temporaries and
  * outputs are carved from the arena (caller has called mdb_arena_begin with enough room).  No host sync.
- * narrow (want_rid must be false): every key is expected within 2^31 of narrow_base - a key outside raises bit 7 of
- * ctx->d_status[0] and the caller redoes the operator wide.  1: hv[i] = fmix32(key) << 32 | row id, 2: hv is an array of 4-byte words fmix32(key) - only in the
+ * narrow (want_rid must be false): every key is expected within 2^31 of narrow_base - a key outside raises
+ * MDB_ST_KEY_OUTSIDE and the caller redoes the operator wide.  1: hv[i] = fmix32(key) << 32 | row id, 2: hv is an array of 4-byte words fmix32(key) - only in the
  * two-level fast layout, see mdb_partition_w32_applies(). */
 /* Semi-join filter of the second partition level: a bitmap of the hashed key values the OTHER table holds, one bit per
  * 2^coarse adjacent values, laid out by first-level digit: digit d owns words [d * words, d * words + words).  The
@@ -93,7 +93,7 @@ struct mdb_part_filter {
 	 * range, known before an exchange (mdb_dev_partition_by_dest_pruned) */
 	bool keep_on;
 	int64_t keep_lo, keep_hi;
-	bool own_on;		/* ... and verify that every key of THIS table lies in [own_lo, own_hi] (a promised range: status bit 10 otherwise) */
+	bool own_on;		/* ... and verify that every key of THIS table lies in [own_lo, own_hi] (a promised range: PART_ST_OWN_RANGE_BROKEN otherwise) */
 	int64_t own_lo, own_hi;
 	bool loose;		/* with level0_only: regions of 1.5 x (instead of 1.25 x) the average size - a column of some 10^4 - 10^5 distinct
 				 * values puts a few dozen of them, with thousands of rows each, into a region */
@@ -126,7 +126,7 @@ size_t mdb_partition_level0_arena_bytes(uint64_t n, int bits1, bool loose = fals
 /* whether narrow = 2 is available for a table of n rows */
 bool mdb_partition_w32_applies(uint64_t n, int bits1, int bits2, bool fast);
 
-/* fast = fixed-capacity regions + cursors (a region overflow sets bit 1 of ctx->d_status[0]: the caller must check it
+/* fast = fixed-capacity regions + cursors (a region overflow raises MDB_ST_REGION_FULL: the caller must check it
  * after the consumer kernel and redo with fast = false, the exact histogram layout) */
 /* digits0_used: how many of the 2^bits1 first-level digits can occur at all (0 = every one) - sizes the fast regions */
 /* digit0_rows: the words are row ids and a first-level digit spans that many of them (0: not so) - sizes the fast first-level regions for
@@ -146,7 +146,7 @@ int mdb_sort_pass(mdb_dev_ctx *ctx, const uint64_t *key_in, const uint32_t *rid_
 
 /* One histogram-free radix level over 4-byte words that lie in caller-described tiles: word w of tile t belongs to segment
  * tiles[t].seg and goes to child seg * 2^bits + ((w >> shift) & (2^bits - 1)); child c owns words_out[c * cap, c * cap + cap),
- * cursor[c] (zeroed by the call) counts its words; bit 1 of ctx->d_status[0] is raised when a child overflows.  Tile starts
+ * cursor[c] (zeroed by the call) counts its words; MDB_ST_REGION_FULL is raised when a child overflows.  Tile starts
  * must be multiples of 4 words.  No host sync. */
 int mdb_partition_words_level(mdb_dev_ctx *ctx, const uint32_t *words_in, const mdb_tile_desc *tiles, uint32_t ntiles, int bits, uint32_t shift,
 			      uint32_t *words_out, uint32_t *cursor, uint32_t nchild, uint32_t cap,
@@ -162,6 +162,14 @@ int mdb_partition_words_level(mdb_dev_ctx *ctx, const uint32_t *words_in, const 
  * after one more partition level of its own - and emits (key, COUNT) pairs; no row ids travel and no result ordering runs
  * (across ranks SQL leaves the order open anyway). */
 #define MDB_SHARD_MAX_TABS 4
+/* flags of mdb_shard_join in word 0 of ctx->d_status beside the common ones (MDB_ST_REGION_FULL: a region overflowed, MDB_ST_LIST_FULL: cap too
+ * small, MDB_ST_KEY_OUTSIDE: a right key outside the window), and the words behind it */
+#define MDB_SHARD_ST_PRODUCT_WIDE 2048u	/* a product of the right tables' counts beyond 32 bits */
+#define MDB_SHARD_ST_PEER_FAILED 16384u	/* a peer's region counters say that its first level failed (k_shard_regions; mdb_dist.hip sets it for its own rank) */
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE, MDB_SHARD_ST_PRODUCT_WIDE, MDB_SHARD_ST_PEER_FAILED }),
+	      "sharded join: two status flags share a bit");
+#define MDB_SHARD_STW_GROUPS 1	/* number of groups written */
+#define MDB_SHARD_STW_JOINED 2	/* [2..3] joined rows (u64) */
 struct mdb_shard_plan {
 	uint32_t world, rank;
 	uint32_t dbits;			/* first-level digit bits: 9 (the join's own first level), or 12 (the wide fan-out form) */
@@ -189,8 +197,7 @@ size_t mdb_shard_arena_bytes(const mdb_shard_plan *plan);
 int mdb_shard_partition(mdb_dev_ctx *ctx, const mdb_shard_plan *plan, int side, const int64_t *keys, const uint64_t *nulls, uint64_t n,
 			const void **regions, const uint32_t **cursors);
 /* receiver: recv[x] = world blocks of block_words[x] words (source-major), cnt[x] = world cursor arrays of D * nsub counters;
- * out_key / out_count (capacity cap): the groups; d_status[1] = their number, d_status[2..3] = joined rows (u64), flags in
- * d_status[0] (bit 1 a region overflowed, bit 3 cap too small, bit 7 a right key outside the window).  No host sync. */
+ * out_key / out_count (capacity cap): the groups; their number, the joined rows and the flags in ctx->d_status (MDB_SHARD_ST*).  No host sync. */
 int mdb_shard_join(mdb_dev_ctx *ctx, const mdb_shard_plan *plan, const void *const *recv, const uint32_t *const *cnt, int64_t *out_key,
 		   int64_t *out_count, uint64_t cap, void *const *arrived = NULL /* [ntab] hipEvent_t or NULL: table x's blocks and counters
 		   have arrived when arrived[x] has happened - the context's stream waits for it right before the first kernel that reads

@@ -266,7 +266,7 @@ __device__ static inline void gc_build_side(const gc_args &a, unsigned long long
 				created = old == 0ull;
 			}
 			if (s == 0xFFFFFFFFu) {
-				mdb_raise(a.status, 1u);
+				mdb_raise(a.status, GC_ST_TABLE_FULL);
 			} else {
 				if (IS_L) {
 					atomicAdd(&s_cnt[s], (unsigned long long)mult_[u]);
@@ -376,7 +376,7 @@ __device__ static inline void gc_side_heavy(const gc_args &a, unsigned long long
 						s = INSERT ? leaf_insert(s_key, GC_SLOTS, lhv) : leaf_find(s_key, GC_SLOTS, lhv);
 					if (s == 0xFFFFFFFFu) {
 						if (INSERT)
-							mdb_raise(a.status, 1u);
+							mdb_raise(a.status, GC_ST_TABLE_FULL);
 					} else if (IS_L) {
 						atomicAdd(&s_cnt[s], (unsigned long long)__popcll(grp));
 						atomicMin(&s_first[s], rmin);
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(GC_THREADS, 8) void k_leaf_group_count(gc_args a)
 		const bool hot = nonempty && (heavy_l || heavy_r);
 		const bool live = HEAVY ? hot : (nonempty && !hot);
 		if (!HEAVY && hot && threadIdx.x == 0)
-			mdb_raise(a.status, 64u);	/* left to the hot-key path */
+			mdb_raise(a.status, GC_ST_HOT_LEAVES);	/* left to the hot-key path */
 		/* a leaf whose left side fits one register batch (the normal case) is emitted by the threads that
 		 * created its table slots; only oversized (skewed) leaves scan the whole table */
 		const uint32_t build_rows = (HAS_R && BUILD_R) ? r1 - r0 : l1 - l0;
@@ -482,7 +482,7 @@ __global__ __launch_bounds__(GC_THREADS, 8) void k_leaf_group_count(gc_args a)
 					const uint32_t want = need > GC_REC_CHUNK ? need : GC_REC_CHUNK;
 					const uint32_t nb = atomicAdd(a.rec_count, want);
 					if (nb + want > a.rec_cap) {
-						mdb_raise(a.status, 8u);	/* list capacity exhausted: sizing bug, reported as an error */
+						mdb_raise(a.status, MDB_ST_LIST_FULL);	/* list capacity exhausted: sizing bug, reported as an error */
 						s_chunk[0] = 0;
 						s_chunk[2] = 0;
 					} else {
@@ -570,9 +570,9 @@ __global__ __launch_bounds__(GC_THREADS, 8) void k_leaf_group_count(gc_args a)
 							mine += c;
 							if (a.kbits) {
 								if (c >> (64 - a.kbits))
-									mdb_raise(a.status, 4u);	/* COUNT(*) does not fit beside the row id */
+									mdb_raise(a.status, GC_ST_COUNT_NOT_REC64);	/* COUNT(*) does not fit beside the row id */
 								if (c >> (32 - (a.kbits < 32 ? a.kbits : 31)))
-									mdb_raise(a.status, 16u);	/* ... nor in a 4-byte record */
+									mdb_raise(a.status, GC_ST_COUNT_NOT_REC32);	/* ... nor in a 4-byte record */
 								recv = ((unsigned long long)first << (64 - a.kbits)) | c;
 							} else {
 								if (first < a.dense_n)
@@ -729,7 +729,7 @@ __device__ static inline void ld_leaf(const gc_args &a, ld_state &st, uint32_t l
 	const bool hot = nonempty && (l1 - l0 >= a.heavy_l || (HAS_R && r1 - r0 >= a.heavy_r));
 	const bool live = nonempty && !hot;
 	if (hot && threadIdx.x == 0)
-		mdb_raise(a.status, 64u);	/* left to the hot-key path (hashed tables in global memory) */
+		mdb_raise(a.status, GC_ST_HOT_LEAVES);	/* left to the hot-key path (hashed tables in global memory) */
 	if (live && a.kbits) {
 		/* record list space, reserved a chunk at a time: one global atomic per ~10-170 leaves (see k_leaf_group_count).
 		 * (Reserving for the DISTINCT right keys instead of the rows - counted with returning adds - left fewer zero-filled
@@ -749,7 +749,7 @@ __device__ static inline void ld_leaf(const gc_args &a, ld_state &st, uint32_t l
 				const uint32_t want = need > GC_REC_CHUNK ? need : GC_REC_CHUNK;
 				const uint32_t nb = atomicAdd(a.rec_count, want);
 				if (nb + want > a.rec_cap) {
-					mdb_raise(a.status, 8u);
+					mdb_raise(a.status, MDB_ST_LIST_FULL);
 					s_chunk[0] = 0;
 					s_chunk[2] = 0;
 				} else {
@@ -802,7 +802,7 @@ __device__ static inline void ld_leaf(const gc_args &a, ld_state &st, uint32_t l
 						c *= st.s_cx[x * T + sl];
 						st.s_cx[x * T + sl] = 0u;
 						if (c >> 32) {		/* the product of the right counts no longer fits: reported, the caller chains 2-table operators */
-							mdb_raise(a.status, 2048u);
+							mdb_raise(a.status, GC_ST_PRODUCT_WIDE);
 							c = 0;
 						}
 					}
@@ -859,18 +859,18 @@ __device__ static inline void ld_leaf(const gc_args &a, ld_state &st, uint32_t l
 						mdb_raise(a.status, GC_ST_LEFT_DUPS);	/* (a matched key with several left rows: mdb_dev_join_keys_ordered asks) */
 					if (a.kbits && a.keyed_cbits) {
 						if (c >> a.keyed_cbits)
-							mdb_raise(a.status, 256u);	/* COUNT(*) does not fit a keyed record: redone with plain records */
+							mdb_raise(a.status, GC_ST_COUNT_NOT_KEYED);	/* COUNT(*) does not fit a keyed record: redone with plain records */
 						recv = ((unsigned long long)first << (64 - a.kbits)) |
 						       ((unsigned long long)((leaf << st.rem) | s) << a.keyed_cbits) | c;
 					} else if (a.kbits) {
 						if (c >> (64 - a.kbits))
-							mdb_raise(a.status, 4u);	/* COUNT(*) does not fit beside the row id */
+							mdb_raise(a.status, GC_ST_COUNT_NOT_REC64);	/* COUNT(*) does not fit beside the row id */
 						if (c >> (32 - (a.kbits < 32 ? a.kbits : 31)))
-							mdb_raise(a.status, 16u);	/* ... nor in a 4-byte record (the ordering sort then moves 8-byte ones) */
+							mdb_raise(a.status, GC_ST_COUNT_NOT_REC32);	/* ... nor in a 4-byte record (the ordering sort then moves 8-byte ones) */
 						recv = a.rec32 ? (unsigned long long)(((uint32_t)first << (32 - a.kbits)) | (uint32_t)c)
 							       : ((unsigned long long)first << (64 - a.kbits)) | c;
 						if (a.rec32 && (c >> (32 - a.kbits)))
-							mdb_raise(a.status, 512u);
+							mdb_raise(a.status, GC_ST_REC32_STALE);
 					} else {
 						if (first < a.dense_n)
 								a.dense_cnt[first] = (int64_t)c;
@@ -1131,7 +1131,7 @@ __global__ __launch_bounds__(GC_THREADS, 8) void k_hot_slices(gc_args a, hot_arg
 					s_key[s] = 0ull;
 				}
 				if (g == 0xFFFFFFFFu) {
-					mdb_raise(a.status, 1u);
+					mdb_raise(a.status, GC_ST_TABLE_FULL);
 				} else {
 					atomicAdd(&gc[g], c2);
 					if (is_l)
@@ -1173,14 +1173,14 @@ __global__ __launch_bounds__(1024) void k_hot_finish(gc_args a, hot_args h)
 		mine += c;
 		if (a.kbits) {
 			if (c >> (64 - a.kbits))
-				mdb_raise(a.status, 4u);
+				mdb_raise(a.status, GC_ST_COUNT_NOT_REC64);
 			if (c >> (32 - (a.kbits < 32 ? a.kbits : 31)))
-				mdb_raise(a.status, 16u);
+				mdb_raise(a.status, GC_ST_COUNT_NOT_REC32);
 			const uint32_t pos = atomicAdd(a.rec_count, 1u);
 			if (pos < a.rec_cap)
 				a.rec[pos] = ((unsigned long long)first << (64 - a.kbits)) | c;
 			else
-				mdb_raise(a.status, 8u);
+				mdb_raise(a.status, MDB_ST_LIST_FULL);
 			nvalid++;
 		} else {
 			if (first < a.dense_n)
@@ -1308,13 +1308,62 @@ struct gc_state {
 	uint64_t xn[GC_MAX_EXTRA];
 };
 
-struct gc_extras {
-	int n;
-	const int64_t *keys[GC_MAX_EXTRA];
-	const uint64_t *nulls[GC_MAX_EXTRA];
-	uint64_t rows[GC_MAX_EXTRA];
+/* one call of the operator as its entry points prepare it: the tables, where the result goes, and the plan so far - the part that
+ * group_count_common's retry loop edits between attempts */
+struct gc_table {
+	const int64_t *keys;
+	const uint64_t *nulls;
+	uint64_t n;
 };
-static thread_local const gc_extras *gc_pending_extras = NULL;	/* set by mdb_dev_join_group_count_multi around its call of the operator */
+struct gc_out {
+	int64_t *key, *count;
+	uint32_t *first;
+	uint64_t cap;
+	uint64_t *groups, *joined;
+};
+struct gc_request {
+	gc_table l, r;			/* (r.n: the rows announced, in the split form) */
+	gc_out out;
+	bool has_r, null_group, keys32;
+	int nextra;			/* further right tables on the same key (mdb_dev_join_group_count_multi) */
+	gc_table x[GC_MAX_EXTRA];
+	bool fast, records, no_build_r, narrow;
+	int64_t base;
+	gc_window win;
+};
+
+/* the state of one attempt from its request; own_call: begin and finish run back to back (gc_state.defer_ok, .own_call) */
+static void gc_state_fill(gc_state *st, const gc_request &rq, bool own_call)
+{
+	memset(st, 0, sizeof(*st));
+	st->keys_l = rq.l.keys;
+	st->null_l = rq.l.nulls;
+	st->n_l = rq.l.n;
+	st->n_r_cap = rq.r.n;
+	st->has_r = rq.has_r;
+	st->null_group = rq.null_group;
+	st->fast = rq.fast;
+	st->want_records = rq.records;
+	st->no_build_r = rq.no_build_r;
+	st->narrow = rq.narrow;
+	st->base = rq.base;
+	st->key_bits = rq.narrow ? rq.win.kbits : 0u;
+	st->key_lo = rq.win.lo;
+	st->selective = rq.win.selective;
+	st->fast1 = rq.win.fast1;
+	st->by_span = rq.win.by_span;
+	st->prunable = rq.win.prunable;
+	st->r_based = rq.win.r_based;
+	st->keys32 = rq.keys32;
+	st->defer_ok = own_call;
+	st->own_call = own_call;
+	st->nextra = rq.has_r ? rq.nextra : 0;
+	for (int x = 0; x < st->nextra; x++) {
+		st->xkeys[x] = rq.x[x].keys;
+		st->xnull[x] = rq.x[x].nulls;
+		st->xn[x] = rq.x[x].n;
+	}
+}
 
 /* a remembered "these columns overflow the digit-per-workgroup leaves' counts" (ctx->lw_bad_*) serves MDB_BAD_LEAF_USES calls */
 static bool gc_lw_bad(mdb_dev_ctx *ctx, const gc_state *st)
@@ -1582,148 +1631,161 @@ static void gc_explain_fill(mdb_dev_ctx *ctx, const gc_state *st, const int64_t 
 		o->groups_as_bits = gc_bits_by_stats(ctx, st->nextra, st->keys_l, keys_r, n_r) ? 3u : 1u /* (a pilot launch decides) */;
 }
 
-static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const int64_t *keys_r, const uint64_t *null_r, uint64_t n_r,
-		     int64_t *out_key, int64_t *out_count, uint32_t *out_first, uint64_t cap, uint64_t *out_groups,
-		     uint64_t *out_joined)
-{
-	const int64_t *keys_l = st->keys_l;
-	const uint64_t *null_l = st->null_l;
-	const uint64_t n_l = st->n_l;
-	const bool has_r = st->has_r, null_group = st->null_group, want_records = st->want_records;
-	/* hash table on the side with fewer rows per leaf (the leaves are sized by the left table) */
-	const bool build_r = has_r && !st->no_build_r && n_r <= n_l;
-	mdb_part_result pl = st->pl, pr;
-	int rc;
+/* ---- gc_finish, the operator's second half, in stages.  They share this record of what one attempt has decided and made so far. */
+struct gc_run {
+	gc_state *st;
+	gc_table r;			/* the right table */
+	gc_out out;
+	bool build_r;			/* hash table on the side with fewer rows per leaf (the leaves are sized by the left table) */
+	mdb_part_result pl, pr, px[GC_MAX_EXTRA];
+	bool records;			/* record mode (the groups sorted by first row id); false: dense mode, the fallback */
+	uint32_t kbits;
+	int sb1, sb2;
+	unsigned long long *rec;
+	int64_t *dense;
+	uint32_t *sel;
+	gc_args a;
+	uint32_t keyed_cbits;
+	bool leaf4;			/* one-level join through k_leaf_wide4 */
+	bool ranged;			/* ... that writes its records into the ordering kernel's ranges */
+	uint32_t rg_n;
+	bool ordered_early;		/* order_presorted was launched behind the leaf kernel, before the status came back */
+	unsigned long long *dn_bits;	/* != NULL: the groups leave as one bit per left row */
+	gc_readback *rb;		/* the status words as last read back (ctx->h_pinned + MDB_HP_STATUS) */
+	uint32_t dn_cleared, dn_exceptions;
+	uint64_t G, list_len;
+};
 
-	st->active = false;
-	memset(&pr, 0, sizeof(pr));
-	if (st->wide12) {
-		/* both tables through one 4096-digit pass each; a key outside the window is reported (the left table's, when the window was
-		 * taken from the right table's keys alone, is dropped: it has no partner) */
-		if (n_r > st->n_r_cap)
-			return mdb_set_err(ctx, -MIDORIDB_ERROR, "right table larger than announced at begin()");
-		void *rb = NULL, *lb = NULL;
-		uint32_t *rcur = NULL, *lcur = NULL;
-		const uint32_t cap_r = mdb_scatter4096_cap(ctx, n_r, false), cap_l = mdb_scatter4096_cap(ctx, n_l, true);
-		rc = mdb_scatter4096(ctx, keys_r, null_r, n_r, st->key_lo, st->key_bits, true, 0u, cap_r, false, "part_scatter_wide12_r", &rb, &rcur);
-		if (rc)
-			return rc;
-		rc = mdb_scatter4096(ctx, keys_l, null_l, n_l, st->key_lo, st->key_bits, !st->r_based, (uint32_t)((1ull << st->key_bits) - 1ull), cap_l, true,
-				     "part_scatter_wide12_l", &lb, &lcur);
-		if (rc)
-			return rc;
-		memset(&pl, 0, sizeof(pl));
-		pl.hv = (uint64_t *)lb;
-		pl.leaf_cnt = lcur;
-		pl.leaf_cap = cap_l;
-		pr.hv = (uint64_t *)rb;
-		pr.leaf_cnt = rcur;
-		pr.leaf_cap = cap_r;
-		pl.nleaves = pr.nleaves = 4096u;
-		pl.bits_total = pr.bits_total = 12u;
-		pl.nsub = pr.nsub = 8u;
-		pl.w32 = pr.w32 = true;
-		pr.w16 = true;
-	}
-	mdb_part_result px[GC_MAX_EXTRA];
-	memset(px, 0, sizeof(px));
-	if (st->wide12 && st->nextra) {
+/* stage 1a: both tables (and a further right one) through one 4096-digit pass each; a key outside the window is reported (the left table's, when the
+ * window was taken from the right table's keys alone, is dropped: it has no partner) */
+static int gc_partition_wide12(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	int rc;
+	if (g->r.n > st->n_r_cap)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "right table larger than announced at begin()");
+	void *rb = NULL, *lb = NULL;
+	uint32_t *rcur = NULL, *lcur = NULL;
+	const uint32_t cap_r = mdb_scatter4096_cap(ctx, g->r.n, false), cap_l = mdb_scatter4096_cap(ctx, st->n_l, true);
+	const uint32_t rel_hi = (uint32_t)((1ull << st->key_bits) - 1ull);
+	rc = mdb_scatter4096(ctx, g->r.keys, g->r.nulls, g->r.n, st->key_lo, st->key_bits, true, 0u, cap_r, false, "part_scatter_wide12_r", &rb, &rcur);
+	if (rc)
+		return rc;
+	rc = mdb_scatter4096(ctx, st->keys_l, st->null_l, st->n_l, st->key_lo, st->key_bits, !st->r_based, rel_hi, cap_l, true, "part_scatter_wide12_l", &lb, &lcur);
+	if (rc)
+		return rc;
+	memset(&g->pl, 0, sizeof(g->pl));
+	g->pl.hv = (uint64_t *)lb;
+	g->pl.leaf_cnt = lcur;
+	g->pl.leaf_cap = cap_l;
+	g->pr.hv = (uint64_t *)rb;
+	g->pr.leaf_cnt = rcur;
+	g->pr.leaf_cap = cap_r;
+	g->pl.nleaves = g->pr.nleaves = 4096u;
+	g->pl.bits_total = g->pr.bits_total = 12u;
+	g->pl.nsub = g->pr.nsub = 8u;
+	g->pl.w32 = g->pr.w32 = true;
+	g->pr.w16 = true;
+	if (st->nextra) {
 		/* the further right table like the first one; its keys outside the window are dropped, not reported: the window holds every key of
 		 * the left table, so such a key joins nothing */
 		void *xb = NULL;
 		uint32_t *xcur = NULL;
 		const uint32_t cap_x = mdb_scatter4096_cap(ctx, st->xn[0], false);
-		rc = mdb_scatter4096(ctx, st->xkeys[0], st->xnull[0], st->xn[0], st->key_lo, st->key_bits, false, (uint32_t)((1ull << st->key_bits) - 1ull), cap_x, false,
-				     "part_scatter_wide12_r", &xb, &xcur);
+		rc = mdb_scatter4096(ctx, st->xkeys[0], st->xnull[0], st->xn[0], st->key_lo, st->key_bits, false, rel_hi, cap_x, false, "part_scatter_wide12_r", &xb, &xcur);
 		if (rc)
 			return rc;
-		px[0].hv = (uint64_t *)xb;
-		px[0].leaf_cnt = xcur;
-		px[0].leaf_cap = cap_x;
+		g->px[0].hv = (uint64_t *)xb;
+		g->px[0].leaf_cnt = xcur;
+		g->px[0].leaf_cap = cap_x;
 	}
-	if (has_r && !st->wide12) {
-		if (n_r > st->n_r_cap)
-			return mdb_set_err(ctx, -MIDORIDB_ERROR, "right table larger than announced at begin()");
-		if (st->narrow && !st->one_level && !mdb_partition_w32_applies(n_r, st->b1, st->b2, st->fast))
-			return GC_RETRY_WIDE;	/* split form: the left side was prepared narrow for a right table of another size */
-		mdb_part_filter rflt;
-		memset(&rflt, 0, sizeof(rflt));
-		rflt.level0_only = st->one_level;
-		rflt.out16 = st->one_level && !mdb_knob_off("MDB_WORDS16");
-		if (st->own_call) {
-			rflt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF;
-			rflt.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
-		}
-		if (st->defer_l) {
-			/* [16] smallest, [17] largest key - window base of the right table (min-max pruning) */
-			rflt.minmax_out = ctx->d_status + GC_ST_MINMAX;
-			rflt.minmax_tiles = (uint32_t *)mdb_arena_take(ctx, mdb_part_minmax_words(n_r) * 4);
-			if (!rflt.minmax_tiles)
-				return -MIDORIDB_INTERNAL;
-		}
-		if (st->defer_l64) {
-			/* [GC_ST_MINMAX64 ..]: smallest, largest key of the right table as two signed 64-bit words */
-			rflt.minmax64_out = reinterpret_cast<long long *>(ctx->d_status + GC_ST_MINMAX64);
-			rflt.minmax64_tiles = (unsigned long long *)mdb_arena_take(ctx, mdb_part_minmax_words(n_r) * 8);
-			if (!rflt.minmax64_tiles)
-				return -MIDORIDB_INTERNAL;
-		}
-		rc = mdb_partition_table(ctx, keys_r, null_r, n_r, st->b1, st->b2, false, false, st->fast, &pr, st->narrow ? 2 : 0, st->keys32,
-					 st->direct ? st->key_lo : st->base, st->direct ? st->key_bits : 0u,
-					 (st->defer_l || st->one_level || st->defer_l64) ? &rflt : NULL);
-		if (rc)
-			return rc;
+	return MIDORIDB_OK;
+}
+
+/* stage 1b: the right table through the radix levels; where the left table waits for it, it leaves its key range behind (min-max pruning) */
+static int gc_partition_right(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	if (g->r.n > st->n_r_cap)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "right table larger than announced at begin()");
+	if (st->narrow && !st->one_level && !mdb_partition_w32_applies(g->r.n, st->b1, st->b2, st->fast))
+		return GC_RETRY_WIDE;	/* split form: the left side was prepared narrow for a right table of another size */
+	mdb_part_filter rflt;
+	memset(&rflt, 0, sizeof(rflt));
+	rflt.level0_only = st->one_level;
+	rflt.out16 = st->one_level && !mdb_knob_off("MDB_WORDS16");
+	if (st->own_call) {
+		rflt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF;
+		rflt.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
+	}
+	if (st->defer_l) {
+		rflt.minmax_out = ctx->d_status + GC_STW_MINMAX;
+		rflt.minmax_tiles = (uint32_t *)mdb_arena_take(ctx, mdb_part_minmax_words(g->r.n) * 4);
+		if (!rflt.minmax_tiles)
+			return -MIDORIDB_INTERNAL;
 	}
 	if (st->defer_l64) {
-		mdb_part_filter flt;
-		memset(&flt, 0, sizeof(flt));
-		flt.range64_in = reinterpret_cast<const long long *>(ctx->d_status + GC_ST_MINMAX64);
-		flt.expect_pruned = st->by_span;
-		rc = mdb_partition_table(ctx, keys_l, null_l, n_l, st->b1, st->b2, true, false, st->fast, &st->pl, 0, st->keys32, st->base, 0u, &flt);
+		rflt.minmax64_out = reinterpret_cast<long long *>(ctx->d_status + GC_STW_MINMAX64);
+		rflt.minmax64_tiles = (unsigned long long *)mdb_arena_take(ctx, mdb_part_minmax_words(g->r.n) * 8);
+		if (!rflt.minmax64_tiles)
+			return -MIDORIDB_INTERNAL;
+	}
+	return mdb_partition_table(ctx, g->r.keys, g->r.nulls, g->r.n, st->b1, st->b2, false, false, st->fast, &g->pr, st->narrow ? 2 : 0, st->keys32,
+				   st->direct ? st->key_lo : st->base, st->direct ? st->key_bits : 0u,
+				   (st->defer_l || st->one_level || st->defer_l64) ? &rflt : NULL);
+}
+
+/* stage 1c: the further right tables, partitioned exactly like the first: same window, same bits, 4-byte words.  Their keys outside the window are
+ * dropped, not reported: the window holds every key of the left table (or of the first right table, with the left one pruned to it), so such a
+ * key joins nothing */
+static int gc_partition_extras(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned + MDB_HP_SEND_RANGE);
+	h[0] = 0u;
+	h[1] = st->key_bits >= 32u ? 0xFFFFFFFFu : ((1u << st->key_bits) - 1u);
+	MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status + GC_STW_WINDOW, h, 8, hipMemcpyHostToDevice, ctx->stream));
+	for (int x = 0; x < st->nextra; x++) {
+		mdb_part_filter xf;
+		memset(&xf, 0, sizeof(xf));
+		xf.range_in = ctx->d_status + GC_STW_WINDOW;
+		if (!mdb_partition_w32_applies(st->xn[x], st->b1, st->b2, st->fast))
+			return GC_NOT_SERVED;
+		int rc = mdb_partition_table(ctx, st->xkeys[x], st->xnull[x], st->xn[x], st->b1, st->b2, false, false, st->fast, &g->px[x], 2, st->keys32,
+					     st->key_lo, st->key_bits, &xf);
 		if (rc)
 			return rc;
-		pl = st->pl;
+		if (!g->px[x].w32 || !g->px[x].leaf_cap || !g->px[x].leaf_cnt || g->px[x].nleaves != (1u << (st->b1 + st->b2)))
+			return GC_NOT_SERVED;
 	}
-	if (st->nextra && !st->wide12) {
-		/* the further right tables, partitioned exactly like the first: same window, same bits, 4-byte words.  Their keys
-		 * outside the window are dropped, not reported: the window holds every key of the left table (or of the first right
-		 * table, with the left one pruned to it), so such a key joins nothing */
-		uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned) + 520;
-		h[0] = 0u;
-		h[1] = st->key_bits >= 32u ? 0xFFFFFFFFu : ((1u << st->key_bits) - 1u);
-		MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status + GC_ST_WINDOW, h, 8, hipMemcpyHostToDevice, ctx->stream));
-		for (int x = 0; x < st->nextra; x++) {
-			mdb_part_filter xf;
-			memset(&xf, 0, sizeof(xf));
-			xf.range_in = ctx->d_status + GC_ST_WINDOW;
-			if (!mdb_partition_w32_applies(st->xn[x], st->b1, st->b2, st->fast))
-				return GC_NOT_SERVED;
-			rc = mdb_partition_table(ctx, st->xkeys[x], st->xnull[x], st->xn[x], st->b1, st->b2, false, false, st->fast, &px[x], 2, st->keys32,
-						 st->key_lo, st->key_bits, &xf);
-			if (rc)
-				return rc;
-			if (!px[x].w32 || !px[x].leaf_cap || !px[x].leaf_cnt || px[x].nleaves != (1u << (st->b1 + st->b2)))
-				return GC_NOT_SERVED;
-		}
-	}
-	if (st->defer_l && !st->semijoin) {
-		mdb_part_filter flt;
-		memset(&flt, 0, sizeof(flt));
-		flt.range_in = ctx->d_status + GC_ST_MINMAX;
+	return MIDORIDB_OK;
+}
+
+/* stage 1d: the left table where it waited for the right one - pruned to the right table's key range (64-bit form, or narrow form), or filtered
+ * through a bitmap of the right table's hashed keys (semi-join) */
+static int gc_partition_left(mdb_dev_ctx *ctx, gc_run *g, bool form64)
+{
+	gc_state *st = g->st;
+	mdb_part_filter flt;
+	memset(&flt, 0, sizeof(flt));
+	int rc;
+	if (form64) {
+		flt.range64_in = reinterpret_cast<const long long *>(ctx->d_status + GC_STW_MINMAX64);
+		flt.expect_pruned = st->by_span;
+		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, true, false, st->fast, &st->pl, 0, st->keys32, st->base, 0u, &flt);
+	} else if (!st->semijoin) {
+		flt.range_in = ctx->d_status + GC_STW_MINMAX;
 		flt.expect_pruned = st->by_span && !st->one_level;
 		flt.level0_only = st->one_level;
 		if (st->own_call) {
 			flt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF + MDB_ZERO_BLK_SLOT;
 			flt.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
 		}
-		rc = mdb_partition_table(ctx, keys_l, null_l, n_l, st->b1, st->b2, false, false, st->fast, &st->pl, 1, st->keys32,
+		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, false, false, st->fast, &st->pl, 1, st->keys32,
 					 st->direct ? st->key_lo : st->base, st->direct ? st->key_bits : 0u, &flt);
-		if (rc)
-			return rc;
-		pl = st->pl;
-	}
-	if (st->semijoin) {
+	} else {
 		/* the right table's hashed keys as a bitmap, then the left table through it */
+		const mdb_part_result &pr = g->pr;
 		const uint32_t coarse = st->semijoin - 1u, rem = st->key_bits - (uint32_t)(st->b1 + st->b2);
 		const size_t bytes = ((size_t)1 << (st->key_bits - coarse)) / 8;
 		uint32_t *bits = (uint32_t *)mdb_arena_take(ctx, bytes);
@@ -1734,475 +1796,635 @@ static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const int64_t *keys_r, cons
 		const uint32_t groups = (pr.nleaves + LB_WAVES - 1) / LB_WAVES, resident = 16u * (uint32_t)ctx->num_cus;
 		MDB_LAUNCH(ctx, "leaf_bitmap", k_leaf_bitmap, groups < resident ? groups : resident, LB_WAVES * MDB_WAVE,
 			   reinterpret_cast<const uint32_t *>(pr.hv), pr.leaf_cnt, pr.leaf_cap, pr.nleaves, rem, coarse, 32u - st->key_bits, bits);
-		mdb_part_filter flt;
-		memset(&flt, 0, sizeof(flt));
-		flt.range_in = ctx->d_status + GC_ST_MINMAX;
+		flt.range_in = ctx->d_status + GC_STW_MINMAX;
 		flt.expect_pruned = st->by_span;
 		flt.bits = bits;
 		flt.words = 1u << (st->key_bits - (uint32_t)st->b1 - coarse - 5u);
 		flt.shift = 32u - st->key_bits + coarse;
-		rc = mdb_partition_table(ctx, keys_l, null_l, n_l, st->b1, st->b2, false, false, st->fast, &st->pl, 1, st->keys32, st->key_lo, st->key_bits,
+		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, false, false, st->fast, &st->pl, 1, st->keys32, st->key_lo, st->key_bits,
 					 &flt);
-		if (rc)
-			return rc;
-		pl = st->pl;
 	}
-	/* ---- result ordering: record mode (sort the groups by first row id) or dense mode (fallback) */
-	uint32_t kbits = 0;
-	int sb1 = 0, sb2 = 0;
-	const bool records = want_records && order_bits(n_l, &kbits, &sb1, &sb2);
-	const uint32_t ord_range = records ? (1u << (kbits - (uint32_t)(sb1 + sb2))) : 0;
-	int64_t *dense = NULL;
-	unsigned long long *rec = NULL;
-	uint32_t *sel = (uint32_t *)mdb_arena_take(ctx, n_l * 4);
-	if (records) {
-		rec = (unsigned long long *)mdb_arena_take(ctx, gc_rec_capacity(ctx, n_l) * 8);
-	} else {
-		dense = (int64_t *)mdb_arena_take(ctx, n_l * 8);
-	}
-	if (!sel || (!rec && !dense))
-		return -MIDORIDB_INTERNAL;
-	/* d_status u32 words: [0] flags, [1] record-list length, [2..3] joined rows (u64), [4..7] NULL-group stats,
-	 * [8] number of records (groups) */
-	uint32_t *d_rec_count = ctx->d_status + 1;
-	uint32_t *d_rec_valid = ctx->d_status + 8;
-	unsigned long long *d_joined = (unsigned long long *)(ctx->d_status + 2);
-	unsigned long long *d_nullst = (unsigned long long *)(ctx->d_status + 4);
-	if (dense)
-		MDB_HIP(ctx, hipMemsetAsync(dense, 0, n_l * 8, ctx->stream));
+	if (!rc)
+		g->pl = st->pl;
+	return rc;
+}
 
-	gc_args a;
-	a.hv_l = pl.hv;
-	a.rid_l = pl.rid;
-	a.off_l = pl.leaf_off;
-	a.cnt_l = pl.leaf_cnt;
-	a.cap_l = pl.leaf_cap;
-	a.hv_r = pr.hv;
-	a.off_r = pr.leaf_off;
-	a.cnt_r = pr.leaf_cnt;
-	a.cap_r = pr.leaf_cap;
-	a.dense_cnt = dense;
+/* stage 1: every table that gc_begin has not partitioned, in the order the stream needs them */
+static int gc_partition(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	int rc;
+	if (st->wide12 && (rc = gc_partition_wide12(ctx, g)))
+		return rc;
+	if (st->has_r && !st->wide12 && (rc = gc_partition_right(ctx, g)))
+		return rc;
+	if (st->defer_l64 && (rc = gc_partition_left(ctx, g, true)))
+		return rc;
+	if (st->nextra && !st->wide12 && (rc = gc_partition_extras(ctx, g)))
+		return rc;
+	if (((st->defer_l && !st->semijoin) || st->semijoin) && (rc = gc_partition_left(ctx, g, false)))
+		return rc;
+	return MIDORIDB_OK;
+}
+
+/* stage 2a: the result's buffers - record mode (sort the groups by first row id) or dense mode (fallback) - and the leaf kernels' arguments as far
+ * as the partitioned tables fix them */
+static int gc_args_begin(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	const uint64_t n_l = st->n_l;
+	g->records = st->want_records && order_bits(n_l, &g->kbits, &g->sb1, &g->sb2);
+	g->sel = (uint32_t *)mdb_arena_take(ctx, n_l * 4);
+	if (g->records)
+		g->rec = (unsigned long long *)mdb_arena_take(ctx, gc_rec_capacity(ctx, n_l) * 8);
+	else
+		g->dense = (int64_t *)mdb_arena_take(ctx, n_l * 8);
+	if (!g->sel || (!g->rec && !g->dense))
+		return -MIDORIDB_INTERNAL;
+	if (g->dense)
+		MDB_HIP(ctx, hipMemsetAsync(g->dense, 0, n_l * 8, ctx->stream));
+	gc_args &a = g->a;
+	a.hv_l = g->pl.hv;
+	a.rid_l = g->pl.rid;
+	a.off_l = g->pl.leaf_off;
+	a.cnt_l = g->pl.leaf_cnt;
+	a.cap_l = g->pl.leaf_cap;
+	a.hv_r = g->pr.hv;
+	a.off_r = g->pr.leaf_off;
+	a.cnt_r = g->pr.leaf_cnt;
+	a.cap_r = g->pr.leaf_cap;
+	a.dense_cnt = g->dense;
 	a.dense_n = (uint32_t)n_l;
-	a.rec = rec;
-	a.rec_count = d_rec_count;
-	a.rec_valid = d_rec_valid;
-	a.rec_cap = records ? (uint32_t)gc_rec_capacity(ctx, n_l) : 0;
-	a.kbits = records ? kbits : 0;
-	a.joined = d_joined;
+	a.rec = g->rec;
+	a.rec_count = ctx->d_status + GC_STW_LIST_LEN;
+	a.rec_valid = ctx->d_status + GC_STW_RECORDS;
+	a.rec_cap = g->records ? (uint32_t)gc_rec_capacity(ctx, n_l) : 0;
+	a.kbits = g->records ? g->kbits : 0;
+	a.joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
 	a.status = ctx->d_status;
-	a.nleaves = pl.nleaves;
+	a.nleaves = g->pl.nleaves;
 	a.nextra = (uint32_t)st->nextra;
 	for (int x = 0; x < GC_MAX_EXTRA; x++) {
-		a.hv_x[x] = x < st->nextra ? reinterpret_cast<const uint32_t *>(px[x].hv) : NULL;
-		a.cnt_x[x] = x < st->nextra ? px[x].leaf_cnt : NULL;
-		a.cap_x[x] = x < st->nextra ? px[x].leaf_cap : 0u;
+		a.hv_x[x] = x < st->nextra ? reinterpret_cast<const uint32_t *>(g->px[x].hv) : NULL;
+		a.cnt_x[x] = x < st->nextra ? g->px[x].leaf_cnt : NULL;
+		a.cap_x[x] = x < st->nextra ? g->px[x].leaf_cap : 0u;
 	}
 	a.narrow = st->narrow ? 1u : 0u;
+	/* 4096 sampled keys with fewer than 4050 distinct values among them: at most a few 10^5 distinct values in the column */
+	a.merge_all = (!st->has_r && ctx->gh_keys == st->keys_l && ctx->gh_n == n_l && ctx->gh_distinct < 4050u) ? 1u : 0u;
+	/* hot = far above the side's average leaf: a much larger probe table spread evenly over the leaves is not skew */
+	const uint64_t nleaves = g->pl.nleaves ? g->pl.nleaves : 1;
+	const uint64_t avg_l = n_l / nleaves, avg_r = st->has_r ? g->r.n / nleaves : 0;
+	const uint64_t hl = 8 * avg_l > GC_HEAVY ? 8 * avg_l : GC_HEAVY, hr = 8 * avg_r > GC_HEAVY ? 8 * avg_r : GC_HEAVY;
+	a.heavy_l = hl > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hl;
+	a.heavy_r = hr > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hr;
+	return MIDORIDB_OK;
+}
+
+/* stage 2b: the form of the group records - keyed, 4-byte, written into the ordering ranges - from what the context remembers of these columns */
+static int gc_choose_records(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	gc_args &a = g->a;
+	const mdb_part_result &pl = g->pl, &pr = g->pr;
+	const int64_t *keys_l = st->keys_l, *keys_r = g->r.keys;
+	const uint64_t n_l = st->n_l, n_r = g->r.n;
+	const bool has_r = st->has_r, records = g->records;
+	const uint32_t kbits = g->kbits;
 	/* keyed records (see gc_args.keyed_cbits) when the join is selective - few groups, their first rows scattered over the left
 	 * table - and a COUNT(*) of at least 4 bits fits beside the row id and the hashed key (10 bits at 10^8 rows, 27 key bits);
 	 * a COUNT that does not fit is reported by the kernel and the operator redone with plain records (and remembered).
 	 * MDB_KEYED_RECORDS=0 switches them off */
-	uint32_t keyed_cbits = 0;
+	g->keyed_cbits = 0;
 	if (st->direct && has_r && !st->nextra && st->selective && records && !ctx->keyed_distrust && pl.leaf_cap && pr.leaf_cap && kbits >= 13 &&
 	    kbits + st->key_bits + 4u <= 64u && !mdb_knob_off("MDB_KEYED_RECORDS"))
-		keyed_cbits = 64u - kbits - st->key_bits;
+		g->keyed_cbits = 64u - kbits - st->key_bits;
 	if (ctx->keyed_distrust > 0)
 		ctx->keyed_distrust--;
-	a.keyed_cbits = keyed_cbits;
+	a.keyed_cbits = g->keyed_cbits;
 	/* 4-byte records straight from the leaf kernel when the last run over these very columns saw every COUNT(*) fit beside the
 	 * row id (variant U: 10^8 records - 0.4 GB less to write and 0.4 GB less for the ordering sort to read) */
 	const bool r32_same = ctx->r32_ok && ctx->r32_kl == keys_l && ctx->r32_nl == n_l && ctx->r32_kr == keys_r && ctx->r32_nr == n_r;
-	a.rec32 = (r32_same && st->direct && !st->one_level && has_r && records && !keyed_cbits && kbits < 32 && sb2 > 0 && pl.leaf_cap && pr.leaf_cap) ? 1u : 0u;
-	/* 4096 sampled keys with fewer than 4050 distinct values among them: at most a few 10^5 distinct values in the column */
-	a.merge_all = (!has_r && ctx->gh_keys == keys_l && ctx->gh_n == n_l && ctx->gh_distinct < 4050u) ? 1u : 0u;
-	{
-		/* hot = far above the side's average leaf: a much larger probe table spread evenly over the leaves is not skew */
-		const uint64_t avg_l = n_l / (pl.nleaves ? pl.nleaves : 1), avg_r = has_r ? n_r / (pl.nleaves ? pl.nleaves : 1) : 0;
-		const uint64_t hl = 8 * avg_l > GC_HEAVY ? 8 * avg_l : GC_HEAVY, hr = 8 * avg_r > GC_HEAVY ? 8 * avg_r : GC_HEAVY;
-		a.heavy_l = hl > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hl;
-		a.heavy_r = hr > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hr;
-	}
+	a.rec32 = (r32_same && st->direct && !st->one_level && has_r && records && !g->keyed_cbits && kbits < 32 && g->sb2 > 0 && pl.leaf_cap && pr.leaf_cap) ? 1u : 0u;
 	/* one-level joins with 2-byte right words: k_leaf_wide4's 4 bytes per key value (two workgroups per CU) unless these columns are known to
 	 * hold more than 31 right or 15 left rows of a key */
-	const bool leaf4 = st->one_level && has_r && pr.w16 && records && !null_group && n_l <= (1ull << 27) && st->key_bits >= (uint32_t)pl.bits_total + 10u &&
-			   !(ctx->l4_bad_keys == keys_l && ctx->l4_bad_nl == n_l && ctx->l4_bad_nr == n_r && ++ctx->l4_bad_uses <= MDB_BAD_LEAF_USES);
+	g->leaf4 = st->one_level && has_r && pr.w16 && records && !st->null_group && n_l <= (1ull << 27) && st->key_bits >= (uint32_t)pl.bits_total + 10u &&
+		   !(ctx->l4_bad_keys == keys_l && ctx->l4_bad_nl == n_l && ctx->l4_bad_nr == n_r && ++ctx->l4_bad_uses <= MDB_BAD_LEAF_USES);
 	/* ... and when the last join over these very columns told how many groups to expect, and they are few enough for the ordering kernel's
 	 * ranges of 2^16 row ids, k_leaf_wide4 writes its records straight into those ranges: no record list, none of the two scatter levels that
 	 * would partition it by row id */
-	uint32_t rg_n = 0;
-	bool ranged = leaf4 && ctx->lg_valid && !ctx->lg_nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r &&
-		      order_ranges_apply(n_l, kbits, ctx->lg_groups + ctx->lg_groups / 8, &rg_n);
+	g->rg_n = 0;
+	g->ranged = g->leaf4 && ctx->lg_valid && !ctx->lg_nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r &&
+		    order_ranges_apply(n_l, kbits, ctx->lg_groups + ctx->lg_groups / 8, &g->rg_n);
 	/* ... or the caller's statistics say so before any join has run (mdb_dev_call_stats): a group needs a right key, and there are at
 	 * most as many of those as values in the right column's range */
-	if (!ranged && leaf4)
-		ranged = gc_ranged_by_stats(ctx, keys_l, keys_r, n_l, n_r, kbits, &rg_n);
+	if (!g->ranged && g->leaf4)
+		g->ranged = gc_ranged_by_stats(ctx, keys_l, keys_r, n_l, n_r, kbits, &g->rg_n);
 	a.rg_rec = NULL;
 	a.rg_cnt = NULL;
 	a.rg_cap = a.rg_shift = a.rg_n = 0;
-	if (ranged) {
-		a.rg_rec = (unsigned long long *)mdb_arena_take(ctx, (size_t)rg_n * ORDER_RANGE_CAP * 8);
-		const bool rg_in_block = st->own_call && rg_n <= MDB_ZERO_BLK_WORDS - 2u * MDB_ZERO_BLK_SLOT;
-		a.rg_cnt = rg_in_block ? ctx->d_status + MDB_ZERO_BLK_OFF + 2u * MDB_ZERO_BLK_SLOT : (uint32_t *)mdb_arena_take(ctx, (size_t)rg_n * 4);
+	if (g->ranged) {
+		a.rg_rec = (unsigned long long *)mdb_arena_take(ctx, (size_t)g->rg_n * ORDER_RANGE_CAP * 8);
+		const bool rg_in_block = st->own_call && g->rg_n <= MDB_ZERO_BLK_WORDS - 2u * MDB_ZERO_BLK_SLOT;
+		a.rg_cnt = rg_in_block ? ctx->d_status + MDB_ZERO_BLK_OFF + 2u * MDB_ZERO_BLK_SLOT : (uint32_t *)mdb_arena_take(ctx, (size_t)g->rg_n * 4);
 		if (!a.rg_rec || !a.rg_cnt)
 			return -MIDORIDB_INTERNAL;
 		/* (the arena hands out whole 256-byte units: cleared as such - a length that is no multiple of 16 bytes costs the runtime a second fill
 		 * kernel, 5 us of the step) */
 		if (!rg_in_block)
-			MDB_HIP(ctx, hipMemsetAsync(a.rg_cnt, 0, mdb_align_up((size_t)rg_n * 4), ctx->stream));
+			MDB_HIP(ctx, hipMemsetAsync(a.rg_cnt, 0, mdb_align_up((size_t)g->rg_n * 4), ctx->stream));
 		a.rg_cap = ORDER_RANGE_CAP;
 		a.rg_shift = ORDER_RANGE_BITS;
-		a.rg_n = rg_n;
+		a.rg_n = g->rg_n;
 	}
-	/* The last join over these columns made nearly every left row a group of COUNT 1 (a primary key joined with another, or with its
-	 * foreign keys - BASELINE configs[2]'s variant U): k_leaf_wide12 then clears one bit per left row that is NO group's first row and
-	 * lists the groups whose COUNT is not 1, instead of a record per group and the ordering sort of 10^8 records (MDB_JOIN_BITS=0: never) */
-	unsigned long long *dn_bits = NULL;
+	return MIDORIDB_OK;
+}
+
+/* stage 2c: The last join over these columns made nearly every left row a group of COUNT 1 (a primary key joined with another, or with its
+ * foreign keys - BASELINE configs[2]'s variant U): k_leaf_wide12 then clears one bit per left row that is NO group's first row and
+ * lists the groups whose COUNT is not 1, instead of a record per group and the ordering sort of 10^8 records (MDB_JOIN_BITS=0: never) */
+static int gc_choose_bits(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	gc_args &a = g->a;
+	const int64_t *keys_l = st->keys_l, *keys_r = g->r.keys;
+	const uint64_t n_l = st->n_l, n_r = g->r.n;
+	int rc;
+	g->dn_bits = NULL;
 	a.dn_bits = NULL;
 	a.dn_exc = NULL;
 	a.dn_exc_cap = 0;
 	a.dn_pilot = 0;
-	a.dn_cnt = ctx->d_status + 12;
+	a.dn_cnt = ctx->d_status + GC_STW_DN_CLEARED;
 	/* (every left row must reach the leaf kernel for its bit to be looked at: no NULL keys, no window that covers the right table's keys
 	 * only - left rows outside it are dropped by the first level; rows dropped for another reason show as G + cleared != n_l below and
 	 * send the call to the record form) */
-	if (gc_bits_possible(st, records, has_r, cap, n_l)) {
-		bool want_bits = false, by_pilot = false, by_stats = false;
-		/* The catalog says (MDB_COL_DISTINCT, measured at ingest): no key twice in the left column, none twice in the right one, and the
-		 * right column holds EVERY value of its range, which covers the left column's - every left row is a group of COUNT 1, whatever
-		 * the statement before this one was: no pilot launch and its host round trip, nothing remembered by the columns' addresses.
-		 * (Two tables only; a promise that does not hold shows below as it does for the other two ways to get here: G + cleared != n_l,
-		 * or more exceptions than the list holds - the call is redone with records.) */
-		if (gc_bits_by_stats(ctx, st->nextra, keys_l, keys_r, n_r)) {
-			want_bits = true;
-			by_stats = true;
-		} else if (ctx->lg_valid && ctx->lg_nextra == (uint32_t)st->nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r) {
-			/* (what the last join over these very columns delivered) */
-			if (ctx->lg_groups >= n_l - n_l / 16 && ctx->lg_joined <= ctx->lg_groups + ctx->lg_groups / 16) {
-				if (ctx->dn_distrust > 0)
-					ctx->dn_distrust--;
-				else
-					want_bits = true;
-			}
-		} else {
-			/* nothing remembered (a first statement): the pilot - the same kernel over the first 64 of the 4096 digits (all rows of a key are
-			 * in one digit: a fair sample of the keys), nothing written but the counters: left rows that are no group's first row, groups
-			 * whose COUNT is not 1.  One in 16 of the rows at most each: the bit-per-row form */
-			a.dn_pilot = 64;
-			if ((rc = leaf_wide12_launch(ctx, a, pl.nleaves, st->key_bits - 12u, pl.nsub, st->nextra)))
-				return rc;
-			a.dn_pilot = 0;
-			uint64_t *hp = ctx->h_pinned;
-			MDB_HIP(ctx, hipMemcpyAsync(&hp[1], ctx->d_status, 56, hipMemcpyDeviceToHost, ctx->stream));
-			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			const uint32_t *pw = reinterpret_cast<const uint32_t *>(&hp[1]);
-			const uint64_t p_groups = pw[8], p_cleared = pw[12], p_exc = pw[13], p_rows = p_groups + p_cleared;
-			want_bits = p_rows && p_cleared * 16 <= p_rows && p_exc * 16 <= p_rows;
-			by_pilot = true;
-			if (mdb_knob_set("MDB_DEBUG_GROUP"))
-				fprintf(stderr, "join + GROUP BY (pilot over 64 digits): %llu left rows, %llu no group's first row, %llu groups of COUNT != 1 -> %s\n",
-					(unsigned long long)p_rows, (unsigned long long)p_cleared, (unsigned long long)p_exc, want_bits ? "a bit per left row" : "records");
-			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 13 * sizeof(uint32_t), ctx->stream));	/* (the flags of word 0 stay: they are facts about the data) */
-		}
-		if (want_bits) {
-			if ((rc = mdb_dense_bits_begin(ctx, n_l, &dn_bits)))
-				return rc;
-			a.dn_bits = reinterpret_cast<unsigned int *>(dn_bits);
-			a.dn_exc_cap = (uint32_t)(n_l / 8 + 4096);
-			a.dn_exc = (unsigned long long *)mdb_arena_take(ctx, (size_t)a.dn_exc_cap * 8);
-			if (!a.dn_exc)
-				return -MIDORIDB_INTERNAL;
-			ctx->plan.groups_as_bits = by_stats ? 3u : by_pilot ? 1u : 2u;
-		}
-	}
-	{
-		/* persistent grid: two 75 KiB workgroups fit one CU's 160 KiB of LDS */
-		const uint32_t resident = 2u * (uint32_t)ctx->num_cus;
-		const uint32_t grid = pl.nleaves < resident ? pl.nleaves : resident;
-		/* (the direct kernel addresses leaf i at i * cap: should a table have fallen back to exact offsets - more than 2^32
-		 * region words - the hashed kernel below joins the compact words just as well, they are injective too) */
-		if (st->wide12) {
-			if ((rc = leaf_wide12_launch(ctx, a, pl.nleaves, st->key_bits - 12u, pl.nsub, st->nextra)))
-				return rc;
-		} else if (st->one_level) {
-			/* ... by ALL the hash bits below the first level's 9 (k_leaf_wide) */
-			if (!pl.nsub || !pl.leaf_cap || (has_r && (!pr.nsub || !pr.w32 || pr.nsub != pl.nsub || pr.nleaves != pl.nleaves)))
-				return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "one-level direct leaves: the tables are not in the first-level layout");
-			const uint32_t rem = st->key_bits - pl.bits_total, shift = 32u - st->key_bits;
-			if (has_r && pr.w16 && leaf4)
-				rc = leaf_wide4_launch(ctx, a, pl.nleaves, rem, shift, pl.nsub);
+	if (!gc_bits_possible(st, g->records, st->has_r, g->out.cap, n_l))
+		return MIDORIDB_OK;
+	bool want_bits = false, by_pilot = false, by_stats = false;
+	/* The catalog says (MDB_COL_DISTINCT, measured at ingest): no key twice in the left column, none twice in the right one, and the
+	 * right column holds EVERY value of its range, which covers the left column's - every left row is a group of COUNT 1, whatever
+	 * the statement before this one was: no pilot launch and its host round trip, nothing remembered by the columns' addresses.
+	 * (Two tables only; a promise that does not hold shows below as it does for the other two ways to get here: G + cleared != n_l,
+	 * or more exceptions than the list holds - the call is redone with records.) */
+	if (gc_bits_by_stats(ctx, st->nextra, keys_l, keys_r, n_r)) {
+		want_bits = true;
+		by_stats = true;
+	} else if (ctx->lg_valid && ctx->lg_nextra == (uint32_t)st->nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r) {
+		/* (what the last join over these very columns delivered) */
+		if (ctx->lg_groups >= n_l - n_l / 16 && ctx->lg_joined <= ctx->lg_groups + ctx->lg_groups / 16) {
+			if (ctx->dn_distrust > 0)
+				ctx->dn_distrust--;
 			else
-				rc = leaf_wide_launch(ctx, a, pl.nleaves, rem, shift, pl.nsub, has_r, has_r && pr.w16);
-			if (rc)
-				return rc;
-		} else if (st->direct && pl.leaf_cap && (!has_r || pr.leaf_cap)) {
-			/* compact narrow form: the leaf's table is indexed by the hash bits the partition left over */
-			const uint32_t rem = st->key_bits - pl.bits_total, shift = 32u - st->key_bits;
-			if (st->nextra && !(pl.leaf_cap && pr.leaf_cap))
-				return GC_NOT_SERVED;
-			const size_t lds = ((size_t)(12 + 4 * st->nextra) << rem) + 32;
-			/* four 512-thread workgroups = the CU's 32 waves (three measured the same, 256-thread workgroups 10-30 % slower) */
-			uint32_t per_cu = (uint32_t)((size_t)(160 * 1024) / lds);
-			per_cu = per_cu > 4 ? 4 : (per_cu < 1 ? 1 : per_cu);
-			const uint32_t dgrid = pl.nleaves < per_cu * (uint32_t)ctx->num_cus ? pl.nleaves : per_cu * (uint32_t)ctx->num_cus;
-			if (has_r) {
-				MDB_LAUNCH_LDS(ctx, "leaf_join_direct", (k_leaf_direct<true, 512, 2048>), dgrid, 512, lds, a, rem, shift);
-			} else {
-				MDB_LAUNCH_LDS(ctx, "leaf_group_direct", (k_leaf_direct<false, 512, 2048>), dgrid, 512, lds, a, rem, shift);
-			}
-		} else if (st->nextra) {
-			return GC_NOT_SERVED;
-		} else if (has_r && build_r && st->narrow) {
-			MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, true, false, true>), grid, GC_THREADS, a);
-		} else if (has_r && build_r) {
-			MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, true, false>), grid, GC_THREADS, a);
-		} else if (has_r && st->narrow) {
-			MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, false, false, true>), grid, GC_THREADS, a);
-		} else if (has_r) {
-			MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, false, false>), grid, GC_THREADS, a);
-		} else if (st->narrow) {
-			MDB_LAUNCH(ctx, "leaf_group_count", (k_leaf_group_count<false, false, false, true>), grid, GC_THREADS, a);
-		} else {
-			MDB_LAUNCH(ctx, "leaf_group_count", (k_leaf_group_count<false, false, false>), grid, GC_THREADS, a);
+				want_bits = true;
 		}
-	}
-	if (null_group && null_l) {
-		MDB_HIP(ctx, hipMemsetAsync(d_nullst + 1, 0xFF, 8, ctx->stream));
-		MDB_LAUNCH(ctx, "null_stats", k_null_stats, 256, 256, null_l, n_l, d_nullst);
-		if (records) {
-			MDB_LAUNCH(ctx, "null_rec", k_null_rec, 1, 64, d_nullst, rec, d_rec_count, d_rec_valid, a.rec_cap, kbits, ctx->d_status);
-		} else {
-			MDB_LAUNCH(ctx, "null_poke", k_null_poke, 1, 64, d_nullst, dense);
-		}
-	}
-
-	/* G, J and the status flags come back with one sync; the sort is sized by G */
-	uint64_t *h = ctx->h_pinned;
-	uint64_t G = 0, list_len = 0;
-	uint32_t *first_out = out_first ? out_first : sel;
-	/* ... except where the leaf kernel has filled the ordering kernel's ranges itself: that kernel needs no size, and is launched right behind it
-	 * (its writes bounded by the caller's capacity; should the status words ask for another path, that path writes the columns again) - the
-	 * step's only sync then comes after its last kernel */
-	bool ordered_early = false;
-	if (ranged && cap) {
-		rc = order_presorted(ctx, a.rg_rec, a.rg_cnt, rg_n, kbits, out_first, out_count, keys_l, out_key, st->keys32, keyed_cbits, st->key_bits,
-				     st->key_lo, cap);
-		if (rc)
-			return rc;
-		ordered_early = true;
-	}
-	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 56, hipMemcpyDeviceToHost, ctx->stream));	/* (words 12, 13: the bit-per-row form's counters) */
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t dn_cleared = reinterpret_cast<const uint32_t *>(&h[1])[12], dn_exceptions = reinterpret_cast<const uint32_t *>(&h[1])[13];
-	if (leaf4 && ((uint32_t)h[1] & (4096u | 8192u)) && !((uint32_t)h[1] & (2u | 128u))) {
-		/* a key with more rows than k_leaf_wide4's count fields hold: the same partitioned tables through k_leaf_wide (16-bit counts), now
-		 * and for these columns; a range of row ids with more groups than its region holds (more groups than last time, or bunched):
-		 * k_leaf_wide4 again, into the record list */
-		const bool counts_bad = ((uint32_t)h[1] & 4096u) != 0;
-		if (counts_bad) {
-			ctx->l4_bad_keys = keys_l;
-			ctx->l4_bad_uses = 0;
-			ctx->l4_bad_nl = n_l;
-			ctx->l4_bad_nr = n_r;
-		}
-		ranged = false;
-		a.rg_rec = NULL;
-		ctx->lg_valid = false;
-		uint32_t *hw = reinterpret_cast<uint32_t *>(ctx->h_pinned) + 528;
-		hw[0] = (uint32_t)h[1] & ~(4096u | 8192u | 256u | 16u | 8u);
-		MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status, hw, 4, hipMemcpyHostToDevice, ctx->stream));
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 12, ctx->stream));	/* record-list length, joined rows */
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 8, 0, 8, ctx->stream));	/* records, largest first row */
-		if ((rc = counts_bad ? leaf_wide_launch(ctx, a, pl.nleaves, st->key_bits - pl.bits_total, 32u - st->key_bits, pl.nsub, true, true)
-				     : leaf_wide4_launch(ctx, a, pl.nleaves, st->key_bits - pl.bits_total, 32u - st->key_bits, pl.nsub)))
-			return rc;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		if (!counts_bad && ((uint32_t)h[1] & 4096u) && !((uint32_t)h[1] & (2u | 128u))) {	/* (the counts overflow as well: seen only now) */
-			ctx->l4_bad_keys = keys_l;
-			ctx->l4_bad_uses = 0;
-			ctx->l4_bad_nl = n_l;
-			ctx->l4_bad_nr = n_r;
-			hw[0] = (uint32_t)h[1] & ~(4096u | 8192u | 256u | 16u | 8u);
-			MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status, hw, 4, hipMemcpyHostToDevice, ctx->stream));
-			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 12, ctx->stream));
-			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 8, 0, 8, ctx->stream));
-			if ((rc = leaf_wide_launch(ctx, a, pl.nleaves, st->key_bits - pl.bits_total, 32u - st->key_bits, pl.nsub, true, true)))
-				return rc;
-			MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
-			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		}
-	}
-	if ((uint32_t)h[1] & 128u)
-		return st->direct ? GC_RETRY_PLAIN : GC_RETRY_WIDE;	/* a key outside the window: the 32-bit hashes mean nothing */
-	if (st->nextra && ((uint32_t)h[1] & (2u | 64u | 2048u)))
-		return GC_NOT_SERVED;	/* skewed keys, hot leaves, a product of counts beyond 32 bits: the chain of two-table operators */
-	if ((uint32_t)h[1] & 2u)
-		return GC_RETRY_EXACT;	/* a leaf outgrew its fixed-capacity region (skewed keys) */
-	if ((uint32_t)h[1] & 1024u) {
-		ctx->lw_bad_uses = 0;
-		ctx->lw_bad_keys = keys_l;	/* a key with 2^16 or more rows on one side: two levels and their hot-key path, now and for these columns */
-		ctx->lw_bad_nl = n_l;
-		ctx->lw_bad_nr = st->n_r_cap;
-		return GC_RETRY_TWO_LEVEL;
-	}
-	if (((uint32_t)h[1] & 64u) && keyed_cbits) {
-		ctx->keyed_distrust = 64;	/* hot leaves go through kernels that write plain records: redo with those everywhere */
-		return GC_RETRY_UNKEYED;
-	}
-	if (a.rec32 && ((uint32_t)h[1] & (64u | 512u))) {
-		ctx->r32_ok = false;		/* a COUNT(*) that no longer fits, or hot leaves (their kernels write 8-byte records) */
-		return GC_RETRY_REC64;
-	}
-	if ((uint32_t)h[1] & 64u) {
-		/* hot keys: the plain kernel left the leaves with GC_HEAVY or more rows on a side to this path */
-		hot_args ha;
-		ha.count = (uint32_t *)mdb_arena_take(ctx, 64);
-		ha.leaf = (uint32_t *)mdb_arena_take(ctx, HOT_MAX * 4);
-		ha.g_key = (unsigned long long *)mdb_arena_take(ctx, (size_t)HOT_MAX * HOT_SLOTS * 8);
-		ha.g_cnt = (unsigned long long *)mdb_arena_take(ctx, (size_t)HOT_MAX * (HOT_SLOTS + 1) * 8);
-		ha.g_first = (uint32_t *)mdb_arena_take(ctx, (size_t)HOT_MAX * (HOT_SLOTS + 1) * 4);
-		if (!ha.count || !ha.leaf || !ha.g_key || !ha.g_cnt || !ha.g_first)
-			return -MIDORIDB_INTERNAL;
-		MDB_HIP(ctx, hipMemsetAsync(ha.count, 0, 4, ctx->stream));
-		if (has_r) {
-			MDB_LAUNCH(ctx, "hot_list", k_hot_list<true>, (pl.nleaves + 255) / 256, 256, a, ha);
-		} else {
-			MDB_LAUNCH(ctx, "hot_list", k_hot_list<false>, (pl.nleaves + 255) / 256, 256, a, ha);
-		}
-		MDB_HIP(ctx, hipMemcpyAsync(&h[9], ha.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t nhot = (uint32_t)h[9];
-		const uint32_t resident = 2u * (uint32_t)ctx->num_cus;
-		if (nhot <= HOT_MAX) {
-			MDB_LAUNCH(ctx, "hot_clear", k_hot_clear, 256, 256, ha);
-			if (has_r) {
-				MDB_LAUNCH(ctx, "hot_slices", k_hot_slices<true>, resident, GC_THREADS, a, ha);
-				MDB_LAUNCH(ctx, "hot_finish", k_hot_finish<true>, nhot, 1024, a, ha);
-			} else {
-				MDB_LAUNCH(ctx, "hot_slices", k_hot_slices<false>, resident, GC_THREADS, a, ha);
-				MDB_LAUNCH(ctx, "hot_finish", k_hot_finish<false>, nhot, 1024, a, ha);
-			}
-		} else {
-			/* very many hot leaves: each is streamed by one workgroup (the HEAVY instance of the leaf kernel) */
-			const uint32_t grid = pl.nleaves < resident ? pl.nleaves : resident;
-			if (has_r && build_r) {
-				MDB_LAUNCH(ctx, "leaf_hot_keys", (k_leaf_group_count<true, true, true>), grid, GC_THREADS, a);
-			} else if (has_r) {
-				MDB_LAUNCH(ctx, "leaf_hot_keys", (k_leaf_group_count<true, false, true>), grid, GC_THREADS, a);
-			} else {
-				MDB_LAUNCH(ctx, "leaf_hot_keys", (k_leaf_group_count<false, false, true>), grid, GC_THREADS, a);
-			}
-		}
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	}
-	if (records) {
-		list_len = h[1] >> 32;
-		G = (uint32_t)h[5];
 	} else {
-		uint32_t *d_total = NULL;
-		rc = mdb_filter_nonzero64(ctx, dense, n_l, sel, &d_total);
+		/* nothing remembered (a first statement): the pilot - the same kernel over the first 64 of the 4096 digits (all rows of a key are
+		 * in one digit: a fair sample of the keys), nothing written but the counters: left rows that are no group's first row, groups
+		 * whose COUNT is not 1.  One in 16 of the rows at most each: the bit-per-row form */
+		a.dn_pilot = 64;
+		if ((rc = leaf_wide12_launch(ctx, a, g->pl.nleaves, st->key_bits - 12u, g->pl.nsub, st->nextra)))
+			return rc;
+		a.dn_pilot = 0;
+		MDB_HIP(ctx, hipMemcpyAsync(g->rb, ctx->d_status, GC_RB_BYTES_DN, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		const uint64_t p_groups = g->rb->groups, p_cleared = g->rb->dn_cleared, p_exc = g->rb->dn_exceptions, p_rows = p_groups + p_cleared;
+		want_bits = p_rows && p_cleared * 16 <= p_rows && p_exc * 16 <= p_rows;
+		by_pilot = true;
+		if (mdb_knob_set("MDB_DEBUG_GROUP"))
+			fprintf(stderr, "join + GROUP BY (pilot over 64 digits): %llu left rows, %llu no group's first row, %llu groups of COUNT != 1 -> %s\n",
+				(unsigned long long)p_rows, (unsigned long long)p_cleared, (unsigned long long)p_exc, want_bits ? "a bit per left row" : "records");
+		/* (the flags of word 0 stay: they are facts about the data) */
+		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + GC_STW_LIST_LEN, 0, GC_RB_BYTES_DN - 4 * GC_STW_LIST_LEN, ctx->stream));
+	}
+	if (want_bits) {
+		if ((rc = mdb_dense_bits_begin(ctx, n_l, &g->dn_bits)))
+			return rc;
+		a.dn_bits = reinterpret_cast<unsigned int *>(g->dn_bits);
+		a.dn_exc_cap = (uint32_t)(n_l / 8 + 4096);
+		a.dn_exc = (unsigned long long *)mdb_arena_take(ctx, (size_t)a.dn_exc_cap * 8);
+		if (!a.dn_exc)
+			return -MIDORIDB_INTERNAL;
+		ctx->plan.groups_as_bits = by_stats ? 3u : by_pilot ? 1u : 2u;
+	}
+	return MIDORIDB_OK;
+}
+
+/* stage 3: the leaf kernel the plan and the tables' layouts ask for, and the NULL group's kernels behind it */
+static int gc_launch_leaf(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	const gc_args &a = g->a;
+	const mdb_part_result &pl = g->pl, &pr = g->pr;
+	const bool has_r = st->has_r;
+	int rc;
+	/* persistent grid: two 75 KiB workgroups fit one CU's 160 KiB of LDS */
+	const uint32_t resident = 2u * (uint32_t)ctx->num_cus;
+	const uint32_t grid = pl.nleaves < resident ? pl.nleaves : resident;
+	/* (the direct kernel addresses leaf i at i * cap: should a table have fallen back to exact offsets - more than 2^32
+	 * region words - the hashed kernel below joins the compact words just as well, they are injective too) */
+	if (st->wide12) {
+		if ((rc = leaf_wide12_launch(ctx, a, pl.nleaves, st->key_bits - 12u, pl.nsub, st->nextra)))
+			return rc;
+	} else if (st->one_level) {
+		/* ... by ALL the hash bits below the first level's 9 (k_leaf_wide) */
+		if (!pl.nsub || !pl.leaf_cap || (has_r && (!pr.nsub || !pr.w32 || pr.nsub != pl.nsub || pr.nleaves != pl.nleaves)))
+			return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "one-level direct leaves: the tables are not in the first-level layout");
+		const uint32_t rem = st->key_bits - pl.bits_total, shift = 32u - st->key_bits;
+		if (has_r && pr.w16 && g->leaf4)
+			rc = leaf_wide4_launch(ctx, a, pl.nleaves, rem, shift, pl.nsub);
+		else
+			rc = leaf_wide_launch(ctx, a, pl.nleaves, rem, shift, pl.nsub, has_r, has_r && pr.w16);
 		if (rc)
 			return rc;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[0], d_total, 4, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		G = (uint32_t)h[0];
+	} else if (st->direct && pl.leaf_cap && (!has_r || pr.leaf_cap)) {
+		/* compact narrow form: the leaf's table is indexed by the hash bits the partition left over */
+		const uint32_t rem = st->key_bits - pl.bits_total, shift = 32u - st->key_bits;
+		if (st->nextra && !(pl.leaf_cap && pr.leaf_cap))
+			return GC_NOT_SERVED;
+		const size_t lds = ((size_t)(12 + 4 * st->nextra) << rem) + 32;
+		/* four 512-thread workgroups = the CU's 32 waves (three measured the same, 256-thread workgroups 10-30 % slower) */
+		uint32_t per_cu = (uint32_t)((size_t)(160 * 1024) / lds);
+		per_cu = per_cu > 4 ? 4 : (per_cu < 1 ? 1 : per_cu);
+		const uint32_t dgrid = pl.nleaves < per_cu * (uint32_t)ctx->num_cus ? pl.nleaves : per_cu * (uint32_t)ctx->num_cus;
+		if (has_r) {
+			MDB_LAUNCH_LDS(ctx, "leaf_join_direct", (k_leaf_direct<true, 512, 2048>), dgrid, 512, lds, a, rem, shift);
+		} else {
+			MDB_LAUNCH_LDS(ctx, "leaf_group_direct", (k_leaf_direct<false, 512, 2048>), dgrid, 512, lds, a, rem, shift);
+		}
+	} else if (st->nextra) {
+		return GC_NOT_SERVED;
+	} else if (has_r && g->build_r && st->narrow) {
+		MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, true, false, true>), grid, GC_THREADS, a);
+	} else if (has_r && g->build_r) {
+		MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, true, false>), grid, GC_THREADS, a);
+	} else if (has_r && st->narrow) {
+		MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, false, false, true>), grid, GC_THREADS, a);
+	} else if (has_r) {
+		MDB_LAUNCH(ctx, "leaf_join_group_count", (k_leaf_group_count<true, false, false>), grid, GC_THREADS, a);
+	} else if (st->narrow) {
+		MDB_LAUNCH(ctx, "leaf_group_count", (k_leaf_group_count<false, false, false, true>), grid, GC_THREADS, a);
+	} else {
+		MDB_LAUNCH(ctx, "leaf_group_count", (k_leaf_group_count<false, false, false>), grid, GC_THREADS, a);
 	}
-	const uint32_t status = (uint32_t)h[1];
-	const uint64_t joined = h[2];
-	if (status & 2u)
+	if (st->null_group && st->null_l) {
+		unsigned long long *d_nullst = (unsigned long long *)(ctx->d_status + GC_STW_NULL_STATS);
+		MDB_HIP(ctx, hipMemsetAsync(d_nullst + 1, 0xFF, 8, ctx->stream));
+		MDB_LAUNCH(ctx, "null_stats", k_null_stats, 256, 256, st->null_l, st->n_l, d_nullst);
+		if (g->records) {
+			MDB_LAUNCH(ctx, "null_rec", k_null_rec, 1, 64, d_nullst, g->rec, a.rec_count, a.rec_valid, a.rec_cap, g->kbits, ctx->d_status);
+		} else {
+			MDB_LAUNCH(ctx, "null_poke", k_null_poke, 1, 64, d_nullst, g->dense);
+		}
+	}
+	return MIDORIDB_OK;
+}
+
+/* the ordering of ranges that the leaf kernel filled itself */
+static int gc_order_presorted(mdb_dev_ctx *ctx, gc_run *g, uint64_t early_cap)
+{
+	const gc_state *st = g->st;
+	return order_presorted(ctx, g->a.rg_rec, g->a.rg_cnt, g->rg_n, g->kbits, g->out.first, g->out.count, st->keys_l, g->out.key, st->keys32, g->keyed_cbits,
+			       st->key_bits, st->key_lo, early_cap);
+}
+
+/* the status words to the host: `bytes` of them from word 0 on, and wait */
+static int gc_read_back(mdb_dev_ctx *ctx, gc_run *g, size_t bytes)
+{
+	MDB_HIP(ctx, hipMemcpyAsync(g->rb, ctx->d_status, bytes, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return MIDORIDB_OK;
+}
+
+/* stage 4: G, J and the status flags come back with one sync; the sort is sized by G ... except where the leaf kernel has filled the ordering kernel's
+ * ranges itself: that kernel needs no size, and is launched right behind it (its writes bounded by the caller's capacity; should the status words
+ * ask for another path, that path writes the columns again) - the step's only sync then comes after its last kernel */
+static int gc_read_status(mdb_dev_ctx *ctx, gc_run *g)
+{
+	int rc;
+	g->ordered_early = false;
+	if (g->ranged && g->out.cap) {
+		if ((rc = gc_order_presorted(ctx, g, g->out.cap)))
+			return rc;
+		g->ordered_early = true;
+	}
+	if ((rc = gc_read_back(ctx, g, GC_RB_BYTES_DN)))	/* (with the bit-per-row form's counters) */
+		return rc;
+	g->dn_cleared = g->rb->dn_cleared;
+	g->dn_exceptions = g->rb->dn_exceptions;
+	return MIDORIDB_OK;
+}
+
+/* k_leaf_wide4's count fields overflow on these columns: k_leaf_wide at once, for MDB_BAD_LEAF_USES calls */
+static void gc_l4_bad_note(mdb_dev_ctx *ctx, const gc_run *g)
+{
+	ctx->l4_bad_keys = g->st->keys_l;
+	ctx->l4_bad_uses = 0;
+	ctx->l4_bad_nl = g->st->n_l;
+	ctx->l4_bad_nr = g->r.n;
+}
+
+/* the same partitioned tables through another one-level leaf kernel: the flags this retry answers (and those the new run raises again if they still
+ * apply) are taken out of word 0, the counters cleared, the status read back */
+static int gc_leaf4_relaunch(mdb_dev_ctx *ctx, gc_run *g, bool wide16)
+{
+	const gc_state *st = g->st;
+	const mdb_part_result &pl = g->pl;
+	int rc;
+	uint32_t *hw = reinterpret_cast<uint32_t *>(ctx->h_pinned + MDB_HP_SEND_FLAGS);
+	hw[0] = g->rb->flags & ~(GC_ST_COUNTS_NOT_4BYTE | GC_ST_RANGE_FULL | GC_ST_COUNT_NOT_KEYED | GC_ST_COUNT_NOT_REC32 | MDB_ST_LIST_FULL);
+	MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status, hw, 4, hipMemcpyHostToDevice, ctx->stream));
+	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + GC_STW_LIST_LEN, 0, 4 * (GC_STW_NULL_STATS - GC_STW_LIST_LEN), ctx->stream));	/* record-list length, joined rows */
+	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + GC_STW_RECORDS, 0, 4 * (GC_STW_SAMPLE - GC_STW_RECORDS), ctx->stream));	/* records, largest first row */
+	if ((rc = wide16 ? leaf_wide_launch(ctx, g->a, pl.nleaves, st->key_bits - pl.bits_total, 32u - st->key_bits, pl.nsub, true, true)
+			 : leaf_wide4_launch(ctx, g->a, pl.nleaves, st->key_bits - pl.bits_total, 32u - st->key_bits, pl.nsub)))
+		return rc;
+	return gc_read_back(ctx, g, GC_RB_BYTES);
+}
+
+/* stage 5: a key with more rows than k_leaf_wide4's count fields hold: the same partitioned tables through k_leaf_wide (16-bit counts), now
+ * and for these columns; a range of row ids with more groups than its region holds (more groups than last time, or bunched):
+ * k_leaf_wide4 again, into the record list */
+static int gc_leaf4_redo(mdb_dev_ctx *ctx, gc_run *g)
+{
+	const uint32_t partition_said = MDB_ST_REGION_FULL | MDB_ST_KEY_OUTSIDE;	/* (the whole operator is redone: nothing to save here) */
+	int rc;
+	if (!(g->leaf4 && (g->rb->flags & (GC_ST_COUNTS_NOT_4BYTE | GC_ST_RANGE_FULL)) && !(g->rb->flags & partition_said)))
+		return MIDORIDB_OK;
+	const bool counts_bad = (g->rb->flags & GC_ST_COUNTS_NOT_4BYTE) != 0;
+	if (counts_bad)
+		gc_l4_bad_note(ctx, g);
+	g->ranged = false;
+	g->a.rg_rec = NULL;
+	ctx->lg_valid = false;
+	if ((rc = gc_leaf4_relaunch(ctx, g, counts_bad)))
+		return rc;
+	if (!counts_bad && (g->rb->flags & GC_ST_COUNTS_NOT_4BYTE) && !(g->rb->flags & partition_said)) {	/* (the counts overflow as well: seen only now) */
+		gc_l4_bad_note(ctx, g);
+		rc = gc_leaf4_relaunch(ctx, g, true);
+	}
+	return rc;
+}
+
+/* What the flags ask for: MIDORIDB_OK (go on), a GC_RETRY_* / GC_NOT_SERVED for the caller's retry loop (with what the context must remember for the
+ * retry), or an error.  Looked at twice per attempt, and each flag belongs to one of the two looks - in this order of precedence:
+ *
+ *   GC_AT_LEAF, when the leaf kernel's status has arrived (what asks for another plan altogether, before the hot-key path spends time on this one):
+ *     1 MDB_ST_KEY_OUTSIDE                                            GC_RETRY_PLAIN (compact window) / GC_RETRY_WIDE
+ *     2 further right tables, and REGION_FULL | HOT_LEAVES | PRODUCT_WIDE  GC_NOT_SERVED
+ *     3 MDB_ST_REGION_FULL                                            GC_RETRY_EXACT
+ *     4 GC_ST_ROWS_NOT_16BIT                                          GC_RETRY_TWO_LEVEL
+ *     5 GC_ST_HOT_LEAVES with keyed records                           GC_RETRY_UNKEYED
+ *     6 4-byte records, and HOT_LEAVES | REC32_STALE                  GC_RETRY_REC64
+ *   GC_AT_END, after the hot-key path (which may raise TABLE_FULL, LIST_FULL and the COUNT flags anew) and the count of the groups:
+ *     7 MDB_ST_REGION_FULL                                            GC_RETRY_EXACT (row 3 has answered it unless the flag appeared since)
+ *     8 GC_ST_COUNT_NOT_KEYED                                         GC_RETRY_UNKEYED
+ *     9 GC_ST_COUNT_NOT_REC64                                         GC_RETRY_DENSE
+ *    10 GC_ST_TABLE_FULL, table built on the right side               GC_RETRY_BUILD_L
+ *    11 GC_ST_TABLE_FULL                                              error
+ *    12 MDB_ST_LIST_FULL                                              error
+ * GC_ST_COUNT_NOT_REC32, GC_ST_LEFT_DUPS, GC_ST_EXC_FULL and HOT_LEAVES at the end are facts for the delivery, not verdicts. */
+enum gc_verdict_at { GC_AT_LEAF, GC_AT_END };
+static int gc_verdict(mdb_dev_ctx *ctx, const gc_run *g, gc_verdict_at at)
+{
+	const gc_state *st = g->st;
+	const uint32_t f = g->rb->flags;
+	if (at == GC_AT_LEAF) {
+		if (f & MDB_ST_KEY_OUTSIDE)
+			return st->direct ? GC_RETRY_PLAIN : GC_RETRY_WIDE;	/* a key outside the window: the 32-bit hashes mean nothing */
+		if (st->nextra && (f & (MDB_ST_REGION_FULL | GC_ST_HOT_LEAVES | GC_ST_PRODUCT_WIDE)))
+			return GC_NOT_SERVED;	/* skewed keys, hot leaves, a product of counts beyond 32 bits: the chain of two-table operators */
+		if (f & MDB_ST_REGION_FULL)
+			return GC_RETRY_EXACT;	/* a leaf outgrew its fixed-capacity region (skewed keys) */
+		if (f & GC_ST_ROWS_NOT_16BIT) {
+			ctx->lw_bad_uses = 0;
+			ctx->lw_bad_keys = st->keys_l;	/* a key with 2^16 or more rows on one side: two levels and their hot-key path, now and for these columns */
+			ctx->lw_bad_nl = st->n_l;
+			ctx->lw_bad_nr = st->n_r_cap;
+			return GC_RETRY_TWO_LEVEL;
+		}
+		if ((f & GC_ST_HOT_LEAVES) && g->keyed_cbits) {
+			ctx->keyed_distrust = 64;	/* hot leaves go through kernels that write plain records: redo with those everywhere */
+			return GC_RETRY_UNKEYED;
+		}
+		if (g->a.rec32 && (f & (GC_ST_HOT_LEAVES | GC_ST_REC32_STALE))) {
+			ctx->r32_ok = false;		/* a COUNT(*) that no longer fits, or hot leaves (their kernels write 8-byte records) */
+			return GC_RETRY_REC64;
+		}
+		return MIDORIDB_OK;
+	}
+	if (f & MDB_ST_REGION_FULL)
 		return GC_RETRY_EXACT;	/* a leaf outgrew its fixed-capacity region (skewed keys) */
-	if (status & 256u) {
+	if (f & GC_ST_COUNT_NOT_KEYED) {
 		ctx->keyed_distrust = 64;	/* a COUNT(*) too large for a keyed record: plain records, now and for a while */
 		return GC_RETRY_UNKEYED;
 	}
-	if (status & 4u)
+	if (f & GC_ST_COUNT_NOT_REC64)
 		return GC_RETRY_DENSE;	/* a COUNT(*) too large to share a 64-bit record with its row id */
-	if ((status & 1u) && build_r)
+	if ((f & GC_ST_TABLE_FULL) && g->build_r)
 		return GC_RETRY_BUILD_L;
-	if (status & 1u)
+	if (f & GC_ST_TABLE_FULL)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL,
 				   "leaf hash table overflow (more than %u distinct keys in one leaf): unsupported key skew", GC_SLOTS);
-	if (status & 8u)
+	if (f & MDB_ST_LIST_FULL)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "group record list exhausted (sizing bug)");
-	if (G > cap)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups",
-				   (unsigned long long)cap, (unsigned long long)G);
-	if (G && records) {
-		/* (one-level leaves report the largest first row id: the sort's first-level regions are sized for the digits below it) */
-		const uint64_t last_first = (uint32_t)(h[5] >> 32);
-		const uint64_t n_ord = (st->one_level && last_first && last_first < n_l) ? last_first + 1 : n_l;
-		if (dn_bits) {
-			if (mdb_knob_set("MDB_DEBUG_GROUP"))
-				fprintf(stderr, "join + GROUP BY (bit per left row): %llu groups, %u rows cleared of %llu, %u exceptions, status %u\n",
-					(unsigned long long)G, dn_cleared, (unsigned long long)n_l, dn_exceptions, status);
-			if ((status & 131072u) || (uint64_t)G + dn_cleared != n_l) {	/* (more groups of COUNT != 1 than last time: the record form) */
-				ctx->dn_distrust = 32;
-				ctx->plan.groups_as_bits = 0;
-				return GC_RETRY_NODENSE;
-			}
-			/* every left row a group: the group keys ARE the left key column, in its order - a caller that said so (MDB_KEYS_MAY_ALIAS) reads
-			 * them there and nothing is copied (0.8 GB read + 0.8 GB written at 10^8 rows); every COUNT 1 and MDB_COUNTS_OPTIONAL: no COUNT
-			 * column either (mdb_dev_last_plan says which) */
-			const bool alias = ctx->key_alias_ok && !st->keys32 && out_key && G == n_l;
-			const bool ones = ctx->counts_optional && dn_exceptions == 0;
-			ctx->plan.keys_are_left_column = alias ? 1u : 0u;
-			ctx->plan.counts_all_one = ones ? 1u : 0u;
-			rc = mdb_dense_emit(ctx, dn_bits, n_l, a.dn_exc, dn_exceptions, out_first, ones ? NULL : out_count, keys_l, st->keys32, alias ? NULL : out_key);
-			if (!rc)
-				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		} else if (ranged && ordered_early)
-			rc = MIDORIDB_OK;	/* (done, and waited for with the status words) */
-		else if (ranged)
-			rc = order_presorted(ctx, a.rg_rec, a.rg_cnt, rg_n, kbits, out_first, out_count, keys_l, out_key, st->keys32, keyed_cbits, st->key_bits,
-					     st->key_lo);
-		else
-			rc = order_records(ctx, rec, list_len, n_ord, kbits, sb1, sb2, out_first, out_count, NULL, keys_l, out_key, st->keys32,
-					   !(status & 16u), keyed_cbits, st->key_bits, st->key_lo, a.rec32 != 0, G);
-		if (rc == GC_RETRY_REC64)
-			ctx->r32_ok = false;
-		if (rc)
-			return rc;
-		/* remember whether 4-byte records would do for these columns */
-		ctx->r32_ok = st->direct && !st->one_level && has_r && !keyed_cbits && !(status & 16u);
-		ctx->r32_kl = keys_l;
-		ctx->r32_nl = n_l;
-		ctx->r32_kr = keys_r;
-		ctx->r32_nr = n_r;
-	} else if (G) {
-		rc = mdb_dev_gather64(ctx, dense, NULL, sel, G, out_count, NULL);
-		if (rc)
-			return rc;
-		if (out_key && st->keys32) {
-			MDB_LAUNCH(ctx, "gather_i32", k_gather_i32, (uint32_t)((G + 255) / 256), 256, reinterpret_cast<const int32_t *>(keys_l), sel, G,
-				   out_key);
-		} else if (out_key) {
-			rc = mdb_dev_gather64(ctx, keys_l, NULL, sel, G, out_key, NULL);
-			if (rc)
-				return rc;
-		}
-		if (out_first)
-			MDB_HIP(ctx, hipMemcpyAsync(out_first, sel, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	}
-	*out_groups = G;
-	if (out_joined)
-		*out_joined = joined;
+	return MIDORIDB_OK;
+}
+
+/* stage 6: hot keys - the plain kernel left the leaves with GC_HEAVY or more rows on a side to this path */
+static int gc_hot_keys(mdb_dev_ctx *ctx, gc_run *g)
+{
+	const gc_args &a = g->a;
+	const bool has_r = g->st->has_r;
+	const uint32_t nleaves = g->pl.nleaves;
+	hot_args ha;
+	ha.count = (uint32_t *)mdb_arena_take(ctx, 64);
+	ha.leaf = (uint32_t *)mdb_arena_take(ctx, HOT_MAX * 4);
+	ha.g_key = (unsigned long long *)mdb_arena_take(ctx, (size_t)HOT_MAX * HOT_SLOTS * 8);
+	ha.g_cnt = (unsigned long long *)mdb_arena_take(ctx, (size_t)HOT_MAX * (HOT_SLOTS + 1) * 8);
+	ha.g_first = (uint32_t *)mdb_arena_take(ctx, (size_t)HOT_MAX * (HOT_SLOTS + 1) * 4);
+	if (!ha.count || !ha.leaf || !ha.g_key || !ha.g_cnt || !ha.g_first)
+		return -MIDORIDB_INTERNAL;
+	MDB_HIP(ctx, hipMemsetAsync(ha.count, 0, 4, ctx->stream));
 	if (has_r) {
+		MDB_LAUNCH(ctx, "hot_list", k_hot_list<true>, (nleaves + 255) / 256, 256, a, ha);
+	} else {
+		MDB_LAUNCH(ctx, "hot_list", k_hot_list<false>, (nleaves + 255) / 256, 256, a, ha);
+	}
+	uint64_t *h = ctx->h_pinned;
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_HOT], ha.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	const uint32_t nhot = (uint32_t)h[MDB_HP_HOT];
+	const uint32_t resident = 2u * (uint32_t)ctx->num_cus;
+	if (nhot <= HOT_MAX) {
+		MDB_LAUNCH(ctx, "hot_clear", k_hot_clear, 256, 256, ha);
+		if (has_r) {
+			MDB_LAUNCH(ctx, "hot_slices", k_hot_slices<true>, resident, GC_THREADS, a, ha);
+			MDB_LAUNCH(ctx, "hot_finish", k_hot_finish<true>, nhot, 1024, a, ha);
+		} else {
+			MDB_LAUNCH(ctx, "hot_slices", k_hot_slices<false>, resident, GC_THREADS, a, ha);
+			MDB_LAUNCH(ctx, "hot_finish", k_hot_finish<false>, nhot, 1024, a, ha);
+		}
+	} else {
+		/* very many hot leaves: each is streamed by one workgroup (the HEAVY instance of the leaf kernel) */
+		const uint32_t grid = nleaves < resident ? nleaves : resident;
+		if (has_r && g->build_r) {
+			MDB_LAUNCH(ctx, "leaf_hot_keys", (k_leaf_group_count<true, true, true>), grid, GC_THREADS, a);
+		} else if (has_r) {
+			MDB_LAUNCH(ctx, "leaf_hot_keys", (k_leaf_group_count<true, false, true>), grid, GC_THREADS, a);
+		} else {
+			MDB_LAUNCH(ctx, "leaf_hot_keys", (k_leaf_group_count<false, false, true>), grid, GC_THREADS, a);
+		}
+	}
+	return gc_read_back(ctx, g, GC_RB_BYTES);
+}
+
+/* the number of groups: with the status words in record mode; dense mode selects the first rows whose COUNT is not 0 and reads their number */
+static int gc_count_groups(mdb_dev_ctx *ctx, gc_run *g)
+{
+	if (g->records) {
+		g->list_len = g->rb->list_len;
+		g->G = g->rb->groups;
+		return MIDORIDB_OK;
+	}
+	uint32_t *d_total = NULL;
+	int rc = mdb_filter_nonzero64(ctx, g->dense, g->st->n_l, g->sel, &d_total);
+	if (rc)
+		return rc;
+	uint64_t *h = ctx->h_pinned;
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_COUNT], d_total, 4, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	g->G = (uint32_t)h[MDB_HP_COUNT];
+	return MIDORIDB_OK;
+}
+
+/* stage 7a: the groups of record mode, ordered by first row id - from the bits, the ranges or the record list */
+static int gc_deliver_records(mdb_dev_ctx *ctx, gc_run *g)
+{
+	gc_state *st = g->st;
+	const gc_out &o = g->out;
+	const uint64_t n_l = st->n_l, G = g->G;
+	const uint32_t status = g->rb->flags;
+	int rc;
+	/* (one-level leaves report the largest first row id: the sort's first-level regions are sized for the digits below it) */
+	const uint64_t last_first = g->rb->last_first;
+	const uint64_t n_ord = (st->one_level && last_first && last_first < n_l) ? last_first + 1 : n_l;
+	if (g->dn_bits) {
+		if (mdb_knob_set("MDB_DEBUG_GROUP"))
+			fprintf(stderr, "join + GROUP BY (bit per left row): %llu groups, %u rows cleared of %llu, %u exceptions, status %u\n",
+				(unsigned long long)G, g->dn_cleared, (unsigned long long)n_l, g->dn_exceptions, status);
+		if ((status & GC_ST_EXC_FULL) || (uint64_t)G + g->dn_cleared != n_l) {	/* (more groups of COUNT != 1 than last time: the record form) */
+			ctx->dn_distrust = 32;
+			ctx->plan.groups_as_bits = 0;
+			return GC_RETRY_NODENSE;
+		}
+		/* every left row a group: the group keys ARE the left key column, in its order - a caller that said so (MDB_KEYS_MAY_ALIAS) reads
+		 * them there and nothing is copied (0.8 GB read + 0.8 GB written at 10^8 rows); every COUNT 1 and MDB_COUNTS_OPTIONAL: no COUNT
+		 * column either (mdb_dev_last_plan says which) */
+		const bool alias = ctx->key_alias_ok && !st->keys32 && o.key && G == n_l;
+		const bool ones = ctx->counts_optional && g->dn_exceptions == 0;
+		ctx->plan.keys_are_left_column = alias ? 1u : 0u;
+		ctx->plan.counts_all_one = ones ? 1u : 0u;
+		rc = mdb_dense_emit(ctx, g->dn_bits, n_l, g->a.dn_exc, g->dn_exceptions, o.first, ones ? NULL : o.count, st->keys_l, st->keys32, alias ? NULL : o.key);
+		if (!rc)
+			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	} else if (g->ranged && g->ordered_early)
+		rc = MIDORIDB_OK;	/* (done, and waited for with the status words) */
+	else if (g->ranged)
+		rc = gc_order_presorted(ctx, g, 0);
+	else
+		rc = order_records(ctx, g->rec, g->list_len, n_ord, g->kbits, g->sb1, g->sb2, o.first, o.count, NULL, st->keys_l, o.key, st->keys32,
+				   !(status & GC_ST_COUNT_NOT_REC32), g->keyed_cbits, st->key_bits, st->key_lo, g->a.rec32 != 0, G);
+	if (rc == GC_RETRY_REC64)
+		ctx->r32_ok = false;
+	if (rc)
+		return rc;
+	/* remember whether 4-byte records would do for these columns */
+	ctx->r32_ok = st->direct && !st->one_level && st->has_r && !g->keyed_cbits && !(status & GC_ST_COUNT_NOT_REC32);
+	ctx->r32_kl = st->keys_l;
+	ctx->r32_nl = n_l;
+	ctx->r32_kr = g->r.keys;
+	ctx->r32_nr = g->r.n;
+	return MIDORIDB_OK;
+}
+
+/* stage 7b: the groups of dense mode - the selected first rows' counts and keys gathered */
+static int gc_deliver_dense(mdb_dev_ctx *ctx, gc_run *g)
+{
+	const gc_state *st = g->st;
+	const gc_out &o = g->out;
+	const uint64_t G = g->G;
+	int rc = mdb_dev_gather64(ctx, g->dense, NULL, g->sel, G, o.count, NULL);
+	if (rc)
+		return rc;
+	if (o.key && st->keys32) {
+		MDB_LAUNCH(ctx, "gather_i32", k_gather_i32, (uint32_t)((G + 255) / 256), 256, reinterpret_cast<const int32_t *>(st->keys_l), g->sel, G, o.key);
+	} else if (o.key) {
+		rc = mdb_dev_gather64(ctx, st->keys_l, NULL, g->sel, G, o.key, NULL);
+		if (rc)
+			return rc;
+	}
+	if (o.first)
+		MDB_HIP(ctx, hipMemcpyAsync(o.first, g->sel, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return MIDORIDB_OK;
+}
+
+/* stage 8: the result's sizes to the caller; what the next call over these columns may use (lg_*, last_left_dups*); the plan record */
+static void gc_remember(mdb_dev_ctx *ctx, const gc_run *g)
+{
+	const gc_state *st = g->st;
+	const uint32_t status = g->rb->flags;
+	const uint64_t joined = g->rb->joined;
+	*g->out.groups = g->G;
+	if (g->out.joined)
+		*g->out.joined = joined;
+	if (st->has_r) {
 		ctx->lg_nextra = (uint32_t)st->nextra;
-		ctx->lg_kl = keys_l;
-		ctx->lg_nl = n_l;
-		ctx->lg_kr = keys_r;
-		ctx->lg_nr = n_r;
-		ctx->lg_groups = G;
+		ctx->lg_kl = st->keys_l;
+		ctx->lg_nl = st->n_l;
+		ctx->lg_kr = g->r.keys;
+		ctx->lg_nr = g->r.n;
+		ctx->lg_groups = g->G;
 		ctx->lg_joined = joined;
 		ctx->lg_valid = true;
 	}
-	ctx->last_left_dups_known = st->direct && has_r && !(status & 64u);	/* (the hot-key kernels and the hashed leaves do not say) */
+	ctx->last_left_dups_known = st->direct && st->has_r && !(status & GC_ST_HOT_LEAVES);	/* (the hot-key kernels and the hashed leaves do not say) */
 	ctx->last_left_dups = (status & GC_ST_LEFT_DUPS) != 0;
 	gc_plan_note(ctx, st);
 	ctx->plan.any_order = 0;
-	ctx->plan.ranged_order = ranged ? 1u : 0u;
+	ctx->plan.ranged_order = g->ranged ? 1u : 0u;
+}
+
+/* second half: partition what waited for the right table, join and count in the leaves, order and deliver the groups.  MIDORIDB_OK, an error, or
+ * a GC_RETRY_* / GC_NOT_SERVED that tells the caller which plan to try instead (gc_verdict) */
+static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const gc_table &right, const gc_out &out)
+{
+	gc_run g;
+	int rc;
+	memset(&g, 0, sizeof(g));
+	g.st = st;
+	g.r = right;
+	g.out = out;
+	g.build_r = st->has_r && !st->no_build_r && right.n <= st->n_l;
+	g.pl = st->pl;
+	g.rb = reinterpret_cast<gc_readback *>(ctx->h_pinned + MDB_HP_STATUS);
+	st->active = false;
+	if ((rc = gc_partition(ctx, &g)) || (rc = gc_args_begin(ctx, &g)) || (rc = gc_choose_records(ctx, &g)) || (rc = gc_choose_bits(ctx, &g)))
+		return rc;
+	if ((rc = gc_launch_leaf(ctx, &g)) || (rc = gc_read_status(ctx, &g)) || (rc = gc_leaf4_redo(ctx, &g)))
+		return rc;
+	if ((rc = gc_verdict(ctx, &g, GC_AT_LEAF)))
+		return rc;
+	if ((g.rb->flags & GC_ST_HOT_LEAVES) && (rc = gc_hot_keys(ctx, &g)))
+		return rc;
+	if ((rc = gc_count_groups(ctx, &g)) || (rc = gc_verdict(ctx, &g, GC_AT_END)))
+		return rc;
+	if (g.G > out.cap)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)out.cap, (unsigned long long)g.G);
+	if (g.G && (rc = g.records ? gc_deliver_records(ctx, &g) : gc_deliver_dense(ctx, &g)))
+		return rc;
+	gc_remember(ctx, &g);
 	return MIDORIDB_OK;
 }
 
@@ -2345,7 +2567,7 @@ int gc_sample_range(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 		*hi = ctx->sr_hi;
 		return MIDORIDB_OK;
 	}
-	long long *mm = (long long *)(ctx->d_status + 10);
+	long long *mm = (long long *)(ctx->d_status + GC_STW_SAMPLE);
 	int64_t *h = (int64_t *)ctx->h_pinned;
 	for (int i = 0; i < 6; i += 2) {
 		h[i] = INT64_MAX;
@@ -2539,65 +2761,50 @@ int gc_narrow_guess(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 	return MIDORIDB_OK;
 }
 
-static int group_count_run(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l,
-			   const int64_t *keys_r, const uint64_t *null_r, uint64_t n_r, bool has_r, bool null_group, bool fast,
-			   bool want_records, bool no_build_r, bool narrow, int64_t base, gc_window win, bool keys32, int64_t *out_key, int64_t *out_count,
-			   uint32_t *out_first, uint64_t cap, uint64_t *out_groups, uint64_t *out_joined)
+static int group_count_run(mdb_dev_ctx *ctx, const gc_request &rq)
 {
-	*out_groups = 0;
-	if (out_joined)
-		*out_joined = 0;
-	if (n_l == 0 || (has_r && n_r == 0))
+	*rq.out.groups = 0;
+	if (rq.out.joined)
+		*rq.out.joined = 0;
+	if (rq.l.n == 0 || (rq.has_r && rq.r.n == 0))
 		return MIDORIDB_OK;
 	gc_state st;
-	memset(&st, 0, sizeof(st));
-	st.keys_l = keys_l;
-	st.null_l = null_l;
-	st.n_l = n_l;
-	st.n_r_cap = n_r;
-	st.has_r = has_r;
-	st.null_group = null_group;
-	st.fast = fast;
-	st.want_records = want_records;
-	st.no_build_r = no_build_r;
-	st.narrow = narrow;
-	st.base = base;
-	st.key_bits = narrow ? win.kbits : 0u;
-	st.key_lo = win.lo;
-	st.selective = win.selective;
-	st.fast1 = win.fast1;
-	st.by_span = win.by_span;
-	st.prunable = win.prunable;
-	st.r_based = win.r_based;
-	st.keys32 = keys32;
-	st.defer_ok = true;
-	st.own_call = true;
-	if (gc_pending_extras && has_r) {
-		st.nextra = gc_pending_extras->n;
-		for (int x = 0; x < st.nextra; x++) {
-			st.xkeys[x] = gc_pending_extras->keys[x];
-			st.xnull[x] = gc_pending_extras->nulls[x];
-			st.xn[x] = gc_pending_extras->rows[x];
-		}
-	}
+	gc_state_fill(&st, rq, true);
 	int rc = gc_begin(ctx, &st);
 	if (rc == GC_EXPLAINED)		/* (mdb_dev_explain_*: gc_begin stopped in front of its arena) */
-		gc_explain_fill(ctx, &st, keys_r, n_r, cap);
+		gc_explain_fill(ctx, &st, rq.r.keys, rq.r.n, rq.out.cap);
 	if (rc)
 		return rc;
-	return gc_finish(ctx, &st, keys_r, null_r, n_r, out_key, out_count, out_first, cap, out_groups, out_joined);
+	return gc_finish(ctx, &st, rq.r, rq.out);
 }
 
-static int group_count_common(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l,
-			      const int64_t *keys_r, const uint64_t *null_r, uint64_t n_r, bool has_r, bool null_group,
-			      int64_t *out_key, int64_t *out_count, uint32_t *out_first, uint64_t cap, uint64_t *out_groups,
-			      uint64_t *out_joined, bool keys32 = false)
+/* the request of a join (has_r) or of a plain GROUP BY with its NULL group (r = nothing), before any plan is made */
+static gc_request gc_request_of(const gc_table &l, const gc_table &r, const gc_out &out, bool has_r, bool keys32 = false)
 {
+	gc_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.l = l;
+	rq.r = r;
+	rq.out = out;
+	rq.has_r = has_r;
+	rq.null_group = !has_r;
+	rq.keys32 = keys32;
+	return rq;
+}
+
+static int group_count_common(mdb_dev_ctx *ctx, gc_request *rq)
+{
+	const int64_t *keys_l = rq->l.keys, *keys_r = rq->has_r ? rq->r.keys : NULL;
+	const uint64_t n_l = rq->l.n, n_r = rq->r.n;
+	const bool has_r = rq->has_r, keys32 = rq->keys32;
 	/* first the histogram-free layout for the second partition level; the exact layout is the fallback
 	 * when skewed keys overflow a leaf region (detected on the device, reported with the results) */
-	bool fast = true, records = true, no_build_r = false, narrow = false;
-	int64_t base = 0;
-	gc_window win = { 0, 0, false, false, false, false };
+	rq->fast = true;
+	rq->records = true;
+	rq->no_build_r = false;
+	rq->narrow = false;
+	rq->base = 0;
+	rq->win = { 0, 0, false, false, false, false };
 	int rc = MIDORIDB_OK;
 	/* plain GROUP BY whose key sample held duplicates (at most a few 10^5 distinct values): the leaves hold a few values with
 	 * hundreds or thousands of rows each, their sizes vary by whole multiples, and the fixed-capacity layout would overflow
@@ -2610,65 +2817,64 @@ static int group_count_common(mdb_dev_ctx *ctx, const int64_t *keys_l, const uin
 		if (ctx->gh_distinct >= 3500u)
 			fast1 = true;
 		else
-			fast = false;
+			rq->fast = false;
 	}
-	rc = gc_narrow_guess(ctx, keys_l, null_l, n_l, has_r ? keys_r : NULL, null_r, n_r, &narrow, &base, &win, keys32, has_r);
+	rc = gc_narrow_guess(ctx, keys_l, rq->l.nulls, n_l, keys_r, rq->r.nulls, n_r, &rq->narrow, &rq->base, &rq->win, keys32, has_r);
 	if (rc)
 		return rc;
 	if (keys32) {		/* int32 columns are inside the plain narrow form's window whatever the sample says; the sample offers the compact one */
-		if (!narrow)
-			win.kbits = 0;
-		narrow = ctx->narrow_mode != 0;
-		base = 0;
+		if (!rq->narrow)
+			rq->win.kbits = 0;
+		rq->narrow = ctx->narrow_mode != 0;
+		rq->base = 0;
 	}
-	win.fast1 = fast1;
+	rq->win.fast1 = fast1;
 	/* the histogram-free layout overflowed on these very columns last time (skewed or heavily duplicated keys): exact at once */
-	if (fast && ctx->ex_keys == keys_l && ctx->ex_nl == n_l && ctx->ex_nr == (has_r ? n_r : 0) && ++ctx->ex_uses < GC_HINT_USES) {
-		fast = false;
-		win.fast1 = false;
+	if (rq->fast && ctx->ex_keys == keys_l && ctx->ex_nl == n_l && ctx->ex_nr == (has_r ? n_r : 0) && ++ctx->ex_uses < GC_HINT_USES) {
+		rq->fast = false;
+		rq->win.fast1 = false;
 	}
 	for (int attempt = 0; attempt < 6; attempt++) {
 		ctx->plan.retries = (uint32_t)attempt;
-		rc = group_count_run(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, has_r, null_group, fast, records, no_build_r, narrow,
-				     base, win, keys32, out_key, out_count, out_first, cap, out_groups, out_joined);
+		rc = group_count_run(ctx, *rq);
 		if ((rc == GC_RETRY_PLAIN || rc == GC_RETRY_WIDE) && ctx->guess_remembered && ctx->narrow_mode == 1 && !keys32) {
 			/* a REMEMBERED verdict proved wrong: the buffers hold other data than when it was made (a caller's allocator handed
 			 * the same addresses out again).  Not a reason to give the narrow forms up: forget, look at the data itself, go on */
 			ctx->nh_result = -1;
 			ctx->sr_valid = 0;
 			ctx->nh_distrust = 1;
-			narrow = false;
-			base = 0;
-			rc = gc_narrow_guess(ctx, keys_l, null_l, n_l, has_r ? keys_r : NULL, null_r, n_r, &narrow, &base, &win, keys32, has_r);
+			rq->narrow = false;
+			rq->base = 0;
+			rc = gc_narrow_guess(ctx, keys_l, rq->l.nulls, n_l, keys_r, rq->r.nulls, n_r, &rq->narrow, &rq->base, &rq->win, keys32, has_r);
 			if (rc)
 				return rc;
-			win.fast1 = fast1 && fast;
+			rq->win.fast1 = fast1 && rq->fast;
 		} else if (rc == GC_RETRY_PLAIN) {
 			/* the sample missed the column's extremes: the plain narrow form (any 2^32-wide window) is tried next,
 			 * and remembered for these columns */
-			win.kbits = 0;
+			rq->win.kbits = 0;
 			if (ctx->narrow_mode == 1)
-				gc_narrow_note(ctx, keys_l, n_l, has_r ? keys_r : NULL, n_r, true, base);
+				gc_narrow_note(ctx, keys_l, n_l, keys_r, n_r, true, rq->base);
 		} else if (rc == GC_RETRY_WIDE) {
-			narrow = false;
+			rq->narrow = false;
 			if (ctx->narrow_mode == 1 && !keys32)
 				ctx->nh_distrust = 8;	/* whatever said "narrow" was wrong: look at the data itself the next few times */
 			if (ctx->narrow_mode == 1 && !keys32)
-				gc_narrow_note(ctx, keys_l, n_l, has_r ? keys_r : NULL, n_r, false);	/* the sample missed a wide key */
+				gc_narrow_note(ctx, keys_l, n_l, keys_r, n_r, false);	/* the sample missed a wide key */
 		} else if (rc == GC_RETRY_EXACT) {
-			fast = false;
-			win.fast1 = false;
+			rq->fast = false;
+			rq->win.fast1 = false;
 			ctx->ex_keys = keys_l;
 			ctx->ex_nl = n_l;
 			ctx->ex_nr = has_r ? n_r : 0;
 			ctx->ex_uses = 0;
 		}	/* (gc_begin then also leaves the narrow form of a join: it is only built on the fast layout) */
 		else if (rc == GC_RETRY_DENSE)
-			records = false;
+			rq->records = false;
 		else if (rc == GC_RETRY_UNKEYED || rc == GC_RETRY_REC64 || rc == GC_RETRY_TWO_LEVEL || rc == GC_RETRY_NODENSE)
 			;		/* (gc_finish has set ctx->keyed_distrust / cleared ctx->r32_ok / noted the columns in ctx->lw_bad_*) */
 		else if (rc == GC_RETRY_BUILD_L)
-			no_build_r = true;
+			rq->no_build_r = true;
 		else
 			break;
 	}
@@ -2788,9 +2994,9 @@ __global__ __launch_bounds__(GC_THREADS) void k_tiny_group_count(tiny_args a)
 		atomicAdd(&s_sum, joined);
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		a.status[0] = base > a.cap ? 4096u : 0u;
-		a.status[1] = base;
-		*(unsigned long long *)(a.status + 2) = s_sum;
+		a.status[MDB_STW_FLAGS] = base > a.cap ? TINY_ST_OVER_CAP : 0u;
+		a.status[GC_STW_LIST_LEN] = base;
+		*(unsigned long long *)(a.status + GC_STW_JOINED) = s_sum;
 	}
 }
 
@@ -2826,12 +3032,12 @@ int tiny_group_count(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nu
 	uint32_t *h = (uint32_t *)ctx->h_pinned;
 	MDB_HIP(ctx, hipMemcpyAsync(h, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h[0] & 4096u)
+	if (h[MDB_STW_FLAGS] & TINY_ST_OVER_CAP)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)cap,
-				   (unsigned long long)h[1]);
-	*out_groups = h[1];
+				   (unsigned long long)h[GC_STW_LIST_LEN]);
+	*out_groups = h[GC_STW_LIST_LEN];
 	if (out_joined)
-		*out_joined = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+		*out_joined = (uint64_t)h[GC_STW_JOINED] | ((uint64_t)h[GC_STW_JOINED + 1] << 32);
 	gc_plan_shape(ctx, 0, 2, 0, 0);
 	return 0;
 }
@@ -2896,21 +3102,21 @@ again: {
 		return rc;
 	MDB_HIP(ctx, hipMemcpyAsync(h, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h[0]) {
+	if (h[MDB_STW_FLAGS]) {
 		if (mdb_knob_set("MDB_DEBUG_UNORDERED"))
-			fprintf(stderr, "unordered form not served: flags %u (k %u, b2 %u, rem %u)\n", h[0], plan.kbits, plan.b2, plan.rem);
-		if ((h[0] & 128u) && remembered && !fresh) {
+			fprintf(stderr, "unordered form not served: flags %u (k %u, b2 %u, rem %u)\n", h[MDB_STW_FLAGS], plan.kbits, plan.b2, plan.rem);
+		if ((h[MDB_STW_FLAGS] & MDB_ST_KEY_OUTSIDE) && remembered && !fresh) {
 			fresh = true;	/* the window came from a remembered sample and the column's contents have changed since */
 			goto again;
 		}
-		if (h[0] & 128u)
+		if (h[MDB_STW_FLAGS] & MDB_ST_KEY_OUTSIDE)
 			ctx->nh_distrust = 8;	/* a right key outside the sampled window: look at the data itself the next few times */
 		return 1;
 	}
 	}
-	*out_groups = h[1];
+	*out_groups = h[MDB_SHARD_STW_GROUPS];
 	if (out_joined)
-		*out_joined = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+		*out_joined = (uint64_t)h[MDB_SHARD_STW_JOINED] | ((uint64_t)h[MDB_SHARD_STW_JOINED + 1] << 32);
 	gc_plan_shape(ctx, 2, plan.b2 ? 2 : 1, 1, 1);
 	return 0;
 }
@@ -2980,14 +3186,14 @@ extern "C" int mdb_dev_group_count_keys(mdb_dev_ctx *ctx, const int64_t *keys, c
 			return rc;
 		MDB_HIP(ctx, hipMemcpyAsync(h, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		if (!h[0]) {
-			*out_groups = h[1];
+		if (!h[MDB_STW_FLAGS]) {
+			*out_groups = h[MDB_SHARD_STW_GROUPS];
 			return MIDORIDB_OK;
 		}
 		if (mdb_knob_set("MDB_DEBUG_UNORDERED"))
-			fprintf(stderr, "group_count_keys not served: flags %u (k %u, b2 %u, rem %u)\n", h[0], plan.kbits, plan.b2, plan.rem);
-		if (!((h[0] & 128u) && remembered && attempt == 0)) {	/* (a remembered sample of a column whose contents changed: taken again, once) */
-			if (h[0] & 128u)
+			fprintf(stderr, "group_count_keys not served: flags %u (k %u, b2 %u, rem %u)\n", h[MDB_STW_FLAGS], plan.kbits, plan.b2, plan.rem);
+		if (!((h[MDB_STW_FLAGS] & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0)) {	/* (a remembered sample of a column whose contents changed: taken again, once) */
+			if (h[MDB_STW_FLAGS] & MDB_ST_KEY_OUTSIDE)
 				ctx->nh_distrust = 8;
 			return 1;
 		}
@@ -3039,8 +3245,8 @@ extern "C" int mdb_dev_join_group_count(mdb_dev_ctx *ctx, const int64_t *keys_l,
 		if (out_joined)
 			*out_joined = 0;
 	}
-	return group_count_common(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, true, false, out_key, out_count, out_first,
-				  cap, out_groups, out_joined);
+	gc_request rq = gc_request_of({ keys_l, null_l, n_l }, { keys_r, null_r, n_r }, { out_key, out_count, out_first, cap, out_groups, out_joined }, true);
+	return group_count_common(ctx, &rq);
 }
 
 /* ---- split form for pipelines whose right table arrives later (multi-GPU exchange) ---- */
@@ -3052,63 +3258,58 @@ static gc_state *gc_pending(mdb_dev_ctx *ctx)
 	return (gc_state *)ctx->pending_op;
 }
 
-static int gc_split_begin(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, uint64_t n_r_max, bool keys32)
+static int gc_split_begin(mdb_dev_ctx *ctx, const gc_table &left, uint64_t n_r_max, bool keys32)
 {
 	gc_state *st = gc_pending(ctx);
 	if (!st)
 		return -MIDORIDB_NOMEM;
-	memset(st, 0, sizeof(*st));
-	st->keys_l = keys_l;
-	st->null_l = null_l;
-	st->n_l = n_l;
-	st->n_r_cap = n_r_max;
-	st->has_r = true;
-	st->null_group = false;
-	st->fast = true;
-	st->want_records = true;
-	st->keys32 = keys32;
-	if (n_l == 0)
-		return MIDORIDB_OK;	/* nothing to prepare; finish() returns the empty result */
-	/* the window comes from the left table's sample alone: the right table is checked as it is partitioned (a key outside
-	 * sends finish() to the unsplit operator, which samples both tables) */
-	gc_window win = { 0, 0, false, false, false, false };
-	int rc = gc_narrow_guess(ctx, keys_l, null_l, n_l, NULL, NULL, 0, &st->narrow, &st->base, &win, keys32);
-	if (rc)
-		return rc;
-	if (keys32) {		/* int32 columns are inside the plain narrow form's window whatever the sample says */
-		if (!st->narrow)
-			win.kbits = 0;
-		st->narrow = ctx->narrow_mode != 0;
-		st->base = 0;
+	gc_request rq = gc_request_of(left, { NULL, NULL, n_r_max }, { NULL, NULL, NULL, 0, NULL, NULL }, true, keys32);
+	rq.fast = true;
+	rq.records = true;
+	if (left.n) {
+		/* the window comes from the left table's sample alone: the right table is checked as it is partitioned (a key outside
+		 * sends finish() to the unsplit operator, which samples both tables) */
+		gc_window win = { 0, 0, false, false, false, false };
+		int rc = gc_narrow_guess(ctx, left.keys, left.nulls, left.n, NULL, NULL, 0, &rq.narrow, &rq.base, &win, keys32);
+		if (rc) {
+			gc_state_fill(st, rq, false);
+			return rc;
+		}
+		if (keys32) {		/* int32 columns are inside the plain narrow form's window whatever the sample says */
+			if (!rq.narrow)
+				win.kbits = 0;
+			rq.narrow = ctx->narrow_mode != 0;
+			rq.base = 0;
+		}
+		rq.win.kbits = win.kbits;	/* (the window alone: what the sample says of the right table's share means nothing here) */
+		rq.win.lo = win.lo;
 	}
-	st->key_bits = st->narrow ? win.kbits : 0u;
-	st->key_lo = win.lo;
+	gc_state_fill(st, rq, false);
+	if (left.n == 0)
+		return MIDORIDB_OK;	/* nothing to prepare; finish() returns the empty result */
 	return gc_begin(ctx, st);
 }
 
-static int gc_split_finish(mdb_dev_ctx *ctx, const int64_t *keys_r, const uint64_t *null_r, uint64_t n_r, int64_t *out_key,
-			   int64_t *out_count, uint32_t *out_first, uint64_t cap, uint64_t *out_groups, uint64_t *out_joined, bool keys32)
+static int gc_split_finish(mdb_dev_ctx *ctx, const gc_table &right, const gc_out &out, bool keys32)
 {
 	gc_state *st = gc_pending(ctx);
 	if (!st || !st->keys_l)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_group_count_finish without begin");
 	if (st->keys32 != keys32)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_group_count_finish: key width differs from begin()");
-	const int64_t *keys_l = st->keys_l;
-	const uint64_t *null_l = st->null_l;
-	const uint64_t n_l = st->n_l;
-	*out_groups = 0;
-	if (out_joined)
-		*out_joined = 0;
+	gc_request whole = gc_request_of({ st->keys_l, st->null_l, st->n_l }, right, out, true, keys32);	/* the unsplit operator over the same tables */
+	*out.groups = 0;
+	if (out.joined)
+		*out.joined = 0;
 	int rc = MIDORIDB_OK;
-	if (n_l == 0 || n_r == 0) {
+	if (whole.l.n == 0 || right.n == 0) {
 		if (st->active)
 			rc = mdb_dev_sync(ctx);		/* drain the prepared left partition */
 		st->active = false;
 		st->keys_l = NULL;
 		return rc;
 	}
-	if (n_r > st->n_r_cap) {
+	if (right.n > st->n_r_cap) {
 		/* more right rows than announced (a skewed exchange sent this GPU more than its share): the scratch arena was
 		 * sized for the announced table - drop the prepared left partition and run the whole operator on the real sizes */
 		rc = mdb_dev_sync(ctx);
@@ -3116,15 +3317,13 @@ static int gc_split_finish(mdb_dev_ctx *ctx, const int64_t *keys_r, const uint64
 		st->keys_l = NULL;
 		if (rc)
 			return rc;
-		return group_count_common(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, true, false, out_key, out_count, out_first, cap,
-					  out_groups, out_joined, keys32);
+		return group_count_common(ctx, &whole);
 	}
-	rc = gc_finish(ctx, st, keys_r, null_r, n_r, out_key, out_count, out_first, cap, out_groups, out_joined);
+	rc = gc_finish(ctx, st, right, out);
 	st->keys_l = NULL;
 	if (rc == GC_RETRY_EXACT || rc == GC_RETRY_DENSE || rc == GC_RETRY_BUILD_L || rc == GC_RETRY_WIDE || rc == GC_RETRY_PLAIN || rc == GC_RETRY_UNKEYED || rc == GC_RETRY_REC64 ||
 	    rc == GC_RETRY_TWO_LEVEL || rc == GC_RETRY_NODENSE)	/* skew / huge counts / wide keys: redo the whole operator */
-		rc = group_count_common(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, true, false, out_key, out_count, out_first,
-					cap, out_groups, out_joined, keys32);
+		rc = group_count_common(ctx, &whole);
 	return rc;
 }
 
@@ -3177,19 +3376,13 @@ extern "C" int mdb_dev_join_group_count_multi(mdb_dev_ctx *ctx, const int64_t *k
 			*out_joined = 0;
 	}
 	if (smallest >= (1u << 16) && n_l >= (1u << 20)) {	/* (small tables: the chain's single-workgroup and one-level forms are quicker) */
-		gc_extras ex;
-		memset(&ex, 0, sizeof(ex));
-		ex.n = n_right - 1;
-		for (int t = 1; t < n_right; t++) {
-			ex.keys[t - 1] = keys_r[t];
-			ex.nulls[t - 1] = null_r ? null_r[t] : NULL;
-			ex.rows[t - 1] = n_r[t];
-		}
+		gc_request rq = gc_request_of({ keys_l, null_l, n_l }, { keys_r[0], null_r ? null_r[0] : NULL, n_r[0] },
+					      { out_key, out_count, out_first, cap, out_groups, out_joined }, true);
+		rq.nextra = n_right - 1;
+		for (int t = 1; t < n_right; t++)
+			rq.x[t - 1] = { keys_r[t], null_r ? null_r[t] : NULL, n_r[t] };
 		mdb_memo_switch(ctx, keys_l, n_l, keys_r[0], n_r[0]);
-		gc_pending_extras = &ex;
-		rc = group_count_common(ctx, keys_l, null_l, n_l, keys_r[0], null_r ? null_r[0] : NULL, n_r[0], true, false, out_key, out_count, out_first, cap,
-					out_groups, out_joined);
-		gc_pending_extras = NULL;
+		rc = group_count_common(ctx, &rq);
 	}
 	if (rc != GC_NOT_SERVED)
 		return rc;
@@ -3259,7 +3452,7 @@ extern "C" int mdb_dev_join_group_count_begin(mdb_dev_ctx *ctx, const int64_t *k
 					      uint64_t n_r_max)
 {
 	mdb_plan_scope plan_scope(ctx);
-	return gc_split_begin(ctx, keys_l, null_l, n_l, n_r_max, false);
+	return gc_split_begin(ctx, { keys_l, null_l, n_l }, n_r_max, false);
 }
 
 extern "C" int mdb_dev_join_group_count_finish(mdb_dev_ctx *ctx, const int64_t *keys_r, const uint64_t *null_r, uint64_t n_r,
@@ -3268,7 +3461,7 @@ extern "C" int mdb_dev_join_group_count_finish(mdb_dev_ctx *ctx, const int64_t *
 {
 	mdb_plan_scope plan_scope(ctx);
 	(void)flags;
-	return gc_split_finish(ctx, keys_r, null_r, n_r, out_key, out_count, out_first, cap, out_groups, out_joined, false);
+	return gc_split_finish(ctx, { keys_r, null_r, n_r }, { out_key, out_count, out_first, cap, out_groups, out_joined }, false);
 }
 
 /* ---- int32 key columns (what arrives over xGMI in the 4-byte wire format): same operator, no widening pass ---- */
@@ -3280,14 +3473,15 @@ extern "C" int mdb_dev_join_group_count_i32(mdb_dev_ctx *ctx, const int32_t *key
 	mdb_plan_scope plan_scope(ctx);
 	(void)flags;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
-	return group_count_common(ctx, reinterpret_cast<const int64_t *>(keys_l), NULL, n_l, reinterpret_cast<const int64_t *>(keys_r), NULL,
-				  n_r, true, false, out_key, out_count, out_first, cap, out_groups, out_joined, true);
+	gc_request rq = gc_request_of({ reinterpret_cast<const int64_t *>(keys_l), NULL, n_l }, { reinterpret_cast<const int64_t *>(keys_r), NULL, n_r },
+				      { out_key, out_count, out_first, cap, out_groups, out_joined }, true, true);
+	return group_count_common(ctx, &rq);
 }
 
 extern "C" int mdb_dev_join_group_count_begin_i32(mdb_dev_ctx *ctx, const int32_t *keys_l, uint64_t n_l, uint64_t n_r_max)
 {
 	mdb_plan_scope plan_scope(ctx);
-	return gc_split_begin(ctx, reinterpret_cast<const int64_t *>(keys_l), NULL, n_l, n_r_max, true);
+	return gc_split_begin(ctx, { reinterpret_cast<const int64_t *>(keys_l), NULL, n_l }, n_r_max, true);
 }
 
 extern "C" int mdb_dev_join_group_count_finish_i32(mdb_dev_ctx *ctx, const int32_t *keys_r, uint64_t n_r, uint32_t flags,
@@ -3296,8 +3490,7 @@ extern "C" int mdb_dev_join_group_count_finish_i32(mdb_dev_ctx *ctx, const int32
 {
 	mdb_plan_scope plan_scope(ctx);
 	(void)flags;
-	return gc_split_finish(ctx, reinterpret_cast<const int64_t *>(keys_r), NULL, n_r, out_key, out_count, out_first, cap, out_groups,
-			       out_joined, true);
+	return gc_split_finish(ctx, { reinterpret_cast<const int64_t *>(keys_r), NULL, n_r }, { out_key, out_count, out_first, cap, out_groups, out_joined }, true);
 }
 
 extern "C" int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, uint32_t flags,
@@ -3369,8 +3562,8 @@ extern "C" int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const 
 			}
 		}
 	}
-	return group_count_common(ctx, keys, nullbits, n, NULL, NULL, 0, false, true, NULL, out_count, out_first, cap, out_groups,
-				  NULL);
+	gc_request rq = gc_request_of({ keys, nullbits, n }, { NULL, NULL, 0 }, { NULL, out_count, out_first, cap, out_groups, NULL }, false);
+	return group_count_common(ctx, &rq);
 }
 
 /* ------------------------------------------------------------------ plans as data (include/mdb_dev.h: mdb_dev_explain_*)

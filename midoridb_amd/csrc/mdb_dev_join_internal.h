@@ -11,6 +11,7 @@
 #define MDB_DEV_JOIN_INTERNAL_H
 
 #include <stdlib.h>
+#include <stddef.h>
 #include "mdb_dev_internal.h"
 
 /* ------------------------------------------------------------------ shared leaf helpers */
@@ -195,13 +196,64 @@ enum gc_internal_rc {
 	GC_EXPLAINED,	/* internal: mdb_dev_explain_*() - the plan is written, nothing was launched */
 	GC_NOT_SERVED,	/* internal: further right tables, but the operator did not take the two-level direct-address form (or a product of counts overflowed, or a hot leaf): the caller chains two-table operators instead */
 };
-#define GC_ST_LEFT_DUPS 32768u	/* status bit 15: a key that has partners has several rows in the LEFT table (raised by the direct-address leaf kernels) */
-/* words of ctx->d_status the fused operator uses beyond [0..9] (flags, record-list length, joined rows, NULL-group stats, records):
- * [10..21] the key sample's six 8-byte extremes (before the operator starts), [16..17] the right table's smallest / largest
- * key - window base (min-max pruning, while it runs) */
-#define GC_ST_MINMAX 16
-#define GC_ST_MINMAX64 40	/* [40..43] the right table's smallest / largest key as two signed 64-bit words (min-max pruning, 64-bit form) */
-#define GC_ST_WINDOW 20	/* [20..21] 0 and 2^key_bits - 1: the whole window as a pruning range (further right tables drop what lies outside) */
+/* ---- the fused operator's flags in word 0 of ctx->d_status (beside the common MDB_ST_* ones), raised by its leaf kernels and the kernels that feed
+ * them, read by gc_finish, tiny_group_count and the three-table caller */
+#define GC_ST_TABLE_FULL 1u		/* a leaf's hash table is full */
+#define GC_ST_COUNT_NOT_REC64 4u	/* a COUNT(*) does not fit a 64-bit record beside the row id */
+#define GC_ST_COUNT_NOT_REC32 16u	/* ... nor a 4-byte record */
+#define GC_ST_HOT_LEAVES 64u		/* leaves left to the hot-key path */
+#define GC_ST_COUNT_NOT_KEYED 256u	/* a COUNT(*) does not fit a keyed record */
+#define GC_ST_REC32_STALE 512u		/* 4-byte records were written on a remembered verdict that no longer holds */
+#define GC_ST_ROWS_NOT_16BIT 1024u	/* a 16-bit row count of the one-level leaves (k_leaf_wide) overflowed */
+#define GC_ST_PRODUCT_WIDE 2048u	/* a product of the right tables' counts beyond 32 bits */
+#define GC_ST_COUNTS_NOT_4BYTE 4096u	/* k_leaf_wide4's count fields overflowed */
+#define GC_ST_RANGE_FULL 8192u		/* an ordering range outgrew its region */
+#define GC_ST_LEFT_DUPS 32768u		/* a key that has partners has several rows in the LEFT table (raised by the direct-address leaf kernels) */
+#define GC_ST_EXC_FULL 131072u		/* the bit-per-row form's exception list overflowed */
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE, GC_ST_TABLE_FULL, GC_ST_COUNT_NOT_REC64, GC_ST_COUNT_NOT_REC32,
+				   GC_ST_HOT_LEAVES, GC_ST_COUNT_NOT_KEYED, GC_ST_REC32_STALE, GC_ST_ROWS_NOT_16BIT, GC_ST_PRODUCT_WIDE, GC_ST_COUNTS_NOT_4BYTE,
+				   GC_ST_RANGE_FULL, GC_ST_LEFT_DUPS, GC_ST_EXC_FULL }),
+	      "fused operator: two status flags share a bit");
+
+/* the single-workgroup operators (k_tiny_group_count, k_tiny_join_pairs) WRITE word 0 - nothing else has run - and word GC_STW_LIST_LEN: the
+ * number of results, and this flag when they are more than the caller's buffers hold */
+#define TINY_ST_OVER_CAP 4096u
+
+/* ---- the words of ctx->d_status the fused operator uses (4-byte word indices).  Shared in time: [10..21] hold the key sample's extremes
+ * BEFORE the operator starts (gc_sample_range reads them back at once); while it runs [12..13] are the bit-per-row counters, [16..17] the
+ * right table's key range and [20..21] the window - all inside the sample's words, which are dead by then. */
+#define GC_STW_LIST_LEN 1	/* slots of the record list handed out so far (the tiny and any-order operators: the number of groups) */
+#define GC_STW_JOINED 2		/* [2..3] joined rows (u64) */
+#define GC_STW_NULL_STATS 4	/* [4..7] NULL group: rows, first row (two u64) */
+#define GC_STW_RECORDS 8	/* real records = groups */
+#define GC_STW_LAST_FIRST 9	/* one-level leaves: the largest first row id; plain GROUP BY's sample: distinct values */
+#define GC_STW_SAMPLE 10	/* [10..21] the key sample's six 8-byte extremes */
+#define GC_STW_DN_CLEARED 12	/* bit-per-row form: bits cleared ... */
+#define GC_STW_DN_EXC 13	/* ... and exceptions listed */
+#define GC_STW_MINMAX 16	/* [16..17] the right table's smallest / largest key - window base (min-max pruning) */
+#define GC_STW_WINDOW 20	/* [20..21] 0 and 2^key_bits - 1: the whole window as a pruning range (further right tables drop what lies outside) */
+#define GC_STW_MINMAX64 40	/* [40..43] the right table's smallest / largest key as two signed 64-bit words (min-max pruning, 64-bit form) */
+
+/* what the host copies back from word 0 on (to ctx->h_pinned + MDB_HP_STATUS): 40 bytes where the bit-per-row counters are not needed, 56 with them */
+struct gc_readback {
+	uint32_t flags;
+	uint32_t list_len;
+	uint64_t joined;
+	uint64_t null_stats[2];
+	uint32_t groups;
+	uint32_t last_first;
+	uint32_t sample_head[2];	/* (not the operator's) */
+	uint32_t dn_cleared;
+	uint32_t dn_exceptions;
+};
+#define GC_RB_BYTES 40
+#define GC_RB_BYTES_DN 56
+static_assert(sizeof(gc_readback) == GC_RB_BYTES_DN && offsetof(gc_readback, flags) == 4 * MDB_STW_FLAGS && offsetof(gc_readback, list_len) == 4 * GC_STW_LIST_LEN &&
+		      offsetof(gc_readback, joined) == 4 * GC_STW_JOINED && offsetof(gc_readback, null_stats) == 4 * GC_STW_NULL_STATS &&
+		      offsetof(gc_readback, groups) == 4 * GC_STW_RECORDS && offsetof(gc_readback, last_first) == 4 * GC_STW_LAST_FIRST &&
+		      offsetof(gc_readback, sample_head) == 4 * GC_STW_SAMPLE && offsetof(gc_readback, dn_cleared) == 4 * GC_STW_DN_CLEARED &&
+		      offsetof(gc_readback, dn_exceptions) == 4 * GC_STW_DN_EXC && GC_RB_BYTES == 4 * GC_STW_SAMPLE,
+	      "gc_readback does not lie over the status words");
 
 struct gc_window {
 	uint32_t kbits;		/* 0 = no compact window */

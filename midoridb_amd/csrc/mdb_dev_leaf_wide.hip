@@ -173,7 +173,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide(gc_args a, uint32_t re
 	const unsigned long long got = lw_block_sum(sums, s_red), asked = lw_block_sum(want, s_red);
 	if (got != (asked | (HAS_R ? rows_r : 0u))) {	/* a 16-bit count overflowed: two levels and their hot-key path take over */
 		if (threadIdx.x == 0)
-			mdb_raise(a.status, 1024u);
+			mdb_raise(a.status, GC_ST_ROWS_NOT_16BIT);
 		return;
 	}
 	uint32_t total;
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide(gc_args a, uint32_t re
 		if (threadIdx.x == 0) {
 			const uint32_t nb = atomicAdd(a.rec_count, total);
 			if (nb + total > a.rec_cap) {
-				mdb_raise(a.status, 8u);
+				mdb_raise(a.status, MDB_ST_LIST_FULL);
 				s_base = 0xFFFFFFFFu;
 			} else {
 				s_base = nb;
@@ -216,13 +216,13 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide(gc_args a, uint32_t re
 			last_first = first > last_first ? first : last_first;
 			if (a.kbits && a.keyed_cbits) {
 				if (c >> a.keyed_cbits)
-					mdb_raise(a.status, 256u);	/* COUNT(*) does not fit a keyed record: redone with plain records */
+					mdb_raise(a.status, GC_ST_COUNT_NOT_KEYED);	/* COUNT(*) does not fit a keyed record: redone with plain records */
 				a.rec[pos++] = ((unsigned long long)first << (64 - a.kbits)) | ((unsigned long long)((leaf << rem) | s) << a.keyed_cbits) | c;
 			} else if (a.kbits) {
 				if (c >> (64 - a.kbits))
-					mdb_raise(a.status, 4u);	/* COUNT(*) does not fit beside the row id */
+					mdb_raise(a.status, GC_ST_COUNT_NOT_REC64);	/* COUNT(*) does not fit beside the row id */
 				if (c >> (32 - (a.kbits < 32 ? a.kbits : 31)))
-					mdb_raise(a.status, 16u);	/* ... nor in a 4-byte record */
+					mdb_raise(a.status, GC_ST_COUNT_NOT_REC32);	/* ... nor in a 4-byte record */
 				a.rec[pos++] = ((unsigned long long)first << (64 - a.kbits)) | c;
 			} else {
 				if (first < a.dense_n)
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide(gc_args a, uint32_t re
 		for (int w = 0; w < LW_THREADS / 64; w++)
 			m = (uint32_t)s_red[w] > m ? (uint32_t)s_red[w] : m;
 		if (m)
-			atomicMax(a.status + 9, m);
+			atomicMax(a.status + GC_STW_LAST_FIRST, m);
 	}
 }
 
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
 	uint32_t leaf = blockIdx.x, buf = 0;
 	if (nsub != LW12_NSUB) {	/* (the caller's layout is not the one this kernel walks: say so, never an empty result) */
 		if (threadIdx.x == 0)
-			mdb_raise(a.status, 1024u);
+			mdb_raise(a.status, GC_ST_ROWS_NOT_16BIT);
 		return;
 	}
 	/* (the bit-per-row form's pilot: the first dn_pilot digits only, nothing written but the counters - gc_args.dn_pilot) */
@@ -640,7 +640,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
 			} else if (total) {
 				nb = atomicAdd(a.rec_count, total);
 				if (nb + total > a.rec_cap) {
-					mdb_raise(a.status, 8u);
+					mdb_raise(a.status, MDB_ST_LIST_FULL);
 					nb = 0xFFFFFFFFu;
 				} else {
 					atomicAdd(a.rec_valid, total);
@@ -736,7 +736,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
 							else if (ep < a.dn_exc_cap)
 								a.dn_exc[ep] = ((unsigned long long)(f[e] & 0x07FFFFFFu) << 32) | c;
 							else
-								mdb_raise(a.status, 131072u);
+								mdb_raise(a.status, GC_ST_EXC_FULL);
 						}
 					}
 				}
@@ -758,9 +758,9 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
 			mdb_raise(a.status, GC_ST_LEFT_DUPS);
 		if (cmax && !DN) {	/* (a COUNT(*) of at most 15 * 31) */
 			if (a.keyed_cbits && (cmax >> a.keyed_cbits))
-				mdb_raise(a.status, 256u);	/* COUNT(*) does not fit a keyed record: redone with plain records */
+				mdb_raise(a.status, GC_ST_COUNT_NOT_KEYED);	/* COUNT(*) does not fit a keyed record: redone with plain records */
 			if (!a.keyed_cbits && (cmax >> (32 - (a.kbits < 32 ? a.kbits : 31))))
-				mdb_raise(a.status, 16u | (a.rec32 ? 512u : 0u));	/* ... a 4-byte record (written on a remembered verdict: redone with 8-byte ones) */
+				mdb_raise(a.status, a.rec32 ? (GC_ST_COUNT_NOT_REC32 | GC_ST_REC32_STALE) : GC_ST_COUNT_NOT_REC32);	/* ... a 4-byte record (written on a remembered verdict: redone with 8-byte ones) */
 		}
 		const unsigned long long sums = ((unsigned long long)sum_cl << 32) | (NX ? 0u : sum_cr);	/* low half: right rows counted, high half: left rows counted */
 		/* a count field that overflowed carried into its neighbour (or out of the word): the fields then sum to less than was added */
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
 		}
 	}
 	if (bad && threadIdx.x == 0)
-		mdb_raise(a.status, 1024u);
+		mdb_raise(a.status, GC_ST_ROWS_NOT_16BIT);
 	joined = lw_block_sum(joined, s_red);
 	if (threadIdx.x == 0 && joined)
 		atomicAdd(a.joined, joined);
@@ -807,7 +807,7 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
 		for (int w = 0; w < LW_THREADS / 64; w++)
 			m = (uint32_t)s_red[w] > m ? (uint32_t)s_red[w] : m;
 		if (m)
-			atomicMax(a.status + 9, m);
+			atomicMax(a.status + GC_STW_LAST_FIRST, m);
 	}
 }
 
@@ -931,7 +931,7 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 		} else if (total) {
 			nb = atomicAdd(a.rec_count, total);
 			if (nb + total > a.rec_cap) {
-				mdb_raise(a.status, 8u);
+				mdb_raise(a.status, MDB_ST_LIST_FULL);
 				nb = 0xFFFFFFFFu;
 			} else {
 				atomicAdd(a.rec_valid, total);
@@ -966,7 +966,7 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 				continue;
 			uint32_t at = atomicAdd(&a.rg_cnt[r], c);
 			if (at + c > a.rg_cap) {
-				mdb_raise(a.status, 8192u);	/* a range outgrew its region: the caller takes the record list and its sort */
+				mdb_raise(a.status, GC_ST_RANGE_FULL);	/* a range outgrew its region: the caller takes the record list and its sort */
 				at = a.rg_cap;
 			}
 			s_rg[r] = at;
@@ -1016,16 +1016,16 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 		mdb_raise(a.status, GC_ST_LEFT_DUPS);
 	if (cmax) {
 		if (a.keyed_cbits && (cmax >> a.keyed_cbits))
-			mdb_raise(a.status, 256u);	/* COUNT(*) does not fit a keyed record: redone with plain records */
+			mdb_raise(a.status, GC_ST_COUNT_NOT_KEYED);	/* COUNT(*) does not fit a keyed record: redone with plain records */
 		if (!a.keyed_cbits && (cmax >> (32 - (a.kbits < 32 ? a.kbits : 31))))
-			mdb_raise(a.status, 16u);	/* ... a 4-byte record */
+			mdb_raise(a.status, GC_ST_COUNT_NOT_REC32);	/* ... a 4-byte record */
 	}
 	/* a count field that overflowed carried into its neighbour (or out of the word): the fields then sum to less than was added */
 	const unsigned long long sums = ((unsigned long long)sum_cl << 32) | sum_cr, want = (unsigned long long)adds << 32;
 	const unsigned long long diff = lw_block_sum(sums - want, s_red);
 	if (diff != (unsigned long long)rows_r) {
 		if (threadIdx.x == 0)
-			mdb_raise(a.status, 4096u);
+			mdb_raise(a.status, GC_ST_COUNTS_NOT_4BYTE);
 		return;
 	}
 	const unsigned long long joined = lw_block_sum((unsigned long long)jsum, s_red);
@@ -1046,7 +1046,7 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 		for (int w = 0; w < LW_THREADS / 64; w++)
 			m = (uint32_t)s_red[w] > m ? (uint32_t)s_red[w] : m;
 		if (m)
-			atomicMax(a.status + 9, m);
+			atomicMax(a.status + GC_STW_LAST_FIRST, m);
 	}
 }
 

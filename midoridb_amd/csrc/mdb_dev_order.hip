@@ -157,7 +157,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_order_leaf_sparse(ord_args a)
 	if (c > a.cap || c > OS_MAX_REC) {	/* the scatter's region overflowed, or more records than the registers of a workgroup hold
 						 * (row ids bunched): the general path takes over */
 		if (threadIdx.x == 0 && a.status)
-			mdb_raise(a.status, 2u);
+			mdb_raise(a.status, MDB_ST_REGION_FULL);
 		return;
 	}
 	const uint32_t range_bits = a.kbits - a.leaf_bits, range = 1u << range_bits;
@@ -339,9 +339,9 @@ int order_records(mdb_dev_ctx *ctx, const unsigned long long *rec, uint64_t list
 				oa.key_lo = key_lo;
 				oa.status = ctx->d_status;
 				MDB_LAUNCH(ctx, "order_leaf_sparse", k_order_leaf_sparse, ps.nleaves, OS_THREADS, oa);
-				MDB_HIP(ctx, hipMemcpyAsync(&h[8], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+				MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_SORT_FLAGS], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
 				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-				if (!((uint32_t)h[8] & 2u))
+				if (!((uint32_t)h[MDB_HP_SORT_FLAGS] & MDB_ST_REGION_FULL))
 					return MIDORIDB_OK;
 				MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));	/* a region overflowed (row ids bunched): the general path */
 			}
@@ -390,9 +390,9 @@ int order_records(mdb_dev_ctx *ctx, const unsigned long long *rec, uint64_t list
 			oa.out_base = obase;
 		}
 		MDB_LAUNCH(ctx, "order_leaf", k_order_leaf, ps.nleaves, ORD_THREADS, oa);
-		MDB_HIP(ctx, hipMemcpyAsync(&h[8], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_SORT_FLAGS], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		if (!sort_fast || !((uint32_t)h[8] & 2u))
+		if (!sort_fast || !((uint32_t)h[MDB_HP_SORT_FLAGS] & MDB_ST_REGION_FULL))
 			break;
 		if (in32)
 			return GC_RETRY_REC64;	/* (a region of the ordering sort overflowed: its exact layout reads 8-byte records) */

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(OUTER_THREADS) void k_outer_place(const uint32_t *_
 		}
 	}
 	if (bad)
-		mdb_raise(status, 1u);
+		mdb_raise(status, MDB_FLAG_SET);
 }
 
 __global__ __launch_bounds__(OUTER_THREADS) void k_outer_words(uint32_t *__restrict__ head_d, const uint32_t *__restrict__ tail_d, uint64_t words)

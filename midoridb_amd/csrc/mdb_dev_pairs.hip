@@ -6,6 +6,13 @@
 #include "mdb_dev_join_internal.h"
 #include "mdb_dev_rowjoin.h"
 
+/* flags of the materialising joins in word 0 of ctx->d_status, beside the common MDB_ST_* ones (the row-order payload join has its own: RJ_ST_*) */
+#define PJ_ST_TABLE_FULL 1u	/* a leaf's hash table is full */
+#define PJ_ST_RIGHT_CHUNKED 16u	/* the emit kernel will sweep a leaf's right rows in several chunks: they must be in row-id order (the exact layout) */
+#define PJ_ST_DUP_RIGHT 32u	/* unique-key forms: a right key occurs twice */
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE, PJ_ST_TABLE_FULL, PJ_ST_RIGHT_CHUNKED, PJ_ST_DUP_RIGHT }),
+	      "pairs join: two status flags share a bit");
+
 /* ------------------------------------------------------------------ materialising join: count phase */
 
 /* ------------------------------------------------------------------ materialising join, unique right keys
@@ -98,7 +105,7 @@ __global__ __launch_bounds__(GC_THREADS, 8) void k_leaf_pairs_unique(pu_args a)
 					const uint32_t want = need > GC_REC_CHUNK ? need : GC_REC_CHUNK;
 					const uint32_t nb = atomicAdd(a.rec_count, want);
 					if (nb + want > a.rec_cap) {
-						mdb_raise(a.status, 8u);
+						mdb_raise(a.status, MDB_ST_LIST_FULL);
 						s_chunk[0] = 0;
 						s_chunk[2] = 0;
 					} else {
@@ -130,15 +137,15 @@ __global__ __launch_bounds__(GC_THREADS, 8) void k_leaf_pairs_unique(pu_args a)
 				const uint32_t rid_r = NARROW ? (uint32_t)hr[u] : rr[u];
 				if (key_r == 0) {
 					if (atomicExch(&s_val[GC_SLOTS], rid_r + 1u) != 0)
-						s_abort = 32u;
+						s_abort = PJ_ST_DUP_RIGHT;
 					continue;
 				}
 				bool created = false;
 				const uint32_t s = leaf_insert(s_key, GC_SLOTS, key_r, &created);
 				if (s == 0xFFFFFFFFu) {
-					s_abort = 1u;
+					s_abort = PJ_ST_TABLE_FULL;
 				} else if (!created) {
-					s_abort = 32u;		/* the key is already there: not a unique-key join */
+					s_abort = PJ_ST_DUP_RIGHT;		/* the key is already there: not a unique-key join */
 				} else {
 					s_val[s] = rid_r + 1u;
 					if (base == r0)
@@ -253,7 +260,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_pairs_count(pj_args a)
 	if (l0 == l1 || r0 == r1)
 		return;
 	if (threadIdx.x == 0 && r1 - r0 > PJ_CHUNK)
-		mdb_raise(a.status, 16u);	/* the emit kernel will sweep this leaf's right rows in several chunks: they must be in row-id order */
+		mdb_raise(a.status, PJ_ST_RIGHT_CHUNKED);	/* the emit kernel will sweep this leaf's right rows in several chunks: they must be in row-id order */
 	for (uint32_t s = threadIdx.x; s <= PJ_SLOTS; s += LEAF_THREADS) {
 		if (s < PJ_SLOTS)
 			s_key[s] = 0ull;
@@ -268,7 +275,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_pairs_count(pj_args a)
 		if (hv != 0) {
 			s = leaf_insert(s_key, PJ_SLOTS, hv);
 			if (s == 0xFFFFFFFFu) {
-				mdb_raise(a.status, 1u);
+				mdb_raise(a.status, PJ_ST_TABLE_FULL);
 				continue;
 			}
 		}
@@ -332,7 +339,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_pairs_emit(pj_args a)
 	for (uint32_t j = r0 + threadIdx.x; j < r1; j += LEAF_THREADS) {
 		const uint64_t hv = a.hv_r[j];
 		if (hv != 0 && leaf_insert(s_key, PJ_SLOTS, hv) == 0xFFFFFFFFu)
-			mdb_raise(a.status, 1u);
+			mdb_raise(a.status, PJ_ST_TABLE_FULL);
 	}
 	__syncthreads();
 
@@ -460,8 +467,8 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
 	a.cnt_r = pr.leaf_cnt;
 	a.cap_r = pr.leaf_cap;
 	a.rec = rec;
-	a.rec_count = ctx->d_status + 1;
-	a.rec_valid = ctx->d_status + 8;
+	a.rec_count = ctx->d_status + GC_STW_LIST_LEN;	/* (the list kernels share the fused operator's words) */
+	a.rec_valid = ctx->d_status + GC_STW_RECORDS;
 	a.rec_cap = (uint32_t)rec_cap;
 	a.kbits = kbits;
 	a.status = ctx->d_status;
@@ -476,15 +483,16 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
 		}
 	}
 	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = (uint32_t)h[1];
-	const uint64_t list_len = h[1] >> 32, J = (uint32_t)h[5];
-	if (status & 128u)
+	const gc_readback *rb = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS]);
+	const uint32_t status = rb->flags;
+	const uint64_t list_len = rb->list_len, J = rb->groups;
+	if (status & MDB_ST_KEY_OUTSIDE)
 		return 2;
-	if (status & 32u)
+	if (status & PJ_ST_DUP_RIGHT)
 		return 3;	/* a right key occurs more than once */
-	if (status & (1u | 2u | 8u))
+	if (status & (PJ_ST_TABLE_FULL | MDB_ST_REGION_FULL | MDB_ST_LIST_FULL))
 		return 1;
 	*out_count = J;
 	if (J == 0)
@@ -581,7 +589,7 @@ __global__ __launch_bounds__(PW_THREADS) void k_leaf_pairs_wide(pw_args a, uint3
 	occupied = lw_block_sum(occupied, s_red);
 	if (occupied != rows_r) {
 		if (threadIdx.x == 0)
-			mdb_raise(a.status, 32u);
+			mdb_raise(a.status, PJ_ST_DUP_RIGHT);
 		return;
 	}
 	unsigned long long pairs = 0;
@@ -758,7 +766,7 @@ static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	a.nsub = pl.nsub;
 	a.match = match;
 	a.n_l = (uint32_t)n_l;
-	a.joined = (unsigned long long *)(ctx->d_status + 2);
+	a.joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
 	a.status = ctx->d_status;
 	const size_t lds = (size_t)4 << rem;
 	MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leaf_pairs_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -770,15 +778,15 @@ static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	if (rc)
 		return rc;
 	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = (uint32_t)h[1];
-	const uint64_t J = h[2];
-	if (status & 128u)
+	const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
+	const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
+	if (status & MDB_ST_KEY_OUTSIDE)
 		return 2;
-	if (status & 32u)
+	if (status & PJ_ST_DUP_RIGHT)
 		return 3;
-	if (status & 2u)
+	if (status & MDB_ST_REGION_FULL)
 		return 1;
 	*out_count = J;
 	if (J == 0)
@@ -913,7 +921,7 @@ __global__ __launch_bounds__(PW_THREADS) void k_leaf_pairs_cell(pp_args a, uint3
 		__syncthreads();
 		if (s_dup) {
 			if (threadIdx.x == 0)
-				mdb_raise(a.status, 32u);
+				mdb_raise(a.status, PJ_ST_DUP_RIGHT);
 			return;
 		}
 		{	/* ---- left rows of this pass's slots: the partner's cell, if there is a partner, to out[left row id] */
@@ -1006,7 +1014,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_leaf_pairs_cell2(pl_args a, uint
 		__syncthreads();
 		if (s_dup) {	/* a right key occurs twice */
 			if (threadIdx.x == 0)
-				mdb_raise(a.status, 32u);
+				mdb_raise(a.status, PJ_ST_DUP_RIGHT);
 			return;
 		}
 		for (uint32_t i0 = 0; i0 < cl; i0 += 2u * PL_THREADS) {
@@ -1101,22 +1109,22 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		if (rc)
 			return rc;
 		uint64_t *h = ctx->h_pinned;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t status = (uint32_t)h[1];
-		const uint64_t J = h[2];
+		const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
+		const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
 		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 			fprintf(stderr, "join_payload (row order): k %u status %u J %llu of %llu left rows\n", kbits, status, (unsigned long long)J,
 				(unsigned long long)n_l);
 		if (status == 0 && J == (uint64_t)npay * n_l)
 			return served(3, kbits, 1);
-		if ((status & 128u) && remembered && attempt == 0) {
+		if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
 			ctx->nh_result = -1;
 			ctx->sr_valid = 0;
 			ctx->nh_distrust = 1;
 			continue;
 		}
-		if (status & 128u) {
+		if (status & MDB_ST_KEY_OUTSIDE) {
 			ctx->nh_distrust = 8;
 		} else {
 			ctx->jp_bad_l = keys_l;
@@ -1174,7 +1182,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		a.cap_r = pr.leaf_cap;
 		a.nleaves = pl.nleaves;
 		a.n_l = (uint32_t)n_l;
-		a.joined = (unsigned long long *)(ctx->d_status + 2);
+		a.joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
 		a.status = ctx->d_status;
 		const uint32_t grid = pl.nleaves < 8u * (uint32_t)ctx->num_cus ? pl.nleaves : 8u * (uint32_t)ctx->num_cus;
 		if (npay > 1) {
@@ -1183,24 +1191,24 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 			MDB_LAUNCH(ctx, "leaf_pairs_payload", k_leaf_pairs_cell2<1>, grid, PL_THREADS, a, rem, shift);
 		}
 		uint64_t *h = ctx->h_pinned;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t status = (uint32_t)h[1];
-		const uint64_t J = h[2];
+		const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
+		const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
 		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 			fprintf(stderr, "join_payload (two levels): k %u b2 %d rem %u status %u J %llu of %llu left rows\n", kbits, b2, rem, status, (unsigned long long)J,
 				(unsigned long long)n_l);
 		if (status == 0 && J == n_l)
 			return served(2, kbits, 2);
-		if ((status & 128u) && remembered && attempt == 0) {
+		if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
 			ctx->nh_result = -1;
 			ctx->sr_valid = 0;
 			ctx->nh_distrust = 1;
 			continue;
 		}
-		if (status & 128u) {
+		if (status & MDB_ST_KEY_OUTSIDE) {
 			ctx->nh_distrust = 8;
-		} else if (!(status & 2u)) {	/* (a region overflow says nothing about the join) */
+		} else if (!(status & MDB_ST_REGION_FULL)) {	/* (a region overflow says nothing about the join) */
 			ctx->jp_bad_l = keys_l;
 			ctx->jp_bad_nl = n_l;
 			ctx->jp_bad_r = keys_r;
@@ -1252,7 +1260,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	a.nleaves = pl.nleaves;
 	a.nsub = pl.nsub;
 	a.n_l = (uint32_t)n_l;
-	a.joined = (unsigned long long *)(ctx->d_status + 2);
+	a.joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
 	a.status = ctx->d_status;
 	if (pl.nsub > PP_MAX_SUB)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: %u sub-regions per digit", pl.nsub);
@@ -1269,18 +1277,18 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 			ac.out[0] = a.out[c];
 			ac.npay = 1;
 			if (c)
-				ac.joined = (unsigned long long *)(ctx->d_status + 6);
+				ac.joined = (unsigned long long *)(ctx->d_status + GC_STW_NULL_STATS + 2)	/* (a word nobody reads) */;
 			MDB_LAUNCH_LDS(ctx, "leaf_pairs_payload", k_leaf_pairs_cell, pl.nleaves, PW_THREADS, lds, ac, rem, shift);
 		}
 	}
 	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = (uint32_t)h[1];
-	const uint64_t J = h[2];
+	const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
+	const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
 	if (status == 0 && J == n_l)
 		return served(1, kbits, 1);
-	if ((status & 128u) && remembered && attempt == 0) {
+	if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
 		/* a REMEMBERED window proved wrong: the buffers hold other data than when it was learned (a caller's allocator handed the
 		 * same addresses out again) - forget, look at the data itself, once more */
 		ctx->nh_result = -1;
@@ -1288,7 +1296,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		ctx->nh_distrust = 1;
 		continue;
 	}
-	if (status & 128u) {	/* a key outside the window after all: the sample is not trusted for a while */
+	if (status & MDB_ST_KEY_OUTSIDE) {	/* a key outside the window after all: the sample is not trusted for a while */
 		ctx->nh_distrust = 8;
 	} else {
 		ctx->jp_bad_l = keys_l;
@@ -1369,10 +1377,10 @@ extern "C" int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_
 	if (rc)
 		return rc;
 	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 40, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = (uint32_t)h[1];
-	const uint64_t J = h[2];
+	const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
+	const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
 	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 		fprintf(stderr, "join_payload_multi (row order): %d tables, %d columns, k %u status %u J %llu of %llu x %d\n", nright, streams, kbits, status,
 			(unsigned long long)J, (unsigned long long)n_l, streams);
@@ -1451,8 +1459,8 @@ __global__ __launch_bounds__(GC_THREADS) void k_tiny_join_pairs(tinyp_args a)
 		}
 	}
 	if (threadIdx.x == 0) {
-		a.status[0] = base > a.cap ? 4096u : 0u;
-		a.status[1] = base;
+		a.status[MDB_STW_FLAGS] = base > a.cap ? TINY_ST_OVER_CAP : 0u;
+		a.status[GC_STW_LIST_LEN] = base;
 	}
 }
 
@@ -1488,7 +1496,7 @@ static int tiny_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64
 	hipError_t e = hipMemcpyAsync(h, ctx->d_status, 8, hipMemcpyDeviceToHost, ctx->stream);
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(ctx->stream);
-	if (e != hipSuccess || (h[0] & 4096u)) {
+	if (e != hipSuccess || (h[MDB_STW_FLAGS] & TINY_ST_OVER_CAP)) {
 		(void)mdb_cached_free(ctx, ol);
 		(void)mdb_cached_free(ctx, orr);
 		if (e != hipSuccess)
@@ -1497,7 +1505,7 @@ static int tiny_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64
 	}
 	*out_l = ol;
 	*out_r = orr;
-	*out_count = h[1];
+	*out_count = h[GC_STW_LIST_LEN];
 	return 0;
 }
 
@@ -1726,7 +1734,7 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 		a.n_l = (uint32_t)n_l;
 		a.out_l = a.out_r = NULL;
 		a.status = ctx->d_status;
-		a.total64 = (unsigned long long *)(ctx->d_status + 2);
+		a.total64 = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
 		a.nleaves = pl.nleaves;
 		MDB_LAUNCH(ctx, "leaf_pairs_count", k_leaf_pairs_count, pl.nleaves, LEAF_THREADS, a);
 
@@ -1734,21 +1742,22 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 		rc = mdb_scan_u32_inplace(ctx, match, mlen, scan_tmp);
 		if (rc)
 			return rc;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[0], match + n_l, 4, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_COUNT], match + n_l, 4, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, 4 * GC_STW_NULL_STATS, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		J = (uint32_t)h[0];
-		const uint32_t status = (uint32_t)h[1];
-		if (fast && (status & (2u | 16u)))
+		J = (uint32_t)h[MDB_HP_COUNT];
+		const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
+		if (fast && (status & (MDB_ST_REGION_FULL | PJ_ST_RIGHT_CHUNKED)))
 			continue;	/* region overflow, or a multi-chunk leaf with unordered right rows */
-		if (status & 1u)
+		if (status & PJ_ST_TABLE_FULL)
 			return mdb_set_err(ctx, -MIDORIDB_INTERNAL,
 					   "leaf hash table overflow (more than %u distinct keys in one leaf): unsupported key skew", PJ_SLOTS);
 		break;
 	}
-	if (h[2] != J)
+	const uint64_t total64 = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
+	if (total64 != J)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join produces %llu rows: more than the 2^32-1 a single call can materialise",
-				   (unsigned long long)h[2]);
+				   (unsigned long long)total64);
 	if (J == 0)
 		return MIDORIDB_OK;
 	uint32_t *ol = NULL, *orr = NULL;

@@ -35,6 +35,9 @@
 #include <type_traits>
 #include "mdb_dev_internal.h"
 
+#define PART_ST_OWN_RANGE_BROKEN 1024u	/* status flag of mdb_dev_partition_by_dest_pruned alone (beside MDB_ST_KEY_OUTSIDE): a key outside the range promised for its column */
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE, PART_ST_OWN_RANGE_BROKEN }), "partition: two status flags share a bit");
+
 #define PART_THREADS 512
 #define PART_WAVES (PART_THREADS / MDB_WAVE)
 #define PART_ITEMS (MDB_TILE / PART_THREADS)		/* 8 keys per thread */
@@ -278,7 +281,7 @@ __device__ static inline void part_load2(const mdb_level_args &a, const mdb_tile
 	}
 	if (LEVEL0 && KEEP && a.own_on && ((valid[0] && (raw_key[0] < a.own_lo || raw_key[0] > a.own_hi)) ||
 				   (valid[1] && (raw_key[1] < a.own_lo || raw_key[1] > a.own_hi))))
-		mdb_raise(a.status, 1024u);
+		mdb_raise(a.status, PART_ST_OWN_RANGE_BROKEN);
 	if (LEVEL0 && KEEP && a.keep_on) {
 		valid[0] = valid[0] && raw_key[0] >= a.keep_lo && raw_key[0] <= a.keep_hi;
 		valid[1] = valid[1] && raw_key[1] >= a.keep_lo && raw_key[1] <= a.keep_hi;
@@ -286,7 +289,7 @@ __device__ static inline void part_load2(const mdb_level_args &a, const mdb_tile
 	/* (with min-max pruning - range_in - a key outside the window is outside the right table's range, which lies inside the
 	 * window: the caller drops the row, nothing to report) */
 	if (LEVEL0 && !a.range_in && ((bad[0] && valid[0]) || (bad[1] && valid[1])))
-		mdb_raise(a.status, 128u);	/* a key outside the int32 range: the narrow form does not apply */
+		mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);	/* a key outside the int32 range: the narrow form does not apply */
 	if (RAW && a.skip_zero) {
 		valid[0] = valid[0] && hv[0] != 0;
 		valid[1] = valid[1] && hv[1] != 0;
@@ -846,7 +849,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_scatter(mdb_level_args a)
 	if (FAST && threadIdx.x < R) {
 		const bool ok = fast_base + total_d <= a.cap;
 		if (!ok)
-			mdb_raise(a.status, 2u);
+			mdb_raise(a.status, MDB_ST_REGION_FULL);
 		s_ok[threadIdx.x] = ok;
 		s_delta[threadIdx.x] = (int32_t)(fast_child * a.cap + fast_base - off_d);
 	}
@@ -885,7 +888,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_scatter(mdb_level_args a)
 			reinterpret_cast<uint32_t *>(a.hv_out)[g] = (uint32_t)h;
 		else if (INV && a.inverse_out == 2) {
 			if (((uint64_t)h + 0x80000000ull) >> 32)
-				mdb_raise(a.status, 128u);	/* the caller's promise (column statistics) does not hold: reported, not truncated */
+				mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);	/* the caller's promise (column statistics) does not hold: reported, not truncated */
 			reinterpret_cast<int32_t *>(a.hv_out)[g] = (int32_t)(int64_t)h;	/* 4-byte wire format */
 		}
 		else if (INV)
@@ -1447,9 +1450,9 @@ static int partition_impl(part_carver &cv, const int64_t *keys, const uint64_t *
 				 * 4-byte read-back and a synchronisation, ~15 us) - 26 000 workgroups that find an empty descriptor and leave
 				 * cost 0.09 ms at 10^8 rows */
 				uint64_t *h = ctx->h_pinned;
-				MDB_HIP(ctx, hipMemcpyAsync(&h[15], reg_nt + nreg0, 4, hipMemcpyDeviceToHost, ctx->stream));
+				MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_PART_TILES], reg_nt + nreg0, 4, hipMemcpyDeviceToHost, ctx->stream));
 				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-				const uint32_t got = (uint32_t)h[15];
+				const uint32_t got = (uint32_t)h[MDB_HP_PART_TILES];
 				real_tiles = got < next_tiles ? (got ? got : 1u) : next_tiles;
 			}
 			used_bits += bits1;
@@ -1799,10 +1802,10 @@ extern "C" int mdb_dev_partition_by_dest_pruned(mdb_dev_ctx *ctx, const int64_t 
 	MDB_HIP(ctx, hipMemcpyAsync(h_off, res.leaf_off, ((size_t)n_dest + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipMemcpyAsync(h_off + n_dest + 1, ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h_off[n_dest + 1] & 1024u)
+	if (h_off[n_dest + 1] & PART_ST_OWN_RANGE_BROKEN)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "partition_by_dest: a key lies outside the range [%lld, %lld] promised for its column",
 				   (long long)own_lo, (long long)own_hi);
-	if (keys32 && (h_off[n_dest + 1] & 128u))
+	if (keys32 && (h_off[n_dest + 1] & MDB_ST_KEY_OUTSIDE))
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "partition_by_dest: a key does not fit the 4-byte wire format (keys32 needs every key in "
 							 "the int32 range: check mdb_dev_key_range)");
 	for (uint32_t d = 0; d < n_dest; d++)

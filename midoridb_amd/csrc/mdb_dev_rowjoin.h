@@ -4,7 +4,31 @@
 #ifndef MDB_DEV_ROWJOIN_H
 #define MDB_DEV_ROWJOIN_H
 
+#include <stddef.h>
 #include "mdb_dev_internal.h"
+
+/* ---- flags of the row-order join and of the GROUP BY forms over a tile- or band-sorted column (mdb_dev_rowjoin.hip, mdb_dev_bandgroup.hip) in
+ * word 0 of ctx->d_status, beside the common MDB_ST_* ones */
+#define RJ_ST_NO_PARTNER 4u		/* join: a left row without partner */
+#define RJ_ST_DUP_RIGHT 32u		/* join: a right key occurs twice */
+#define RJ_ST_COUNT_NOT_REC32 512u	/* GROUP BY: a COUNT does not fit beside its row id in 32 bits (the ordering sort keeps 8-byte records) */
+#define RJ_ST_RANGE_FULL 8192u		/* GROUP BY: an ordering range outgrew its region */
+#define RJ_ST_EXC_FULL 16384u		/* GROUP BY, bit-per-row form: more keys with several rows than the exception list holds */
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE, RJ_ST_NO_PARTNER, RJ_ST_DUP_RIGHT, RJ_ST_COUNT_NOT_REC32,
+				   RJ_ST_RANGE_FULL, RJ_ST_EXC_FULL }),
+	      "row-order join / GROUP BY: two status flags share a bit");
+/* ... and the words behind it: the join keeps its joined rows in [2..3]; the GROUP BY forms lay theirs out as struct rj_readback */
+#define RJ_STW_JOINED 2		/* join: [2..3] joined rows (u64) */
+#define RJ_STW_GROUPS 1		/* GROUP BY: groups */
+#define RJ_STW_LIST_LEN 2	/* GROUP BY: slots of the record list handed out */
+#define RJ_STW_DENSE 4		/* GROUP BY, bit-per-row form: [4] rows that are not the first of their key, [5] exceptions, [6] rows seen */
+struct rj_readback {		/* what the GROUP BY forms copy back from word 0 on (to ctx->h_pinned + MDB_HP_STATUS): 16 bytes, or all 32 in the bit-per-row form */
+	uint32_t flags, groups, list_len, unused3;
+	uint32_t not_first, exceptions, rows_seen, unused7;
+};
+static_assert(sizeof(rj_readback) == 32 && offsetof(rj_readback, groups) == 4 * RJ_STW_GROUPS && offsetof(rj_readback, list_len) == 4 * RJ_STW_LIST_LEN &&
+		      offsetof(rj_readback, not_first) == 4 * RJ_STW_DENSE,
+	      "rj_readback does not lie over the status words");
 
 /* whether the form serves a join of n_l x n_r rows over a compact key window of 2^kbits values: windows of up to 2^27 values, key and
  * payload columns without NULL keys and 16-byte aligned */
@@ -12,13 +36,13 @@ bool mdb_rowjoin_serves(uint64_t n_l, uint64_t n_r, uint32_t kbits, const void *
 			const void *const *pay_in, void *const *out, int npay);
 uint32_t mdb_rowjoin_dbits(uint32_t kbits);
 size_t mdb_rowjoin_arena_bytes(uint64_t n_l, uint64_t n_r, uint32_t kbits, int npay);
-/* queues everything on ctx->stream (the arena begun, ctx->d_status cleared by the caller); no host sync.  Afterwards d_status[0] holds
- * the flags (4 a left row without partner, 32 duplicate right key, 128 key outside the window), d_status[2..3] the joined rows (u64) */
+/* queues everything on ctx->stream (the arena begun, ctx->d_status cleared by the caller); no host sync.  Afterwards the flag word holds
+ * RJ_ST_NO_PARTNER, RJ_ST_DUP_RIGHT, MDB_ST_KEY_OUTSIDE as they apply, words RJ_STW_JOINED.. the joined rows (u64) */
 int mdb_rowjoin_run(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l, const int64_t *keys_r, uint64_t n_r, const void *const *pay_in,
 		    int64_t win_lo, uint32_t kbits, int npay, void *const *out);
 
 /* ... of ONE left key column with several right tables on that key (mdb_dev_join_payload_multi): the left table is sorted once, one leaf
- * launch and one placement pass serve every (right table, payload column) pair - at most four.  d_status[2..3] then holds the (left row,
+ * launch and one placement pass serve every (right table, payload column) pair - at most four.  Words RJ_STW_JOINED.. then hold the (left row,
  * payload column) pairs served: the columns x the left rows when every left row found its partner in every table */
 struct mdb_rowjoin_right {
 	const int64_t *keys;

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(RJ_THREADS) void k_rj_tile_sort(rj_sort_args a, uin
 		}
 	}
 	if (bad)
-		mdb_raise(a.status, 128u);
+		mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);
 	__syncthreads();
 	/* exclusive scan of the D counters: thread t owns 1, 2 or 4 consecutive words of two counters each (D = 8 ... 8192; with fewer than
 	 * 2048 digits the first D / 2 threads own one word each) */
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_leaf(rj_leaf_args a)
 	}
 	}
 	if (miss)
-		mdb_raise(a.status, 4u);	/* a left row without partner */
+		mdb_raise(a.status, RJ_ST_NO_PARTNER);	/* a left row without partner */
 	{
 #pragma unroll
 		for (int o = 32; o; o >>= 1)
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_leaf(rj_leaf_args a)
 		if (t)
 			atomicAdd(a.joined, t);
 		if (s_dup)	/* a right key occurs twice */
-			mdb_raise(a.status, 32u);
+			mdb_raise(a.status, RJ_ST_DUP_RIGHT);
 	}
 }
 
@@ -795,7 +795,7 @@ int mdb_rowjoin_run_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l,
 	la.tstride = tstride_l;
 	la.dbits = dbits;
 	la.sbits = sbits;
-	la.joined = (unsigned long long *)(ctx->d_status + 2);
+	la.joined = (unsigned long long *)(ctx->d_status + RJ_STW_JOINED);
 	la.status = ctx->d_status;
 #define RJ_LAUNCH_LEAF(L, LONG)                                                                                                                   \
 	do {                                                                                                                                      \
@@ -966,7 +966,7 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_group_leaf_dense(rg_grou
 		return;
 	if (ebase + nexc > a.exc_cap) {		/* (more keys with several rows than the list holds: the caller takes the record form) */
 		if (lane == 0)
-			mdb_raise(a.status, 16384u);
+			mdb_raise(a.status, RJ_ST_EXC_FULL);
 		return;
 	}
 	for (uint32_t i0 = wave * 64u; i0 < S; i0 += blockDim.x) {
@@ -1025,7 +1025,7 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_group_leaf(rg_group_args
 				continue;
 			uint32_t at = atomicAdd(&a.rg_cnt[r], c);
 			if (at + c > a.rg_cap) {
-				mdb_raise(a.status, 8192u);	/* a range outgrew its region: the caller takes the record list and its sort */
+				mdb_raise(a.status, RJ_ST_RANGE_FULL);	/* a range outgrew its region: the caller takes the record list and its sort */
 				at = a.rg_cap;
 			}
 			s_rg[r] = at;
@@ -1049,7 +1049,7 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_group_leaf(rg_group_args
 		cmax = s_count[i] > cmax ? s_count[i] : cmax;
 	}
 	if (cmax >> (32u - a.row_bits))		/* (a COUNT that does not fit beside its row id in 32 bits: the ordering sort keeps 8-byte records) */
-		mdb_raise(a.status, 512u);
+		mdb_raise(a.status, RJ_ST_COUNT_NOT_REC32);
 	uint32_t total;
 	uint32_t at = mdb_block_excl_scan(mine, s_tmp, &total);
 	if (threadIdx.x == 0) {
@@ -1057,7 +1057,7 @@ __global__ __launch_bounds__(RJ_LEAF_THREADS) void k_rj_group_leaf(rg_group_args
 		if (total) {
 			nb = atomicAdd(a.rec_count, total);
 			if (nb + total > a.rec_cap) {
-				mdb_raise(a.status, 8u);	/* (sized for every key value of the window and every row: cannot happen) */
+				mdb_raise(a.status, MDB_ST_LIST_FULL);	/* (sized for every key value of the window and every row: cannot happen) */
 				nb = 0xFFFFFFFFu;
 			} else {
 				atomicAdd(a.groups, total);
@@ -1162,8 +1162,8 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 	ga.dbits = dbits;
 	ga.sbits = sbits;
 	ga.row_bits = row_bits;
-	ga.groups = ctx->d_status + 1;
-	ga.rec_count = ctx->d_status + 2;
+	ga.groups = ctx->d_status + RJ_STW_GROUPS;
+	ga.rec_count = ctx->d_status + RJ_STW_LIST_LEN;
 	ga.status = ctx->d_status;
 	const uint32_t threads = sbits >= 14u ? 1024u : sbits == 13u ? 512u : 256u;
 	const int lpp = dbits >= 13 ? 8 : dbits == 12 ? 16 : dbits == 11 ? 32 : 64;
@@ -1188,19 +1188,19 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 	 * that are not the first of their key.  One in 16 at most: the groups leave as one bit per row + exceptions (mdb_dev_dense.hip)
 	 * instead of a record each and a sort of the records.  MDB_GROUP_DENSE=0: never. */
 	if (dense_ok) {
-		ga.dense_cnt = ctx->d_status + 4;
+		ga.dense_cnt = ctx->d_status + RJ_STW_DENSE;
 		ga.dense_bits = NULL;
 		ga.exc = NULL;
 		RJ_LAUNCH_DENSE_ANY(D < 64u ? D : 64u);
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 32, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, sizeof(rj_readback), hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t *ps = reinterpret_cast<const uint32_t *>(&h[1]);
-		if (ps[0] & 128u) {
+		const rj_readback *ps = reinterpret_cast<const rj_readback *>(&h[MDB_HP_STATUS]);
+		if (ps->flags & MDB_ST_KEY_OUTSIDE) {
 			*outside = true;
 			return 1;
 		}
-		const uint64_t pilot_dups = ps[4], pilot_rows = ps[6];
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
+		const uint64_t pilot_dups = ps->not_first, pilot_rows = ps->rows_seen;
+		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status + RJ_STW_GROUPS, 0, sizeof(rj_readback) - 4 * RJ_STW_GROUPS, ctx->stream));
 		if (pilot_rows && pilot_dups * 16u <= pilot_rows) {
 			unsigned long long *bits = NULL;
 			const uint64_t exc_cap = n / 8 + 4096;
@@ -1212,13 +1212,13 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 				return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "GROUP BY over a tile-sorted column: %s", ctx->err);
 			ga.exc_cap = (uint32_t)exc_cap;
 			RJ_LAUNCH_DENSE_ANY(D);
-			MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 32, hipMemcpyDeviceToHost, ctx->stream));
+			MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, sizeof(rj_readback), hipMemcpyDeviceToHost, ctx->stream));
 			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			const uint32_t dstatus = ps[0], groups = ps[1], n_exc = ps[5];
+			const uint32_t dstatus = ps->flags, groups = ps->groups, n_exc = ps->exceptions;
 			if (mdb_knob_set("MDB_DEBUG_GROUP"))
 				fprintf(stderr, "group_count (tile sort, dense): pilot %llu of %llu rows not first; %u groups, %u rows not first, %u exceptions, status %u\n",
-					(unsigned long long)pilot_dups, (unsigned long long)pilot_rows, groups, ps[4], n_exc, dstatus);
-			if (!(dstatus & 16384u) && (uint64_t)groups + ps[4] == n) {
+					(unsigned long long)pilot_dups, (unsigned long long)pilot_rows, groups, ps->not_first, n_exc, dstatus);
+			if (!(dstatus & RJ_ST_EXC_FULL) && (uint64_t)groups + ps->not_first == n) {
 				if (groups > cap)
 					return mdb_set_err(ctx, -MIDORIDB_ERROR, "GROUP BY: %u groups, room for %llu", groups, (unsigned long long)cap);
 				if ((rc = mdb_dense_emit(ctx, bits, n, ga.exc, n_exc, out_first, out_count)))
@@ -1269,21 +1269,21 @@ int mdb_group_count_tiled(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, int
 		else
 			RJ_LAUNCH_GROUP(64);
 #undef RJ_LAUNCH_GROUP
-		MDB_HIP(ctx, hipMemcpyAsync(&h[1], ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, offsetof(rj_readback, not_first), hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t *hs = reinterpret_cast<const uint32_t *>(&h[1]);
-		const uint32_t status = hs[0], groups = hs[1], list_len = hs[2];
-		if (status & 128u) {
+		const rj_readback *hs = reinterpret_cast<const rj_readback *>(&h[MDB_HP_STATUS]);
+		const uint32_t status = hs->flags, groups = hs->groups, list_len = hs->list_len;
+		if (status & MDB_ST_KEY_OUTSIDE) {
 			*outside = true;
 			return 1;
 		}
-		if (status & 8u)
+		if (status & MDB_ST_LIST_FULL)
 			return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "GROUP BY over a tile-sorted column: the record list overflowed");
-		if (status & 512u)
+		if (status & RJ_ST_COUNT_NOT_REC32)
 			MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));	/* (the ordering kernels raise flags of their own there) */
-		if (attempt == 0 && (status & 8192u))
+		if (attempt == 0 && (status & RJ_ST_RANGE_FULL))
 			continue;	/* more groups in a range of first rows than its region holds: the list and its sort */
-		const bool rec32 = attempt == 1 && !(status & 512u) && row_bits < 32u;
+		const bool rec32 = attempt == 1 && !(status & RJ_ST_COUNT_NOT_REC32) && row_bits < 32u;
 		if (groups > cap)
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "GROUP BY: %u groups, room for %llu", groups, (unsigned long long)cap);
 		if (attempt == 0) {

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(THREADS, 4 /* waves per SIMD: one workgroup of 1024
 					const unsigned long long rel = kk[e] - (unsigned long long)a.key_lo;
 					const bool take = ok[e] && rel <= limit;
 					if (a.report && ok[e] && !take)
-						mdb_raise(a.status, 128u);	/* a right key outside the window: the caller's form does not apply */
+						mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);	/* a right key outside the window: the caller's form does not apply */
 					uint32_t pk = 0xFFFFFFFFu;
 					if (take) {
 						const uint32_t h = mdb_mixk((uint32_t)rel, a.kbits);
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(THREADS, 4 /* waves per SIMD: one workgroup of 1024
 				if (cnt[j]) {
 					const uint32_t d = tid * DPT + (uint32_t)j;
 					if (base[j] + cnt[j] + HDR > a.cap) {
-						mdb_raise(a.status, 2u);	/* the region is full: reported, the operator takes its exact path */
+						mdb_raise(a.status, MDB_ST_REGION_FULL);	/* the region is full: reported, the operator takes its exact path */
 						atomicOr(&s_bad[ord >> 5], 1u << (ord & 31u));
 						s_any_bad = 1u;
 					}
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_scatter4096_stream(shw_scatter_a
 					SHS_REQUEST((k >> 1) + (int)RING - (int)NPAIR, prow0, plen, tid);
 			}
 			if (a.report && oow)
-				mdb_raise(a.status, 128u);	/* a right key outside the window: the caller's form does not apply */
+				mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);	/* a right key outside the window: the caller's form does not apply */
 		}
 		if (ABLATE & 4)
 			t3_ = __builtin_amdgcn_s_memtime();
@@ -538,7 +538,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_scatter4096_stream(shw_scatter_a
 				if (cnt[j]) {
 					const uint32_t d = tid * DPT + (uint32_t)j;
 					if (base[j] + cnt[j] + HDR > a.cap) {
-						mdb_raise(a.status, 2u);	/* the region is full: reported, the operator takes its exact path */
+						mdb_raise(a.status, MDB_ST_REGION_FULL);	/* the region is full: reported, the operator takes its exact path */
 						s_any_bad = 1u;			/* ... and nothing of this tile is written */
 					}
 					s_delta[ord] = (d * a.nsub + sub) * a.cap + base[j] + HDR - st0[j];

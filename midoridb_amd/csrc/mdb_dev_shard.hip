@@ -245,7 +245,7 @@ int mdb_shard_partition(mdb_dev_ctx *ctx, const mdb_shard_plan *p, int side, con
 	if (side != 1) {
 		/* the left table (and any further right table) keeps the rows inside the right table's (global) key range = the
 		 * window: what lies outside joins nothing on any rank */
-		uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned) + 512;
+		uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned + MDB_HP_SEND_SHARD);
 		h[0] = 0u;
 		h[1] = (uint32_t)p->l_rel_hi;
 		MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status + SH_RANGE_WORD, h, 8, hipMemcpyHostToDevice, ctx->stream));
@@ -295,10 +295,10 @@ __global__ void k_shard_regions(const uint32_t *__restrict__ cnt, uint32_t world
 	const uint32_t dl = r / (world * nsub), q = (r / nsub) % world, s = r % nsub;
 	uint32_t c = cnt[(size_t)q * D * nsub + (size_t)s * D + d0 + dl];	/* (the sender's cursors are laid out sub-major) */
 	if (c == 0xFFFFFFFFu) {
-		mdb_raise(status, 16384u);	/* rank q's first level failed: it sent counters that say so instead of counts (mdb_dist.hip) */
+		mdb_raise(status, MDB_SHARD_ST_PEER_FAILED);	/* rank q's first level failed: it sent counters that say so instead of counts (mdb_dist.hip) */
 		c = 0;
 	} else if (c > cap) {
-		mdb_raise(status, 2u);		/* the sender's region overflowed (it said so on its own rank as well) */
+		mdb_raise(status, MDB_ST_REGION_FULL);		/* the sender's region overflowed (it said so on its own rank as well) */
 		c = cap;
 	}
 	reg_start[r] = q * block_words + (dl * nsub + s) * cap;
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(THREADS) void k_shard_leaf(sh_leaf_args a)
 				for (uint32_t x = 2; x < a.ntab; x++)
 					c *= sh_lds[x * T + sl];
 				if (c >> 32) {
-					mdb_raise(a.status, 2048u);
+					mdb_raise(a.status, MDB_SHARD_ST_PRODUCT_WIDE);
 					c = 0;
 				}
 				s_cr[sl] = (uint32_t)c;
@@ -457,9 +457,9 @@ __global__ __launch_bounds__(THREADS) void k_shard_leaf(sh_leaf_args a)
 	if (!total)
 		return;
 	if (threadIdx.x == 0) {
-		const uint32_t nb = atomicAdd(a.status + 1, total);
+		const uint32_t nb = atomicAdd(a.status + MDB_SHARD_STW_GROUPS, total);
 		if ((uint64_t)nb + total > a.out_cap) {
-			mdb_raise(a.status, 8u);
+			mdb_raise(a.status, MDB_ST_LIST_FULL);
 			s_base = 0xFFFFFFFFu;
 		} else {
 			s_base = nb;
@@ -502,7 +502,7 @@ __global__ __launch_bounds__(THREADS) void k_shard_leaf(sh_leaf_args a)
 		for (int w = 0; w < THREADS / 64; w++)
 			t += s_red[w];
 		if (t)
-			atomicAdd(reinterpret_cast<unsigned long long *>(a.status + 2), t);
+			atomicAdd(reinterpret_cast<unsigned long long *>(a.status + MDB_SHARD_STW_JOINED), t);
 	}
 }
 
@@ -655,9 +655,9 @@ __global__ __launch_bounds__(THREADS) void k_shard_leaf_wide(sh_leaf_args a)
 	if (threadIdx.x == 0) {
 		uint32_t nb = 0;
 		if (total) {
-			nb = atomicAdd(a.status + 1, total);
+			nb = atomicAdd(a.status + MDB_SHARD_STW_GROUPS, total);
 			if ((uint64_t)nb + total > a.out_cap) {
-				mdb_raise(a.status, 8u);
+				mdb_raise(a.status, MDB_ST_LIST_FULL);
 				nb = 0xFFFFFFFFu;
 			}
 		}
@@ -713,7 +713,7 @@ __global__ __launch_bounds__(THREADS) void k_shard_leaf_wide(sh_leaf_args a)
 			for (int w = 0; w < THREADS / 64; w++)
 				t += s_red[w];
 			if (t)
-				mdb_raise(a.status, 2048u);
+				mdb_raise(a.status, MDB_SHARD_ST_PRODUCT_WIDE);
 		}
 		__syncthreads();
 	}
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(THREADS) void k_shard_leaf_wide(sh_leaf_args a)
 		for (int w = 0; w < THREADS / 64; w++)
 			t += s_red[w];
 		if (t)
-			atomicAdd(reinterpret_cast<unsigned long long *>(a.status + 2), t);
+			atomicAdd(reinterpret_cast<unsigned long long *>(a.status + MDB_SHARD_STW_JOINED), t);
 	}
 }
 

@@ -111,6 +111,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_nullflag(const uint64_t *
 #define SORT_LEAF_THREADS 512
 #define SORT_BUCKETS 1024u
 #define SORT_BUCKET_MAX 1024u
+/* flags of the leaf sort in word 0 of ctx->d_status: either sends the caller to its general path */
+#define SORT_ST_BUCKET_FULL 256u	/* more than SORT_BUCKET_MAX records in one bucket */
+#define SORT_ST_REDO (MDB_ST_REGION_FULL | SORT_ST_BUCKET_FULL)
+static_assert(mdb_flags_distinct({ MDB_ST_REGION_FULL, MDB_ST_LIST_FULL, MDB_ST_KEY_OUTSIDE, SORT_ST_BUCKET_FULL }), "sort: two status flags share a bit");
 #define SORT_PACK_MIN_ROWS (1u << 18)
 
 #define SORT_PACK_MAX_KEYS 4
@@ -361,7 +365,7 @@ __global__ __launch_bounds__(SORT_LEAF_THREADS) void k_sort_leaf(const uint64_t 
 			const uint32_t st = s_cnt[b], m = s_cnt[b + 1] - st;
 			uint32_t r = 0;
 			if (m > SORT_BUCKET_MAX) {
-				mdb_raise(status, 256u);
+				mdb_raise(status, SORT_ST_BUCKET_FULL);
 			} else {
 				for (uint32_t x = 0; x < m; x++)
 					r += s_w[st + x] < v[e];
@@ -444,9 +448,9 @@ static int sort_perm_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, i
 		MDB_LAUNCH(ctx, "orderby_pack", k_sort_pack, grid, SORT_THREADS, pa, n, u, sampled ? outside : (uint32_t *)NULL);
 		if (!sampled)
 			break;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[12], outside, 4, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_SORT_OUTSIDE], outside, 4, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		if (!(uint32_t)h[12])
+		if (!(uint32_t)h[MDB_HP_SORT_OUTSIDE])
 			break;
 	}
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
@@ -475,9 +479,9 @@ static int sort_perm_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, i
 	const uint32_t bshift = 64u - (uint32_t)(b1 + b2) - 10u;
 	MDB_LAUNCH(ctx, "orderby_leaf", k_sort_leaf, ps.nleaves, SORT_LEAF_THREADS, (const uint64_t *)ps.hv, (const uint32_t *)ps.leaf_cnt,
 		   (const uint32_t *)obase, ps.leaf_cap, up, (uint32_t)((1ull << rb) - 1ull), bshift, ctx->d_status, out, vk, rb, (uint32_t *)NULL);
-	MDB_HIP(ctx, hipMemcpyAsync(&h[8], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_SORT_FLAGS], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if ((uint32_t)h[8] & (2u | 256u))
+	if ((uint32_t)h[MDB_HP_SORT_FLAGS] & SORT_ST_REDO)
 		return 1;	/* a region or a bucket overflowed: the values are too unevenly spread for this path */
 	*perm = out;
 	if (vkey)
@@ -545,9 +549,9 @@ int mdb_sort_pairs(mdb_dev_ctx *ctx, const uint32_t *a, const uint32_t *b, uint6
 	MDB_LAUNCH(ctx, "pairs_leaf", k_sort_leaf, ps.nleaves, SORT_LEAF_THREADS, (const uint64_t *)ps.hv, (const uint32_t *)ps.leaf_cnt,
 		   (const uint32_t *)obase, ps.leaf_cap, up, (uint32_t)((1ull << rb) - 1ull), bshift, ctx->d_status, out_b, (uint64_t *)NULL, rb, out_a);
 	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[8], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_SORT_FLAGS], ctx->d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return ((uint32_t)h[8] & (2u | 256u)) ? 1 : 0;
+	return ((uint32_t)h[MDB_HP_SORT_FLAGS] & SORT_ST_REDO) ? 1 : 0;
 }
 
 /* ---- tiny inputs: one workgroup ranks every row by counting ---------------------------------------------------------
@@ -1143,9 +1147,9 @@ static int group_multi_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys,
 			MDB_LAUNCH(ctx, "groupby_pack", k_sort_pack, grid, SORT_THREADS, pa, n, (uint64_t *)comp, sampled ? outside : (uint32_t *)NULL);
 			if (!sampled)
 				return MIDORIDB_OK;
-			MDB_HIP(ctx, hipMemcpyAsync(&h[12], outside, 4, hipMemcpyDeviceToHost, ctx->stream));
+			MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_SORT_OUTSIDE], outside, 4, hipMemcpyDeviceToHost, ctx->stream));
 			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			if (!(uint32_t)h[12])
+			if (!(uint32_t)h[MDB_HP_SORT_OUTSIDE])
 				return MIDORIDB_OK;
 		}
 	};
@@ -1232,7 +1236,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_any_no_row(const uint32_t *__r
 	for (uint64_t k = (uint64_t)blockIdx.x * SORT_THREADS + threadIdx.x; k < n; k += (uint64_t)gridDim.x * SORT_THREADS)
 		any = any || rid[k] == MDB_NO_ROW;
 	if (__ballot(any) && mdb_lane() == 0)
-		mdb_raise(flag, 1u);
+		mdb_raise(flag, MDB_FLAG_SET);
 }
 
 struct resolved_keys {

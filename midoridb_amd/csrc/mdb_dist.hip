@@ -772,15 +772,17 @@ static int dist_send_table(mdb_dist *d, int i, const int64_t *keys, const uint64
 	return MIDORIDB_OK;
 }
 
+#define DIST_STW_SUMS 32	/* [32..37] of ctx->d_status: the three summed counters (8-byte words beyond what the operators use) */
+#define DIST_ST_EXACT_PATH (MDB_ST_REGION_FULL | MDB_SHARD_ST_PRODUCT_WIDE)	/* what the exact path answers */
 /* the operator's flag word as three counters the ranks can sum: a region overflowed (the exact path answers), a right key outside
  * the window, anything else */
 __global__ void k_status_words(const uint32_t *status, uint64_t *out)
 {
 	if (threadIdx.x == 0) {
-		const uint32_t f = status[0];
-		out[0] = (f & (2u | 2048u)) ? 1u : 0u;
-		out[1] = (f & 128u) ? 1u : 0u;
-		out[2] = (f & ~(2u | 128u | 2048u)) ? 1u : 0u;
+		const uint32_t f = status[MDB_STW_FLAGS];
+		out[0] = (f & DIST_ST_EXACT_PATH) ? 1u : 0u;
+		out[1] = (f & MDB_ST_KEY_OUTSIDE) ? 1u : 0u;
+		out[2] = (f & ~(DIST_ST_EXACT_PATH | MDB_ST_KEY_OUTSIDE)) ? 1u : 0u;
 	}
 }
 
@@ -811,7 +813,6 @@ static bool dist_fault_injected(const mdb_dist *d, const char *step)
 	return mdb_knob_str("MDB_DIST_FAULT", e, sizeof(e)) && strncmp(e, step, l) == 0 && e[l] == ':' && atoi(e + l + 1) == d->rank;
 }
 
-#define DIST_PEER_FAILED 16384u	/* status bit: a peer's region counters say that its first level failed (k_shard_regions) */
 
 static int dist_join_fused(mdb_dist *d, int ntab, const int64_t *const *keys, const uint64_t *const *nulls, const uint64_t *ns, const int64_t glo[2],
 			   const int64_t ghi[2], bool promised, bool alloc_out, int64_t **out_key_p, int64_t **out_count_p, uint64_t cap,
@@ -977,8 +978,8 @@ static int dist_join_fused(mdb_dist *d, int ntab, const int64_t *const *keys, co
 		/* (the same holds for the receiver's launches: the peers are told through the status exchange) */
 		prc = rc;
 		snprintf(perr, sizeof(perr), "%s", mdb_dev_last_error(ctx));
-		uint32_t *h1 = reinterpret_cast<uint32_t *>(ctx->h_pinned) + 520;
-		h1[0] = DIST_PEER_FAILED;
+		uint32_t *h1 = reinterpret_cast<uint32_t *>(ctx->h_pinned + MDB_HP_SEND_RANGE);
+		h1[0] = MDB_SHARD_ST_PEER_FAILED;
 		DIST_HIP(d, hipMemcpyAsync(ctx->d_status, h1, 4, hipMemcpyHostToDevice, ctx->stream));
 	}
 	/* ---- G, J and the flags come back with ONE host synchronisation; what went wrong anywhere sends every rank the same way:
@@ -989,7 +990,7 @@ static int dist_join_fused(mdb_dist *d, int ntab, const int64_t *const *keys, co
 	bool reduced_on_device = false;
 	if (d->own_transport) {
 		rccl_transport *rt = (rccl_transport *)d->t.self;
-		uint64_t *dflags = reinterpret_cast<uint64_t *>(ctx->d_status + 32);	/* (three 8-byte words beyond what the operators use) */
+		uint64_t *dflags = reinterpret_cast<uint64_t *>(ctx->d_status + DIST_STW_SUMS);
 		hipLaunchKernelGGL(k_status_words, dim3(1), dim3(64), 0, ctx->stream, ctx->d_status, dflags);
 		ncclResult_t nr = ncclAllReduce(dflags, dflags, 3, ncclUint64, ncclSum, rt->status, ctx->stream);
 		if (nr != ncclSuccess)
@@ -1005,14 +1006,14 @@ static int dist_join_fused(mdb_dist *d, int ntab, const int64_t *const *keys, co
 		(void)mdb_dev_free(ctx, fail_blocks);
 		(void)mdb_dev_free(ctx, fail_counters);
 	}
-	const uint32_t flags = h[0];
-	const uint64_t G = h[1], J = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+	const uint32_t flags = h[MDB_STW_FLAGS];
+	const uint64_t G = h[MDB_SHARD_STW_GROUPS], J = (uint64_t)h[MDB_SHARD_STW_JOINED] | ((uint64_t)h[MDB_SHARD_STW_JOINED + 1] << 32);
 	if (reduced_on_device) {
-		memcpy(st, h + 32, sizeof(st));
+		memcpy(st, h + DIST_STW_SUMS, sizeof(st));
 	} else {
-		st[0] = (flags & (2u | 2048u)) ? 1u : 0u;
-		st[1] = (flags & 128u) ? 1u : 0u;
-		st[2] = ((flags & ~(2u | 128u | 2048u)) || prc) ? 1u : 0u;
+		st[0] = (flags & DIST_ST_EXACT_PATH) ? 1u : 0u;
+		st[1] = (flags & MDB_ST_KEY_OUTSIDE) ? 1u : 0u;
+		st[2] = ((flags & ~(DIST_ST_EXACT_PATH | MDB_ST_KEY_OUTSIDE)) || prc) ? 1u : 0u;
 		rc = d->t.allreduce_sum_u64(d->t.self, st, 3);
 	}
 	if (timed) {
@@ -1036,7 +1037,7 @@ static int dist_join_fused(mdb_dist *d, int ntab, const int64_t *const *keys, co
 	if (rc)
 		return fused_fail(ctx, alloc_out, out_key, out_count, dist_err(d, rc, "status exchange failed%s%s", d->own_transport ? ": " : "", transport_err(d)));
 	if (st[2]) {
-		if (flags & DIST_PEER_FAILED)
+		if (flags & MDB_SHARD_ST_PEER_FAILED)
 			return fused_fail(ctx, alloc_out, out_key, out_count, dist_err(d, -MIDORIDB_ERROR, "sharded join: a peer failed in its first partition level (its own message says why); no result"));
 		return fused_fail(ctx, alloc_out, out_key, out_count, dist_err(d, -MIDORIDB_INTERNAL, "sharded join: failed on %llu rank(s) (status %u on this rank)", (unsigned long long)st[2], flags));
 	}
