@@ -105,6 +105,8 @@ struct mdb_part_filter {
 	uint32_t *cursor0_ext;	/* != NULL: the first level's region cursors live here (cursor0_ext_words of them at least), ALREADY ZERO - the caller's
 				 * one memset covers them (ctx->d_status + MDB_ZERO_BLK_OFF) - instead of an arena block and a memset of its own */
 	uint32_t cursor0_ext_words;
+	bool selective;		/* with range_in, compact narrow form: the caller KNOWS (the last join over these columns, or the caller's statistics) that
+				 * few rows lie inside the range: the first level runs its selective instance (k_part_scatter<pf_key_cf_sel>) */
 	bool expect_pruned;	/* with range_in: the caller expects most rows to be dropped (key sample): the second level's grid is then
 				 * sized by the tiles that exist (a 4-byte read-back + synchronisation) instead of by the table */
 };

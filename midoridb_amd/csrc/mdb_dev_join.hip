@@ -1761,6 +1761,8 @@ static int gc_partition_extras(mdb_dev_ctx *ctx, gc_run *g)
 	return MIDORIDB_OK;
 }
 
+static bool gc_learned_selective(const mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l, const int64_t *keys_r, uint64_t n_r);
+
 /* stage 1d: the left table where it waited for the right one - pruned to the right table's key range (64-bit form, or narrow form), or filtered
  * through a bitmap of the right table's hashed keys (semi-join) */
 static int gc_partition_left(mdb_dev_ctx *ctx, gc_run *g, bool form64)
@@ -1776,6 +1778,9 @@ static int gc_partition_left(mdb_dev_ctx *ctx, gc_run *g, bool form64)
 	} else if (!st->semijoin) {
 		flt.range_in = ctx->d_status + GC_STW_MINMAX;
 		flt.expect_pruned = st->by_span && !st->one_level;
+		/* (a key sample's guess keeps the general first level: what the last join over these columns delivered, or the caller's statistics) */
+		flt.selective = st->selective && (gc_learned_selective(ctx, st->keys_l, st->n_l, g->r.keys, g->r.n) ||
+						  (ctx->cs_on && !ctx->explain_as_sample && ctx->cs_kl == st->keys_l && ctx->cs_has_r && ctx->cs_kr == g->r.keys));
 		flt.level0_only = st->one_level;
 		if (st->own_call) {
 			flt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF + MDB_ZERO_BLK_SLOT;

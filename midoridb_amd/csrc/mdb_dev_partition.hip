@@ -482,6 +482,9 @@ struct pf_key_rid_stable_hist : pf_base { static constexpr bool LEVEL0 = true; s
 struct pf_key_cf_t2 : pf_key_cf { static constexpr uint32_t TMUL = PART_TMUL; };
 struct pf_key_w32_out16_cf_t2 : pf_key_w32_out16_cf { static constexpr uint32_t TMUL = PART_TMUL; };
 struct pf_word_raw_w32_t2 : pf_word_raw_w32 { static constexpr uint32_t TMUL = PART_TMUL; };
+/* the pruned left table of a join known to be selective: a body of its own (part_sel_tile, after the generic kernel) */
+struct pf_key_cf_sel : pf_key_cf {  };
+struct pf_key_cf_sel_t2 : pf_key_cf_sel { static constexpr uint32_t TMUL = PART_TMUL; };
 /* min-max pruning in the 64-bit form: the right table's first level records its key range (mm64), the left table's drops the rows outside (r64) */
 struct pf_key_mm64 : pf_base { static constexpr bool LEVEL0 = true; static constexpr bool FAST = true; static constexpr bool MM64 = true; };
 struct pf_key_rid_r64 : pf_base { static constexpr bool LEVEL0 = true; static constexpr bool HAS_RID = true; static constexpr bool FAST = true; static constexpr bool R64 = true; };
@@ -937,6 +940,172 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_scatter(mdb_level_args a)
 	}
 }
 
+/* ---- selective first level: the pruned left table (compact narrow form, no NULL bitmap) of a join in which few rows survive ------
+ *
+ * The generic body above is sized for a tile whose every row survives: a staging buffer of TILE words and four per-row register
+ * arrays that stay live across its barriers - 70 KiB of LDS and 90 registers in the 8192-row form, two workgroups per CU.  Where the
+ * right table's key range keeps one left row in 16 (the benchmark's variant D) the pass is a streaming read, and what hides a stream's
+ * HBM latency is residency.  Here a row is tested as its key arrives; only a survivor is hashed, ranked in its digit (returning LDS
+ * atomic) and appended to a list of PART_SEL_CAP entries - its word, its digit and its rank.  After one cursor atomic per non-empty
+ * digit every entry goes straight to its place in its region (no digit scan: the rank is the offset inside the run; no staging by
+ * digit: the runs average under two words).  28 KiB of LDS: four workgroups per CU, as the right table's pass has.
+ *
+ * Same tiles, grid, words, regions, cursors and overflow flag as the generic body.  A tile with more survivors than the list holds
+ * is redone in rounds of PART_SEL_CAP rows, which cannot overflow it, with a flush after each - exact for any tile; so are partial
+ * tiles and a column that starts 8 bytes off a 16-byte boundary (every 16-byte load is aligned: positions count from the aligned
+ * address below the column's first key). */
+#define PART_SEL_CAP 2048u
+static_assert(MDB_TILE % PART_SEL_CAP == 0 && PART_SEL_CAP % (2u * PART_THREADS) == 0, "selective first level: rounds of whole pairs per thread");
+
+struct part_sel_lds {
+	uint64_t word[PART_SEL_CAP];
+	uint32_t meta[PART_SEL_CAP];		/* digit << 16 | rank inside the digit */
+	uint32_t cnt[PART_MAX_R];
+	uint32_t base[PART_MAX_R];		/* where the digit's run begins in hv_out (PART_INVALID: its region is full) */
+	uint32_t n;				/* survivors so far (may pass PART_SEL_CAP: the entries beyond are not kept) */
+};
+
+/* a survivor into its slot of the list: hashed, ranked in its digit */
+__device__ static inline void part_sel_append(const mdb_level_args &a, part_sel_lds &s, uint32_t slot, uint64_t rel, uint32_t rid, uint32_t dshift)
+{
+	const uint32_t h = mdb_mixk((uint32_t)rel, a.narrow_kbits) << (32u - a.narrow_kbits);
+	const uint32_t d = (h >> dshift) & (a.R - 1u);
+	const uint32_t rank = atomicAdd(&s.cnt[d], 1u);
+	s.word[slot] = ((uint64_t)h << 32) | rid;
+	s.meta[slot] = (d << 16) | rank;
+}
+
+/* two adjacent rows (row ids rid, rid + 1): every lane of the wave calls - the wave's survivors take their slots with ONE atomic */
+__device__ static inline void part_sel_pair(const mdb_level_args &a, part_sel_lds &s, uint64_t key0, uint64_t key1, uint32_t rid, bool in0, bool in1,
+					    uint64_t range_lo, uint64_t range_hi, uint32_t dshift)
+{
+	const uint64_t rel0 = key0 - (uint64_t)a.narrow_base, rel1 = key1 - (uint64_t)a.narrow_base;
+	const bool ok0 = in0 && rel0 >= range_lo && rel0 <= range_hi, ok1 = in1 && rel1 >= range_lo && rel1 <= range_hi;
+	const uint64_t m0 = __ballot(ok0), m1 = __ballot(ok1);
+	if (!(m0 | m1))
+		return;		/* (uniform) */
+	const uint32_t leader = (uint32_t)__ffsll((long long)(m0 | m1)) - 1u, n0 = (uint32_t)__popcll(m0);
+	uint32_t first = 0;
+	if (mdb_lane() == leader)
+		first = atomicAdd(&s.n, n0 + (uint32_t)__popcll(m1));
+	first = (uint32_t)__builtin_amdgcn_readlane((int)first, (int)leader);
+	const uint64_t lt = mdb_lanemask_lt();
+	const uint32_t slot0 = first + (uint32_t)__popcll(m0 & lt), slot1 = first + n0 + (uint32_t)__popcll(m1 & lt);
+	if (ok0 && slot0 < PART_SEL_CAP)
+		part_sel_append(a, s, slot0, rel0, rid, dshift);
+	if (ok1 && slot1 < PART_SEL_CAP)
+		part_sel_append(a, s, slot1, rel1, rid + 1u, dshift);
+}
+
+/* scan-free flush of the list's first n entries (called behind a barrier): reserve, write */
+__device__ static inline void part_sel_flush(const mdb_level_args &a, part_sel_lds &s, uint32_t n)
+{
+	for (uint32_t d = threadIdx.x; d < a.R; d += PART_THREADS) {
+		const uint32_t total = s.cnt[d];
+		uint32_t base = PART_INVALID;
+		if (total) {
+			const uint32_t sub = blockIdx.x % a.nsub, child = d * a.nsub + sub;
+			const uint32_t at = atomicAdd(&a.cursor[sub * a.R + d], total);	/* (sub-major cursors: see the generic body) */
+			if (at + total <= a.cap)
+				base = child * a.cap + at;
+			else
+				mdb_raise(a.status, MDB_ST_REGION_FULL);
+		}
+		s.base[d] = base;
+	}
+	__syncthreads();
+	for (uint32_t i = threadIdx.x; i < n; i += PART_THREADS) {
+		const uint32_t meta = s.meta[i], base = s.base[meta >> 16];
+		if (base != PART_INVALID)
+			a.hv_out[base + (meta & 0xFFFFu)] = s.word[i];
+	}
+}
+
+template <uint32_t TMUL>
+__device__ static inline void part_sel_tile(const mdb_level_args &a)
+{
+	constexpr uint32_t TILE = MDB_TILE * TMUL;
+	constexpr int PAIRS = (int)(TILE / (2u * PART_THREADS));
+	__shared__ part_sel_lds s;
+	const uint32_t t = part_tile_of_block();
+	if (t >= a.ntiles)
+		return;
+	/* positions count from the 16-byte aligned address at or below the first key: row id = position - lead */
+	const uint32_t lead = (uint32_t)(((uintptr_t)a.keys >> 3) & 1u);
+	const uint64_t *const src = reinterpret_cast<const uint64_t *>(a.keys) - lead;
+	const uint64_t start = (uint64_t)t * TILE, end = (uint64_t)lead + a.n;
+	const uint64_t range_lo = a.range_in[0], range_hi = a.range_in[1];
+	const uint32_t dshift = a.shift - 32u;	/* the digit's place inside the 32-bit hash */
+	const bool full = start >= lead && start + TILE <= end;	/* (uniform) */
+	if (full) {
+		ulonglong2 pre[PAIRS];
+		typedef unsigned long long ull2_nt __attribute__((ext_vector_type(2)));
+#pragma unroll
+		for (int r = 0; r < PAIRS; r++) {	/* the tile's loads together (see part_preload2) */
+			const ull2_nt v = __builtin_nontemporal_load(reinterpret_cast<const ull2_nt *>(src + start + 2u * ((uint32_t)r * PART_THREADS + threadIdx.x)));
+			pre[r] = make_ulonglong2(v.x, v.y);
+		}
+		for (uint32_t d = threadIdx.x; d < a.R; d += PART_THREADS)
+			s.cnt[d] = 0;
+		if (threadIdx.x == 0)
+			s.n = 0;
+		__syncthreads();
+		const uint32_t rid0 = (uint32_t)start - lead + 2u * threadIdx.x;
+#pragma unroll
+		for (int r = 0; r < PAIRS; r++) {
+			part_sel_pair(a, s, pre[r].x, pre[r].y, rid0 + 2u * (uint32_t)r * PART_THREADS, true, true, range_lo, range_hi, dshift);
+		}
+		__syncthreads();
+		const uint32_t n = s.n;
+		if (n <= PART_SEL_CAP) {	/* (uniform) */
+			part_sel_flush(a, s, n);
+			return;
+		}
+		__syncthreads();	/* more survivors than the list holds: every thread has read s.n - the tile is redone in rounds */
+	}
+	for (uint32_t round = 0; round < TILE / PART_SEL_CAP; round++) {
+		const uint64_t rstart = start + (uint64_t)round * PART_SEL_CAP;
+		if (rstart >= end)
+			break;		/* (uniform) */
+		for (uint32_t d = threadIdx.x; d < a.R; d += PART_THREADS)
+			s.cnt[d] = 0;
+		if (threadIdx.x == 0)
+			s.n = 0;
+		__syncthreads();
+#pragma unroll
+		for (uint32_t q = 0; q < PART_SEL_CAP / (2u * PART_THREADS); q++) {
+			const uint64_t p0 = rstart + 2u * (q * PART_THREADS + threadIdx.x);
+			const bool in0 = p0 >= lead && p0 < end, in1 = p0 + 1u < end;
+			uint64_t k0 = 0, k1 = 0;
+			if (in0 && in1) {
+				const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(src + p0);
+				k0 = v.x;
+				k1 = v.y;
+			} else if (in0) {
+				k0 = src[p0];
+			} else if (in1) {
+				k1 = src[p0 + 1u];
+			}
+			part_sel_pair(a, s, k0, k1, (uint32_t)p0 - lead, in0, in1, range_lo, range_hi, dshift);
+		}
+		__syncthreads();
+		part_sel_flush(a, s, s.n);	/* (at most PART_SEL_CAP rows went in) */
+		__syncthreads();		/* the list and the counters have been read */
+	}
+}
+
+template <>
+__global__ __launch_bounds__(PART_THREADS) void k_part_scatter<pf_key_cf_sel>(mdb_level_args a)
+{
+	part_sel_tile<1u>(a);
+}
+
+template <>
+__global__ __launch_bounds__(PART_THREADS) void k_part_scatter<pf_key_cf_sel_t2>(mdb_level_args a)
+{
+	part_sel_tile<PART_TMUL>(a);
+}
+
 /* ---- segment bookkeeping between levels -------------------------------------------------------
  *
  * After a level's scan, child segment q = (parent p, digit d) starts at scanned[tb[p]*R + d*nt_p].
@@ -1270,6 +1439,14 @@ static int partition_impl(part_carver &cv, const int64_t *keys, const uint64_t *
 		if (!stop0)
 			pay_buf1[c] = (uint64_t *)cv.take((uint64_t)nleaves_total * fast_cap * 8);
 	}
+	/* the pruned left table of the compact narrow form (hash | row id words over an int64 column, no NULL bitmap) when the caller expects a
+	 * selective join: k_part_scatter<pf_key_cf_sel> (MDB_SELECTIVE_L0=0: never, 2: whatever the caller expects) */
+	const long long sel_knob = dry ? 0 : mdb_knob_int("MDB_SELECTIVE_L0", 1);
+	const bool sel0 = !dry && fast0 && flt && flt->range_in && !nullbits && !raw_hv && !want_rid && !w32 && !npay && !flt->minmax64_out &&
+			  (flags & PART_F_NARROW_RID) && narrow_kbits && !(flags & PART_F_KEYS32) && (sel_knob == 2 || (sel_knob != 0 && flt->selective));
+	/* ... which reads a column from any 8-byte boundary; every other first level loads pairs of keys from where the column starts */
+	if (!dry && keys && !(flags & PART_F_KEYS32) && ((uintptr_t)keys & 15) && !sel0)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "key columns must be 16-byte aligned on the device (8-byte for int32 keys)");
 
 	/* segments of the current level */
 	uint32_t S = 1;
@@ -1404,6 +1581,14 @@ static int partition_impl(part_carver &cv, const int64_t *keys, const uint64_t *
 					MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key_mm64>), grid8(ntiles), PART_THREADS, a);
 					MDB_LAUNCH(ctx, "part_minmax", k_part_minmax64_reduce, 1, 1024, (const unsigned long long *)a.minmax64_out, ntiles,
 						   flt->minmax64_out);
+				} else if (sel0) {
+					const uint64_t span = n + (((uintptr_t)keys >> 3) & 1u);	/* (positions from the aligned address below the first key) */
+					const uint32_t trows = t2 ? PART_TMUL * MDB_TILE : MDB_TILE;
+					a.ntiles = (uint32_t)((span + trows - 1) / trows);
+					if (t2)
+						MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf_sel_t2>), grid8(a.ntiles), PART_THREADS, a);
+					else
+						MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf_sel>), grid8(a.ntiles), PART_THREADS, a);
 				} else if (a.range_in && cf && t2) {
 					a.ntiles = ntiles2;
 					MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf_t2>), grid8(ntiles2), PART_THREADS, a);
@@ -1647,7 +1832,7 @@ int mdb_partition_table(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *n
 	part_carver cv = { ctx, false, 0, false };
 	if (stable && !want_rid)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "stable partitioning is only built with row ids");
-	if ((uintptr_t)keys & (keys32 ? 7 : 15))
+	if ((uintptr_t)keys & 7)	/* (int64 columns: 16 bytes, unless the selective first level takes them - partition_impl) */
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "key columns must be 16-byte aligned on the device (8-byte for int32 keys)");
 	return partition_impl(cv, keys, nullbits, n, bits1, bits2, want_rid,
 			      (stable ? PART_F_STABLE : 0u) | (fast ? PART_F_FAST : 0u) | (narrow == 1 ? PART_F_NARROW_RID : 0u) |
