@@ -475,7 +475,10 @@ struct pf_key_rid : pf_base { static constexpr bool LEVEL0 = true; static conste
 struct pf_key_rid_stable_hist : pf_base { static constexpr bool LEVEL0 = true; static constexpr bool HAS_RID = true; static constexpr bool STABLE = true; };
 /* the same with tiles of 2 x MDB_TILE rows (tables of 2^25 rows and more: half the cursor atomics, runs twice as long - whole 32-byte sectors of
  * 2-byte words; 10^8 rows: the right table's pass 0.241 -> 0.222 ms, the ordering sort's first level 0.174 -> 0.155, same-box A/B.  Smaller tables
- * keep MDB_TILE: fewer tiles than workgroup slots leave CUs idle) */
+ * keep MDB_TILE: fewer tiles than workgroup slots leave CUs idle).  4 x MDB_TILE at PART_THREADS means 32 rows per thread, and those cost the
+ * registers that keep every wave slot filled: the right table's pass in 16384-row tiles is <pf_key_w32_out16_cf_t4>, 1024 threads of 16 rows -
+ * 0.232 -> 0.207 ms, same-box A/B; the same body with 512 threads of 32 rows (105 registers, half the wave slots) 0.236:
+ * profiles/micro/right_pass_tile4/ab.txt) */
 #ifndef PART_TMUL
 #define PART_TMUL 2u
 #endif
@@ -485,6 +488,8 @@ struct pf_word_raw_w32_t2 : pf_word_raw_w32 { static constexpr uint32_t TMUL = P
 /* the pruned left table of a join known to be selective: a body of its own (part_sel_tile, after the generic kernel) */
 struct pf_key_cf_sel : pf_key_cf {  };
 struct pf_key_cf_sel_t2 : pf_key_cf_sel { static constexpr uint32_t TMUL = PART_TMUL; };
+/* the right table of the one-level join in tiles of 4 x MDB_TILE rows, 1024 threads: a body of its own (after the selective first level) */
+struct pf_key_w32_out16_cf_t4 : pf_key_w32_out16_cf { static constexpr uint32_t TMUL = 4u; };
 /* min-max pruning in the 64-bit form: the right table's first level records its key range (mm64), the left table's drops the rows outside (r64) */
 struct pf_key_mm64 : pf_base { static constexpr bool LEVEL0 = true; static constexpr bool FAST = true; static constexpr bool MM64 = true; };
 struct pf_key_rid_r64 : pf_base { static constexpr bool LEVEL0 = true; static constexpr bool HAS_RID = true; static constexpr bool FAST = true; static constexpr bool R64 = true; };
@@ -1106,6 +1111,175 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_scatter<pf_key_cf_sel_t2>
 	part_sel_tile<PART_TMUL>(a);
 }
 
+/* ---- the right table's first level in tiles of 16384 rows (compact narrow form over an int64 column, no NULL bitmap, 2-byte words out) --
+ *
+ * What bounds the right table's pass is its runs: with 512 digits a (tile, digit) run of an 8192-row tile is 16 two-byte words
+ * that begin on any 2-byte boundary - most runs straddle two 32-byte sectors and fill neither.  A tile of 16384 rows makes a run 64 bytes and
+ * halves the cursor atomics.  The generic body takes its thread count from PART_THREADS, and 32 rows per thread cost it its registers; here
+ * PART_T4_THREADS = 1024 threads keep 16 rows each, and a row is its hash and its rank - the digit is found again from the hash, a bit per
+ * row says whether it takes part: 64 KiB of staging + 5 KiB of per-digit words, two workgroups per CU = every wave slot.
+ *
+ * Same words, regions, cursors, status flags and per-tile (min, ~max) pairs as <pf_key_w32_out16_cf_t2>, for full and partial tiles: the steps
+ * below carry the numbers of the generic body's steps they restate (1 load - with the minmax_final preset and the per-tile pair that follow it
+ * there -, 2 rank, 3 scan and cursor atomic, 4 stage and MDB_ST_REGION_FULL, 5 write-out).  A change to the region / cursor protocol or to the
+ * status flags is made there, in part_sel_flush and here. */
+#define PART_T4_THREADS 1024
+#define PART_T4_TILE (4u * MDB_TILE)
+#define PART_T4_ITEMS ((int)(PART_T4_TILE / PART_T4_THREADS))
+#define PART_T4_WAVES (PART_T4_THREADS / MDB_WAVE)
+static_assert(PART_T4_ITEMS % 2 == 0 && PART_T4_ITEMS <= 32 && PART_MAX_R <= PART_T4_THREADS, "16384-row tiles: whole pairs per thread, one valid bit per row, a thread per digit");
+
+template <>
+__global__ __launch_bounds__(PART_T4_THREADS) void k_part_scatter<pf_key_w32_out16_cf_t4>(mdb_level_args a)
+{
+	constexpr uint32_t TILE = PART_T4_TILE;
+	constexpr int ITEMS = PART_T4_ITEMS;
+	__shared__ uint32_t s_hv[TILE];
+	__shared__ uint32_t s_cnt[PART_MAX_R];		/* per-digit counters, then tile-local digit starts */
+	__shared__ int32_t s_delta[PART_MAX_R];	/* global start of the digit's run minus its tile-local start */
+	__shared__ uint8_t s_ok[PART_MAX_R];		/* the digit's run fits its region */
+	__shared__ uint32_t s_tmp[32];
+	__shared__ uint32_t s_mm[2 * PART_T4_WAVES];
+
+	if (a.minmax_final && blockIdx.x == 0 && threadIdx.x == 0) {
+		a.minmax_final[0] = 0xFFFFFFFFu;
+		a.minmax_final[1] = 0u;
+	}
+	const uint32_t t = part_tile_of_block();
+	const uint64_t start = (uint64_t)t * TILE;
+	if (t >= a.ntiles || start >= a.n)
+		return;
+	const uint32_t len = (a.n - start) < TILE ? (uint32_t)(a.n - start) : TILE;
+	const uint32_t R = a.R;
+	const uint32_t wave = threadIdx.x >> 6, lane = mdb_lane();
+	if (threadIdx.x < R)
+		s_cnt[threadIdx.x] = 0;
+
+	/* 1. load: the tile starts on an even row of a 16-byte aligned column; a full tile's loads are issued together (see part_preload2) */
+	const uint64_t *const src = reinterpret_cast<const uint64_t *>(a.keys) + start;
+	ulonglong2 pre[ITEMS / 2];
+	uint32_t in = 0;	/* bit r: row r of this thread exists */
+	if (len == TILE) {	/* (uniform) */
+		typedef unsigned long long ull2_nt __attribute__((ext_vector_type(2)));
+#pragma unroll
+		for (int r = 0; r < ITEMS / 2; r++) {
+			const ull2_nt v = __builtin_nontemporal_load(reinterpret_cast<const ull2_nt *>(src + 2u * ((uint32_t)r * PART_T4_THREADS + threadIdx.x)));
+			pre[r] = make_ulonglong2(v.x, v.y);
+		}
+		in = ITEMS == 32 ? 0xFFFFFFFFu : (1u << (ITEMS & 31)) - 1u;
+	} else {
+#pragma unroll
+		for (int r = 0; r < ITEMS / 2; r++) {
+			const uint32_t e0 = 2u * ((uint32_t)r * PART_T4_THREADS + threadIdx.x);
+			pre[r] = make_ulonglong2(0ull, 0ull);
+			if (e0 + 1u < len) {
+				pre[r] = *reinterpret_cast<const ulonglong2 *>(src + e0);
+				in |= 3u << (2 * r);
+			} else if (e0 < len) {
+				pre[r].x = src[e0];
+				in |= 1u << (2 * r);
+			}
+		}
+	}
+	uint64_t range_lo = 0, range_hi = ~0ull;
+	if (a.range_in) {
+		range_lo = a.range_in[0];
+		range_hi = a.range_in[1];
+	}
+	uint32_t hv[ITEMS];
+	uint32_t seen_min = 0xFFFFFFFFu, seen_max = 0u;
+	bool any_bad = false;
+#pragma unroll
+	for (int r = 0; r < ITEMS; r++) {
+		const uint64_t rel = ((r & 1) ? pre[r / 2].y : pre[r / 2].x) - (uint64_t)a.narrow_base;
+		bool valid = (in >> r) & 1u;
+		any_bad = any_bad || (valid && (rel >> a.narrow_kbits));
+		hv[r] = mdb_mixk((uint32_t)rel, a.narrow_kbits) << (32u - a.narrow_kbits);
+		if (a.range_in)		/* (uniform) */
+			valid = valid && rel >= range_lo && rel <= range_hi;
+		if (a.minmax_out && valid) {	/* (a valid row of a narrow form: rel < 2^32) */
+			seen_min = rel < seen_min ? (uint32_t)rel : seen_min;
+			seen_max = rel > seen_max ? (uint32_t)rel : seen_max;
+		}
+		if (!valid)
+			in &= ~(1u << r);
+	}
+	/* (with min-max pruning - range_in - a key outside the window is outside the other table's range: dropped, nothing to report) */
+	if (any_bad && !a.range_in)
+		mdb_raise(a.status, MDB_ST_KEY_OUTSIDE);
+	if (a.minmax_out) {
+#pragma unroll
+		for (int o = MDB_WAVE / 2; o > 0; o >>= 1) {
+			const uint32_t omin = (uint32_t)__shfl_xor((int)seen_min, o, MDB_WAVE), omax = (uint32_t)__shfl_xor((int)seen_max, o, MDB_WAVE);
+			seen_min = omin < seen_min ? omin : seen_min;
+			seen_max = omax > seen_max ? omax : seen_max;
+		}
+		if (lane == 0) {
+			s_mm[2 * wave] = seen_min;
+			s_mm[2 * wave + 1] = seen_max;
+		}
+	}
+	__syncthreads();
+	if (a.minmax_out && threadIdx.x == 0) {		/* one pair of plain stores per tile, reduced by k_part_minmax_reduce */
+		uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+#pragma unroll
+		for (int w = 0; w < PART_T4_WAVES; w++) {
+			mn = s_mm[2 * w] < mn ? s_mm[2 * w] : mn;
+			mx = s_mm[2 * w + 1] > mx ? s_mm[2 * w + 1] : mx;
+		}
+		a.minmax_out[2 * t] = mn;
+		a.minmax_out[2 * t + 1] = ~mx;		/* (stored inverted) */
+	}
+
+	/* 2. rank inside the digit: one returning LDS atomic per row */
+	uint32_t rank[ITEMS];
+#pragma unroll
+	for (int r = 0; r < ITEMS; r++)
+		rank[r] = ((in >> r) & 1u) ? atomicAdd(&s_cnt[part_digit<true>(a, hv[r])], 1u) : 0u;
+	__syncthreads();
+
+	/* 3. digit totals -> tile-local starts; one cursor atomic per non-empty digit reserves the run's place in sub-region blockIdx % nsub
+	 *    (sub-major cursors: see the generic body) */
+	const uint32_t total_d = threadIdx.x < R ? s_cnt[threadIdx.x] : 0u;
+	uint32_t tile_total;
+	const uint32_t off_d = mdb_block_excl_scan(total_d, s_tmp, &tile_total);
+	uint32_t fast_base = 0;
+	const uint32_t sub = blockIdx.x % a.nsub;
+	if (threadIdx.x < R) {
+		s_cnt[threadIdx.x] = off_d;
+		fast_base = total_d ? atomicAdd(&a.cursor[sub * R + threadIdx.x], total_d) : 0u;
+	}
+	__syncthreads();
+
+	/* 4. stage sorted by digit */
+#pragma unroll
+	for (int r = 0; r < ITEMS; r++)
+		if ((in >> r) & 1u)
+			s_hv[s_cnt[part_digit<true>(a, hv[r])] + rank[r]] = hv[r];
+	if (threadIdx.x < R) {
+		const bool ok = fast_base + total_d <= a.cap;
+		if (!ok)
+			mdb_raise(a.status, MDB_ST_REGION_FULL);
+		s_ok[threadIdx.x] = ok;
+		s_delta[threadIdx.x] = (int32_t)((threadIdx.x * a.nsub + sub) * a.cap + fast_base - off_d);
+	}
+	__syncthreads();
+
+	/* 5. write out: consecutive threads write consecutive 2-byte words inside each digit's run */
+	uint16_t *const out = reinterpret_cast<uint16_t *>(a.hv_out);
+#pragma unroll
+	for (int k = 0; k < ITEMS; k++) {
+		const uint32_t i = threadIdx.x + (uint32_t)k * PART_T4_THREADS;
+		if (i >= tile_total)
+			continue;
+		const uint32_t h = s_hv[i];
+		const uint32_t d = part_digit<true>(a, h);
+		if (!s_ok[d])
+			continue;	/* overflowed child: the whole operator is re-run on the exact path */
+		out[(uint32_t)((int32_t)i + s_delta[d])] = (uint16_t)(h >> a.out16_shift);
+	}
+}
+
 /* ---- segment bookkeeping between levels -------------------------------------------------------
  *
  * After a level's scan, child segment q = (parent p, digit d) starts at scanned[tb[p]*R + d*nt_p].
@@ -1545,7 +1719,16 @@ static int partition_impl(part_carver &cv, const int64_t *keys, const uint64_t *
 				} else if (w32) {
 					if (out16) {
 						a.out16_shift = 32u - narrow_kbits;
-						if (cf && t2) {
+						/* ... and of 4 x MDB_TILE rows, 1024 threads, for an int64 column without a NULL bitmap (MDB_TILE4=0: never; MDB_TILE2=0
+						 * asks for MDB_TILE rows everywhere: not these either) */
+						const long long t4min = mdb_knob_int("MDB_TILE4_MIN", 0);	/* (tests: the form on small tables) */
+						const bool t4 = cf && !nullbits && n >= (t4min > 0 ? (uint64_t)t4min : (1ull << 25)) && !mdb_knob_off("MDB_TILE4") &&
+								!mdb_knob_off("MDB_TILE2");
+						if (t4) {
+							a.ntiles = (uint32_t)((n + PART_T4_TILE - 1) / PART_T4_TILE);
+							MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_out16_cf_t4>),
+								   grid8(a.ntiles), PART_T4_THREADS, a);
+						} else if (cf && t2) {
 							a.ntiles = ntiles2;
 							MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_out16_cf_t2>),
 								   grid8(ntiles2), PART_THREADS, a);
