@@ -462,6 +462,46 @@ int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, const ui
  * all n_l * n_r pairs in (l, r) order, into caller buffers of that capacity. */
 int mdb_dev_cross_pairs(mdb_dev_ctx *ctx, uint64_t n_l, uint64_t n_r, uint32_t *out_l, uint32_t *out_r);
 
+/* ------------------------------------------------------------------ composite equi-join keys
+ *
+ * ON a.x = b.x AND a.y = b.y [AND ...] (the reference evaluates the whole ON expression per pair, executor_select.c:1128): the
+ * equality columns whose value ranges fit 63 bits together become ONE 8-byte key per row, and the pair operators above join on
+ * the whole conjunction instead of on its first equality (whose pairs the others would then thin).
+ *
+ * mdb_dev_join_key_layout() - a pure host computation, no device, no context: for each of the k column pairs (l[c], r[c] = the
+ * statistics of the two sides' columns; min, max only; supersets of the live values are fine, nothing downstream trusts them)
+ * the field is the INTERSECTION of the two ranges - a value outside it equals nothing on the other side -, lo = max(l.min, r.min),
+ * span = min(l.max, r.max) - lo in unsigned 64-bit arithmetic (no signed overflow anywhere: [INT64_MIN, INT64_MAX] spans 2^64 - 1,
+ * 64 bits, and is never taken), bits = the bit length of span (a single value: 0 bits).  Columns are taken in the order given while
+ * the running total stays <= 63; a column that does not fit is skipped (it stays a residual predicate of the caller's) and later
+ * ones that fit are still taken, up to MDB_JOIN_KEY_MAX_COLS; the first taken column is the most significant.  ntaken < 2: not
+ * served.  empty: some taken column's ranges do not intersect, or one side holds no non-NULL value (min > max) - nothing can match
+ * (such a column is taken with a field of 0 bits); there is nothing to pack. */
+#define MDB_JOIN_KEY_MAX_COLS 4
+struct mdb_join_key_layout {
+	uint32_t ntaken, total_bits, empty;
+	int32_t taken[MDB_JOIN_KEY_MAX_COLS];	/* indices into the k columns given, in the order given */
+	int64_t lo[MDB_JOIN_KEY_MAX_COLS];	/* max(l.min, r.min) */
+	uint64_t span[MDB_JOIN_KEY_MAX_COLS];	/* min(l.max, r.max) - lo */
+	uint32_t bits[MDB_JOIN_KEY_MAX_COLS], shift[MDB_JOIN_KEY_MAX_COLS];
+};
+int mdb_dev_join_key_layout(const struct mdb_dev_col_stats *l, const struct mdb_dev_col_stats *r, int k, struct mdb_join_key_layout *out);
+/* mdb_dev_join_key_pack() packs ONE side: cols[0 .. lay->ntaken) in the layout's order, each read at stream position i as
+ * values[rid ? rid[i] : i].  out_key[i] = sum over the columns of (v_c - lo_c) << shift_c, always in [0, 2^63).  The row gets NO key -
+ * its bit in out_nullbits set, out_key[i] = 0 - when a cell is NULL, its row id is MDB_NO_ROW or a value lies outside
+ * [lo_c, lo_c + span_c]: every row is tested against its field, so the packing is exact whatever the ranges were taken from (no
+ * status flag, no retry).  *out_nulls = the rows without a key: when it is 0 the caller hands the join operator a NULL bitmap pointer.
+ * One streaming pass: 8 bytes per column and row read (+ 4 per distinct row-id vector), 8 bytes + 1 bit written; every one of the
+ * (n + 63) / 64 bitmap words is written whole (the unused bits of the last one 0), nothing beyond them and out_key[n) is touched.
+ * lay->ntaken < 2 or lay->empty: an error.  n == 0: nothing happens.  Synchronises. */
+struct mdb_join_key_col {
+	const int64_t *values;
+	const uint64_t *nullbits;
+	const uint32_t *rid;	/* NULL = identity; may hold MDB_NO_ROW */
+};
+int mdb_dev_join_key_pack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *lay, const struct mdb_join_key_col *cols, uint64_t n,
+			  int64_t *out_key, uint64_t *out_nullbits, uint64_t *out_nulls);
+
 /* ------------------------------------------------------------------ LEFT / RIGHT OUTER JOIN: outer completion
  *
  * The grammar accepts LEFT [OUTER] JOIN and RIGHT [OUTER] JOIN (reference src/parser/midorisql.y:229-233); the reference's

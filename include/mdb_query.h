@@ -141,6 +141,14 @@ int mdb_database_groups_any_order(struct database *db, int on);
  * statistics said that every row of the other side finds exactly one partner in them (their key column holds no value twice, no NULL, and every
  * value of its range, which covers the other side's) and the statement read nothing of them but that key.  MDB_JOIN_ELIMINATION=0: never. */
 unsigned long long mdb_database_joins_eliminated(struct database *db);
+/* Composite join keys: joins of this database's SELECT statements so far that ran on a PACKED composite key - an ON clause with two or
+ * more equalities `earlier-table column = joined-table column` over non-DOUBLE columns whose value ranges fit 63 bits together
+ * (mdb_dev_join_key_layout / mdb_dev_join_key_pack, mdb_dev.h): the pair operator joins on all of them at once and only the other conjuncts
+ * are evaluated on the pairs.  A join whose layout proves that nothing can match (disjoint ranges) counts too: it was answered without a
+ * launch.  Not taken - the join runs on the first equality and filters, as before - in sharded mode, when the joined table's first such
+ * column is measured distinct (nothing can explode), when fewer than two columns fit, and with MDB_COMPOSITE_JOIN=0.  The rows and their
+ * order are the same either way. */
+unsigned long long mdb_database_composite_joins(struct database *db);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

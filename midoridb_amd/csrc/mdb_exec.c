@@ -569,6 +569,142 @@ int join_with_payload(struct exec *x, int t, const struct mdb_expr *kr, const in
 	return payload_shadow(x, t, kr->col_idx, vl, pc, np, out);
 }
 
+/* ------------------------------------------------------------------ composite join keys
+ *
+ * ON A.x = B.x AND A.y = B.y [AND ...]: the reference evaluates the whole ON expression per pair (executor_select.c:1128).  Joining on the
+ * first equality and filtering the pairs by the others materialises every pair of the FIRST column - 8 values in x and 5000 in y over two
+ * tables of 40 000 rows are 2 x 10^8 pairs where the conjunction has 4 x 10^4 - so the equalities whose columns' value ranges fit 63 bits
+ * together are packed into one key per row (mdb_dev_join_key_layout / mdb_dev_join_key_pack, mdb_dev.h) and the pair operator joins on all
+ * of them at once.  composite_join_plan() decides, composite_join_pack() packs both sides; join_next_table and outer_join_next_table use
+ * both.  The rule:
+ *   - the conjuncts `earlier-table column = table-t column`, both sides non-DOUBLE (DOUBLE keeps its IEEE `==`: double_join_keys, or a
+ *     residual), at least two of them;
+ *   - not in sharded mode (the shuffle places rows by the first key), not with MDB_COMPOSITE_JOIN=0;
+ *   - not when table t's column of the first such conjunct is measured distinct: no row of the stream then has more than one partner on
+ *     that column alone, nothing can explode, and the one-key plans (with their unique-key forms) are kept;
+ *   - at least two columns fit (a column that does not fit stays a residual, later ones may still be taken).
+ * Ranges are the catalog's (a base column's range is a superset for a stream or a filtered table: the pack tests every row against its
+ * field, nothing is assumed), measured with mdb_dev_key_range for column types the catalog keeps none for (VARCHAR ids).
+ * Rows and their order are the same as without: the pairs come out (left position, right position)-ordered either way, and a residual
+ * filter keeps that order. */
+struct composite_key {
+	struct mdb_join_key_layout lay;
+	const struct mdb_expr *kl[MDB_JOIN_KEY_MAX_COLS], *kr[MDB_JOIN_KEY_MAX_COLS];	/* the taken conjuncts' sides, layout order */
+	uint32_t mask;			/* bit i: conjunct i of the ON clause is answered by the packed key */
+	bool empty;			/* the layout says that nothing can match: nothing was packed, there are no pairs */
+	const int64_t *vl, *vr;		/* the packed key columns: the stream's, table t's (its rows rsel) */
+	const uint64_t *nl, *nr;	/* their NULL bits; NULL: every row has a key */
+	struct mdb_dev_col_stats st[2];	/* their own statistics for mdb_dev_call_stats: the operator takes no key sample */
+};
+
+static int composite_key_range(struct exec *x, struct mdb_table *tb, struct mdb_column *col, struct mdb_dev_col_stats *st)
+{
+	int rc = mdb_col_range(x->cat, tb, col, &st->min, &st->max);
+	if (rc == 1) {	/* (no catalog range for this type) */
+		const uint64_t rows = tb->device_only ? tb->dev_rows : tb->nrows;
+		st->min = 0;
+		st->max = -1;
+		if (rows && mdb_dev_key_range(x->dev, col->d_data, col->d_nullbits, rows, &st->min, &st->max))
+			return dev_fail(x, "measuring a key column's range");
+		rc = MIDORIDB_OK;
+	}
+	return rc ? dev_fail(x, "reading a key column's range") : MIDORIDB_OK;
+}
+
+/* 0: the join of table t runs on a composite key (ck->lay, ck->mask, ck->kl / kr filled), 1: it does not, < 0: error */
+static int composite_join_plan(struct exec *x, int t, struct mdb_expr *const *conj, int nconj, struct composite_key *ck)
+{
+	struct mdb_select *s = x->s;
+	struct mdb_table *rt = s->tabs[t].t;
+	const struct mdb_expr *ql[32], *qr[32];
+	struct mdb_dev_col_stats sl[32], sr[32];
+	int qi[32], q = 0;
+	memset(ck, 0, sizeof(*ck));
+	if (nconj < 2 || nconj > 32 || x->cat->dist || !x->n || !rt->nrows || x->orig_tab[t] || mdb_knob_off("MDB_COMPOSITE_JOIN"))
+		return 1;
+	for (int i = 0; i < nconj; i++) {
+		const struct mdb_expr *c = conj[i];
+		if (c->kind != MDB_EX_CMP || c->op != MDB_CMP_EQ || c->kids[0]->kind != MDB_EX_FIELD || c->kids[1]->kind != MDB_EX_FIELD)
+			continue;
+		const struct mdb_expr *a = c->kids[0], *b = c->kids[1];
+		if (!(a->tbl_idx >= 0 && a->tbl_idx < t && b->tbl_idx == t)) {
+			const struct mdb_expr *sw = a;
+			a = b;
+			b = sw;
+		}
+		if (!(a->tbl_idx >= 0 && a->tbl_idx < t && b->tbl_idx == t) || a->type == MDB_CT_DOUBLE || b->type == MDB_CT_DOUBLE)
+			continue;
+		if (!s->tabs[a->tbl_idx].t->cols[a->col_idx].d_data || !rt->cols[b->col_idx].d_data)
+			return 1;
+		ql[q] = a;
+		qr[q] = b;
+		qi[q++] = i;
+	}
+	if (q < 2 || mdb_col_distinct(x->cat, rt, &rt->cols[qr[0]->col_idx]))
+		return 1;
+	memset(sl, 0, sizeof(sl));
+	memset(sr, 0, sizeof(sr));
+	for (int i = 0; i < q; i++) {
+		struct mdb_table *lt = s->tabs[ql[i]->tbl_idx].t;
+		int rc;
+		if ((rc = composite_key_range(x, lt, &lt->cols[ql[i]->col_idx], &sl[i])) || (rc = composite_key_range(x, rt, &rt->cols[qr[i]->col_idx], &sr[i])))
+			return rc;
+	}
+	if (mdb_dev_join_key_layout(sl, sr, q, &ck->lay))
+		return 1;
+	if (!ck->lay.empty && ck->lay.ntaken < 2)
+		return 1;
+	ck->empty = ck->lay.empty != 0;
+	for (uint32_t c = 0; c < ck->lay.ntaken; c++) {
+		ck->kl[c] = ql[ck->lay.taken[c]];
+		ck->kr[c] = qr[ck->lay.taken[c]];
+		ck->mask |= 1u << qi[ck->lay.taken[c]];
+	}
+	return 0;
+}
+
+/* ... and the two packed key columns: the stream's rows through their row-id vectors (no gather per key column; a tuple without a row of
+ * the table - MDB_NO_ROW - gets no key), table t's rows rsel[0 .. r_rows) (NULL: all).  An empty layout packs nothing. */
+static int composite_join_pack(struct exec *x, int t, struct composite_key *ck, const uint32_t *rsel, uint64_t r_rows)
+{
+	struct mdb_select *s = x->s;
+	const uint64_t rows[2] = { x->n, r_rows };
+	x->composite_joins++;
+	if (ck->empty)
+		return MIDORIDB_OK;
+	for (int side = 0; side < 2; side++) {
+		struct mdb_join_key_col cols[MDB_JOIN_KEY_MAX_COLS];
+		const uint64_t n = rows[side];
+		uint64_t nulls = 0, top = 0;
+		for (uint32_t c = 0; c < ck->lay.ntaken; c++) {
+			const struct mdb_expr *f = side ? ck->kr[c] : ck->kl[c];
+			const struct mdb_column *col = &s->tabs[f->tbl_idx].t->cols[f->col_idx];
+			cols[c].values = col->d_data;
+			cols[c].nullbits = col->d_nullbits;
+			cols[c].rid = side ? rsel : x->rid[f->tbl_idx];
+			top |= ck->lay.span[c] << ck->lay.shift[c];
+		}
+		int64_t *key = dalloc(x, (n ? n : 1) * 8);
+		uint64_t *nb = dalloc(x, ((n + 63) / 64 + 1) * 8);
+		if (!key || !nb)
+			return dev_fail(x, "allocating a composite key column");
+		if (mdb_dev_join_key_pack(x->dev, &ck->lay, cols, n, key, nb, &nulls))
+			return dev_fail(x, "packing a composite join key");
+		ck->st[side].min = 0;
+		ck->st[side].max = (int64_t)top;	/* (below 2^63: the fields do not overlap) */
+		ck->st[side].rows = n;
+		ck->st[side].nulls = nulls;
+		if (side) {
+			ck->vr = key;
+			ck->nr = nulls ? nb : NULL;
+		} else {
+			ck->vl = key;
+			ck->nl = nulls ? nb : NULL;
+		}
+	}
+	return MIDORIDB_OK;
+}
+
 /* S LEFT / RIGHT [OUTER] JOIN T ON c (S = the stream of the tables joined so far, T = table t).  SQL's meaning, in the emission order of
  * the inner join: the pairs for which the WHOLE ON expression is true, and every row of the PRESERVED side (LEFT: S, RIGHT: T) without
  * such a pair once, the other side's tables at MDB_NO_ROW (their cells read as NULL); rows come preserved-side-major.  None of the inner
@@ -603,9 +739,18 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 	}
 	for (int i = 0; i < npconj; i++)
 		tconj[ntconj++] = pconj[i];
+	struct composite_key ck;
+	const int crc = composite_join_plan(x, t, conj, nconj, &ck);
+	if (crc < 0)
+		return crc;
+	const bool comp = crc == 0;	/* the equalities of ck.mask are one packed key: none of them is a residual, no other conjunct is the key */
 	for (int i = 0; i < nconj; i++) {
 		struct mdb_expr *c = conj[i];
-		if (key < 0 && c->kind == MDB_EX_CMP && c->op == MDB_CMP_EQ && c->kids[0]->kind == MDB_EX_FIELD && c->kids[1]->kind == MDB_EX_FIELD) {
+		if (comp && ((ck.mask >> i) & 1u)) {
+			key = i;
+			continue;
+		}
+		if (!comp && key < 0 && c->kind == MDB_EX_CMP && c->op == MDB_CMP_EQ && c->kids[0]->kind == MDB_EX_FIELD && c->kids[1]->kind == MDB_EX_FIELD) {
 			struct mdb_expr *a = c->kids[0], *b = c->kids[1];
 			if (a->tbl_idx < t && b->tbl_idx == t) {
 				kl = a;
@@ -633,7 +778,16 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 		const int64_t *vl;
 		const uint64_t *nl, *nr;
 		const void *vr;
-		if (kl->type == MDB_CT_DOUBLE) {
+		if (comp) {
+			if ((rc = composite_join_pack(x, t, &ck, rsel, r_rows)))
+				return rc;
+			vl = ck.vl;
+			nl = ck.nl;
+			vr = ck.vr;
+			nr = ck.nr;
+			if (!ck.empty)
+				(void)(left ? mdb_dev_call_stats(x->dev, vl, &ck.st[0], vr, &ck.st[1]) : mdb_dev_call_stats(x->dev, vr, &ck.st[1], vl, &ck.st[0]));
+		} else if (kl->type == MDB_CT_DOUBLE) {
 			const void *dl;
 			if ((rc = double_join_keys(x, &s->tabs[kl->tbl_idx].t->cols[kl->col_idx], x->rid[kl->tbl_idx], n_s, &dl, &nl)) ||
 			    (rc = double_join_keys(x, &rt->cols[kr->col_idx], rsel, r_rows, &vr, &nr)))
@@ -642,9 +796,16 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 		} else if ((rc = stream_column(x, kl, &vl, &nl)) || (rc = table_column(x, t, kr, rsel, r_rows, &vr, &nr))) {
 			return rc;
 		}
-		if (left ? mdb_dev_join_pairs(x->dev, vl, nl, n_s, vr, nr, r_rows, &ps, &pt, &J)
-			 : mdb_dev_join_pairs(x->dev, vr, nr, r_rows, vl, nl, n_s, &pt, &ps, &J))
-			return dev_fail(x, "hash join");
+		if (comp && ck.empty) {
+			J = 0;		/* (no pair: every preserved row is unmatched) */
+		} else {
+			const int jrc = left ? mdb_dev_join_pairs(x->dev, vl, nl, n_s, vr, nr, r_rows, &ps, &pt, &J)
+					     : mdb_dev_join_pairs(x->dev, vr, nr, r_rows, vl, nl, n_s, &pt, &ps, &J);
+			if (comp)
+				op_stats_end(x);
+			if (jrc)
+				return dev_fail(x, "hash join");
+		}
 		if ((ps && track(x, ps)) || (pt && track(x, pt)))
 			return -MIDORIDB_NOMEM;
 	} else if (key < 0) {
@@ -741,6 +902,7 @@ int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, 
 	int nconj = 0, key = -1;
 	const struct mdb_expr *kl = NULL, *kr = NULL;
 	uint32_t *pl = NULL, *pr = NULL;
+	uint32_t answered = 0;	/* the ON conjuncts the join operator itself answers: the key, or the equalities of a composite key */
 	uint64_t J = 0;
 	int rc;
 
@@ -864,7 +1026,27 @@ int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, 
 				return MIDORIDB_OK;
 			}
 		}
+		answered = 1u << key;
+		struct composite_key ck;
+		ck.empty = false;
 		if (x->n && r_rows) {
+			/* none of the one-key shortcuts served: several equalities as ONE packed key, when the rule above says so */
+			const int crc = composite_join_plan(x, t, conj, nconj, &ck);
+			if (crc <= 0)
+				op_stats_end(x);
+			if (crc < 0 || (crc == 0 && (rc = composite_join_pack(x, t, &ck, rsel, r_rows))))
+				return crc < 0 ? crc : rc;
+			if (crc == 0) {
+				answered = ck.mask;
+				vl = ck.vl;
+				nl = ck.nl;
+				vr = ck.vr;
+				nr = ck.nr;
+				if (!ck.empty)
+					(void)mdb_dev_call_stats(x->dev, vl, &ck.st[0], vr, &ck.st[1]);
+			}
+		}
+		if (x->n && r_rows && !ck.empty) {
 			const int jrc = mdb_dev_join_pairs(x->dev, vl, nl, x->n, vr, nr, r_rows, &pl, &pr, &J);
 			op_stats_end(x);
 			if (jrc)
@@ -920,7 +1102,7 @@ int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, 
 				return rc;
 		} else {
 			for (int i = 0; i < nconj; i++)
-				if (i != key && (rc = stream_filter(x, t + 1, conj[i])))
+				if (!((answered >> i) & 1u) && (rc = stream_filter(x, t + 1, conj[i])))
 					return rc;
 		}
 		x->joined_rows = x->n;
@@ -1948,6 +2130,7 @@ grouped:
 	rc = MIDORIDB_OK;
 out:
 	cat->joins_eliminated += (uint64_t)x.joins_eliminated;
+	cat->composite_joins += (uint64_t)x.composite_joins;
 	shard_cleanup(&x);
 	free_all(&x);
 	mdb_result_free(res);

@@ -52,6 +52,7 @@ struct exec {
 	bool need[MDB_MAX_TABS][MDB_MAX_COLS];
 	const struct where_split *ws;		/* the WHERE conjuncts pushed down to single tables (general plan; NULL: none are) */
 	int joins_eliminated;			/* tables that were not joined at all: the catalog said every row of the stream has exactly one partner (join_next_table) */
+	int composite_joins;			/* joins that ran on a packed composite key (composite_join_keys) */
 	bool joined_ahead[MDB_MAX_TABS];	/* table t was joined together with an earlier table on the same key (join_with_payload_multi) */
 	/* LEFT / RIGHT OUTER JOIN: rid[t] may hold MDB_NO_ROW (table t is the NULL-supplied side of a join that left rows without partner) -
 	 * every column of t read through rid[t] needs a NULL bitmap of its own, whether or not the column has one */

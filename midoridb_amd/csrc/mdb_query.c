@@ -310,6 +310,12 @@ unsigned long long mdb_database_joins_eliminated(struct database *db)
 	return cat ? cat->joins_eliminated : 0ull;
 }
 
+unsigned long long mdb_database_composite_joins(struct database *db)
+{
+	struct mdb_catalog *cat = db ? db->tables : NULL;
+	return cat ? cat->composite_joins : 0ull;
+}
+
 double query_exec_ms(struct result_set *res)
 {
 	return res && res->table ? ((struct mdb_result *)res->table)->exec_ms : 0.0;

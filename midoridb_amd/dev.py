@@ -66,6 +66,44 @@ class PlanInfo(ctypes.Structure):
                                                 "pairs_identity")]
 
 
+JOIN_KEY_MAX_COLS = 4     # MDB_JOIN_KEY_MAX_COLS
+
+
+class JoinKeyLayout(ctypes.Structure):
+    """struct mdb_join_key_layout: the bit fields of a packed composite join key"""
+    _fields_ = [("ntaken", c_uint32), ("total_bits", c_uint32), ("empty", c_uint32), ("taken", c_int32 * JOIN_KEY_MAX_COLS),
+                ("lo", c_int64 * JOIN_KEY_MAX_COLS), ("span", c_uint64 * JOIN_KEY_MAX_COLS), ("bits", c_uint32 * JOIN_KEY_MAX_COLS),
+                ("shift", c_uint32 * JOIN_KEY_MAX_COLS)]
+
+
+class JoinKeyCol(ctypes.Structure):
+    """struct mdb_join_key_col"""
+    _fields_ = [("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p)]
+
+
+def join_key_layout(left, right, lib=None):
+    """the layout of a composite join key from the two sides' column ranges, without a GPU (mdb_dev_join_key_layout).
+    left / right: one (min, max) per equality column, in the ON clause's order -> dict with ntaken, total_bits, empty and, per taken
+    column, taken / lo / span / bits / shift, plus "raw": the structure itself for DeviceCtx.join_key_pack"""
+    lib = lib or load_library()
+    _bind(lib)
+    k = len(left)
+    if len(right) != k:
+        raise ValueError("join_key_layout: one range per column and side")
+    sl, sr = (ColStats * max(k, 1))(), (ColStats * max(k, 1))()
+    for i in range(k):
+        sl[i].min, sl[i].max = int(left[i][0]), int(left[i][1])
+        sr[i].min, sr[i].max = int(right[i][0]), int(right[i][1])
+    lay = JoinKeyLayout()
+    rc = lib.mdb_dev_join_key_layout(sl, sr, k, byref(lay))
+    if rc != 0:
+        raise RuntimeError(f"mdb_dev_join_key_layout failed ({rc})")
+    out = {"ntaken": int(lay.ntaken), "total_bits": int(lay.total_bits), "empty": int(lay.empty), "raw": lay}
+    for f in ("taken", "lo", "span", "bits", "shift"):
+        out[f] = [int(getattr(lay, f)[i]) for i in range(lay.ntaken)]
+    return out
+
+
 class ExplainRequest(ctypes.Structure):
     """struct mdb_dev_explain_request"""
     _fields_ = [("left", ColStats), ("right", ColStats), ("further_tables", c_uint32), ("further_rows", c_uint64 * 2), ("left_nulls_bitmap", c_uint32),
@@ -175,6 +213,8 @@ def _bind(lib):
         "mdb_dev_distinct_sel": ([P, POINTER(SortKey), c_int, c_uint64, P, POINTER(c_uint64)], c_int),
         "mdb_dev_group_count_multi": ([P, POINTER(SortKey), c_int, c_uint64, P, P, c_uint64, POINTER(c_uint64)], c_int),
         "mdb_dev_join_pairs": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
+        "mdb_dev_join_key_layout": ([POINTER(ColStats), POINTER(ColStats), c_int, POINTER(JoinKeyLayout)], c_int),
+        "mdb_dev_join_key_pack": ([P, POINTER(JoinKeyLayout), POINTER(JoinKeyCol), c_uint64, P, P, POINTER(c_uint64)], c_int),
         "mdb_dev_outer_complete": ([P, P, P, c_uint64, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys_ordered": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64), POINTER(c_int)], c_int),
@@ -211,7 +251,7 @@ DEV_SYMBOLS = [
     "mdb_dev_ctx_create", "mdb_dev_ctx_destroy", "mdb_dev_ctx_set_stream", "mdb_dev_last_error", "mdb_dev_sync",
     "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
     "mdb_dev_host_alloc", "mdb_dev_host_free", "mdb_dev_h2d", "mdb_dev_d2h", "mdb_dev_prof_enable", "mdb_dev_prof_reset", "mdb_dev_prof_read", "mdb_dev_prof_symbols", "mdb_dev_filter",
-    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_outer_complete", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
+    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_key_layout", "mdb_dev_join_key_pack", "mdb_dev_outer_complete", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
@@ -576,6 +616,24 @@ class DeviceCtx:
             return (torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.int32, device=self.device))
         # tensors over the library's own buffers (no copy); they go back to its allocator when the tensors are collected
         return self._adopt(pl, J, torch.int32), self._adopt(pr, J, torch.int32)
+
+    def join_key_pack(self, layout, cols, n, out_key=None, out_nullbits=None):
+        """One side of a composite join key (mdb_dev_join_key_pack).  layout: join_key_layout()'s result (or its "raw" structure);
+        cols: [(values, nullbits or None, rid or None), ...] for the taken columns, in the layout's order; n: stream length ->
+        (keys[n] int64, NULL-bit words int64[(n + 63) // 64], rows without a key).  out_key / out_nullbits: tensors to write into."""
+        lay = layout["raw"] if isinstance(layout, dict) else layout
+        if len(cols) != lay.ntaken:
+            raise ValueError("join_key_pack: one column per taken field of the layout")
+        arr = (JoinKeyCol * max(len(cols), 1))()
+        for i, (v, nb, rid) in enumerate(cols):
+            arr[i] = JoinKeyCol(v.data_ptr(), nb.data_ptr() if nb is not None else None, rid.data_ptr() if rid is not None else None)
+        if out_key is None:
+            out_key = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if out_nullbits is None:
+            out_nullbits = torch.empty((n + 63) // 64 or 1, dtype=torch.int64, device=self.device)
+        nulls = c_uint64()
+        self._chk(self.lib.mdb_dev_join_key_pack(self.h, byref(lay), arr, n, _ptr(out_key), _ptr(out_nullbits), byref(nulls)), "join_key_pack")
+        return out_key[:n], out_nullbits[:(n + 63) // 64], int(nulls.value)
 
     def outer_complete(self, pairs_p, pairs_o, n_p):
         """LEFT / RIGHT OUTER JOIN's completion: the pairs (ascending preserved-side positions, partner positions; None, None for no
