@@ -134,43 +134,56 @@ __global__ __launch_bounds__(ORD_THREADS) void k_order_leaf(ord_args a)
 #define OS_PER_THREAD 8
 #define OS_MAX_REC (OS_THREADS * OS_PER_THREAD)
 
-__global__ __launch_bounds__(OS_THREADS) void k_order_leaf_sparse(ord_args a)
+/* The LDS is 76 KiB - prefixes of at most OS_MAX_REC as 16-bit words - so that TWO workgroups share a CU: one's loads are on their way while the
+ * other ranks and writes (with 32-bit prefixes it was 128 bytes more than half a CU's LDS: one workgroup per CU, 1526 ranges in six rounds).  A
+ * workgroup's global round trips are two, not three: the records are asked for as soon as the range's count is there, behind the counts of the
+ * earlier ranges and before everything that has a barrier - clear, bits and scans run while they travel. */
+__global__ __launch_bounds__(OS_THREADS, 8 /* waves per SIMD: two workgroups per CU */) void k_order_leaf_sparse(ord_args a)
 {
 	__shared__ uint32_t s_bits[1u << (OS_RANGE_BITS - 5)];
-	__shared__ uint32_t s_pfx[1u << (OS_RANGE_BITS - 5)];
+	__shared__ uint16_t s_pfx[1u << (OS_RANGE_BITS - 5)];
 	__shared__ unsigned long long s_stage[OS_MAX_REC];	/* the records at their ranks */
 	__shared__ uint32_t s_scan[32];
+	static_assert(OS_MAX_REC <= 0xFFFFu, "a prefix fits s_pfx");
 	const uint32_t leaf = blockIdx.x;
 	const uint32_t c = a.cnt[leaf], b = leaf * a.cap, e = b + c;
 	if (!c)
 		return;
-	uint32_t base;
-	if (a.out_base) {
-		base = a.out_base[leaf];
-	} else {		/* (uniform) no scanned counts: the leaves before this one are few enough (<= 1536) to be added up here */
-		uint32_t mine = 0;
-		for (uint32_t i = threadIdx.x; i < leaf; i += OS_THREADS)
-			mine += a.cnt[i];
-		(void)mdb_block_excl_scan(mine, s_scan, &base);
-		__syncthreads();	/* (s_scan is used again below) */
-	}
 	if (c > a.cap || c > OS_MAX_REC) {	/* the scatter's region overflowed, or more records than the registers of a workgroup hold
 						 * (row ids bunched): the general path takes over */
 		if (threadIdx.x == 0 && a.status)
 			mdb_raise(a.status, MDB_ST_REGION_FULL);
 		return;
 	}
-	const uint32_t range_bits = a.kbits - a.leaf_bits, range = 1u << range_bits;
-	const uint32_t words = range_bits > 5 ? 1u << (range_bits - 5) : 1u;
-	for (uint32_t w = threadIdx.x; w < words; w += OS_THREADS)
-		s_bits[w] = 0u;
-	__syncthreads();
+	/* no scanned counts: the leaves before this one are few enough (<= 1536) to be added up here - two loads a thread, asked for first and without
+	 * a branch (a branch around them waits for their answers before the records are asked for); with scanned counts both read cnt[leaf] again */
+	const uint32_t nbefore = a.out_base ? 0u : leaf;
+	uint32_t before[2];
+#pragma unroll
+	for (int k = 0; k < 2; k++) {
+		const uint32_t i = threadIdx.x + (uint32_t)k * OS_THREADS;
+		before[k] = a.cnt[i < nbefore ? i : leaf];
+	}
 	unsigned long long r[OS_PER_THREAD];
 #pragma unroll
 	for (int k = 0; k < OS_PER_THREAD; k++) {
 		const uint32_t i = b + threadIdx.x + (uint32_t)k * OS_THREADS;
 		r[k] = a.rec[i < e ? i : b];	/* (unconditional loads - issued together; past the end: the first record, dropped) */
 	}
+	const uint32_t range_bits = a.kbits - a.leaf_bits, range = 1u << range_bits;
+	const uint32_t words = range_bits > 5 ? 1u << (range_bits - 5) : 1u;
+	for (uint32_t w = threadIdx.x; w < words; w += OS_THREADS)
+		s_bits[w] = 0u;
+	uint32_t base;
+	if (a.out_base) {
+		base = a.out_base[leaf];
+	} else {
+		uint32_t mine = (threadIdx.x < leaf ? before[0] : 0u) + (threadIdx.x + OS_THREADS < leaf ? before[1] : 0u);
+		for (uint32_t i = threadIdx.x + 2u * OS_THREADS; i < leaf; i += OS_THREADS)
+			mine += a.cnt[i];
+		(void)mdb_block_excl_scan(mine, s_scan, &base);
+	}
+	__syncthreads();	/* (the bits are clear; s_scan is used again below) */
 #pragma unroll
 	for (int k = 0; k < OS_PER_THREAD; k++) {
 		const uint32_t i = b + threadIdx.x + (uint32_t)k * OS_THREADS;
@@ -194,7 +207,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_order_leaf_sparse(ord_args a)
 	for (uint32_t q = 0; q < per; q++) {
 		const uint32_t w = threadIdx.x * per + q;
 		if (w < words) {
-			s_pfx[w] = run;
+			s_pfx[w] = (uint16_t)run;
 			run += (uint32_t)__popc(s_bits[w]);
 		}
 	}
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_order_leaf_sparse(ord_args a)
 		if (!r[k])
 			continue;
 		const uint32_t idx = (uint32_t)(r[k] >> (64 - a.kbits)) & (range - 1);
-		s_stage[s_pfx[idx >> 5] + (uint32_t)__popc(s_bits[idx >> 5] & ((1u << (idx & 31u)) - 1u))] = r[k];
+		s_stage[(uint32_t)s_pfx[idx >> 5] + (uint32_t)__popc(s_bits[idx >> 5] & ((1u << (idx & 31u)) - 1u))] = r[k];
 	}
 	__syncthreads();
 	for (uint32_t i = threadIdx.x; i < total; i += OS_THREADS) {
