@@ -501,6 +501,12 @@ struct mdb_join_key_col {
 };
 int mdb_dev_join_key_pack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *lay, const struct mdb_join_key_col *cols, uint64_t n,
 			  int64_t *out_key, uint64_t *out_nullbits, uint64_t *out_nulls);
+/* mdb_dev_join_key_unpack() is the inverse for rows that have a key (the packed GROUP keys that mdb_dev_join_group_count returns for
+ * two packed sides; a group key is never NULL): out_cols[c][i] = lo_c + ((keys[i] >> shift_c) & (2^bits_c - 1)) for the lay->ntaken
+ * caller buffers of n cells each, in unsigned 64-bit arithmetic (exact for a lo near either end of the int64 range); a field of 0
+ * bits yields lo_c.  One streaming pass: 8 bytes per key read, 8 * ntaken written; nothing outside out_cols[c][0 .. n) is touched.
+ * lay->ntaken < 2 or lay->empty: an error, nothing is written.  n == 0: nothing happens.  Synchronises. */
+int mdb_dev_join_key_unpack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *lay, const int64_t *keys, uint64_t n, int64_t *const *out_cols);
 
 /* ------------------------------------------------------------------ LEFT / RIGHT OUTER JOIN: outer completion
  *

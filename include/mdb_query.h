@@ -149,6 +149,15 @@ unsigned long long mdb_database_joins_eliminated(struct database *db);
  * column is measured distinct (nothing can explode), when fewer than two columns fit, and with MDB_COMPOSITE_JOIN=0.  The rows and their
  * order are the same either way. */
 unsigned long long mdb_database_composite_joins(struct database *db);
+/* The fused join + GROUP BY + COUNT(*) operator on a composite key: SELECT statements of this database so far that were answered by
+ * mdb_dev_join_group_count over the two tables' PACKED keys - two tables, INNER JOIN, one GPU, every conjunct of the ON clause an equality
+ * the packed key takes (2 ... 4 of them, the rule of the counter above), no WHERE conjunct over both tables, and either GROUP BY one side
+ * of every equality (any order, sides may mix) with the group fields and / or COUNT(*) selected, or SELECT COUNT(*) alone.  No pair is
+ * written, so the joined rows may number far beyond 2^32 - 1; the packed group keys go back to key columns through
+ * mdb_dev_join_key_unpack.  A statement whose layout proves that nothing can match counts too.  mdb_database_composite_joins() does
+ * NOT rise for such a statement: no pair join ran.  Not taken with MDB_COMPOSITE_JOIN=0 or MDB_COMPOSITE_FUSED=0 (the latter switches
+ * off this plan alone: pair join on the packed key + multi-field GROUP BY, as before); same rows, same order. */
+unsigned long long mdb_database_composite_fused(struct database *db);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

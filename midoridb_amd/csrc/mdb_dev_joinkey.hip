@@ -8,6 +8,8 @@
  *   mdb_dev_join_key_layout  pure host: the bit field of every column pair from the two sides' value ranges
  *   mdb_dev_join_key_pack    one streaming kernel per side: key = sum (v_c - lo_c) << shift_c, a row with a NULL cell, without a
  *                            row (MDB_NO_ROW) or with a value outside its field gets no key (NULL bit set): it can match nothing
+ *   mdb_dev_join_key_unpack  the way back, one streaming kernel: packed group keys -> the key columns (the fused join + GROUP BY
+ *                            operator on a packed key, mdb_exec.c: composite_fused_plan)
  */
 #include "mdb_dev_common.h"
 
@@ -295,5 +297,108 @@ extern "C" int mdb_dev_join_key_pack(mdb_dev_ctx *ctx, const struct mdb_join_key
 	MDB_HIP(ctx, hipMemcpyAsync(h + MDB_HP_COUNT, a.out_nulls, 8, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	*out_nulls = h[MDB_HP_COUNT];
+	return MIDORIDB_OK;
+}
+
+/* ------------------------------------------------------------------ the unpack kernel
+ *
+ * The way back for GROUP keys (the fused join + GROUP BY operator on a packed key returns packed group keys): out_c[i] = lo_c +
+ * ((key_i >> shift_c) & (2^bits_c - 1)) in unsigned 64-bit arithmetic.  The same shape as the pack - 256 threads over 2048 consecutive
+ * keys, two consecutive keys per lane and round, one 16-byte non-temporal load of the keys (read once), one 16-byte store per output
+ * column, the 8-byte forms for a buffer that is not 16-byte aligned - without its LDS word, atomics and bitmap: a group key is never
+ * NULL.  A lane whose keys lie behind n loads and stores nothing. */
+struct jku_args {
+	const int64_t *keys;
+	int64_t *out[MDB_JOIN_KEY_MAX_COLS];
+	int64_t lo[MDB_JOIN_KEY_MAX_COLS];
+	uint64_t mask[MDB_JOIN_KEY_MAX_COLS];		/* 2^bits - 1; a field of 0 bits: 0 */
+	uint32_t shift[MDB_JOIN_KEY_MAX_COLS];
+	uint32_t vec_in;				/* keys is 16-byte aligned */
+	uint32_t vec_out;				/* bit c: out[c] is 16-byte aligned */
+	uint64_t n;
+};
+
+template <int NC>
+__global__ __launch_bounds__(JK_THREADS) void k_join_key_unpack(const jku_args a)
+{
+	const unsigned long long *src = reinterpret_cast<const unsigned long long *>(a.keys);
+#pragma unroll
+	for (uint32_t r = 0; r < JK_ROUNDS; r++) {
+		const uint64_t i0 = (uint64_t)blockIdx.x * JK_ROWS_PER_WG + (uint64_t)r * JK_ROWS_PER_ROUND + 2u * threadIdx.x;
+		if (i0 >= a.n)
+			continue;
+		const bool in1 = i0 + 1 < a.n;
+		uint64_t k0, k1 = 0;
+		if (in1 && a.vec_in) {
+			const jk_ull2 k = __builtin_nontemporal_load(reinterpret_cast<const jk_ull2 *>(src + i0));
+			k0 = k.x;
+			k1 = k.y;
+		} else {
+			k0 = __builtin_nontemporal_load(src + i0);
+			if (in1)
+				k1 = __builtin_nontemporal_load(src + i0 + 1);
+		}
+#pragma unroll
+		for (int c = 0; c < NC; c++) {
+			const uint64_t v0 = (uint64_t)a.lo[c] + ((k0 >> a.shift[c]) & a.mask[c]);
+			const uint64_t v1 = (uint64_t)a.lo[c] + ((k1 >> a.shift[c]) & a.mask[c]);
+			unsigned long long *dst = reinterpret_cast<unsigned long long *>(a.out[c]);
+			if (in1 && ((a.vec_out >> c) & 1u)) {
+				jk_ull2 v;
+				v.x = v0;
+				v.y = v1;
+				*reinterpret_cast<jk_ull2 *>(dst + i0) = v;
+			} else {
+				dst[i0] = v0;
+				if (in1)
+					dst[i0 + 1] = v1;
+			}
+		}
+	}
+}
+
+extern "C" int mdb_dev_join_key_unpack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *lay, const int64_t *keys, uint64_t n,
+				       int64_t *const *out_cols)
+{
+	if (!ctx || !lay)
+		return -MIDORIDB_ERROR;
+	if (lay->ntaken < 2 || lay->ntaken > MDB_JOIN_KEY_MAX_COLS || lay->empty)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_key_unpack: the layout takes %u columns%s (2 ... %d unpack)", lay->ntaken,
+				   lay->empty ? " and is empty" : "", MDB_JOIN_KEY_MAX_COLS);
+	uint32_t below = 0;
+	for (int c = (int)lay->ntaken - 1; c >= 0; c--) {
+		if (lay->bits[c] != jk_bit_length(lay->span[c]) || lay->shift[c] != below || below + lay->bits[c] > 63)
+			return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_key_unpack: field %d of the layout is not what mdb_dev_join_key_layout makes", c);
+		below += lay->bits[c];
+	}
+	if (n == 0)
+		return MIDORIDB_OK;
+	if (!keys || !out_cols)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_key_unpack: keys and destination columns are required");
+	const uint64_t blocks = (n + JK_ROWS_PER_WG - 1) / JK_ROWS_PER_WG;
+	if (blocks > 0x7FFFFFFFull)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_key_unpack: %llu keys are more than one launch addresses", (unsigned long long)n);
+	jku_args a;
+	memset(&a, 0, sizeof(a));
+	for (uint32_t c = 0; c < lay->ntaken; c++) {
+		if (!out_cols[c])
+			return mdb_set_err(ctx, -MIDORIDB_ERROR, "join_key_unpack: column %u has no destination", c);
+		a.out[c] = out_cols[c];
+		a.lo[c] = lay->lo[c];
+		a.mask[c] = lay->bits[c] ? (1ull << lay->bits[c]) - 1ull : 0ull;	/* (bits <= 63) */
+		a.shift[c] = lay->shift[c];
+		if (((uintptr_t)out_cols[c] & 15u) == 0)
+			a.vec_out |= 1u << c;
+	}
+	a.keys = keys;
+	a.vec_in = ((uintptr_t)keys & 15u) == 0;
+	a.n = n;
+	if (lay->ntaken == 2)
+		MDB_LAUNCH(ctx, "join_key_unpack", (k_join_key_unpack<2>), (uint32_t)blocks, JK_THREADS, a);
+	else if (lay->ntaken == 3)
+		MDB_LAUNCH(ctx, "join_key_unpack", (k_join_key_unpack<3>), (uint32_t)blocks, JK_THREADS, a);
+	else
+		MDB_LAUNCH(ctx, "join_key_unpack", (k_join_key_unpack<4>), (uint32_t)blocks, JK_THREADS, a);
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return MIDORIDB_OK;
 }

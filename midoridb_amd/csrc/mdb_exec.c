@@ -23,7 +23,8 @@
  *
  * plus one fused plan for the north-star shape (JOIN ... ON l = r GROUP BY that key, COUNT(*)),
  * which never materialises the joined rows (mdb_dev_join_group_count); it is chained over further
- * tables joined on the same key and also answers SELECT COUNT(*) over such joins.  After the
+ * tables joined on the same key and also answers SELECT COUNT(*) over such joins; over two tables it also runs on a
+ * packed composite key (ON l.x = r.x AND l.y = r.y GROUP BY those keys: composite_fused_plan).  After the
  * reference's phases come the clauses it parses but never executes - HAVING, DISTINCT, ORDER BY,
  * LIMIT (select_tail) - and, at the end of the file, DELETE and UPDATE on the device mirror.
  *
@@ -113,14 +114,30 @@ int stream_apply_sel(struct exec *x, int ntabs_in_stream, const uint32_t *sel, u
 		x->d_count = nc;
 	}
 	if (x->fused) {
-		int64_t *nk = dalloc(x, (n_new ? n_new : 1) * 8);
-		if (!nk || (n_new && mdb_dev_gather64(x->dev, x->d_fused_key, NULL, sel, n_new, nk, NULL)))
-			return dev_fail(x, "re-mapping the group key");
-		x->d_fused_key = nk;
+		for (int k = 0; k < (x->nfused ? x->nfused : 1); k++) {	/* (a composite key: every key column of the stream) */
+			const int64_t *from = x->nfused ? x->d_fused_keys[k] : x->d_fused_key;
+			int64_t *nk = dalloc(x, (n_new ? n_new : 1) * 8);
+			if (!nk || (n_new && mdb_dev_gather64(x->dev, from, NULL, sel, n_new, nk, NULL)))
+				return dev_fail(x, "re-mapping the group key");
+			if (x->nfused)
+				x->d_fused_keys[k] = nk;
+			if (!k)
+				x->d_fused_key = nk;
+		}
 		x->n = n_new;
 		return MIDORIDB_OK;
 	}
 	return stream_select(x, ntabs_in_stream, sel, n_new);
+}
+
+/* the key column of the fused stream that holds field (tbl_idx, col_idx): the one there is, or - on a composite key - the column of the
+ * ON equality that names the field on either side */
+int64_t *fused_key_column(const struct exec *x, int tbl_idx, int col_idx)
+{
+	for (int i = 0; i < x->nfused_map; i++)
+		if (x->fused_tbl[i] == tbl_idx && x->fused_col[i] == col_idx)
+			return x->d_fused_keys[x->fused_at[i]];
+	return x->d_fused_key;
 }
 
 /* device pointer to a column's key/value vector for the current stream (gathered when needed) */
@@ -664,12 +681,14 @@ static int composite_join_plan(struct exec *x, int t, struct mdb_expr *const *co
 }
 
 /* ... and the two packed key columns: the stream's rows through their row-id vectors (no gather per key column; a tuple without a row of
- * the table - MDB_NO_ROW - gets no key), table t's rows rsel[0 .. r_rows) (NULL: all).  An empty layout packs nothing. */
-static int composite_join_pack(struct exec *x, int t, struct composite_key *ck, const uint32_t *rsel, uint64_t r_rows)
+ * the table - MDB_NO_ROW - gets no key), table t's rows rsel[0 .. r_rows) (NULL: all).  An empty layout packs nothing.
+ * left_table (the fused plan, whose left side is no stream yet): the left side is the left table's rows lsel[0 .. l_rows) (NULL: all),
+ * read through that selection vector the same way. */
+static int composite_pack_sides(struct exec *x, struct composite_key *ck, bool left_table, const uint32_t *lsel, uint64_t l_rows, const uint32_t *rsel,
+				uint64_t r_rows)
 {
 	struct mdb_select *s = x->s;
-	const uint64_t rows[2] = { x->n, r_rows };
-	x->composite_joins++;
+	const uint64_t rows[2] = { left_table ? l_rows : x->n, r_rows };
 	if (ck->empty)
 		return MIDORIDB_OK;
 	for (int side = 0; side < 2; side++) {
@@ -681,7 +700,7 @@ static int composite_join_pack(struct exec *x, int t, struct composite_key *ck, 
 			const struct mdb_column *col = &s->tabs[f->tbl_idx].t->cols[f->col_idx];
 			cols[c].values = col->d_data;
 			cols[c].nullbits = col->d_nullbits;
-			cols[c].rid = side ? rsel : x->rid[f->tbl_idx];
+			cols[c].rid = side ? rsel : left_table ? lsel : x->rid[f->tbl_idx];
 			top |= ck->lay.span[c] << ck->lay.shift[c];
 		}
 		int64_t *key = dalloc(x, (n ? n : 1) * 8);
@@ -703,6 +722,128 @@ static int composite_join_pack(struct exec *x, int t, struct composite_key *ck, 
 		}
 	}
 	return MIDORIDB_OK;
+}
+
+static int composite_join_pack(struct exec *x, int t, struct composite_key *ck, const uint32_t *rsel, uint64_t r_rows)
+{
+	(void)t;
+	x->composite_joins++;
+	return composite_pack_sides(x, ck, false, NULL, 0, rsel, r_rows);
+}
+
+/* The fused join + GROUP BY + COUNT(*) operator on a packed composite key:
+ *     SELECT A.x, A.y, COUNT(*) FROM A JOIN B ON A.x = B.x AND A.y = B.y GROUP BY A.x, A.y      and      SELECT COUNT(*) FROM the same join
+ * without a pair, a gathered key column or a multi-field GROUP BY: both tables (their rows that pass the pushed WHERE conjuncts) are
+ * packed, mdb_dev_join_group_count joins and groups the packed keys as it does one key column, mdb_dev_join_key_unpack turns the packed
+ * group keys back into the key columns.  It applies to exactly two tables of an inner join, one GPU, when EVERY conjunct of the ON clause
+ * is an equality the composite key takes (composite_join_plan's rule and layout, nothing left as a residual; the two sides of an equality of
+ * one type), no WHERE conjunct reads both tables, and the statement groups by one side of every equality (any order, sides may mix) or is
+ * count-only.  MDB_COMPOSITE_JOIN=0 switches it off with the other composite-key plans, MDB_COMPOSITE_FUSED=0 alone.
+ * The groups come in the order of each key tuple's first left row that has a partner (MDB_ORDER_FIRST on the packed key: equal tuples are
+ * equal keys) - what the pair join + multi-field GROUP BY returns.
+ * 0: answered - the stream is (d_fused_keys[0 .. nfused), d_count), x->n set; 1: not such a statement, nothing changed; < 0: error. */
+static int composite_fused_plan(struct exec *x, const struct where_split *ws, bool only_count)
+{
+	struct mdb_select *s = x->s;
+	struct mdb_catalog *cat = x->cat;
+	struct mdb_expr *conj[32];
+	struct composite_key ck;
+	int nconj = 0, rc;
+
+	if (s->ntabs != 2 || x->has_outer || s->join_type[1] != 1 || cat->dist || !s->on[1] || ws->nresidual || s->select_all || mdb_knob_off("MDB_COMPOSITE_FUSED"))
+		return 1;
+	if (only_count ? s->ngroup != 0 : (s->ngroup < 2 || s->ngroup > MDB_JOIN_KEY_MAX_COLS))
+		return 1;
+	collect_conjuncts(s->on[1], conj, &nconj, 32);
+	if (nconj < 2 || nconj > MDB_JOIN_KEY_MAX_COLS || (!only_count && s->ngroup != nconj))
+		return 1;
+	for (int i = 0; i < nconj; i++) {
+		const struct mdb_expr *c = conj[i];
+		if (c->kind != MDB_EX_CMP || c->op != MDB_CMP_EQ || c->kids[0]->kind != MDB_EX_FIELD || c->kids[1]->kind != MDB_EX_FIELD ||
+		    c->kids[0]->tbl_idx == c->kids[1]->tbl_idx || c->kids[0]->type != c->kids[1]->type || c->kids[0]->type == MDB_CT_DOUBLE)
+			return 1;
+	}
+	for (int g = 0; g < s->ngroup; g++)
+		if (s->group[g]->kind != MDB_EX_FIELD)
+			return 1;
+	x->n = s->tabs[0].t->nrows;	/* (the plan asks whether there is a left stream at all; none is made here) */
+	rc = composite_join_plan(x, 1, conj, nconj, &ck);
+	x->n = 0;
+	if (rc)
+		return rc;
+	if (ck.lay.ntaken != (uint32_t)nconj)
+		return 1;
+	/* GROUP BY one side of every taken equality: each group field finds an equality of its own */
+	bool used[MDB_JOIN_KEY_MAX_COLS] = { false };
+	for (int g = 0; g < s->ngroup; g++) {
+		int c = 0;
+		while (c < nconj && (used[c] || !(field_eq(s->group[g], ck.kl[c]) || field_eq(s->group[g], ck.kr[c]))))
+			c++;
+		if (c == nconj)
+			return 1;
+		used[c] = true;
+	}
+
+	x->composite_fused++;
+	x->nfused = nconj;
+	x->nfused_map = 0;
+	for (int c = 0; c < nconj; c++)
+		for (int side = 0; side < 2; side++) {
+			const struct mdb_expr *f = side ? ck.kr[c] : ck.kl[c];
+			x->fused_tbl[x->nfused_map] = f->tbl_idx;
+			x->fused_col[x->nfused_map] = f->col_idx;
+			x->fused_at[x->nfused_map++] = c;
+		}
+	uint64_t G = 0, J = 0;
+	if (!ck.empty) {
+		const uint32_t *lsel, *rsel;
+		uint64_t l_rows, r_rows;
+		if ((rc = table_filter(x, 0, ws->push[0], ws->npush[0], &lsel, &l_rows)) || (rc = table_filter(x, 1, ws->push[1], ws->npush[1], &rsel, &r_rows)))
+			return rc;
+		if (l_rows && r_rows) {
+			if ((rc = composite_pack_sides(x, &ck, true, lsel, l_rows, rsel, r_rows)))
+				return rc;
+			/* a group needs a packed key that both sides hold: no more groups than rows of either side or values of the packed field */
+			uint64_t cap = l_rows < r_rows ? l_rows : r_rows;
+			const uint64_t top = (uint64_t)ck.st[0].max;	/* (below 2^63) */
+			cap = top + 1 < cap ? top + 1 : cap;
+			int64_t *pk = dalloc(x, cap * 8);
+			x->d_count = dalloc(x, cap * 8);
+			if (!pk || !x->d_count)
+				return dev_fail(x, "allocating group outputs");
+			/* the packed columns' own statistics, as the pair path hands them over: temporaries, nothing measured distinct */
+			(void)mdb_dev_call_stats(x->dev, ck.vl, &ck.st[0], ck.vr, &ck.st[1]);
+			const int frc = mdb_dev_join_group_count(x->dev, ck.vl, ck.nl, l_rows, ck.vr, ck.nr, r_rows,
+								  ((only_count || cat->groups_any_order) ? 0u : MDB_ORDER_FIRST) | MDB_KEYS_MAY_ALIAS, pk, x->d_count, NULL, cap,
+								  &G, &J);
+			op_stats_end(x);
+			if (frc)
+				return dev_fail(x, "join + group count on a composite key");
+			struct mdb_dev_plan_info pi;
+			const int64_t *gk = pk;
+			if (mdb_dev_last_plan(x->dev, &pi) == 0 && pi.keys_are_left_column && G == l_rows)
+				gk = ck.vl;	/* (every left row a group: the packed left column holds the group keys, none were written) */
+			if (G && !only_count) {
+				for (int c = 0; c < nconj; c++)
+					if (!(x->d_fused_keys[c] = dalloc(x, G * 8)))
+						return dev_fail(x, "allocating group outputs");
+				if (mdb_dev_join_key_unpack(x->dev, &ck.lay, gk, G, x->d_fused_keys))
+					return dev_fail(x, "unpacking the group keys");
+			}
+		}
+	}
+	if (!G)
+		J = 0;
+	for (int c = 0; c < nconj; c++)	/* (no group, or count-only: columns that are never read, but there) */
+		if (!x->d_fused_keys[c] && !(x->d_fused_keys[c] = dalloc(x, 8)))
+			return dev_fail(x, "allocating group outputs");
+	if (!x->d_count && !(x->d_count = dalloc(x, 8)))
+		return dev_fail(x, "allocating group outputs");
+	x->d_fused_key = x->d_fused_keys[0];
+	x->fused = true;
+	x->n = only_count ? J : G;
+	x->joined_rows = J;
+	return 0;
 }
 
 /* S LEFT / RIGHT [OUTER] JOIN T ON c (S = the stream of the tables joined so far, T = table t).  SQL's meaning, in the emission order of
@@ -1276,7 +1417,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	double t0;
 	const struct mdb_expr *fkeys[MDB_MAX_TABS];
 	const struct mdb_expr *kj[2] = { NULL, NULL };
-	int fused;
+	int fused, cfrc = 1;
 
 	*out = NULL;
 	memset(&x, 0, sizeof(x));
@@ -1599,6 +1740,12 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 		x.fused = true;
 		x.n = only_count ? J : G;	/* COUNT(*) without GROUP BY = the stream length = the joined rows */
 		x.joined_rows = J;
+	} else if (!keys_only && split_ok && (cfrc = composite_fused_plan(&x, &ws, only_count)) <= 0) {
+		/* ---- the fused plan on a packed composite key (several ON equalities): answered, or an error */
+		if (cfrc < 0) {
+			rc = cfrc;
+			goto out;
+		}
 	} else if (keys_only) {
 		/* ---- a two-table equi-join whose select list names nothing but the two key columns (BASELINE configs[3]: SELECT * over
 		 *      two key columns), any order allowed (mdb_database_groups_any_order): both sides hold the same value in every
@@ -1967,7 +2114,8 @@ grouped:
 			if (!out_rows || count_only)
 				continue;
 			if (fused >= 0 || x.fused) {
-				d_vals[c] = x.d_fused_key;	/* only the group key can be selected (S4); both sides hold the same value */
+				/* only the group key can be selected (S4); both sides hold the same value.  A composite key: the field's key column */
+				d_vals[c] = fused_key_column(&x, key_tbl[key], key_col[key]);
 				continue;
 			}
 			if (direct_vals) {			/* scan + WHERE + projection plan: the columns are final already */
@@ -2131,6 +2279,7 @@ grouped:
 out:
 	cat->joins_eliminated += (uint64_t)x.joins_eliminated;
 	cat->composite_joins += (uint64_t)x.composite_joins;
+	cat->composite_fused += (uint64_t)x.composite_fused;
 	shard_cleanup(&x);
 	free_all(&x);
 	mdb_result_free(res);

@@ -35,6 +35,13 @@ struct exec {
 	int64_t *d_count;		/* COUNT(*) column of the stream (after GROUP BY), device */
 	bool fused;			/* north-star plan: the stream is (d_fused_key, d_count), no row ids */
 	int64_t *d_fused_key;
+	/* the fused plan on a packed composite key (composite_fused_plan): the stream carries nfused >= 2 key columns d_fused_keys[0 .. nfused)
+	 * (d_fused_key is the first of them) and a map from the fields of the ON equalities to them - both sides of an equality name the
+	 * same column.  nfused == 0: the stream has the one key column d_fused_key, whatever field is asked for (fused_key_column) */
+	int nfused;
+	int64_t *d_fused_keys[MDB_JOIN_KEY_MAX_COLS];
+	int fused_tbl[2 * MDB_JOIN_KEY_MAX_COLS], fused_col[2 * MDB_JOIN_KEY_MAX_COLS], fused_at[2 * MDB_JOIN_KEY_MAX_COLS];
+	int nfused_map;
 	uint64_t joined_rows;
 	/* per joined table: its equi-join key column holds, in every tuple of the stream, the value of an earlier table's column
 	 * (INT64-represented types: the join compared all 64 bits; never NULL - a NULL key joins nothing): the projection reads
@@ -53,6 +60,7 @@ struct exec {
 	const struct where_split *ws;		/* the WHERE conjuncts pushed down to single tables (general plan; NULL: none are) */
 	int joins_eliminated;			/* tables that were not joined at all: the catalog said every row of the stream has exactly one partner (join_next_table) */
 	int composite_joins;			/* joins that ran on a packed composite key (composite_join_keys) */
+	int composite_fused;			/* the statement ran the fused join + GROUP BY operator on a packed composite key (composite_fused_plan) */
 	bool joined_ahead[MDB_MAX_TABS];	/* table t was joined together with an earlier table on the same key (join_with_payload_multi) */
 	/* LEFT / RIGHT OUTER JOIN: rid[t] may hold MDB_NO_ROW (table t is the NULL-supplied side of a join that left rows without partner) -
 	 * every column of t read through rid[t] needs a NULL bitmap of its own, whether or not the column has one */
@@ -98,6 +106,7 @@ void *dalloc(struct exec *x, size_t bytes);
 void free_all(struct exec *x);
 int stream_select(struct exec *x, int ntabs_in_stream, const uint32_t *sel, uint64_t n_new);
 int stream_apply_sel(struct exec *x, int ntabs_in_stream, const uint32_t *sel, uint64_t n_new);
+int64_t *fused_key_column(const struct exec *x, int tbl_idx, int col_idx);
 int stream_column(struct exec *x, const struct mdb_expr *f, const int64_t **vals, const uint64_t **nulls);
 int double_join_keys(struct exec *x, const struct mdb_column *col, const uint32_t *rid, uint64_t n, const void **vals, const uint64_t **nulls);
 void mark_needed(struct exec *x, const struct mdb_expr *e);

@@ -10,7 +10,7 @@
 
 /* device binding of a column-like operand for the current stream: a table column read through the table's
  * row-id vector, the COUNT(*) column (HAVING), or - in the fused north-star plan, whose stream carries no row
- * ids - the group key column (the only field S4 lets such a query name) */
+ * ids - the group key column (the only field S4 lets such a query name; on a composite key: the key column of that field) */
 void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values, const uint64_t **nullbits, const uint32_t **rid)
 {
 	if (f->kind == MDB_EX_COUNT) {
@@ -18,7 +18,7 @@ void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values,
 		*nullbits = NULL;
 		*rid = NULL;
 	} else if (x->fused) {
-		*values = x->d_fused_key;
+		*values = fused_key_column(x, f->tbl_idx, f->col_idx);
 		*nullbits = NULL;
 		*rid = NULL;
 	} else {

@@ -215,6 +215,7 @@ def _bind(lib):
         "mdb_dev_join_pairs": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_key_layout": ([POINTER(ColStats), POINTER(ColStats), c_int, POINTER(JoinKeyLayout)], c_int),
         "mdb_dev_join_key_pack": ([P, POINTER(JoinKeyLayout), POINTER(JoinKeyCol), c_uint64, P, P, POINTER(c_uint64)], c_int),
+        "mdb_dev_join_key_unpack": ([P, POINTER(JoinKeyLayout), P, c_uint64, POINTER(c_void_p)], c_int),
         "mdb_dev_outer_complete": ([P, P, P, c_uint64, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys_ordered": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64), POINTER(c_int)], c_int),
@@ -251,7 +252,7 @@ DEV_SYMBOLS = [
     "mdb_dev_ctx_create", "mdb_dev_ctx_destroy", "mdb_dev_ctx_set_stream", "mdb_dev_last_error", "mdb_dev_sync",
     "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
     "mdb_dev_host_alloc", "mdb_dev_host_free", "mdb_dev_h2d", "mdb_dev_d2h", "mdb_dev_prof_enable", "mdb_dev_prof_reset", "mdb_dev_prof_read", "mdb_dev_prof_symbols", "mdb_dev_filter",
-    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_key_layout", "mdb_dev_join_key_pack", "mdb_dev_outer_complete", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
+    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_key_layout", "mdb_dev_join_key_pack", "mdb_dev_join_key_unpack", "mdb_dev_outer_complete", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
@@ -634,6 +635,19 @@ class DeviceCtx:
         nulls = c_uint64()
         self._chk(self.lib.mdb_dev_join_key_pack(self.h, byref(lay), arr, n, _ptr(out_key), _ptr(out_nullbits), byref(nulls)), "join_key_pack")
         return out_key[:n], out_nullbits[:(n + 63) // 64], int(nulls.value)
+
+    def join_key_unpack(self, layout, keys, n, out_cols=None):
+        """Packed keys back to their columns (mdb_dev_join_key_unpack): out_cols[c][i] = lo_c + field c of keys[i] for rows that have a
+        key.  layout: join_key_layout()'s result (or its "raw" structure); keys: int64[n] -> [int64[n]] * ntaken.  out_cols: tensors
+        to write into."""
+        lay = layout["raw"] if isinstance(layout, dict) else layout
+        if out_cols is None:
+            out_cols = [torch.empty(max(n, 1), dtype=torch.int64, device=self.device) for _ in range(lay.ntaken)]
+        if len(out_cols) != lay.ntaken:
+            raise ValueError("join_key_unpack: one output per taken field of the layout")
+        arr = (c_void_p * max(len(out_cols), 1))(*[o.data_ptr() for o in out_cols])
+        self._chk(self.lib.mdb_dev_join_key_unpack(self.h, byref(lay), _ptr(keys), n, arr), "join_key_unpack")
+        return [o[:n] for o in out_cols]
 
     def outer_complete(self, pairs_p, pairs_o, n_p):
         """LEFT / RIGHT OUTER JOIN's completion: the pairs (ascending preserved-side positions, partner positions; None, None for no
