@@ -97,15 +97,62 @@ def outer_join_rows(dev, res):
                                       "note": "query_execute() with results kept on the device; the statements alternate"}
 
 
+def in_set_rows(dev, res):
+    """in_set_1e8: WHERE k IN (list) over 10^8 INT64 rows through mdb_dev_filter (bitmap, scan, positions) at about 1 % and about 50 %
+    selectivity - a 1000-value list (MDB_P_IN_SET, table in LDS) and a 10^6-value list (table in global memory) beside the two forms that
+    ran before lists compiled to a lookup: an 8-value list (k_pred_bits_terms) and one comparison.  The column is a permutation modulo
+    (list length / selectivity), the list a random choice of that domain.  pred_ms = the predicate kernel alone (HIP events)."""
+    n = 100_000_000
+    rng = np.random.default_rng(5)
+    out = {"rows": n, "lds_values": dev.in_set_lds_values(), "cases": {}}
+    for sel in (0.01, 0.5):
+        for name, k in (("one_compare", 0), ("terms_8", 8), ("set_1000", 1000), ("set_1000000", 1_000_000)):
+            domain = n if k == 0 else int(round(k / sel))
+            v = dev.gen_keys(n, 0, n, 7, 0 if domain == n else domain)
+            keep = None
+            if k == 0:
+                prog = [(D.P_CMP_COL_CONST, D.CMP_LT, D.T_INT64, 0, 0, int(sel * n))]
+            elif k <= 8:
+                prog = []
+                for i in range(k):
+                    prog.append((D.P_CMP_COL_CONST, D.CMP_EQ, D.T_INT64, 0, 0, i))
+                    if i:
+                        prog.append((D.P_OR, 0, 0, 0, 0, 0))
+            else:
+                keep = dev.make_set(rng.choice(domain, k, replace=False))
+                prog = [keep.insn(0)]
+            ms, kern, m = timed(dev, lambda: dev.filter(prog, [(v, None, None)], n).numel())
+            pred = {kk: vv for kk, vv in kern.items() if kk in ("filter_in_set", "filter_pred_bits", "scan_project")}
+            out["cases"][f"{name}@{sel}"] = {"list_values": k, "domain": domain, "rows_out": m, "selectivity": m / n, "ms": ms,
+                                             "pred_ms": sum(pred.values()), "kernels_ms": kern,
+                                             "column_GBs_pred": 8 * n / (sum(pred.values()) * 1e-3) / 1e9 if pred else None}
+            if keep is not None:
+                keep.close()
+            del v
+            torch.cuda.empty_cache()
+        c = out["cases"]
+        out[f"lds_over_terms8@{sel}"] = {"pred_ms": c[f"set_1000@{sel}"]["pred_ms"] / c[f"terms_8@{sel}"]["pred_ms"],
+                                         "ms": c[f"set_1000@{sel}"]["ms"] / c[f"terms_8@{sel}"]["ms"], "target": 1.25}
+    res["in_set_1e8"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04", "operators.json"))
     ap.add_argument("--configs1", action="store_true", help="only the two BASELINE configs[0..1] shapes (scan_filter_1e8, join_payload_1e7): "
                                                              "what profiles/collect.sh runs under rocprofv3")
     ap.add_argument("--outer", action="store_true", help="only the outer join's rows (outer_complete_1e8, left_join_pairs_1e8)")
+    ap.add_argument("--in-set", action="store_true", help="only the IN-list rows (in_set_1e8: set lookups beside an 8-value term list and one comparison)")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.in_set:
+        in_set_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.outer:
         outer_join_rows(dev, res)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)

@@ -255,7 +255,88 @@ enum mdb_pred_op {
 	MDB_P_IN_BITS       = 9,	/* push (bit <col a's value> of the device bit table at imm is set) ^ cmp, false for a NULL cell and for
 					 * a value beyond the table's b 64-bit words: set membership of small non-negative ids - LIKE over a
 					 * VARCHAR column, whose cells are dictionary ids (the pattern is matched once per distinct string) */
+	MDB_P_IN_SET        = 10,	/* push (col a's value is a member of the device set at imm) ^ (cmp != 0); false for a NULL cell and for a
+					 * MDB_NO_ROW cell (as MDB_P_IN_BITS): IN / NOT IN lists of any length.  imm = device address of a set
+					 * image (below), b = log2 of its slot count, type = how values compare */
 };
+
+/* ------------------------------------------------------------------ device sets (MDB_P_IN_SET)
+ *
+ * A set is an open-addressing hash table of 8-byte slots, built on the host (mdb_set_build) and uploaded once per statement.
+ * The image is an array of 2 + slots 64-bit words, 16-byte aligned:
+ *
+ *     word 0        the EMPTY marker: a bit pattern the builder has proven absent from the members (it probes candidates against the
+ *                   finished table until one misses; with fewer than 2^64 members one always does).  All 2^64 patterns stay legal
+ *                   members - INT64_MIN, -1 and 0 among them -; a cell that happens to equal the marker is a non-member and is
+ *                   answered as one (the probe tests "empty" before "equal")
+ *     word 1        the slot count: a power of two >= 16, at least twice the number of members (load <= 1/2; a set whose table then
+ *                   still fits MDB_SET_LDS_SLOTS is built at load <= 1/4)
+ *     words 2 ...   the slots: a member's bits or the marker.  A member sits at the first free slot from mdb_set_slot_of() on,
+ *                   linear probing, wrapping around
+ *
+ * Members are canonical and distinct, and the table is sized by their number, not by the length of the list: the builder drops duplicates and, for MDB_T_DOUBLE, turns -0.0 into +0.0 and drops NaNs.
+ * How a cell compares (`type`):
+ *     MDB_T_INT64   bit for bit
+ *     MDB_T_DOUBLE  as IEEE `==`: a -0.0 cell is looked up as +0.0 (one member), a NaN cell is a member of nothing - IN is false and
+ *                   NOT IN is true for it, as `a = b` and `a <> b` are
+ * A NULL cell fails IN and NOT IN alike.  The probe ends at an empty slot - which the load factor guarantees exists - AND after at
+ * most `slots` steps: an image that is wrong gives a wrong answer, never a spin. */
+#define MDB_SET_MAX_VALUES (1ull << 26)	/* members (list values) a set takes: a table of 2^27 slots, 1 GiB */
+#define MDB_SET_MIN_LOG2 4
+#define MDB_SET_MAX_LOG2 27
+#define MDB_SET_LDS_SLOTS 4096u		/* slot count up to which the one-instruction filter kernel stages the table in LDS (32 KiB per workgroup) */
+
+#if defined(__HIPCC__)
+#define MDB_SET_HD __host__ __device__
+#else
+#define MDB_SET_HD
+#endif
+/* first slot of a value: the two halves folded together, times an odd 64-bit constant, top bits - all 64 bits of the value reach the
+ * slot number, so keys that differ only in high bits or only in low bits spread */
+static inline MDB_SET_HD uint64_t mdb_set_slot_of(uint64_t bits, unsigned log2_slots)
+{
+	bits ^= bits >> 32;
+	return (bits * 0x9E3779B97F4A7C15ull) >> (64u - log2_slots);
+}
+/* the canonical bits of a value, 0 = it equals nothing (a NaN of MDB_T_DOUBLE) */
+static inline MDB_SET_HD int mdb_set_canonical(int type, uint64_t *bits)
+{
+	if (type == 1) {	/* MDB_T_DOUBLE */
+		if ((*bits << 1) == 0)
+			*bits = 0;
+		else if ((*bits << 1) > 0xFFE0000000000000ull)
+			return 0;
+	}
+	return 1;
+}
+
+struct mdb_set_image {
+	uint64_t *words;	/* malloc'ed: marker, slot count, slots (above) */
+	uint64_t slots;
+	uint64_t members;	/* distinct canonical values */
+	uint64_t empty;		/* words[0] */
+	uint64_t longest_run;	/* longest run of occupied slots (cyclic): no lookup, hit or miss, takes more steps than this + 1 */
+	uint32_t log2_slots;
+	int32_t type;		/* enum mdb_valtype */
+};
+/* host builder and host probe (mdb_set.c, no device involved).  values: n 8-byte values (the bits of doubles for MDB_T_DOUBLE), any
+ * order, duplicates allowed, n = 0 allowed; n > MDB_SET_MAX_VALUES or an unknown type: -MIDORIDB_ERROR, no memory: -MIDORIDB_NOMEM.
+ * mdb_set_image_contains() walks the same hash and probe sequence as the kernels. */
+int mdb_set_build(const int64_t *values, uint64_t n, int type, struct mdb_set_image *out);
+void mdb_set_image_free(struct mdb_set_image *img);
+int mdb_set_image_contains(const struct mdb_set_image *img, int64_t value);
+
+/* A set in device memory: built from n host values, alive until mdb_dev_set_free().  mdb_dev_set_insn() fills the one predicate
+ * instruction that tests column slot `slot` against it (negate != 0: NOT IN).  More than MDB_SET_MAX_VALUES values:
+ * -MIDORIDB_ERROR with a message. */
+typedef struct mdb_dev_set mdb_dev_set;
+struct mdb_pred_insn;
+int mdb_dev_set_create(mdb_dev_ctx *ctx, const int64_t *host_values, uint64_t n, int type, mdb_dev_set **set);
+int mdb_dev_set_insn(const mdb_dev_set *set, int slot, int negate, struct mdb_pred_insn *insn);
+int mdb_dev_set_free(mdb_dev_ctx *ctx, mdb_dev_set *set);
+/* the largest number of list values whose table the one-instruction kernel stages in LDS (MDB_SET_LDS_SLOTS / 2); larger sets are
+ * probed in global memory (L2 / Infinity Cache) */
+uint64_t mdb_dev_in_set_lds_values(void);
 /* comparison codes = the reference's enum ast_comparison_type (include/parser/ast.h:71-84) */
 enum mdb_cmp { MDB_CMP_LT = 1, MDB_CMP_GT = 2, MDB_CMP_NE = 3, MDB_CMP_EQ = 4, MDB_CMP_LE = 5, MDB_CMP_GE = 6 };
 enum mdb_valtype { MDB_T_INT64 = 0, MDB_T_DOUBLE = 1 };
@@ -271,6 +352,9 @@ struct mdb_pred_insn {
 
 #define MDB_PRED_MAX_INSNS 64
 #define MDB_PRED_MAX_SLOTS 16
+/* comparisons of ONE column with constants, all ANDed or all ORed, that the one-column term kernels take (mdb_dev_filter.hip); the
+ * executor expands an IN / NOT IN list of up to this many values into such terms and compiles a longer one to MDB_P_IN_SET / MDB_P_IN_BITS */
+#define MDB_FILTER_MAX_TERMS 8
 
 struct mdb_col_binding {
 	const void *values;		/* dptr: 8-byte values of the base column */

@@ -158,6 +158,12 @@ unsigned long long mdb_database_composite_joins(struct database *db);
  * NOT rise for such a statement: no pair join ran.  Not taken with MDB_COMPOSITE_JOIN=0 or MDB_COMPOSITE_FUSED=0 (the latter switches
  * off this plan alone: pair join on the packed key + multi-field GROUP BY, as before); same rows, same order. */
 unsigned long long mdb_database_composite_fused(struct database *db);
+/* IN / NOT IN lists of this database's statements so far (WHERE, ON, HAVING of SELECT; WHERE of DELETE / UPDATE) that were compiled to
+ * ONE device lookup: lists of more than 8 values - a hash-set probe (MDB_P_IN_SET, mdb_dev.h) for INTEGER / DOUBLE / TINYINT
+ * columns, a bit per dictionary id (MDB_P_IN_BITS) for VARCHAR columns.  Such a list may be of any length.  Lists of up to 8 values
+ * compile to one comparison per value as before and do not count; with MDB_IN_SET=0 every list does, and a list the device program
+ * cannot hold (33 values and more) is refused as "predicate too large". */
+unsigned long long mdb_database_in_set_lookups(struct database *db);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

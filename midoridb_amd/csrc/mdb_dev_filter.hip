@@ -70,6 +70,33 @@ __device__ static inline bool pred_cmp(int32_t cmp, int32_t type, uint64_t x, ui
 	return false;
 }
 
+/* MDB_P_IN_SET: is x (canonical bits) in the table?  slots / log2 / empty as in the set image (mdb_dev.h).  The probe ends at an
+ * empty slot or after `slots` steps, whichever comes first: bounded whatever the table holds. */
+template <typename Slots>
+__device__ static inline bool set_probe(Slots slots, uint32_t log2, uint64_t empty, uint64_t x)
+{
+	const uint32_t mask = (1u << log2) - 1u;
+	uint32_t i = (uint32_t)mdb_set_slot_of(x, log2);
+	for (uint32_t step = 0; step <= mask; step++, i = (i + 1u) & mask) {
+		const uint64_t s = slots[i];
+		if (s == empty)
+			return false;
+		if (s == x)
+			return true;
+	}
+	return false;
+}
+
+/* the MDB_P_IN_SET step of the interpreters: okx = the cell is not NULL */
+__device__ static inline bool pred_in_set(const mdb_pred_insn &in, bool okx, uint64_t x)
+{
+	const uint64_t *const tab = reinterpret_cast<const uint64_t *>((uintptr_t)in.imm);
+	bool member = false;
+	if (okx && mdb_set_canonical(in.type, &x))
+		member = set_probe(tab + 2, (uint32_t)in.b, tab[0], x);
+	return okx && (member != (in.cmp != 0));
+}
+
 __device__ static inline bool pred_eval(const pred_args &p, uint64_t k)
 {
 	uint64_t st = 0;	/* boolean stack, top = bit 0 */
@@ -103,6 +130,12 @@ __device__ static inline bool pred_eval(const pred_args &p, uint64_t k)
 			const bool in_table = okx && (x >> 6) < (uint64_t)(uint32_t)in.b;
 			const bool hit = in_table && ((reinterpret_cast<const uint64_t *>((uintptr_t)in.imm)[x >> 6] >> (x & 63u)) & 1u);
 			b = okx && (hit != (in.cmp != 0));
+			st = (st << 1) | (uint64_t)b;
+			break;
+		}
+		case MDB_P_IN_SET: {
+			const bool okx = pred_load(p.cols[in.a], k, &x);
+			b = pred_in_set(in, okx, x);
 			st = (st << 1) | (uint64_t)b;
 			break;
 		}
@@ -195,6 +228,11 @@ __device__ static inline void pred_eval_pair(const pred_args &p, uint64_t k0, bo
 			b1 = okx[1] && (h1 != (in.cmp != 0));
 			break;
 		}
+		case MDB_P_IN_SET:
+			load(in.a, x, okx);
+			b0 = pred_in_set(in, okx[0], x[0]);
+			b1 = pred_in_set(in, okx[1], x[1]);
+			break;
 		case MDB_P_CONST:
 			b0 = b1 = in.imm != 0;
 			break;
@@ -686,7 +724,7 @@ __global__ __launch_bounds__(SP_THREADS, 4) void k_scan_project_cmp1(const int64
 /* The next commonest predicates - several comparisons of ONE INT64 base-table column with constants, all joined by AND
  * (ranges: fa >= 3 AND fa <= 900 AND fa <> 5) or all joined by OR (IN lists) - also without the interpreter: the column
  * is loaded once, the terms are evaluated in registers (uniform switch per term). */
-#define FILT_MAX_TERMS 8
+#define FILT_MAX_TERMS MDB_FILTER_MAX_TERMS
 struct filt_terms {
 	int32_t cmp[FILT_MAX_TERMS];
 	int64_t imm[FILT_MAX_TERMS];
@@ -786,6 +824,133 @@ __global__ __launch_bounds__(FILT_THREADS) void k_pred_bits_terms(const int64_t 
 	}
 	if (threadIdx.x == 0)
 		block_counts[bid] = s_cnt;
+}
+
+/* A program that is exactly ONE MDB_P_IN_SET over a base-table column (the pushed-down WHERE k IN (...), DELETE / UPDATE): the shape of
+ * k_pred_bits_terms - 16-byte loads of two rows, the wave's eight spans requested before the first is looked at, one ballot word per
+ * 64 rows, the same bitmap / block counts / fused tail - with the term list replaced by a hash probe.
+ *   LDS = true   the table (<= MDB_SET_LDS_SLOTS slots, 32 KiB) is copied into LDS once per workgroup.  The workgroups are persistent -
+ *                4 per CU (4 x 32.6 KiB of the CU's 160 KiB; 16 waves, 4 per SIMD: what 8-byte LDS reads need to reach their rate),
+ *                each walking row blocks until none is left - so the copy is paid once per workgroup, not once per 32 KiB of rows.
+ *                A probe is an 8-byte LDS read: 32 lanes per LDS cycle over 32 slot-wide bank pairs; hashed slots collide on a bank
+ *                pair about 3 deep in the worst lane group of a read, ~6 LDS cycles per 64 probes, far below the rate at which HBM
+ *                delivers 64 rows.  A probe that goes on to the next slot reads the neighbouring bank pair.
+ *   LDS = false  larger tables are probed where they lie (L2 / Infinity Cache).
+ * The first probe of all 16 rows of a lane is requested before any is judged; only rows whose first slot held another member go on.
+ * Row blocks come from the ticket counter in the single-pass form (every block a workgroup waits for was taken before its own, by
+ * a workgroup that is running), and strided by the grid otherwise. */
+struct filt_inset {
+	const uint64_t *tab;	/* the set image: marker, slot count, slots */
+	uint32_t log2;
+	int32_t negate;
+	int32_t type;
+	uint32_t nblocks;	/* row blocks of FILT_TUPLES_PER_BLOCK rows */
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(FILT_THREADS) void k_pred_bits_inset(const int64_t *__restrict__ vals, const uint64_t *__restrict__ nullbits,
+								  filt_inset s, uint64_t n, uint64_t *__restrict__ bits,
+								  uint32_t *__restrict__ block_counts, fp_fused fz)
+{
+	__shared__ __attribute__((aligned(16))) uint64_t s_tab[LDS ? MDB_SET_LDS_SLOTS : 2];
+	__shared__ uint32_t s_cnt, s_bid;
+	const uint64_t empty = s.tab[0];
+	const uint64_t *const gslots = s.tab + 2;
+	const uint32_t mask = (1u << s.log2) - 1u;
+	if (LDS) {
+		const uint32_t pairs = (mask + 1u) >> 1;	/* (uniform; <= MDB_SET_LDS_SLOTS / 2 by the launch's choice of LDS) */
+		for (uint32_t i = threadIdx.x; i < pairs && i < MDB_SET_LDS_SLOTS / 2; i += FILT_THREADS)
+			reinterpret_cast<ulonglong2 *>(s_tab)[i] = reinterpret_cast<const ulonglong2 *>(gslots)[i];
+	}
+	auto slot_at = [&](uint32_t i) -> uint64_t { return LDS ? s_tab[i] : gslots[i]; };
+	const uint32_t wave = threadIdx.x >> 6;
+	for (uint32_t it = 0;; it++) {
+		if (threadIdx.x == 0) {
+			s_cnt = 0;
+			s_bid = fz.state ? atomicAdd(fz.ticket, 1u) : blockIdx.x + it * gridDim.x;
+		}
+		__syncthreads();	/* (first turn: also the table copy) */
+		const uint32_t bid = s_bid;
+		if (bid >= s.nblocks)
+			break;		/* (uniform) */
+		const uint64_t word0 = (uint64_t)bid * FILT_WORDS_PER_BLOCK + (uint64_t)wave * FILT_WORDS_PER_WAVE;
+		constexpr int SPANS = FILT_WORDS_PER_WAVE / 2;
+		uint64_t x[SPANS][2], first[SPANS][2];
+		uint32_t at[SPANS][2], cnt = 0;
+#pragma unroll
+		for (int u = 0; u < SPANS; u++) {
+			const uint64_t k0 = ((word0 + 2 * u) << 6) + 2ull * mdb_lane();
+			ulonglong2 q = make_ulonglong2(0, 0);
+			if (k0 + 1 < n)
+				q = *reinterpret_cast<const ulonglong2 *>(vals + k0);
+			else if (k0 < n)
+				q.x = (uint64_t)vals[k0];
+			x[u][0] = q.x;
+			x[u][1] = q.y;
+		}
+#pragma unroll
+		for (int u = 0; u < SPANS; u++) {
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				uint64_t v = x[u][h];
+				if (s.type == MDB_T_DOUBLE && (v << 1) == 0)
+					v = 0;	/* -0.0 is looked up as +0.0; a NaN cell is settled below */
+				x[u][h] = v;
+				at[u][h] = (uint32_t)mdb_set_slot_of(v, s.log2);
+				first[u][h] = slot_at(at[u][h]);
+			}
+		}
+#pragma unroll
+		for (int u = 0; u < SPANS; u++) {
+			const uint64_t word = word0 + 2 * u;
+			const uint64_t k0 = (word << 6) + 2ull * mdb_lane();
+			bool pass[2];
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				const uint64_t v = x[u][h];
+				bool member = first[u][h] == v && v != empty;
+				if (!member && first[u][h] != empty) {	/* the first slot holds another member: go on, at most mask further steps */
+					uint32_t i = (at[u][h] + 1u) & mask;
+					for (uint32_t step = 0; step < mask; step++, i = (i + 1u) & mask) {
+						const uint64_t sl = slot_at(i);
+						if (sl == empty)
+							break;
+						if (sl == v) {
+							member = true;
+							break;
+						}
+					}
+				}
+				if (s.type == MDB_T_DOUBLE && (v << 1) > 0xFFE0000000000000ull)
+					member = false;	/* NaN: a member of nothing */
+				pass[h] = (k0 + h < n) && (member != (s.negate != 0));
+			}
+			if (nullbits && k0 < n) {
+				const uint64_t w = nullbits[k0 >> 6] >> (k0 & 63);
+				pass[0] = pass[0] && !(w & 1ull);
+				pass[1] = pass[1] && !(w & 2ull);
+			}
+			const uint64_t m0 = __ballot(pass[0]), m1 = __ballot(pass[1]);
+			if ((word << 6) < n) {
+				const uint64_t wa = filt_interleave32((uint32_t)m0, (uint32_t)m1);
+				const uint64_t wb = filt_interleave32((uint32_t)(m0 >> 32), (uint32_t)(m1 >> 32));
+				if (mdb_lane() == 0) {
+					bits[word] = wa;
+					if (((word + 1) << 6) < n)
+						bits[word + 1] = wb;
+				}
+				cnt += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
+			}
+		}
+		if (mdb_lane() == 0 && cnt)
+			atomicAdd(&s_cnt, cnt);
+		__syncthreads();
+		if (fz.state)
+			filt_fused_tail(fz, bid, s_cnt, bits, n);
+		else if (threadIdx.x == 0)
+			block_counts[bid] = s_cnt;
+		__syncthreads();	/* s_cnt, s_bid and the tail's offsets are rewritten in the next turn */
+	}
 }
 
 /* is the program "terms on ONE INT64 column, all ANDed or all ORed"?  (a NULL makes every term false - and with it both the
@@ -971,6 +1136,25 @@ static int filter_run(mdb_dev_ctx *ctx, int mode, const pred_args *p, int n_cols
 			case MDB_CMP_EQ: MDB_LAUNCH(ctx, "filter_pred_bits", k_pred_bits_cmp1<MDB_CMP_EQ>, nb, FILT_THREADS, v, nbits, i0.imm, n, bits, bc, fz); break;
 			case MDB_CMP_LE: MDB_LAUNCH(ctx, "filter_pred_bits", k_pred_bits_cmp1<MDB_CMP_LE>, nb, FILT_THREADS, v, nbits, i0.imm, n, bits, bc, fz); break;
 			default: MDB_LAUNCH(ctx, "filter_pred_bits", k_pred_bits_cmp1<MDB_CMP_GE>, nb, FILT_THREADS, v, nbits, i0.imm, n, bits, bc, fz); break;
+			}
+		} else if (direct && p->n_insns == 1 && i0.op == MDB_P_IN_SET) {
+			/* one set lookup over a base-table column; with `fuse` the same kernel goes on into the fused tail (the bitmap form of
+			 * the single pass: the one-pass scan_project_body keeps 16384 rows in registers and has no LDS left for a table) */
+			const int64_t *v = (const int64_t *)p->cols[i0.a].values;
+			const uint64_t *nbits = p->cols[i0.a].nullbits;
+			filt_inset si;
+			si.tab = reinterpret_cast<const uint64_t *>((uintptr_t)i0.imm);
+			si.log2 = (uint32_t)i0.b;
+			si.negate = i0.cmp != 0;
+			si.type = i0.type;
+			si.nblocks = filt_blocks(n);
+			const bool in_lds = ((uint64_t)1 << si.log2) <= MDB_SET_LDS_SLOTS;
+			const uint32_t resident = (uint32_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 4u;	/* persistent workgroups: 4 per CU, by LDS and by registers */
+			const uint32_t grid = si.nblocks < resident ? si.nblocks : resident;
+			if (in_lds) {
+				MDB_LAUNCH(ctx, "filter_in_set", k_pred_bits_inset<true>, grid, FILT_THREADS, v, nbits, si, n, bits, bc, fz);
+			} else {
+				MDB_LAUNCH(ctx, "filter_in_set", k_pred_bits_inset<false>, grid, FILT_THREADS, v, nbits, si, n, bits, bc, fz);
 			}
 		} else if (filt_terms ft; fuse && direct && filter_one_column_terms(p, &ft, &tslot, &tor)) {
 			/* ranges / IN lists over one column: the same single pass */
@@ -1176,8 +1360,19 @@ static int filter_prepare(mdb_dev_ctx *ctx, const struct mdb_pred_insn *prog, in
 		case MDB_P_CMP_CONST_COL:
 		case MDB_P_ISNULL:
 		case MDB_P_IN_BITS:
+		case MDB_P_IN_SET:
 			if (in.op == MDB_P_IN_BITS && (!in.imm || in.b < 0))
 				return mdb_set_err(ctx, -MIDORIDB_ERROR, "filter: a bit-table test without a table");
+			if (in.op == MDB_P_IN_SET) {
+				if (!in.imm || ((uintptr_t)in.imm & 15))
+					return mdb_set_err(ctx, -MIDORIDB_ERROR, "filter: a set test without a (16-byte aligned) table");
+				if (in.b < MDB_SET_MIN_LOG2 || in.b > MDB_SET_MAX_LOG2 || (in.type != MDB_T_INT64 && in.type != MDB_T_DOUBLE))
+					return mdb_set_err(ctx, -MIDORIDB_ERROR, "filter: a set test with a slot count of 2^%d or an unknown value type", in.b);
+				/* a table from the library's allocator must hold the image that the size field promises */
+				const size_t have = mdb_dev_alloc_size(ctx, (const void *)(uintptr_t)in.imm);
+				if (have && have < ((size_t)2 + ((size_t)1 << in.b)) * 8)
+					return mdb_set_err(ctx, -MIDORIDB_ERROR, "filter: a set test whose table is smaller than its 2^%d slots", in.b);
+			}
 			if (in.a < 0 || in.a >= n_cols)
 				return mdb_set_err(ctx, -MIDORIDB_ERROR, "filter: bad column slot");
 			depth++;
@@ -1208,4 +1403,79 @@ static int filter_prepare(mdb_dev_ctx *ctx, const struct mdb_pred_insn *prog, in
 		memcpy(p.cols, cols, sizeof(mdb_col_binding) * (size_t)n_cols);
 	p.n_insns = n_insns;
 	return MIDORIDB_OK;
+}
+
+/* ------------------------------------------------------------------ device sets (MDB_P_IN_SET) */
+
+struct mdb_dev_set {
+	void *d_words;		/* the image (mdb_dev.h) in a buffer of mdb_dev_alloc */
+	uint64_t slots, members;
+	uint32_t log2_slots;
+	int32_t type;
+};
+
+extern "C" uint64_t mdb_dev_in_set_lds_values(void)
+{
+	return MDB_SET_LDS_SLOTS / 2;
+}
+
+extern "C" int mdb_dev_set_create(mdb_dev_ctx *ctx, const int64_t *host_values, uint64_t n, int type, mdb_dev_set **set)
+{
+	if (!ctx || !set || (n && !host_values))
+		return ctx ? mdb_set_err(ctx, -MIDORIDB_ERROR, "set_create: no values or no place for the set") : -MIDORIDB_ERROR;
+	*set = NULL;
+	if (n > MDB_SET_MAX_VALUES)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "set_create: %llu values, a set takes at most %llu", (unsigned long long)n,
+				   (unsigned long long)MDB_SET_MAX_VALUES);
+	if (type != MDB_T_INT64 && type != MDB_T_DOUBLE)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "set_create: unknown value type %d", type);
+	struct mdb_set_image img;
+	int rc = mdb_set_build(host_values, n, type, &img);
+	if (rc)
+		return mdb_set_err(ctx, rc, "set_create: building the table of %llu values failed", (unsigned long long)n);
+	mdb_dev_set *s = (mdb_dev_set *)calloc(1, sizeof(*s));
+	if (!s) {
+		mdb_set_image_free(&img);
+		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "set_create: out of memory");
+	}
+	const size_t bytes = (size_t)(2 + img.slots) * 8;
+	rc = mdb_dev_alloc(ctx, bytes, &s->d_words);
+	if (!rc)
+		rc = mdb_dev_h2d(ctx, s->d_words, img.words, bytes);
+	s->slots = img.slots;
+	s->members = img.members;
+	s->log2_slots = img.log2_slots;
+	s->type = type;
+	mdb_set_image_free(&img);
+	if (rc) {
+		if (s->d_words)
+			mdb_dev_free(ctx, s->d_words);
+		free(s);
+		return rc;
+	}
+	*set = s;
+	return MIDORIDB_OK;
+}
+
+extern "C" int mdb_dev_set_insn(const mdb_dev_set *set, int slot, int negate, struct mdb_pred_insn *insn)
+{
+	if (!set || !insn || slot < 0 || slot >= MDB_PRED_MAX_SLOTS)
+		return -MIDORIDB_ERROR;
+	memset(insn, 0, sizeof(*insn));
+	insn->op = MDB_P_IN_SET;
+	insn->cmp = negate ? 1 : 0;
+	insn->type = set->type;
+	insn->a = slot;
+	insn->b = (int32_t)set->log2_slots;
+	insn->imm = (int64_t)(uintptr_t)set->d_words;
+	return MIDORIDB_OK;
+}
+
+extern "C" int mdb_dev_set_free(mdb_dev_ctx *ctx, mdb_dev_set *set)
+{
+	if (!set)
+		return MIDORIDB_OK;
+	int rc = set->d_words ? mdb_dev_free(ctx, set->d_words) : MIDORIDB_OK;
+	free(set);
+	return rc;
 }

@@ -265,8 +265,7 @@ int table_filter(struct exec *x, int t, const struct mdb_expr *const *conj, int 
 		for (int i = 0; i < nconj; i++)
 			if (pred_compile(x, &p, conj[i]) || (i && pred_emit(&p, MDB_P_AND, 0, 0, 0, 0, 0))) {
 				x->rid[t] = saved;
-				snprintf(x->err, x->errlen, "execution phase: predicate too large for the device program (max %d steps, %d columns)\n",
-					 MDB_PRED_MAX_INSNS, MDB_PRED_MAX_SLOTS);
+				pred_compile_failed(x);
 				return -MIDORIDB_ERROR;
 			}
 		x->rid[t] = saved;
@@ -985,8 +984,7 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 		memset(&p, 0, sizeof(p));
 		for (int i = 0; i < nresid && !rc; i++)
 			if (pred_compile(x, &p, resid[i]) || (i && pred_emit(&p, MDB_P_AND, 0, 0, 0, 0, 0))) {
-				snprintf(x->err, x->errlen, "execution phase: predicate too large for the device program (max %d steps, %d columns)\n",
-					 MDB_PRED_MAX_INSNS, MDB_PRED_MAX_SLOTS);
+				pred_compile_failed(x);
 				rc = -MIDORIDB_ERROR;
 			}
 		sel = rc ? NULL : dalloc(x, J * 4);
@@ -1783,8 +1781,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 		memset(&p, 0, sizeof(p));
 		for (int i = 0; i < ws.npush[0]; i++)
 			if (pred_compile(&x, &p, ws.push[0][i]) || (i && pred_emit(&p, MDB_P_AND, 0, 0, 0, 0, 0))) {
-				ERR("execution phase: predicate too large for the device program (max %d steps, %d columns)\n", MDB_PRED_MAX_INSNS,
-				    MDB_PRED_MAX_SLOTS);
+				pred_compile_failed(&x);
 				rc = -MIDORIDB_ERROR;
 				goto out;
 			}

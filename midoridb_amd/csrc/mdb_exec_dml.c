@@ -270,8 +270,7 @@ int dml_select_rows(struct mdb_catalog *cat, struct mdb_dml *d, struct exec *x, 
 		memset(&p, 0, sizeof(p));
 		if (pred_compile(x, &p, d->where) ||
 		    (complement && (pred_emit(&p, MDB_P_CONST, 0, 0, 0, 0, 1) || pred_emit(&p, MDB_P_XOR, 0, 0, 0, 0, 0)))) {
-			ERR("execution phase: predicate too large for the device program (max %d steps, %d columns)\n", MDB_PRED_MAX_INSNS,
-			    MDB_PRED_MAX_SLOTS);
+			pred_compile_failed(x);
 			return -MIDORIDB_ERROR;
 		}
 		v = dalloc(x, t->nrows * 4);

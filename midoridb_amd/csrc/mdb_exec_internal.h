@@ -65,6 +65,7 @@ struct exec {
 	/* LEFT / RIGHT OUTER JOIN: rid[t] may hold MDB_NO_ROW (table t is the NULL-supplied side of a join that left rows without partner) -
 	 * every column of t read through rid[t] needs a NULL bitmap of its own, whether or not the column has one */
 	bool may_be_absent[MDB_MAX_TABS];
+	bool pred_err_said;			/* pred_compile() failed for a cause it has written into err itself (pred_compile_failed keeps it) */
 	bool has_outer;				/* some join of the statement is an outer join: no plan that assumes inner semantics */
 };
 
@@ -125,6 +126,7 @@ int pred_emit(struct pred_prog *p, int op, int cmp, int type, int a, int b, int6
 int64_t lit_bits_for(const struct mdb_expr *v, int coltype);
 bool const_cmp(int op, const struct mdb_expr *l, const struct mdb_expr *r);
 int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e);
+void pred_compile_failed(struct exec *x);
 int stream_filter(struct exec *x, int ntabs_in_stream, const struct mdb_expr *e);
 void collect_conjuncts(struct mdb_expr *e, struct mdb_expr **out, int *n, int cap);
 uint64_t expr_tables(const struct mdb_expr *e);

@@ -118,6 +118,91 @@ static bool like_match(const char *s, size_t n, const char *pat, size_t m)
 	return j == m;
 }
 
+/* An IN / NOT IN list of more values than the term kernels take (MDB_FILTER_MAX_TERMS, mdb_dev.h) compiles to ONE lookup
+ * instead of one comparison and one OR / AND per value, which MDB_PRED_MAX_INSNS ends at 32 values:
+ *   VARCHAR columns    MDB_P_IN_BITS over a bit per dictionary id, as LIKE builds it (a string no cell holds has id -1: no bit)
+ *   every other type   MDB_P_IN_SET over a hash table of the non-NULL literals (mdb_set.c), uploaded into a statement buffer
+ * A NULL literal keeps its meaning: in IN it adds nothing, in NOT IN it makes the test false for every row (x <> NULL is never true).
+ * A list without effective members: IN is false, NOT IN is `x IS NOT NULL`.  Shorter lists compile exactly as before.
+ * MDB_IN_SET=0 expands every list as before. */
+
+/* a lookup table could not be built or uploaded: the statement's error says so (pred_compile_failed leaves it standing) */
+static int lookup_failed(struct exec *x, const char *what, size_t bytes)
+{
+	snprintf(x->err, x->errlen, "execution phase: IN list: %s (%zu bytes): %s\n", what, bytes, x->dev ? mdb_dev_last_error(x->dev) : "");
+	x->pred_err_said = true;
+	return -1;
+}
+
+/* what a failed pred_compile() leaves in the statement's error: the program's limits, unless the compiler has named another cause */
+void pred_compile_failed(struct exec *x)
+{
+	if (!x->pred_err_said)
+		snprintf(x->err, x->errlen, "execution phase: predicate too large for the device program (max %d steps, %d columns)\n",
+			 MDB_PRED_MAX_INSNS, MDB_PRED_MAX_SLOTS);
+	x->pred_err_said = false;
+}
+
+static int pred_compile_in_lookup(struct exec *x, struct pred_prog *p, const struct mdb_expr *e, int a)
+{
+	const struct mdb_expr *f = e->kids[0];
+	const int neg = e->op ? 1 : 0, k = e->nkids - 1;
+	int rc = -1;
+
+	for (int i = 1; neg && i <= k; i++)
+		if (e->kids[i]->kind == MDB_EX_NULL)
+			return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
+	if (f->type == MDB_CT_VARCHAR) {
+		const struct mdb_strdict *d = stmt_dict;
+		const uint64_t words = ((d ? d->n : 0) + 1 + 63) / 64;
+		uint64_t *bits = calloc((size_t)words, 8);
+		void *dbits;
+		if (!bits)
+			return lookup_failed(x, "no host memory for the dictionary bits", (size_t)words * 8);
+		for (int i = 1; i <= k; i++) {
+			const int64_t id = e->kids[i]->kind == MDB_EX_NULL ? -1 : lit_bits_for(e->kids[i], f->type);
+			if (id >= 0 && (uint64_t)id < words * 64)
+				bits[id >> 6] |= 1ull << (id & 63);
+		}
+		dbits = dalloc(x, (size_t)words * 8);
+		if (dbits && !mdb_dev_h2d(x->dev, dbits, bits, (size_t)words * 8))
+			rc = pred_emit(p, MDB_P_IN_BITS, neg, MDB_T_INT64, a, (int)(words > 0x7FFFFFFF ? 0x7FFFFFFF : words), (int64_t)(uintptr_t)dbits);
+		else
+			(void)lookup_failed(x, "the dictionary bits could not be placed on the device", (size_t)words * 8);
+		free(bits);
+	} else {
+		const int type = f->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+		int64_t *vals = malloc(sizeof(int64_t) * (size_t)k);
+		struct mdb_set_image img;
+		uint64_t n = 0;
+		if (!vals)
+			return lookup_failed(x, "no host memory for the values", sizeof(int64_t) * (size_t)k);
+		for (int i = 1; i <= k; i++)
+			if (e->kids[i]->kind != MDB_EX_NULL)
+				vals[n++] = lit_bits_for(e->kids[i], f->type);
+		if (mdb_set_build(vals, n, type, &img)) {
+			free(vals);
+			return lookup_failed(x, n > MDB_SET_MAX_VALUES ? "more values than a set takes" : "no host memory for the set", (size_t)n * 8);
+		}
+		free(vals);
+		if (!img.members) {	/* (NaN literals only) */
+			mdb_set_image_free(&img);
+			return neg ? pred_emit(p, MDB_P_ISNULL, 1, 0, a, 0, 0) : pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
+		} else {
+			const size_t bytes = (size_t)(2 + img.slots) * 8;
+			void *dtab = dalloc(x, bytes);
+			if (dtab && !mdb_dev_h2d(x->dev, dtab, img.words, bytes))
+				rc = pred_emit(p, MDB_P_IN_SET, neg, type, a, (int)img.log2_slots, (int64_t)(uintptr_t)dtab);
+			else
+				(void)lookup_failed(x, "the set could not be placed on the device", bytes);
+		}
+		mdb_set_image_free(&img);
+	}
+	if (!rc && x->cat)
+		x->cat->in_set_lookups++;
+	return rc;
+}
+
 int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 {
 	int rc = 0, a, b;
@@ -169,6 +254,8 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 		a = pred_slot(x, p, f);
 		if (a < 0)
 			return -1;
+		if (e->nkids - 1 > MDB_FILTER_MAX_TERMS && !mdb_knob_off("MDB_IN_SET"))
+			return pred_compile_in_lookup(x, p, e, a);
 		for (int i = 1; i < e->nkids; i++) {
 			const struct mdb_expr *v = e->kids[i];
 			if (v->kind == MDB_EX_NULL)
@@ -223,8 +310,7 @@ int stream_filter(struct exec *x, int ntabs_in_stream, const struct mdb_expr *e)
 		return MIDORIDB_OK;
 	memset(&p, 0, sizeof(p));
 	if (pred_compile(x, &p, e)) {
-		snprintf(x->err, x->errlen, "execution phase: predicate too large for the device program (max %d steps, %d columns)\n",
-			 MDB_PRED_MAX_INSNS, MDB_PRED_MAX_SLOTS);
+		pred_compile_failed(x);
 		return -MIDORIDB_ERROR;
 	}
 	sel = dalloc(x, x->n * 4);

@@ -322,6 +322,12 @@ unsigned long long mdb_database_composite_fused(struct database *db)
 	return cat ? cat->composite_fused : 0ull;
 }
 
+unsigned long long mdb_database_in_set_lookups(struct database *db)
+{
+	struct mdb_catalog *cat = db ? db->tables : NULL;
+	return cat ? cat->in_set_lookups : 0ull;
+}
+
 double query_exec_ms(struct result_set *res)
 {
 	return res && res->table ? ((struct mdb_result *)res->table)->exec_ms : 0.0;

@@ -18,6 +18,7 @@ MDB_COUNTS_OPTIONAL = 4
 
 # predicate opcodes / comparison codes / value types (include/mdb_dev.h)
 P_CMP_COL_CONST, P_CMP_CONST_COL, P_CMP_COL_COL, P_ISNULL, P_CONST, P_AND, P_OR, P_XOR = 1, 2, 3, 4, 5, 6, 7, 8
+P_IN_BITS, P_IN_SET = 9, 10
 CMP_LT, CMP_GT, CMP_NE, CMP_EQ, CMP_LE, CMP_GE = 1, 2, 3, 4, 5, 6
 T_INT64, T_DOUBLE = 0, 1
 
@@ -25,6 +26,12 @@ T_INT64, T_DOUBLE = 0, 1
 class PredInsn(ctypes.Structure):
     _fields_ = [("op", c_int32), ("cmp", c_int32), ("type", c_int32), ("a", c_int32), ("b", c_int32),
                 ("pad", c_int32), ("imm", c_int64)]
+
+
+class SetImage(ctypes.Structure):
+    """struct mdb_set_image: the host image of a device set (include/mdb_dev.h)"""
+    _fields_ = [("words", POINTER(c_uint64)), ("slots", c_uint64), ("members", c_uint64), ("empty", c_uint64), ("longest_run", c_uint64),
+                ("log2_slots", c_uint32), ("type", c_int32)]
 
 
 class ColBinding(ctypes.Structure):
@@ -240,6 +247,13 @@ def _bind(lib):
         "mdb_dev_join_group_count_multi": ([P, P, P, c_uint64, c_int, POINTER(P), POINTER(P), POINTER(c_uint64), c_uint32, P, P, P, c_uint64,
                                             POINTER(c_uint64), POINTER(c_uint64)], c_int),
         "mdb_dev_gen_payload": ([P, P, c_uint64, c_uint64, c_uint64, c_int], c_int),
+        "mdb_set_build": ([P, c_uint64, c_int, POINTER(SetImage)], c_int),
+        "mdb_set_image_free": ([POINTER(SetImage)], None),
+        "mdb_set_image_contains": ([POINTER(SetImage), c_int64], c_int),
+        "mdb_dev_set_create": ([P, P, c_uint64, c_int, POINTER(P)], c_int),
+        "mdb_dev_set_insn": ([P, c_int, c_int, POINTER(PredInsn)], c_int),
+        "mdb_dev_set_free": ([P, P], c_int),
+        "mdb_dev_in_set_lds_values": ([], c_uint64),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -256,6 +270,7 @@ DEV_SYMBOLS = [
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
+    "mdb_set_build", "mdb_set_image_free", "mdb_set_image_contains", "mdb_dev_set_create", "mdb_dev_set_insn", "mdb_dev_set_free", "mdb_dev_in_set_lds_values",
 ]
 
 
@@ -303,6 +318,33 @@ class _LibBuffer:
         except Exception:
             pass
         self._ptr = 0
+
+
+class DeviceSet:
+    """A set in device memory (mdb_dev_set); released with the object or by close()."""
+
+    def __init__(self, ctx, values, typ=T_INT64):
+        a = np.ascontiguousarray(values, dtype=np.float64 if typ == T_DOUBLE else np.int64).view(np.int64)
+        self._ctx, self.type, self.h = ctx, typ, c_void_p()
+        ctx._chk(ctx.lib.mdb_dev_set_create(ctx.h, c_void_p(a.ctypes.data) if a.size else None, a.size, typ, byref(self.h)), "set_create")
+
+    def insn(self, slot, negate=False):
+        """(op, cmp, type, a, b, imm) testing column slot `slot` against the set"""
+        i = PredInsn()
+        if self._ctx.lib.mdb_dev_set_insn(self.h, slot, 1 if negate else 0, byref(i)) != 0:
+            raise DeviceError("mdb_dev_set_insn failed")
+        return (i.op, i.cmp, i.type, i.a, i.b, i.imm)
+
+    def close(self):
+        if getattr(self, "h", None) and self._ctx.h:
+            self._ctx.lib.mdb_dev_set_free(self._ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceCtx:
@@ -744,6 +786,15 @@ class DeviceCtx:
         cnt = c_uint64()
         self._chk(self.lib.mdb_dev_filter(self.h, insns, len(prog), binds, len(cols), n, _ptr(sel), byref(cnt)), "filter")
         return sel[:cnt.value]
+
+    def make_set(self, values, typ=T_INT64):
+        """a device set of the given values (int64, or float64 with typ=T_DOUBLE) for P_IN_SET (mdb_dev_set_create) -> DeviceSet: it keeps
+        the table alive, and .insn(slot, negate=False) is the instruction tuple for filter() / filter_project()"""
+        return DeviceSet(self, values, typ)
+
+    def in_set_lds_values(self):
+        """the largest list the one-instruction set kernel stages in LDS (mdb_dev_in_set_lds_values)"""
+        return int(self.lib.mdb_dev_in_set_lds_values())
 
     def gather64(self, src, src_null, idx, n, dst_nulls=False):
         """dst_nulls: write NULL bits also for a source without a bitmap (idx may hold NO_ROW)"""

@@ -41,7 +41,7 @@ QUERY_SYMBOLS = [
     "mdb_query_execute_rpn", "query_column_double", "query_column_is_null", "query_column_count", "query_column_name",
     "query_column_type", "query_row_count", "query_column_data", "query_exec_ms", "query_joined_rows",
     "mdb_table_append_columns", "mdb_table_generate", "mdb_sql_to_rpn", "query_column_text", "mdb_result_text_at",
-    "mdb_database_device", "mdb_database_set_dist", "mdb_database_results_on_device", "mdb_database_groups_any_order", "mdb_database_joins_eliminated", "mdb_database_composite_joins", "mdb_database_composite_fused", "query_column_data_device", "query_column_nulls_device", "mdb_table_generate_shard",
+    "mdb_database_device", "mdb_database_set_dist", "mdb_database_results_on_device", "mdb_database_groups_any_order", "mdb_database_joins_eliminated", "mdb_database_composite_joins", "mdb_database_composite_fused", "mdb_database_in_set_lookups", "query_column_data_device", "query_column_nulls_device", "mdb_table_generate_shard",
 ]
 
 
@@ -103,6 +103,8 @@ def _bind(lib):
     lib.mdb_database_composite_joins.restype = ctypes.c_ulonglong
     lib.mdb_database_composite_fused.argtypes = [PDB]
     lib.mdb_database_composite_fused.restype = ctypes.c_ulonglong
+    lib.mdb_database_in_set_lookups.argtypes = [PDB]
+    lib.mdb_database_in_set_lookups.restype = ctypes.c_ulonglong
     lib.query_column_data_device.argtypes = [PRS, c_int]
     lib.query_column_data_device.restype = c_void_p
     lib.query_column_nulls_device.argtypes = [PRS, c_int]
@@ -193,6 +195,11 @@ class DB:
         """SELECT statements of this database so far that the fused join + GROUP BY operator answered on a packed composite key
         (mdb_database_composite_fused); composite_joins() does not rise for them"""
         return int(self.lib.mdb_database_composite_fused(ctypes.byref(self.db)))
+
+    def in_set_lookups(self):
+        """IN / NOT IN lists of this database's statements so far that were compiled to one device lookup - lists of more than 8
+        values (mdb_database_in_set_lookups)"""
+        return int(self.lib.mdb_database_in_set_lookups(ctypes.byref(self.db)))
 
     def results_on_device(self, on=True):
         """SELECT results stay in HBM until a consumer reads them (mdb_database_results_on_device)"""
