@@ -498,7 +498,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 	    mdb_knob_off("MDB_GROUP_BANDED"))
 		return 1;
 	/* the regions overflowed on this very column last time (a hot key): not tried again for a while */
-	if (ctx->ex_keys == keys && ctx->ex_nl == n && ctx->ex_nr == 0 && ctx->ex_uses < GC_HINT_USES)
+	if (ctx->vd[VD_EXACT].holds(keys, n, NULL, 0))
 		return 1;
 	const uint32_t dbits = bg_dbits(kbits), sbits = kbits - dbits, D = 1u << dbits;
 	if (sbits > 14u)
@@ -667,10 +667,7 @@ int mdb_group_count_banded(mdb_dev_ctx *ctx, const int64_t *keys, uint64_t n, in
 		return 1;
 	}
 	if (status & MDB_ST_REGION_FULL) {	/* a region overflowed: the caller's other forms; remembered for this column */
-		ctx->ex_keys = keys;
-		ctx->ex_nl = n;
-		ctx->ex_nr = 0;
-		ctx->ex_uses = 0;
+		ctx->vd[VD_EXACT].note(keys, n, NULL, 0);
 		return 1;
 	}
 	if (status & MDB_ST_LIST_FULL)

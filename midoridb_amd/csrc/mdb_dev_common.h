@@ -13,6 +13,7 @@
 #include <string>
 #include <unordered_map>
 #include "mdb_dev.h"
+#include "mdb_dev_memo.h"
 
 #define MDB_WAVE 64
 
@@ -21,80 +22,8 @@ struct mdb_prof_rec {
 	hipEvent_t start, stop;
 };
 
-/* What the join / GROUP BY operators remember about key columns (sampled ranges, key forms, duplicate flags, layouts that
- * overflowed): verdicts keyed by the columns' device addresses and lengths, each verified on the device when it is used - a
- * stale one costs a failed attempt, never a result.  The live set belongs to ONE pair of key columns (memo_key); the context
- * keeps the sets of the last MDB_MEMO_SLOTS pairs (mdb_memo_switch, mdb_dev_core.hip), so queries that alternate over several
- * table pairs do not evict each other's verdicts and pay the key sample + its host sync on every call. */
-struct mdb_col_memo {
-	/* outcome of the last narrow-form decision, keyed by the key columns it was made for: a repeated query over the same
-	 * columns skips the sampling kernel and its sync (every key is still verified while it is partitioned) */
-	const void *nh_kl, *nh_kr;
-	uint64_t nh_nl, nh_nr;
-	int nh_result;			/* -1 nothing remembered, 0 wide, 1 narrow */
-	int64_t nh_base;		/* the window centre that went with "narrow" */
-	uint32_t nh_kbits;		/* ... and the compact window the sample offered (0 = none): [nh_lo, nh_lo + 2^nh_kbits) */
-	int64_t nh_lo;
-	bool nh_r_based;		/* ... and the compact window was taken from the right table's keys alone */
-	int64_t sr_rlo, sr_rhi;		/* the right table's sampled extremes (last sample) */
-	bool nh_prunable;		/* ... or at least not all of it (min-max pruning worth recording the right table's range) */
-	bool nh_by_span;		/* ... because its sampled SPAN is small (min-max pruning does the work, no bitmap) */
-	bool nh_selective;		/* ... and whether the right table looked like it covers a small part of the left table's keys */
-	uint64_t sr_span_l, sr_span_r;	/* spans of the two tables' sampled keys (last sample) */
-	/* range of the last key sample (smallest / largest of 2 x 4096 evenly spaced keys), by the columns it was taken from */
-	const void *sr_kl, *sr_kr;
-	uint64_t sr_nl, sr_nr;
-	int64_t sr_lo, sr_hi;
-	int sr_valid;
-	const void *gh_keys;		/* distinct values among the sampled keys of a column (group_hashed_try) */
-	uint64_t gh_n;
-	uint32_t gh_distinct;
-	int gh_uses;
-	int sr_uses, nh_uses;		/* remembered verdicts expire after a few uses: the same buffer may hold other data by then */
-	int nh_distrust;		/* > 0: a remembered "narrow" just proved wrong (buffer reused for other data): sample again for a while */
-	const void *ex_keys;		/* left key column (and the two row counts) whose histogram-free partition layout overflowed last time: */
-	uint64_t ex_nl, ex_nr;		/* the exact layout at once, for a few uses (a failed attempt costs a whole partition pass) */
-	int ex_uses;
-	const void *pw_bad_keys;	/* right key column (and row count) the one-level unique-key join (join_pairs_unique_wide) gave up on */
-	uint64_t pw_bad_n;
-	const void *jk_dup_l, *jk_dup_r;	/* key columns whose join had COUNTs above 1 (mdb_dev_join_keys asks for the COUNT column at once) */
-	uint64_t jk_dup_nl, jk_dup_nr;
-	int jk_dup_uses;
-	const void *jp_bad_l, *jp_bad_r;	/* key columns mdb_dev_join_payload found not to be an every-left-row-has-its-partner join */
-	uint64_t jp_bad_nl, jp_bad_nr;
-	int jp_bad_skips;
-	const void *pu_dup_keys;	/* right key column that the unique-key join found duplicates in (not tried again) */
-	uint64_t pu_dup_n;
-	const void *pu_dupl_keys;	/* ... and the left key column that did (both: a true N:M join, the general path) */
-	uint64_t pu_dupl_n;
-	int pu_dup_skips;
-	bool r32_ok;			/* the last join over (r32_kl, r32_nl, r32_kr, r32_nr) fitted every COUNT(*) into a 4-byte group record */
-	const void *r32_kl, *r32_kr;
-	uint64_t r32_nl, r32_nr;
-	const void *lw_bad_keys;	/* the left key column (and the two row counts) for which a 16-bit row count of the one-level direct leaves */
-	uint64_t lw_bad_nl, lw_bad_nr;	/* (k_leaf_wide) overflowed last: two levels for these columns */
-	const void *l4_bad_keys;	/* ... and the one for which k_leaf_wide4's 5-bit / 4-bit counts did (more than 31 right or 15 left rows of a key): */
-	uint64_t l4_bad_nl, l4_bad_nr;	/* k_leaf_wide's 16-bit counts at once */
-	int lw_bad_uses, l4_bad_uses;	/* both verdicts serve MDB_BAD_LEAF_USES calls, then the fast form is tried again: the columns go by address and length,
-					 * and a caller's allocator hands the same addresses out for other data */
-	int keyed_distrust;		/* > 0: a COUNT(*) did not fit a keyed group record lately - plain records for the next operators */
-	const void *lg_kl, *lg_kr;	/* the last join over (lg_kl, lg_nl, lg_kr, lg_nr) delivered lg_groups groups: when that is under a quarter of the */
-	uint64_t lg_nl, lg_nr, lg_groups;	/* left rows, most left rows find no partner whatever the tables' sizes and ranges say (a right table */
-	bool lg_valid;			/* of few distinct keys spread over the left table's range): the next join filters them early */
-	uint32_t lg_nextra;		/* (further right tables of that join: the three-table operator remembers too) */
-	uint64_t lg_joined;		/* ... and lg_joined joined rows: nearly every left row a group of COUNT 1 -> the groups as one bit per row (k_leaf_wide12) */
-	int dn_distrust;		/* calls for which that form is not tried (its exception list overflowed) */
-};
-
-#define MDB_MEMO_SLOTS 8
-#define MDB_BAD_LEAF_USES 32
-struct mdb_memo_key {
-	const void *kl, *kr;
-	uint64_t nl, nr;
-	bool operator==(const mdb_memo_key &o) const { return kl == o.kl && kr == o.kr && nl == o.nl && nr == o.nr; }
-};
-
-struct mdb_dev_ctx : mdb_col_memo {
+/* (the base: what the operators remember about key columns, mdb_dev_memo.h) */
+struct mdb_dev_ctx : mdb_memo_store {
 	int device;
 	int num_cus;			/* compute units of the device (256 on MI355X) */
 	hipStream_t stream;		/* stream every operator launches on */
@@ -121,8 +50,6 @@ struct mdb_dev_ctx : mdb_col_memo {
 	/* mdb_dev_explain_*(): the operator's own decision code runs and stops in front of its first launch (a context without a device) */
 	bool explaining;
 	bool explain_as_sample;		/* ... as if the statistics were what a key sample found: the forms only a catalog's promise opens are not taken */
-	mdb_memo_key memo_key;		/* the key-column pair the live mdb_col_memo belongs to */
-	std::vector<std::pair<mdb_memo_key, mdb_col_memo>> memo_lru;	/* the other pairs' sets, most recently used last */
 	/* mdb_dev_alloc / mdb_dev_free recycle buffers (stream-ordered reuse on the context's stream): a query
 	 * allocates dozens of temporaries and hipMalloc/hipFree cost 0.1-0.3 ms each */
 	std::unordered_map<void *, size_t> live;		/* buffers handed out -> size */
@@ -180,10 +107,6 @@ static inline void mdb_explain_sampled(mdb_dev_ctx *ctx)
 		ctx->plan.samples = 1;
 	}
 }
-
-/* make the live memo the one of the key-column pair (kl, nl, kr, nr) - kr = NULL for a one-column operator (GROUP BY): the set
- * of the pair used before is put aside, the pair's own set (or an empty one) comes back (mdb_dev_core.hip) */
-void mdb_memo_switch(mdb_dev_ctx *ctx, const void *kl, uint64_t nl, const void *kr, uint64_t nr);
 
 #define MDB_HIP(ctx, call)                                                                         \
 	do {                                                                                       \

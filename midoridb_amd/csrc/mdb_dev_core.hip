@@ -30,13 +30,6 @@ extern "C" int mdb_dev_device_count(void)
 	return n;
 }
 
-
-static void memo_reset(mdb_col_memo &m)
-{
-	memset(&m, 0, sizeof(m));	/* (plain data: pointers, counters, flags) */
-	m.nh_result = -1;
-}
-
 extern "C" int mdb_dev_ctx_create(int device, void *stream, mdb_dev_ctx **out)
 {
 	if (!out)
@@ -77,8 +70,6 @@ extern "C" int mdb_dev_ctx_create(int device, void *stream, mdb_dev_ctx **out)
 	ctx->pending_op = NULL;
 	ctx->cache_bytes = 0;
 	ctx->narrow_mode = 1;
-	memo_reset(*ctx);
-	ctx->memo_key = mdb_memo_key{ NULL, NULL, 0, 0 };
 	{
 		char e[3];	/* whole-suite soaks: force one form (see mdb_dev_set_narrow_keys) */
 		if (mdb_knob_str("MDB_NARROW_KEYS", e, sizeof(e)) && e[0] >= '0' && e[0] <= '2' && !e[1])
@@ -339,87 +330,6 @@ int mdb_cached_alloc(mdb_dev_ctx *ctx, size_t bytes, void **dptr)
 	return MIDORIDB_OK;
 }
 
-/* What the operators remember about a key column - sampled ranges, narrow-form verdicts, duplicate flags ... - is keyed by
- * the column's ADDRESS and length.  A buffer that is released (its address will be handed out again), or written to
- * through the library (UPDATE: mdb_dev_scatter_set64; an upload into an existing buffer), takes what was learned about it
- * along: the next operator over that address samples afresh instead of trusting a verdict about other data (results never
- * depended on it - every verdict is verified on the device - but a wrong one costs a failed attempt, for up to 8 uses). */
-static void memo_drop(mdb_col_memo &m, uintptr_t a, uintptr_t b)
-{
-	auto hit = [a, b](const void *p) { return p && (uintptr_t)p >= a && (uintptr_t)p < b; };
-	if (hit(m.nh_kl) || hit(m.nh_kr))
-		m.nh_result = -1;
-	if (hit(m.sr_kl) || hit(m.sr_kr))
-		m.sr_valid = 0;
-	if (hit(m.gh_keys))
-		m.gh_keys = NULL;
-	if (hit(m.ex_keys))
-		m.ex_keys = NULL;
-	if (hit(m.pw_bad_keys))
-		m.pw_bad_keys = NULL;
-	if (hit(m.pu_dup_keys))
-		m.pu_dup_keys = NULL;
-	if (hit(m.pu_dupl_keys))
-		m.pu_dupl_keys = NULL;
-	if (hit(m.r32_kl) || hit(m.r32_kr))
-		m.r32_ok = false;
-	if (hit(m.lw_bad_keys))
-		m.lw_bad_keys = NULL;
-	if (hit(m.l4_bad_keys))
-		m.l4_bad_keys = NULL;
-	if (hit(m.lg_kl) || hit(m.lg_kr))
-		m.lg_valid = false;
-	if (hit(m.jk_dup_l) || hit(m.jk_dup_r))
-		m.jk_dup_l = m.jk_dup_r = NULL;
-	if (hit(m.jp_bad_l) || hit(m.jp_bad_r))
-		m.jp_bad_l = m.jp_bad_r = NULL;
-}
-
-static void mdb_hints_drop(mdb_dev_ctx *ctx, const void *lo, size_t bytes)
-{
-	const uintptr_t a = (uintptr_t)lo, b = a + (bytes ? bytes : 1);
-	memo_drop(*ctx, a, b);
-	/* the sets put aside for other column pairs: a set whose own columns are touched goes altogether */
-	for (size_t i = 0; i < ctx->memo_lru.size();) {
-		const mdb_memo_key &k = ctx->memo_lru[i].first;
-		const bool own = (k.kl && (uintptr_t)k.kl >= a && (uintptr_t)k.kl < b) || (k.kr && (uintptr_t)k.kr >= a && (uintptr_t)k.kr < b);
-		if (own) {
-			ctx->memo_lru.erase(ctx->memo_lru.begin() + (long)i);
-			continue;
-		}
-		memo_drop(ctx->memo_lru[i].second, a, b);
-		i++;
-	}
-}
-
-void mdb_memo_switch(mdb_dev_ctx *ctx, const void *kl, uint64_t nl, const void *kr, uint64_t nr)
-{
-	const mdb_memo_key key{ kl, kr, nl, kr ? nr : 0 };
-	if (ctx->memo_key == key)
-		return;
-	/* put the live set aside under the pair it belongs to */
-	if (ctx->memo_key.kl) {
-		size_t i = 0;
-		while (i < ctx->memo_lru.size() && !(ctx->memo_lru[i].first == ctx->memo_key))
-			i++;
-		if (i < ctx->memo_lru.size())
-			ctx->memo_lru.erase(ctx->memo_lru.begin() + (long)i);
-		ctx->memo_lru.push_back(std::make_pair(ctx->memo_key, static_cast<const mdb_col_memo &>(*ctx)));
-		if (ctx->memo_lru.size() > MDB_MEMO_SLOTS)
-			ctx->memo_lru.erase(ctx->memo_lru.begin());
-	}
-	size_t i = 0;
-	while (i < ctx->memo_lru.size() && !(ctx->memo_lru[i].first == key))
-		i++;
-	if (i < ctx->memo_lru.size()) {
-		static_cast<mdb_col_memo &>(*ctx) = ctx->memo_lru[i].second;
-		ctx->memo_lru.erase(ctx->memo_lru.begin() + (long)i);
-	} else {
-		memo_reset(*ctx);
-	}
-	ctx->memo_key = key;
-}
-
 int mdb_cached_free(mdb_dev_ctx *ctx, void *dptr)
 {
 	if (!dptr)
@@ -440,7 +350,7 @@ int mdb_cached_free(mdb_dev_ctx *ctx, void *dptr)
 		}
 	}
 	const size_t sz = it->second;
-	mdb_hints_drop(ctx, dptr, sz);
+	mdb_memo_drop(ctx, dptr, sz);
 	ctx->live.erase(it);
 	/* reuse is ordered by the context's stream: whoever gets the buffer next launches after every kernel
 	 * that still reads it */
@@ -521,7 +431,7 @@ extern "C" int mdb_dev_memset(mdb_dev_ctx *ctx, void *dptr, int byte, size_t byt
 extern "C" int mdb_dev_h2d(mdb_dev_ctx *ctx, void *dptr, const void *host, size_t bytes)
 {
 	if (bytes) {
-		mdb_hints_drop(ctx, dptr, bytes);
+		mdb_memo_drop(ctx, dptr, bytes);
 		MDB_HIP(ctx, hipMemcpyAsync(dptr, host, bytes, hipMemcpyHostToDevice, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	}
@@ -1275,7 +1185,7 @@ extern "C" int mdb_dev_scatter_set64(mdb_dev_ctx *ctx, void *dst, uint64_t *dst_
 		return MIDORIDB_OK;
 	if (set_null && !dst_nullbits)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "scatter_set64: SET NULL needs a NULL bitmap");
-	mdb_hints_drop(ctx, dst, 8);	/* (hints are keyed by a column's first byte) */
+	mdb_memo_drop(ctx, dst, 8);	/* (hints are keyed by a column's first byte) */
 	MDB_LAUNCH(ctx, "scatter_set64", k_scatter_set64, stream_grid(n), STREAM_THREADS, (uint64_t *)dst,
 		   (unsigned long long *)dst_nullbits, idx, n, (uint64_t)value_bits, set_null);
 	return MIDORIDB_OK;

@@ -344,7 +344,7 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	MDB_HIP(ctx, hipMemcpyAsync(h32, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
-		ctx->sr_valid = 0;	/* the sample missed a value outside its range: not to be reused */
+		ctx->vd[VD_SAMPLE].clear();	/* the sample missed a value outside its range: not to be reused */
 	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
 		return 1;	/* a value outside the window: the partitioned path */
 	ctx->plan.small_form = 2;
@@ -592,7 +592,7 @@ int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 		return 1;	/* (mdb_dev_explain_group_count passes no outputs: whether a column has few distinct values is no statistic a catalog hands over) */
 	/* distinct values in a sample of the column, remembered like the range sample */
 	uint32_t distinct;
-	if (ctx->gh_keys == keys && ctx->gh_n == n && ++ctx->gh_uses < GC_HINT_USES) {
+	if (ctx->vd[VD_DISTINCT].serve(keys, n, NULL, 0, MDB_HINT_SERVES)) {
 		distinct = ctx->gh_distinct;
 	} else {
 		uint32_t *d = ctx->d_status + GC_STW_LAST_FIRST;	/* (free before the operator starts) */
@@ -601,10 +601,8 @@ int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 		MDB_HIP(ctx, hipMemcpyAsync(h, d, 4, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		distinct = h[0];
-		ctx->gh_keys = keys;
-		ctx->gh_n = n;
+		ctx->vd[VD_DISTINCT].note(keys, n, NULL, 0);
 		ctx->gh_distinct = distinct;
-		ctx->gh_uses = 0;
 	}
 	if (distinct > GH_SAMPLE_MAX)
 		return 1;

@@ -1365,16 +1365,10 @@ static void gc_state_fill(gc_state *st, const gc_request &rq, bool own_call)
 	}
 }
 
-/* a remembered "these columns overflow the digit-per-workgroup leaves' counts" (ctx->lw_bad_*) serves MDB_BAD_LEAF_USES calls */
+/* a remembered "these columns overflow the digit-per-workgroup leaves' counts" (VD_LW_BAD) serves MDB_BAD_SERVES calls */
 static bool gc_lw_bad(mdb_dev_ctx *ctx, const gc_state *st)
 {
-	if (!(ctx->lw_bad_keys == st->keys_l && ctx->lw_bad_nl == st->n_l && ctx->lw_bad_nr == st->n_r_cap))
-		return false;
-	if (++ctx->lw_bad_uses > MDB_BAD_LEAF_USES) {
-		ctx->lw_bad_keys = NULL;
-		return false;
-	}
-	return true;
+	return ctx->vd[VD_LW_BAD].serve(st->keys_l, st->n_l, NULL, st->n_r_cap, MDB_BAD_SERVES);
 }
 
 /* first half: size and claim the scratch arena, clear the status words, partition the left table */
@@ -1876,7 +1870,7 @@ static int gc_args_begin(mdb_dev_ctx *ctx, gc_run *g)
 	}
 	a.narrow = st->narrow ? 1u : 0u;
 	/* 4096 sampled keys with fewer than 4050 distinct values among them: at most a few 10^5 distinct values in the column */
-	a.merge_all = (!st->has_r && ctx->gh_keys == st->keys_l && ctx->gh_n == n_l && ctx->gh_distinct < 4050u) ? 1u : 0u;
+	a.merge_all = (!st->has_r && ctx->vd[VD_DISTINCT].holds(st->keys_l, n_l, NULL, 0) && ctx->gh_distinct < 4050u) ? 1u : 0u;
 	/* hot = far above the side's average leaf: a much larger probe table spread evenly over the leaves is not skew */
 	const uint64_t nleaves = g->pl.nleaves ? g->pl.nleaves : 1;
 	const uint64_t avg_l = n_l / nleaves, avg_r = st->has_r ? g->r.n / nleaves : 0;
@@ -1909,17 +1903,17 @@ static int gc_choose_records(mdb_dev_ctx *ctx, gc_run *g)
 	a.keyed_cbits = g->keyed_cbits;
 	/* 4-byte records straight from the leaf kernel when the last run over these very columns saw every COUNT(*) fit beside the
 	 * row id (variant U: 10^8 records - 0.4 GB less to write and 0.4 GB less for the ordering sort to read) */
-	const bool r32_same = ctx->r32_ok && ctx->r32_kl == keys_l && ctx->r32_nl == n_l && ctx->r32_kr == keys_r && ctx->r32_nr == n_r;
+	const bool r32_same = ctx->r32_ok && ctx->vd[VD_REC32].holds(keys_l, n_l, keys_r, n_r);
 	a.rec32 = (r32_same && st->direct && !st->one_level && has_r && records && !g->keyed_cbits && kbits < 32 && g->sb2 > 0 && pl.leaf_cap && pr.leaf_cap) ? 1u : 0u;
 	/* one-level joins with 2-byte right words: k_leaf_wide4's 4 bytes per key value (two workgroups per CU) unless these columns are known to
 	 * hold more than 31 right or 15 left rows of a key */
 	g->leaf4 = st->one_level && has_r && pr.w16 && records && !st->null_group && n_l <= (1ull << 27) && st->key_bits >= (uint32_t)pl.bits_total + 10u &&
-		   !(ctx->l4_bad_keys == keys_l && ctx->l4_bad_nl == n_l && ctx->l4_bad_nr == n_r && ++ctx->l4_bad_uses <= MDB_BAD_LEAF_USES);
+		   !ctx->vd[VD_L4_BAD].serve(keys_l, n_l, NULL, n_r, MDB_BAD_SERVES);
 	/* ... and when the last join over these very columns told how many groups to expect, and they are few enough for the ordering kernel's
 	 * ranges of 2^16 row ids, k_leaf_wide4 writes its records straight into those ranges: no record list, none of the two scatter levels that
 	 * would partition it by row id */
 	g->rg_n = 0;
-	g->ranged = g->leaf4 && ctx->lg_valid && !ctx->lg_nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r &&
+	g->ranged = g->leaf4 && !ctx->lg_nextra && ctx->vd[VD_LAST_GROUPS].holds(keys_l, n_l, keys_r, n_r) &&
 		    order_ranges_apply(n_l, kbits, ctx->lg_groups + ctx->lg_groups / 8, &g->rg_n);
 	/* ... or the caller's statistics say so before any join has run (mdb_dev_call_stats): a group needs a right key, and there are at
 	 * most as many of those as values in the right column's range */
@@ -1975,7 +1969,7 @@ static int gc_choose_bits(mdb_dev_ctx *ctx, gc_run *g)
 	if (gc_bits_by_stats(ctx, st->nextra, keys_l, keys_r, n_r)) {
 		want_bits = true;
 		by_stats = true;
-	} else if (ctx->lg_valid && ctx->lg_nextra == (uint32_t)st->nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r) {
+	} else if (ctx->lg_nextra == (uint32_t)st->nextra && ctx->vd[VD_LAST_GROUPS].holds(keys_l, n_l, keys_r, n_r)) {
 		/* (what the last join over these very columns delivered) */
 		if (ctx->lg_groups >= n_l - n_l / 16 && ctx->lg_joined <= ctx->lg_groups + ctx->lg_groups / 16) {
 			if (ctx->dn_distrust > 0)
@@ -2120,13 +2114,10 @@ static int gc_read_status(mdb_dev_ctx *ctx, gc_run *g)
 	return MIDORIDB_OK;
 }
 
-/* k_leaf_wide4's count fields overflow on these columns: k_leaf_wide at once, for MDB_BAD_LEAF_USES calls */
+/* k_leaf_wide4's count fields overflow on these columns: k_leaf_wide at once, for MDB_BAD_SERVES calls */
 static void gc_l4_bad_note(mdb_dev_ctx *ctx, const gc_run *g)
 {
-	ctx->l4_bad_keys = g->st->keys_l;
-	ctx->l4_bad_uses = 0;
-	ctx->l4_bad_nl = g->st->n_l;
-	ctx->l4_bad_nr = g->r.n;
+	ctx->vd[VD_L4_BAD].note(g->st->keys_l, g->st->n_l, NULL, g->r.n);
 }
 
 /* the same partitioned tables through another one-level leaf kernel: the flags this retry answers (and those the new run raises again if they still
@@ -2161,7 +2152,7 @@ static int gc_leaf4_redo(mdb_dev_ctx *ctx, gc_run *g)
 		gc_l4_bad_note(ctx, g);
 	g->ranged = false;
 	g->a.rg_rec = NULL;
-	ctx->lg_valid = false;
+	ctx->vd[VD_LAST_GROUPS].clear();
 	if ((rc = gc_leaf4_relaunch(ctx, g, counts_bad)))
 		return rc;
 	if (!counts_bad && (g->rb->flags & GC_ST_COUNTS_NOT_4BYTE) && !(g->rb->flags & partition_said)) {	/* (the counts overflow as well: seen only now) */
@@ -2202,10 +2193,8 @@ static int gc_verdict(mdb_dev_ctx *ctx, const gc_run *g, gc_verdict_at at)
 		if (f & MDB_ST_REGION_FULL)
 			return GC_RETRY_EXACT;	/* a leaf outgrew its fixed-capacity region (skewed keys) */
 		if (f & GC_ST_ROWS_NOT_16BIT) {
-			ctx->lw_bad_uses = 0;
-			ctx->lw_bad_keys = st->keys_l;	/* a key with 2^16 or more rows on one side: two levels and their hot-key path, now and for these columns */
-			ctx->lw_bad_nl = st->n_l;
-			ctx->lw_bad_nr = st->n_r_cap;
+			/* a key with 2^16 or more rows on one side: two levels and their hot-key path, now and for these columns */
+			ctx->vd[VD_LW_BAD].note(st->keys_l, st->n_l, NULL, st->n_r_cap);
 			return GC_RETRY_TWO_LEVEL;
 		}
 		if ((f & GC_ST_HOT_LEAVES) && g->keyed_cbits) {
@@ -2346,10 +2335,7 @@ static int gc_deliver_records(mdb_dev_ctx *ctx, gc_run *g)
 		return rc;
 	/* remember whether 4-byte records would do for these columns */
 	ctx->r32_ok = st->direct && !st->one_level && st->has_r && !g->keyed_cbits && !(status & GC_ST_COUNT_NOT_REC32);
-	ctx->r32_kl = st->keys_l;
-	ctx->r32_nl = n_l;
-	ctx->r32_kr = g->r.keys;
-	ctx->r32_nr = g->r.n;
+	ctx->vd[VD_REC32].note(st->keys_l, n_l, g->r.keys, g->r.n);
 	return MIDORIDB_OK;
 }
 
@@ -2385,14 +2371,10 @@ static void gc_remember(mdb_dev_ctx *ctx, const gc_run *g)
 	if (g->out.joined)
 		*g->out.joined = joined;
 	if (st->has_r) {
+		ctx->vd[VD_LAST_GROUPS].note(st->keys_l, st->n_l, g->r.keys, g->r.n);
 		ctx->lg_nextra = (uint32_t)st->nextra;
-		ctx->lg_kl = st->keys_l;
-		ctx->lg_nl = st->n_l;
-		ctx->lg_kr = g->r.keys;
-		ctx->lg_nr = g->r.n;
 		ctx->lg_groups = g->G;
 		ctx->lg_joined = joined;
-		ctx->lg_valid = true;
 	}
 	ctx->last_left_dups_known = st->direct && st->has_r && !(status & GC_ST_HOT_LEAVES);	/* (the hot-key kernels and the hashed leaves do not say) */
 	ctx->last_left_dups = (status & GC_ST_LEFT_DUPS) != 0;
@@ -2555,19 +2537,13 @@ int gc_sample_range(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 			ctx->sr_span_r = ~0ull;
 		ctx->sr_rlo = has_r ? r.min : INT64_MAX;
 		ctx->sr_rhi = has_r ? r.max : INT64_MIN;
-		ctx->sr_kl = keys_l;
-		ctx->sr_nl = n_l;
-		ctx->sr_kr = keys_r;
-		ctx->sr_nr = n_r;
+		ctx->vd[VD_SAMPLE].note(keys_l, n_l, keys_r, n_r);
 		ctx->sr_lo = *lo;
 		ctx->sr_hi = *hi;
-		ctx->sr_valid = 1;
-		ctx->sr_uses = 0;
 		ctx->plan.from_stats = 1;
 		return MIDORIDB_OK;
 	}
-	if (!fresh && ctx->sr_valid && ctx->sr_kl == keys_l && ctx->sr_nl == n_l && ctx->sr_kr == keys_r && ctx->sr_nr == n_r &&
-	    ++ctx->sr_uses < GC_HINT_USES) {
+	if (!fresh && ctx->vd[VD_SAMPLE].serve(keys_l, n_l, keys_r, n_r, MDB_HINT_SERVES)) {
 		*lo = ctx->sr_lo;
 		*hi = ctx->sr_hi;
 		return MIDORIDB_OK;
@@ -2595,14 +2571,9 @@ int gc_sample_range(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 	ctx->sr_span_r = h[4] <= h[5] ? (uint64_t)h[5] - (uint64_t)h[4] + 1 : 0;
 	ctx->sr_rlo = h[4];
 	ctx->sr_rhi = h[5];
-	ctx->sr_kl = keys_l;
-	ctx->sr_nl = n_l;
-	ctx->sr_kr = keys_r;
-	ctx->sr_nr = n_r;
+	ctx->vd[VD_SAMPLE].note(keys_l, n_l, keys_r, n_r);
 	ctx->sr_lo = *lo;
 	ctx->sr_hi = *hi;
-	ctx->sr_valid = 1;
-	ctx->sr_uses = 0;
 	return MIDORIDB_OK;
 }
 
@@ -2611,13 +2582,9 @@ void gc_narrow_note(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l, const
 {
 	ctx->nh_kbits = narrow ? key_bits : 0u;
 	ctx->nh_lo = key_lo;
-	ctx->nh_kl = keys_l;
-	ctx->nh_nl = n_l;
-	ctx->nh_kr = keys_r;
-	ctx->nh_nr = keys_r ? n_r : 0;
+	ctx->vd[VD_NARROW].note(keys_l, n_l, keys_r, keys_r ? n_r : 0);
 	ctx->nh_result = narrow ? 1 : 0;
 	ctx->nh_base = base;
-	ctx->nh_uses = 0;
 }
 
 /* *narrow: try the narrow form; *base: centre of the 2^32-wide window of key values it will be tried with (0 = the plain
@@ -2629,8 +2596,7 @@ void gc_narrow_note(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l, const
  * the bitmap filter only drops rows that can have no partner) */
 static bool gc_learned_selective(const mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l, const int64_t *keys_r, uint64_t n_r)
 {
-	return ctx->lg_valid && !ctx->lg_nextra && ctx->lg_kl == keys_l && ctx->lg_nl == n_l && ctx->lg_kr == keys_r && ctx->lg_nr == n_r && keys_r &&
-	       ctx->lg_groups < n_l / 4;
+	return !ctx->lg_nextra && ctx->vd[VD_LAST_GROUPS].holds(keys_l, n_l, keys_r, n_r) && keys_r && ctx->lg_groups < n_l / 4;
 }
 
 /* exact: [lo, hi] is the catalog's range of the column (every key lies inside), not a sample's: no margin around it */
@@ -2694,9 +2660,8 @@ int gc_narrow_guess(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *nul
 	} else if (ctx->nh_distrust > 0) {
 		ctx->nh_distrust--;
 		fresh = true;
-	} else if (ctx->nh_result >= 0 && ctx->nh_kl == keys_l && ctx->nh_nl == n_l && ctx->nh_kr == keys_r && ctx->nh_nr == (keys_r ? n_r : 0) &&
-		   !(ctx->nh_r_based && !prune_ok) &&	/* (a window of the right table's keys alone is no use to a call that cannot prune) */
-		   ++ctx->nh_uses < GC_HINT_USES) {
+	} else if (!(ctx->nh_r_based && !prune_ok) &&	/* (a window of the right table's keys alone is no use to a call that cannot prune) */
+		   ctx->vd[VD_NARROW].serve(keys_l, n_l, keys_r, keys_r ? n_r : 0, MDB_HINT_SERVES)) {
 		*narrow = ctx->nh_result == 1;	/* same columns as last time: what held then (gc_narrow_note) */
 		ctx->guess_remembered = true;
 		*base = ctx->nh_base;
@@ -2818,7 +2783,7 @@ static int group_count_common(mdb_dev_ctx *ctx, gc_request *rq)
 	 * the one-level form applies: its 256 or 512 first-level regions hold 50 values or more each; sized at 1.5 x the average
 	 * (mdb_part_filter.loose) they take the variation of that number */
 	bool fast1 = false;
-	if (!has_r && ctx->gh_keys == keys_l && ctx->gh_n == n_l && ctx->gh_distinct < 4050u) {
+	if (!has_r && ctx->vd[VD_DISTINCT].holds(keys_l, n_l, NULL, 0) && ctx->gh_distinct < 4050u) {
 		if (ctx->gh_distinct >= 3500u)
 			fast1 = true;
 		else
@@ -2835,7 +2800,7 @@ static int group_count_common(mdb_dev_ctx *ctx, gc_request *rq)
 	}
 	rq->win.fast1 = fast1;
 	/* the histogram-free layout overflowed on these very columns last time (skewed or heavily duplicated keys): exact at once */
-	if (rq->fast && ctx->ex_keys == keys_l && ctx->ex_nl == n_l && ctx->ex_nr == (has_r ? n_r : 0) && ++ctx->ex_uses < GC_HINT_USES) {
+	if (rq->fast && ctx->vd[VD_EXACT].serve(keys_l, n_l, NULL, has_r ? n_r : 0, MDB_HINT_SERVES)) {
 		rq->fast = false;
 		rq->win.fast1 = false;
 	}
@@ -2845,9 +2810,7 @@ static int group_count_common(mdb_dev_ctx *ctx, gc_request *rq)
 		if ((rc == GC_RETRY_PLAIN || rc == GC_RETRY_WIDE) && ctx->guess_remembered && ctx->narrow_mode == 1 && !keys32) {
 			/* a REMEMBERED verdict proved wrong: the buffers hold other data than when it was made (a caller's allocator handed
 			 * the same addresses out again).  Not a reason to give the narrow forms up: forget, look at the data itself, go on */
-			ctx->nh_result = -1;
-			ctx->sr_valid = 0;
-			ctx->nh_distrust = 1;
+			ctx->forget_guess();
 			rq->narrow = false;
 			rq->base = 0;
 			rc = gc_narrow_guess(ctx, keys_l, rq->l.nulls, n_l, keys_r, rq->r.nulls, n_r, &rq->narrow, &rq->base, &rq->win, keys32, has_r);
@@ -2869,15 +2832,12 @@ static int group_count_common(mdb_dev_ctx *ctx, gc_request *rq)
 		} else if (rc == GC_RETRY_EXACT) {
 			rq->fast = false;
 			rq->win.fast1 = false;
-			ctx->ex_keys = keys_l;
-			ctx->ex_nl = n_l;
-			ctx->ex_nr = has_r ? n_r : 0;
-			ctx->ex_uses = 0;
+			ctx->vd[VD_EXACT].note(keys_l, n_l, NULL, has_r ? n_r : 0);
 		}	/* (gc_begin then also leaves the narrow form of a join: it is only built on the fast layout) */
 		else if (rc == GC_RETRY_DENSE)
 			rq->records = false;
 		else if (rc == GC_RETRY_UNKEYED || rc == GC_RETRY_REC64 || rc == GC_RETRY_TWO_LEVEL || rc == GC_RETRY_NODENSE)
-			;		/* (gc_finish has set ctx->keyed_distrust / cleared ctx->r32_ok / noted the columns in ctx->lw_bad_*) */
+			;		/* (gc_finish has set ctx->keyed_distrust / cleared ctx->r32_ok / noted the columns in VD_LW_BAD) */
 		else if (rc == GC_RETRY_BUILD_L)
 			rq->no_build_r = true;
 		else
@@ -3068,7 +3028,7 @@ static int gc_unordered_try(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint6
 again: {
 	int64_t lo = 0, hi = 0;
 	int rc = gc_sample_range(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, fresh || ctx->nh_distrust > 0, &lo, &hi);
-	const bool remembered = ctx->sr_uses > 0;
+	const bool remembered = ctx->vd[VD_SAMPLE].served();
 	if (rc)
 		return rc;
 	if (!ctx->sr_span_r || !ctx->sr_span_l)
@@ -3164,7 +3124,7 @@ extern "C" int mdb_dev_group_count_keys(mdb_dev_ctx *ctx, const int64_t *keys, c
 		int rc = gc_sample_range(ctx, keys, NULL, n, NULL, NULL, 0, attempt > 0 || ctx->nh_distrust > 0, &lo, &hi);
 		if (rc)
 			return rc;
-		const bool remembered = ctx->sr_uses > 0;
+		const bool remembered = ctx->vd[VD_SAMPLE].served();
 		uint32_t kb = 0;
 		int64_t wlo = 0;
 		if (lo <= hi)
@@ -3542,7 +3502,7 @@ extern "C" int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const 
 			int rc = gc_sample_range(ctx, keys, NULL, n, NULL, NULL, 0, attempt > 0 || ctx->nh_distrust > 0, &lo, &hi);
 			if (rc)
 				return rc;
-			const bool remembered = ctx->sr_uses > 0;
+			const bool remembered = ctx->vd[VD_SAMPLE].served();
 			uint32_t kb = 0;
 			int64_t wlo = 0;
 			if (lo <= hi)
@@ -3585,8 +3545,7 @@ static mdb_dev_ctx *explain_ctx(const struct mdb_dev_explain_request *rq, bool h
 	mdb_dev_ctx *ctx = new (std::nothrow) mdb_dev_ctx();
 	if (!ctx)
 		return NULL;
-	memset(static_cast<mdb_col_memo *>(ctx), 0, sizeof(mdb_col_memo));
-	ctx->nh_result = -1;
+	memo_reset(*ctx);
 	ctx->device = -1;
 	ctx->num_cus = rq->num_cus ? (int)rq->num_cus : 256;
 	ctx->narrow_mode = 1;

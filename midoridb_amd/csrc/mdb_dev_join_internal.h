@@ -191,7 +191,7 @@ enum gc_internal_rc {
 	GC_RETRY_PLAIN,	/* internal: a key outside the compact window (the sample missed the column's extremes): redo in the plain narrow form */
 	GC_RETRY_UNKEYED,	/* internal: a COUNT(*) does not fit a keyed group record (ctx->keyed_distrust is set): redo with plain records */
 	GC_RETRY_REC64,	/* internal: 4-byte group records were written on a remembered verdict that no longer holds: redo with 8-byte ones */
-	GC_RETRY_TWO_LEVEL,	/* internal: a 16-bit row count of k_leaf_wide overflowed (ctx->lw_bad_* remember the columns): redo with two levels */
+	GC_RETRY_TWO_LEVEL,	/* internal: a 16-bit row count of k_leaf_wide overflowed (VD_LW_BAD remembers the columns): redo with two levels */
 	GC_RETRY_NODENSE,	/* internal: the bit-per-row form of the groups met more groups of COUNT != 1 than its list holds (ctx->dn_distrust is set) */
 	GC_EXPLAINED,	/* internal: mdb_dev_explain_*() - the plan is written, nothing was launched */
 	GC_NOT_SERVED,	/* internal: further right tables, but the operator did not take the two-level direct-address form (or a product of counts overflowed, or a hot leaf): the caller chains two-table operators instead */
@@ -271,10 +271,6 @@ struct gc_window {
 #define TINY_ROWS (GC_THREADS * LEAF_BATCH)	/* rows per table up to which ONE workgroup does the whole operator in LDS */
 #define GC_NARROW_MIN_ROWS (1u << 20)
 #define GC_NARROW_SAMPLE 4096u
-#define GC_HINT_USES 32		/* a remembered sample / verdict serves this many calls, then the data is looked at again (one tiny
-				 * kernel + sync - ~50 us, a tenth of a 10^7-row query - in 32 calls; a buffer refilled with another
-				 * distribution runs that long on a plan that is exact but may not be the best; a hint the data
-				 * contradicts is noticed by the kernels at once) */
 
 /* position of sample t: pseudo-random, not evenly spaced - generated or periodic data (an affine sequence, a table sorted by
  * a low-cardinality column) looks very different at a fixed stride than it is */

@@ -1081,7 +1081,7 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	    mdb_knob_off("MDB_JOIN_PAYLOAD"))
 		return 1;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
-	if (ctx->jp_bad_l == keys_l && ctx->jp_bad_nl == n_l && ctx->jp_bad_r == keys_r && ctx->jp_bad_nr == n_r && ++ctx->jp_bad_skips < 32)
+	if (ctx->vd[VD_JP_BAD].serve(keys_l, n_l, keys_r, n_r, MDB_HINT_SERVES))
 		return 1;	/* (these columns were not such a join last time: not tried again for a while) */
 	for (int attempt = 0; attempt < 2; attempt++) {
 	bool narrow = false;
@@ -1119,20 +1119,13 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		if (status == 0 && J == (uint64_t)npay * n_l)
 			return served(3, kbits, 1);
 		if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
-			ctx->nh_result = -1;
-			ctx->sr_valid = 0;
-			ctx->nh_distrust = 1;
+			ctx->forget_guess();
 			continue;
 		}
-		if (status & MDB_ST_KEY_OUTSIDE) {
+		if (status & MDB_ST_KEY_OUTSIDE)
 			ctx->nh_distrust = 8;
-		} else {
-			ctx->jp_bad_l = keys_l;
-			ctx->jp_bad_nl = n_l;
-			ctx->jp_bad_r = keys_r;
-			ctx->jp_bad_nr = n_r;
-			ctx->jp_bad_skips = 0;
-		}
+		else
+			ctx->vd[VD_JP_BAD].note(keys_l, n_l, keys_r, n_r);
 		return 1;
 	}
 	if (win.kbits > 9u + PW_MAX_REM) {
@@ -1201,20 +1194,13 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		if (status == 0 && J == n_l)
 			return served(2, kbits, 2);
 		if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
-			ctx->nh_result = -1;
-			ctx->sr_valid = 0;
-			ctx->nh_distrust = 1;
+			ctx->forget_guess();
 			continue;
 		}
-		if (status & MDB_ST_KEY_OUTSIDE) {
+		if (status & MDB_ST_KEY_OUTSIDE)
 			ctx->nh_distrust = 8;
-		} else if (!(status & MDB_ST_REGION_FULL)) {	/* (a region overflow says nothing about the join) */
-			ctx->jp_bad_l = keys_l;
-			ctx->jp_bad_nl = n_l;
-			ctx->jp_bad_r = keys_r;
-			ctx->jp_bad_nr = n_r;
-			ctx->jp_bad_skips = 0;
-		}
+		else if (!(status & MDB_ST_REGION_FULL))	/* (a region overflow says nothing about the join) */
+			ctx->vd[VD_JP_BAD].note(keys_l, n_l, keys_r, n_r);
 		return 1;
 	}
 	const int b1 = 9;
@@ -1291,20 +1277,13 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
 		/* a REMEMBERED window proved wrong: the buffers hold other data than when it was learned (a caller's allocator handed the
 		 * same addresses out again) - forget, look at the data itself, once more */
-		ctx->nh_result = -1;
-		ctx->sr_valid = 0;
-		ctx->nh_distrust = 1;
+		ctx->forget_guess();
 		continue;
 	}
-	if (status & MDB_ST_KEY_OUTSIDE) {	/* a key outside the window after all: the sample is not trusted for a while */
+	if (status & MDB_ST_KEY_OUTSIDE)	/* a key outside the window after all: the sample is not trusted for a while */
 		ctx->nh_distrust = 8;
-	} else {
-		ctx->jp_bad_l = keys_l;
-		ctx->jp_bad_nl = n_l;
-		ctx->jp_bad_r = keys_r;
-		ctx->jp_bad_nr = n_r;
-		ctx->jp_bad_skips = 0;
-	}
+	else
+		ctx->vd[VD_JP_BAD].note(keys_l, n_l, keys_r, n_r);
 	return 1;
 	}
 	return 1;
@@ -1522,13 +1501,12 @@ static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	/* a compact window of at most 2^24 key values: one partition level, see join_pairs_unique_wide (MDB_ONE_LEVEL=0 switches
 	 * it off).  What it cannot do - a key outside the window after all, a first-level region overflow - goes the usual way */
 	if (narrow && win.kbits >= 9u + PW_MIN_REM && win.kbits <= 9u + PW_MAX_REM && n_l <= PW_MAX_LEFT && n_l + n_r >= (1ull << 20) &&
-	    !(ctx->pw_bad_keys == keys_r && ctx->pw_bad_n == n_r) && !ld_disabled() &&
+	    !ctx->vd[VD_PW_BAD].holds(NULL, 0, keys_r, n_r) && !ld_disabled() &&
 	    !mdb_knob_off("MDB_ONE_LEVEL")) {
 		urc = join_pairs_unique_wide(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, win.kbits, win.lo, out_l, out_r, out_count);
 		if (urc <= 0 || urc == 3)
 			return urc;
-		ctx->pw_bad_keys = keys_r;
-		ctx->pw_bad_n = n_r;
+		ctx->vd[VD_PW_BAD].note(NULL, 0, keys_r, n_r);
 	}
 	urc = join_pairs_unique(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, narrow, base, out_l, out_r, out_count);
 	if (urc == 2) {	/* the sample (or what was remembered about these columns) missed a wide key */
@@ -1642,33 +1620,23 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 		uint32_t *ul = NULL, *ur = NULL;
 		uint64_t uj = 0;
 		int urc = 3;
-		bool right_dups = ctx->pu_dup_keys == keys_r && ctx->pu_dup_n == n_r;
-		bool left_dups = ctx->pu_dupl_keys == keys_l && ctx->pu_dupl_n == n_l;
-		if ((right_dups || left_dups) && ++ctx->pu_dup_skips > 32) {	/* the buffers may hold other data by now: look again once in a while */
-			right_dups = left_dups = false;
-			ctx->pu_dup_keys = ctx->pu_dupl_keys = NULL;
-		}
+		bool right_dups = false, left_dups = false;
+		ctx->dup_sides(keys_l, n_l, keys_r, n_r, &left_dups, &right_dups);
 		bool right_unique = false;
 		if (!right_dups) {
 			urc = join_pairs_unique_auto(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &ul, &ur, &uj);
 			if (urc < 0)
 				return urc;
 			right_unique = urc == 0;
-			if (urc == 3) {
-				ctx->pu_dup_keys = keys_r;
-				ctx->pu_dup_n = n_r;
-				ctx->pu_dup_skips = 0;
-			}
+			if (urc == 3)
+				ctx->dup_side_note(true, keys_r, n_r);
 		}
 		if (urc == 3 && !left_dups && n_l + n_r >= SORT_SWAP_MIN_ROWS) {	/* small tables: the general path has fewer launches */
 			urc = join_pairs_unique_left(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &ul, &ur, &uj);
 			if (urc < 0)
 				return urc;
-			if (urc == 3) {
-				ctx->pu_dupl_keys = keys_l;
-				ctx->pu_dupl_n = n_l;
-				ctx->pu_dup_skips = 0;
-			}
+			if (urc == 3)
+				ctx->dup_side_note(false, keys_l, n_l);
 		}
 		if (urc == 0) {
 			*out_l = ul;
@@ -1867,7 +1835,7 @@ extern "C" int mdb_dev_join_keys_ordered(mdb_dev_ctx *ctx, const int64_t *keys_l
 	if (!n_l || !n_r)
 		return MIDORIDB_OK;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
-	if (ctx->jk_dup_l == keys_l && ctx->jk_dup_nl == n_l && ctx->jk_dup_r == keys_r && ctx->jk_dup_nr == n_r && ++ctx->jk_dup_uses < 32)
+	if (ctx->vd[VD_JK_DUP].serve(keys_l, n_l, keys_r, n_r, MDB_HINT_SERVES))
 		return MIDORIDB_OK;	/* (these columns had duplicates last time) */
 	int64_t *gk = NULL, *gc = NULL;
 	if (mdb_dev_alloc(ctx, n_l * 8, (void **)&gk) || mdb_dev_alloc(ctx, n_l * 8, (void **)&gc)) {
@@ -1917,13 +1885,8 @@ extern "C" int mdb_dev_join_keys_ordered(mdb_dev_ctx *ctx, const int64_t *keys_l
 	(void)mdb_dev_free(ctx, gc);
 	if (rc || J != G) {
 		(void)mdb_dev_free(ctx, gk);
-		if (!rc) {
-			ctx->jk_dup_l = keys_l;
-			ctx->jk_dup_nl = n_l;
-			ctx->jk_dup_r = keys_r;
-			ctx->jk_dup_nr = n_r;
-			ctx->jk_dup_uses = 0;
-		}
+		if (!rc)
+			ctx->vd[VD_JK_DUP].note(keys_l, n_l, keys_r, n_r);
 		return rc;
 	}
 	*out_key = gk;
@@ -1952,18 +1915,13 @@ extern "C" int mdb_dev_join_keys(mdb_dev_ctx *ctx, const int64_t *keys_l, const 
 	 * 2.0): J == G says that this was right; otherwise - or when these columns had duplicates last time - once more with counts */
 	int rc = MIDORIDB_OK;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
-	const bool had_dups = ctx->jk_dup_l == keys_l && ctx->jk_dup_nl == n_l && ctx->jk_dup_r == keys_r && ctx->jk_dup_nr == n_r && ++ctx->jk_dup_uses < 32;
+	const bool had_dups = ctx->vd[VD_JK_DUP].serve(keys_l, n_l, keys_r, n_r, MDB_HINT_SERVES);
 	if (n_l && n_r && !had_dups) {
 		ctx->unordered_no_counts = 1;
 		rc = mdb_dev_join_group_count(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, 0u, gk, gc, NULL, cap, &G, &J);
 		ctx->unordered_no_counts = 0;
-		if (!rc && J != G) {
-			ctx->jk_dup_l = keys_l;
-			ctx->jk_dup_nl = n_l;
-			ctx->jk_dup_r = keys_r;
-			ctx->jk_dup_nr = n_r;
-			ctx->jk_dup_uses = 0;
-		}
+		if (!rc && J != G)
+			ctx->vd[VD_JK_DUP].note(keys_l, n_l, keys_r, n_r);
 	}
 	if (!rc && n_l && n_r && (had_dups || J != G))
 		rc = mdb_dev_join_group_count(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, 0u, gk, gc, NULL, cap, &G, &J);

@@ -2704,6 +2704,65 @@ def test_column_memo_keeps_several_table_pairs(dev):
     assert prof.get("key_sample", (0, 0.0))[0] == 1, prof.get("key_sample")
 
 
+# what each block of test_remembered_verdicts_expire_on_schedule paid for: (samples, retries, key_sample launches, key_sample_distinct
+# launches).  Not reasoned out - other verdicts (exact layout, leaf overflows, distrust back-offs) add samples of their own: recorded by
+# running this very test body on the commit before the memo became one keyed-verdict type (mdb_dev_memo.h), and held exactly since.
+MEMO_EXPIRY_RECORDED = {
+    "join_group_count x 70": (3, 0, 3, 0),
+    "group_count x 70": (3, 0, 3, 3),
+    "join_keys x 40": (1, 0, 1, 0),
+}
+
+
+def test_remembered_verdicts_expire_on_schedule(dev):
+    """A remembered verdict serves a fixed number of calls, then the data is looked at again: the key samples, distinct samples and
+    retries that 70 + 70 + 40 repeated calls over one pair of columns pay are the counts recorded above, to the launch.  600 000 rows
+    per table is the smallest size at which the key sample runs at all (GC_NARROW_MIN_ROWS rows over both tables); keys in
+    [0, 300 000) repeat, so the duplicate and overflow verdicts take part.  A context of its own: nothing remembered from other tests."""
+    n, dom = 600_000, 300_000
+    rng = np.random.default_rng(31)
+    kl, kr = rng.integers(0, dom, n).astype(np.int64), rng.integers(0, dom, n).astype(np.int64)
+    ctx = D.DeviceCtx(0)
+    try:
+        ctx.set_narrow_keys(1)
+        a, b = ctx.to_dev(kl), ctx.to_dev(kr)
+        ek, ec, ef, ej = orc.join_group_count(kl, None, kr, None)
+        e_first, e_cnt = orc.group_count(kl, None)
+        el, _ = orc.join_pairs(kl, None, kr, None)
+        e_keys = np.sort(kl[el])
+
+        def jgc(check):
+            k, c, f, j = ctx.join_group_count(a, None, b, None)
+            if check:
+                assert j == ej and np.array_equal(_np(k), ek) and np.array_equal(_np(c), ec)
+                assert np.array_equal(_np(f).view(np.uint32).astype(np.int64), ef)
+
+        def gc(check):
+            first, cnt = ctx.group_count(a, None)
+            if check:
+                assert np.array_equal(_np(first).view(np.uint32).astype(np.int64), e_first) and np.array_equal(_np(cnt), e_cnt)
+
+        def jk(check):
+            got = ctx.join_keys(a, None, b, None)
+            if check:
+                assert got.numel() == len(el) and np.array_equal(np.sort(_np(got)), e_keys)
+
+        ctx.prof_enable(True)
+        seen = {}
+        for name, call, calls in (("join_group_count x 70", jgc, 70), ("group_count x 70", gc, 70), ("join_keys x 40", jk, 40)):
+            ctx.prof_reset()
+            c0 = ctx.counters()
+            for i in range(1, calls + 1):
+                call(i in (1, 33, calls))
+            c1, prof = ctx.counters(), ctx.prof_read()
+            seen[name] = (c1["samples"] - c0["samples"], c1["retries"] - c0["retries"], prof.get("key_sample", (0, 0.0))[0],
+                          prof.get("key_sample_distinct", (0, 0.0))[0])
+            print(name, seen[name])
+        assert seen == MEMO_EXPIRY_RECORDED
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("shape", ["unique_3", "dups_3", "four_tables", "selective", "wide_keys", "small", "skew", "nulls"])
 def test_join_group_count_multi_same_key(dev, shape):
     """mdb_dev_join_group_count_multi: L JOIN R0 JOIN R1 [JOIN R2] on ONE key + GROUP BY + COUNT(*) (BASELINE configs[4] shape) - every table
