@@ -136,6 +136,47 @@ def in_set_rows(dev, res):
     res["in_set_1e8"] = out
 
 
+def aggregate_rows(dev, res, n=100_000_000):
+    """aggregate_1e8: GROUP BY k, SUM(v) over 10^8 rows at 4, 1000 and 10^5 groups with INT64 v (groups in LDS up to
+    mdb_dev_group_aggregate_lds_groups(1), sorted segments beyond) and DOUBLE v (sorted segments: a floating-point sum is never
+    order-free), and SUM(v) without GROUP BY.  Per case: group_count_ms = the same shape's GROUP BY k, COUNT(*) (mdb_dev_group_count,
+    which the aggregate operator needs first and which this operator does not change), aggregate_ms = mdb_dev_group_aggregate alone,
+    wall time per call with its synchronisation; copy_ms = a device-to-device copy of one 8-byte column of the same rows in the same
+    run - 16 bytes moved per row, what one key and one value per row are at the box's copy rate."""
+    out = {"rows": n, "lds_groups_1_aggregate": dev.group_aggregate_lds_groups(1), "cases": {}}
+    src = torch.empty(n, dtype=torch.int64, device=dev.device).zero_()
+    dst = torch.empty_like(src)
+    copy_ms = []
+    for _ in range(6):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dst.copy_(src)
+        torch.cuda.synchronize()
+        copy_ms.append((time.perf_counter() - t0) * 1e3)
+    del src, dst
+    out["copy_ms"] = min(copy_ms[1:])
+    out["copy_ms_all"] = copy_ms[1:]
+    out["copy_GBs"] = 16 * n / (out["copy_ms"] * 1e-3) / 1e9
+    v = dev.gen_payload(n, 0, 11, 0)
+    d = dev.gen_payload(n, 0, 12, 1)
+    for groups in (4, 1000, 100_000):
+        keys = dev.gen_keys(n, 0, n, 43, groups)
+        gms, gkern, (first, cnt) = timed(dev, lambda: dev.group_count(keys, None), reps=3, warmup=1)
+        dkeys = [(keys, None, None, D.T_INT64, False)]
+        for name, col, ty in (("int64", v, D.T_INT64), ("double", d, D.T_DOUBLE)):
+            ams, akern, got = timed(dev, lambda: dev.group_aggregate(dkeys, n, first, [(D.AGG_SUM, ty, col, None, None)]), reps=3, warmup=1)
+            out["cases"][f"sum_{name}@{groups}"] = {"groups": int(first.numel()), "form": got[2], "group_count_ms": gms, "aggregate_ms": ams,
+                                                    "statement_ms": gms + ams, "aggregate_over_copy": ams / out["copy_ms"],
+                                                    "group_count_kernels_ms": gkern, "kernels_ms": akern}
+        del keys, first, cnt
+        torch.cuda.empty_cache()
+    for name, col, ty in (("int64", v, D.T_INT64), ("double", d, D.T_DOUBLE)):
+        ams, akern, got = timed(dev, lambda: dev.group_aggregate([], n, None, [(D.AGG_SUM, ty, col, None, None)]), reps=3, warmup=1)
+        out["cases"][f"sum_{name}@ungrouped"] = {"groups": 1, "form": got[2], "aggregate_ms": ams, "aggregate_over_copy": ams / out["copy_ms"],
+                                                  "kernels_ms": akern}
+    res["aggregate_1e8"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04", "operators.json"))
@@ -143,9 +184,18 @@ def main():
                                                              "what profiles/collect.sh runs under rocprofv3")
     ap.add_argument("--outer", action="store_true", help="only the outer join's rows (outer_complete_1e8, left_join_pairs_1e8)")
     ap.add_argument("--in-set", action="store_true", help="only the IN-list rows (in_set_1e8: set lookups beside an 8-value term list and one comparison)")
+    ap.add_argument("--aggregates", action="store_true", help="only the SUM / MIN / MAX / AVG rows (aggregate_1e8: GROUP BY k, SUM(v) at 4, 1000 and 10^5 "
+                                                               "groups with INT64 and DOUBLE v, and SUM(v) without GROUP BY)")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.aggregates:
+        aggregate_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.in_set:
         in_set_rows(dev, res)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -448,6 +498,8 @@ def main():
 
     torch.cuda.empty_cache()
     outer_join_rows(dev, res)
+    torch.cuda.empty_cache()
+    aggregate_rows(dev, res)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

@@ -638,6 +638,48 @@ int mdb_dev_group_count(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *n
 int mdb_dev_group_count_keys(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, int64_t *out_key,
 			     int64_t *out_count, uint64_t cap, uint64_t *out_groups);
 
+/* ------------------------------------------------------------------ SUM / MIN / MAX / AVG per group
+ *
+ * An extension: the reference's lexer knows COUNT( only (src/parser/midorisql.l:139-142) and its executor counts rows
+ * (inc_count_cols, src/engine/executor_select.c:1465-1524).  After mdb_dev_group_count / mdb_dev_group_count_multi have delivered
+ * first[G] (ascending stream positions of the groups' first rows) one call folds the cells of up to MDB_AGG_MAX_AGGS columns into
+ * their rows' groups: row i of the stream reads values[rid ? rid[i] : i] of every column, as struct mdb_sort_key does.
+ *
+ *   cells       a NULL cell - its NULL bit set, or a row id of MDB_NO_ROW - is skipped; a group without a non-NULL cell is NULL
+ *               (out = 0, its bit in out_nullbits set; all (G + 63) / 64 words of out_nullbits are written, unused bits 0)
+ *   SUM         MDB_T_INT64 cells: int64_t, two's complement, WRAPS on overflow; MDB_T_DOUBLE cells: double
+ *   MIN, MAX    the cells' own type; MDB_T_DOUBLE in the order mdb_dev_sort_perm documents (IEEE order, -0.0 before +0.0)
+ *   AVG         double: (double)sum / (double)non-NULL cells with the wrapped int64 sum, or sum / cells for MDB_T_DOUBLE
+ *   NaN cells   outside the contract (a sum that meets one is NaN; where MIN / MAX put one is unspecified)
+ *
+ * nkeys == 0: the whole stream is one group (first may be NULL, G = 1).  nkeys == MDB_AGG_IDENTITY: group i is row i (G = n; what
+ * mdb_dev_group_count's identity form stands for), keys and first are not read.  Otherwise keys[0 .. nkeys) are the group key columns
+ * (`desc` is ignored; NULL equals NULL, DOUBLE keys compare by their bits) and first[] must be what the GROUP BY operators delivered
+ * for them: a key without a group fails the call.
+ *
+ * *out_form (may be NULL) = the form that ran: 1 groups in LDS - every aggregate is order-free (any function over MDB_T_INT64 cells,
+ * MIN / MAX over MDB_T_DOUBLE), at most one key column and G <= mdb_dev_group_aggregate_lds_groups(naggs); MDB_AGG_LDS=0 turns it
+ * off -, 2 sorted segments (a stable sort of the stream by the keys, every group one run, folded in an order that depends on n, the
+ * permutation and the launch geometry alone), 3 the identity.  No floating-point atomics in any form: the same input gives the same
+ * bytes.  Synchronises. */
+enum mdb_agg_op { MDB_AGG_SUM = 1, MDB_AGG_MIN = 2, MDB_AGG_MAX = 3, MDB_AGG_AVG = 4 };
+#define MDB_AGG_MAX_AGGS 8
+#define MDB_AGG_IDENTITY (-1)
+struct mdb_agg {
+	int32_t op;			/* enum mdb_agg_op */
+	int32_t type;			/* enum mdb_valtype of the cells */
+	const void *values;		/* as struct mdb_sort_key */
+	const uint64_t *nullbits;
+	const uint32_t *rid;
+	void *out;			/* int64_t[G] or double[G] */
+	uint64_t *out_nullbits;		/* (G + 63) / 64 words, written in full */
+};
+int mdb_dev_group_aggregate(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, const uint32_t *first, uint64_t G,
+			    const struct mdb_agg *aggs, int naggs, uint32_t *out_form);
+/* the largest G the LDS form takes for naggs aggregates (160 KiB of LDS hold the key table at load <= 1/2 and 16 bytes per aggregate
+ * and group); 0 for naggs outside 1 ... MDB_AGG_MAX_AGGS */
+uint64_t mdb_dev_group_aggregate_lds_groups(int naggs);
+
 /* ------------------------------------------------------------------ fused north-star pipeline
  *
  * SELECT l.key, COUNT(*) FROM L INNER JOIN R ON l.key = r.key GROUP BY l.key

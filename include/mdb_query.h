@@ -164,6 +164,12 @@ unsigned long long mdb_database_composite_fused(struct database *db);
  * compile to one comparison per value as before and do not count; with MDB_IN_SET=0 every list does, and a list the device program
  * cannot hold (33 values and more) is refused as "predicate too large". */
 unsigned long long mdb_database_in_set_lookups(struct database *db);
+/* SUM / MIN / MAX / AVG (an extension: upstream has COUNT only): SELECT statements of this database so far whose aggregates ran through
+ * mdb_dev_group_aggregate (mdb_dev.h), by the form the operator took - *lds_form: groups in LDS (integer cells, or MIN / MAX over DOUBLE,
+ * one group column or none, few enough groups), *sorted_form: sorted segments (SUM / AVG over DOUBLE, several group columns, many groups,
+ * MDB_AGG_LDS=0).  A GROUP BY over a column measured to hold no value twice answers with the cells themselves and counts in neither.
+ * Either pointer may be NULL. */
+int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_form, unsigned long long *sorted_form);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

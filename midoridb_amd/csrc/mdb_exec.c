@@ -113,6 +113,18 @@ int stream_apply_sel(struct exec *x, int ntabs_in_stream, const uint32_t *sel, u
 			return dev_fail(x, "re-mapping COUNT(*)");
 		x->d_count = nc;
 	}
+	for (int i = 0; i < x->nagg; i++) {	/* SUM / MIN / MAX / AVG columns of the grouped stream, with their NULL bits */
+		void *nv;
+		uint64_t *nb;
+		if (!x->d_agg[i])
+			continue;
+		nv = dalloc(x, (n_new ? n_new : 1) * 8);
+		nb = dalloc(x, ((n_new + 63) / 64 + 1) * 8);
+		if (!nv || !nb || (n_new && mdb_dev_gather64(x->dev, x->d_agg[i], x->d_agg_nulls[i], sel, n_new, nv, nb)))
+			return dev_fail(x, "re-mapping an aggregate column");
+		x->d_agg[i] = nv;
+		x->d_agg_nulls[i] = nb;
+	}
 	if (x->fused) {
 		for (int k = 0; k < (x->nfused ? x->nfused : 1); k++) {	/* (a composite key: every key column of the stream) */
 			const int64_t *from = x->nfused ? x->d_fused_keys[k] : x->d_fused_key;
@@ -1069,7 +1081,8 @@ int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, 
 			}
 		}
 	}
-	if (key >= 0 && nconj == 1 && !npconj && !x->cat->dist && x->n && only_key_needed(x, t, kr->col_idx) && join_is_total_by_catalog(x, kl, kr)) {
+	if (key >= 0 && nconj == 1 && !npconj && !x->cat->dist && x->n && !x->nagg /* (SUM / MIN / MAX / AVG: the materialising join, always) */ &&
+	    only_key_needed(x, t, kr->col_idx) && join_is_total_by_catalog(x, kl, kr)) {
 		/* join elimination: the catalog says every row of the stream has exactly one partner, and only t's key is read */
 		const int64_t *vl;
 		const uint64_t *nl;
@@ -1333,6 +1346,38 @@ double now_ms(void)
 }
 
 /* is the plan the fused north-star shape?  returns the group field's side (0 = left key, 1 = right key) or -1 */
+/* SUM / MIN / MAX / AVG: one mdb_dev_group_aggregate call for all aggregates of the statement, over the stream as it is BEFORE its rows are
+ * reduced to the groups' first rows (first[G] of the GROUP BY operator over gk[0 .. nk); nk == 0: one group, nk == MDB_AGG_IDENTITY: group i is
+ * row i).  The result columns d_agg[] have G rows and belong to the grouped stream. */
+static int stream_aggregate(struct exec *x, const struct mdb_sort_key *gk, int nk, const uint32_t *first, uint64_t G)
+{
+	struct mdb_agg ag[MDB_AGG_MAX_AGGS];
+	uint32_t form = 0;
+
+	for (int i = 0; i < x->nagg; i++) {
+		const int t = x->agg_tbl[i];
+		const struct mdb_column *col = &x->s->tabs[t].t->cols[x->agg_col[i]];
+		ag[i].op = x->agg_op[i];
+		ag[i].type = col->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+		ag[i].values = col->d_data;
+		ag[i].nullbits = col->d_nullbits;
+		ag[i].rid = x->rid[t];
+		if (!ag[i].values && !(ag[i].values = dalloc(x, 8)))	/* (an empty table under an outer join: every tuple is at "no row", no cell is read) */
+			return dev_fail(x, "aggregates");
+		x->d_agg[i] = dalloc(x, G * 8);
+		x->d_agg_nulls[i] = dalloc(x, ((G + 63) / 64 + 1) * 8);
+		ag[i].out = x->d_agg[i];
+		ag[i].out_nullbits = x->d_agg_nulls[i];
+		if (!x->d_agg[i] || !x->d_agg_nulls[i])
+			return dev_fail(x, "allocating aggregate columns");
+	}
+	if (mdb_dev_group_aggregate(x->dev, gk, nk, x->n, first, G, ag, x->nagg, &form))
+		return dev_fail(x, "SUM / MIN / MAX / AVG");
+	if (form == 1 || form == 2)
+		x->agg_calls[form - 1]++;
+	return MIDORIDB_OK;
+}
+
 /* The fused plan applies to  T0 JOIN T1 ON k0 = k1 [JOIN T2 ON (k0 | k1) = k2 ...] GROUP BY one of those keys, COUNT(*):
  * every join is an equi-join on the SAME key (each ON clause ties the new table's column to a key column already
  * in the chain); a WHERE clause must be pushable below the joins (where_pushable).  keys[t] = the key field of
@@ -1441,8 +1486,18 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	 *      of every FROM table left to right; projected afterwards to the select list */
 	for (int i = 0; i < s->nsel; i++)
 		has_count |= s->sel[i]->kind == MDB_EX_COUNT;
+	/* SUM / MIN / MAX / AVG of the select list, each (function, column) once: result column "SUM(<table>.<column>)", ordered with all the others */
+	for (int i = 0; i < s->nsel; i++)
+		if (s->sel[i]->kind == MDB_EX_AGG && agg_index(&x, s->sel[i]) < 0 && x.nagg < MDB_AGG_MAX_AGGS) {
+			x.agg_op[x.nagg] = s->sel[i]->op;
+			x.agg_tbl[x.nagg] = s->sel[i]->tbl_idx;
+			x.agg_col[x.nagg] = s->sel[i]->col_idx;
+			x.agg_type[x.nagg] = s->sel[i]->type;
+			x.nagg++;
+		}
+	const bool has_agg = x.nagg > 0;
 	{
-		int total = has_count;
+		int total = has_count + x.nagg;
 		for (int t = 0; t < s->ntabs; t++)
 			total += s->tabs[t].t->ncols;
 		keys = calloc((size_t)total, sizeof(*keys));
@@ -1456,6 +1511,12 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 		if (has_count) {
 			strcpy(keys[nkeys], "COUNT(*)");
 			key_tbl[nkeys] = -1;
+			nkeys++;
+		}
+		for (int a = 0; a < x.nagg; a++) {	/* key_tbl = -2 - a: the statement's a-th aggregate */
+			snprintf(keys[nkeys], MDB_NAME_LEN, "%s(%.56s.%.56s)", mdb_agg_name(x.agg_op[a]), s->tabs[x.agg_tbl[a]].t->name,
+				 s->tabs[x.agg_tbl[a]].t->cols[x.agg_col[a]].name);
+			key_tbl[nkeys] = -2 - a;
 			nkeys++;
 		}
 		for (int t = 0; t < s->ntabs; t++)
@@ -1497,7 +1558,8 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	bool only_count = has_count && !s->ngroup && !s->select_all;
 	for (int i = 0; i < s->nsel; i++)
 		only_count = only_count && s->sel[i]->kind == MDB_EX_COUNT;
-	fused = s->ntabs <= PUSH_TABS && !x.has_outer ? fused_chain(s, fkeys, only_count) : -1;	/* (the fused operator is an inner join) */
+	/* (the fused operator is an inner join and knows COUNT(*) only: a statement with SUM / MIN / MAX / AVG materialises its join) */
+	fused = s->ntabs <= PUSH_TABS && !x.has_outer && !has_agg ? fused_chain(s, fkeys, only_count) : -1;
 	if (fused >= 0 && !cat->dist && split_ok) {
 		/* join elimination: when the catalog says every right table of the chain is a complete primary key over the first table's key range,
 		 * the fused join + GROUP BY operator has nothing to find out - the general plan drops those joins (join_next_table) and groups the
@@ -1511,7 +1573,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	/* the join of two key columns, nothing else selected: in the reference's order it is tried as a primary-key join first (the keys with
 	 * partners in the left table's row order; large tables only: the attempt runs the ordered join + GROUP BY operator), and left to the
 	 * materialising join below when a key has several rows on a side */
-	bool keys_only = !x.has_outer && keys_only_join(s, cat, has_count, key_tbl, key_col, src, ncols, kj);
+	bool keys_only = !x.has_outer && keys_only_join(s, cat, has_count || has_agg, key_tbl, key_col, src, ncols, kj);
 	int64_t *keys_ordered = NULL;
 	uint64_t keys_ordered_rows = 0;
 	if (keys_only && !cat->groups_any_order) {
@@ -1738,7 +1800,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 		x.fused = true;
 		x.n = only_count ? J : G;	/* COUNT(*) without GROUP BY = the stream length = the joined rows */
 		x.joined_rows = J;
-	} else if (!keys_only && split_ok && (cfrc = composite_fused_plan(&x, &ws, only_count)) <= 0) {
+	} else if (!keys_only && split_ok && !has_agg && (cfrc = composite_fused_plan(&x, &ws, only_count)) <= 0) {
 		/* ---- the fused plan on a packed composite key (several ON equalities): answered, or an error */
 		if (cfrc < 0) {
 			rc = cfrc;
@@ -1770,7 +1832,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 		x.fused = true;
 		x.n = J;
 		x.joined_rows = J;
-	} else if (s->ntabs == 1 && s->where && split_ok && !ws.nresidual && ws.npush[0] && !s->ngroup && !has_count && !s->distinct &&
+	} else if (s->ntabs == 1 && s->where && split_ok && !ws.nresidual && ws.npush[0] && !s->ngroup && !has_count && !has_agg && !s->distinct &&
 		   !s->norder && !s->having && !s->has_limit && s->tabs[0].t->nrows && ncols && ncols <= MDB_GATHER_MAX_COLS) {
 		/* ---- scan + WHERE + projection of one table (BASELINE configs[0] shape): the predicate bitmap is turned
 		 *      straight into the compacted result columns (mdb_dev_filter_project) - no selection vector, no gathers */
@@ -1846,7 +1908,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 			bool placed = false;
 			for (int g = 0; g < s->ngroup; g++)
 				placed = placed || in_part(&x, s->group[g]);
-			if (!placed && cat->groups_any_order && s->ngroup == 1 && !x.fused && !s->select_all && !s->distinct &&
+			if (!placed && cat->groups_any_order && s->ngroup == 1 && !x.fused && !s->select_all && !s->distinct && !has_agg &&
 			    s->group[0]->kind == MDB_EX_FIELD && s->group[0]->type != MDB_CT_DOUBLE && s->group[0]->type != MDB_CT_VARCHAR) {
 				/* any order allowed and only the group key and COUNT(*) can be named (S4): no rows need to travel - every rank's ONE
 				 * partition pass over its key column, the first-level regions exchanged, counted where they land
@@ -1931,7 +1993,7 @@ exchange_rows:
 			 * ids or an ordering sort - the stream becomes what the fused plan's is (S4: only the group key and COUNT(*) can be
 			 * named from here on) */
 			if (cat->groups_any_order && !cat->dist && !x.fused && x.n && s->group[0]->kind == MDB_EX_FIELD && s->group[0]->type != MDB_CT_DOUBLE &&
-			    !s->select_all && !s->distinct && !x.may_be_absent[s->group[0]->tbl_idx] &&
+			    !s->select_all && !s->distinct && !has_agg /* (the (key, COUNT) pairs carry no rows to aggregate) */ && !x.may_be_absent[s->group[0]->tbl_idx] &&
 			    s->tabs[s->group[0]->tbl_idx].t->cols[s->group[0]->col_idx].null_count == 0) {
 				int64_t *gk = dalloc(&x, x.n * 8), *gc = dalloc(&x, x.n * 8);
 				uint64_t Gk = 0;
@@ -1980,6 +2042,16 @@ exchange_rows:
 				 * result kept on the device holds the table's columns */
 				struct mdb_dev_plan_info pi;
 				const bool identity = x.n && G == x.n && mdb_dev_last_plan(x.dev, &pi) == 0 && pi.group_form == 3;
+				if (has_agg && G) {
+					struct mdb_sort_key gk1;	/* (the key column as the GROUP BY operator read it: gathered already where the stream has row ids) */
+					gk1.values = kv;
+					gk1.nullbits = kn;
+					gk1.rid = NULL;
+					gk1.type = s->group[0]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+					gk1.desc = 0;
+					if ((rc = stream_aggregate(&x, &gk1, identity ? MDB_AGG_IDENTITY : 1, first, G)))
+						goto out;
+				}
 				if (!identity && (rc = stream_select(&x, s->ntabs, first, G)))
 					goto out;
 			}
@@ -2004,6 +2076,8 @@ exchange_rows:
 				rc = dev_fail(&x, "group count");
 				goto out;
 			}
+			if (has_agg && G && (rc = stream_aggregate(&x, gk, s->ngroup, first, G)))
+				goto out;
 			{
 				int64_t *cnt = x.d_count;	/* stream_select must not re-map the fresh counts */
 				x.d_count = NULL;
@@ -2013,6 +2087,9 @@ exchange_rows:
 					goto out;
 			}
 		}
+		/* SUM / MIN / MAX / AVG without GROUP BY: the whole stream is one group (an empty stream: no row, as SELECT COUNT(*) answers it) */
+		if (has_agg && !s->ngroup && x.n && (rc = stream_aggregate(&x, NULL, 0, NULL, 1)))
+			goto out;
 	}
 
 grouped:
@@ -2037,7 +2114,7 @@ grouped:
 		}
 	}
 	/* ---- HAVING -> DISTINCT -> ORDER BY -> LIMIT (SQL order of evaluation; extension) */
-	if ((rc = select_tail(&x, has_count)))
+	if ((rc = select_tail(&x, has_count || has_agg)))
 		goto out;
 
 	/* ---- projection + COUNT-only handling */
@@ -2047,7 +2124,7 @@ grouped:
 		goto out;
 	}
 	{
-		bool count_only = has_count && !s->ngroup;	/* SELECT COUNT(*) FROM ... [WHERE ...] */
+		bool count_only = (has_count || has_agg) && !s->ngroup;	/* SELECT COUNT(*) [, SUM(v) ...] FROM ... [WHERE ...]: one row */
 		uint64_t out_rows = count_only ? (x.n ? 1 : 0) : x.n;	/* the reference returns no row for an empty input */
 		if (count_only && s->has_limit && (s->limit_off > 0 || s->limit_cnt == 0))
 			out_rows = 0;
@@ -2076,7 +2153,8 @@ grouped:
 			int key = src[c];
 			memcpy(res->colname[c], keys[key], MDB_NAME_LEN);
 			for (int i = 0; s->sel_alias && !s->select_all && i < s->nsel; i++)	/* `item AS name` names the column (the first alias of an item wins) */
-				if (s->sel_alias[i][0] && (key_tbl[key] < 0 ? s->sel[i]->kind == MDB_EX_COUNT
+				if (s->sel_alias[i][0] && (key_tbl[key] <= -2 ? s->sel[i]->kind == MDB_EX_AGG && agg_index(&x, s->sel[i]) == -2 - key_tbl[key]
+							   : key_tbl[key] < 0 ? s->sel[i]->kind == MDB_EX_COUNT
 									      : s->sel[i]->kind == MDB_EX_FIELD && s->sel[i]->tbl_idx == key_tbl[key] && s->sel[i]->col_idx == key_col[key])) {
 					mdb_copy_name(res->colname[c], s->sel_alias[i]);
 					break;
@@ -2089,6 +2167,20 @@ grouped:
 				}
 				if (out_rows <= 1)
 					res->data[c][0] = 0;
+			}
+			if (key_tbl[key] <= -2) {	/* SUM / MIN / MAX / AVG: an ordinary typed column with its NULL bitmap - one row without GROUP BY */
+				const int a = -2 - key_tbl[key];
+				res->coltype[c] = x.agg_type[a];
+				if (out_rows) {
+					if (!x.d_agg[a]) {
+						ERR("execution phase: internal error (aggregate not computed)\n");
+						rc = -MIDORIDB_INTERNAL;
+						break;
+					}
+					d_vals[c] = x.d_agg[a];
+					d_nulls[c] = x.d_agg_nulls[a];
+				}
+				continue;
 			}
 			if (key_tbl[key] < 0) {
 				res->coltype[c] = MDB_CT_INTEGER;
@@ -2277,6 +2369,8 @@ out:
 	cat->joins_eliminated += (uint64_t)x.joins_eliminated;
 	cat->composite_joins += (uint64_t)x.composite_joins;
 	cat->composite_fused += (uint64_t)x.composite_fused;
+	cat->aggregate_calls[0] += (uint64_t)x.agg_calls[0];
+	cat->aggregate_calls[1] += (uint64_t)x.agg_calls[1];
 	shard_cleanup(&x);
 	free_all(&x);
 	mdb_result_free(res);

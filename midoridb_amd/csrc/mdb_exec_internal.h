@@ -67,7 +67,24 @@ struct exec {
 	bool may_be_absent[MDB_MAX_TABS];
 	bool pred_err_said;			/* pred_compile() failed for a cause it has written into err itself (pred_compile_failed keeps it) */
 	bool has_outer;				/* some join of the statement is an outer join: no plan that assumes inner semantics */
+	/* SUM / MIN / MAX / AVG: the select list's aggregates, each (function, column) once.  After GROUP BY (or over the whole stream, without one)
+	 * d_agg[i] / d_agg_nulls[i] are their result columns over the grouped stream: row k belongs to row k of the stream, as d_count[k] does, and
+	 * follows it through HAVING, DISTINCT, ORDER BY and LIMIT (stream_apply_sel).  A statement with one of them takes the general plan only */
+	int nagg;
+	int agg_op[MDB_AGG_MAX_AGGS], agg_tbl[MDB_AGG_MAX_AGGS], agg_col[MDB_AGG_MAX_AGGS], agg_type[MDB_AGG_MAX_AGGS];	/* agg_type: the result's column type */
+	void *d_agg[MDB_AGG_MAX_AGGS];
+	uint64_t *d_agg_nulls[MDB_AGG_MAX_AGGS];
+	int agg_calls[2];			/* mdb_dev_group_aggregate calls by form: [0] groups in LDS, [1] sorted segments */
 };
+
+/* which of the statement's aggregates e (MDB_EX_AGG, resolved) is; -1: none */
+static inline int agg_index(const struct exec *x, const struct mdb_expr *e)
+{
+	for (int i = 0; i < x->nagg; i++)
+		if (x->agg_op[i] == e->op && x->agg_tbl[i] == e->tbl_idx && x->agg_col[i] == e->col_idx)
+			return i;
+	return -1;
+}
 
 struct pred_prog {
 	struct mdb_pred_insn insn[MDB_PRED_MAX_INSNS];
@@ -99,6 +116,10 @@ int operand_type(const struct mdb_expr *o, const struct mdb_expr *other, bool dm
 int check_predicate_x(const struct mdb_expr *e, const char *clause, bool dml, char *err, size_t errlen);
 int check_predicate(const struct mdb_expr *e, const char *clause, char *err, size_t errlen);
 bool expr_has_count(const struct mdb_expr *e);
+bool expr_has_agg(const struct mdb_expr *e);
+bool agg_eq(const struct mdb_expr *a, const struct mdb_expr *b);
+const char *mdb_agg_name(int op);
+int mdb_agg_result_type(int op, int coltype);
 int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, const char *clause, char *err, size_t errlen);
 int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, size_t errlen);
 int dev_fail(struct exec *x, const char *what);

@@ -17,6 +17,11 @@ void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values,
 		*values = x->d_count;
 		*nullbits = NULL;
 		*rid = NULL;
+	} else if (f->kind == MDB_EX_AGG) {	/* a result column of mdb_dev_group_aggregate over the grouped stream (resolve_agg_refs: it is one of the statement's) */
+		const int i = agg_index(x, f);
+		*values = i >= 0 ? x->d_agg[i] : NULL;
+		*nullbits = i >= 0 ? x->d_agg_nulls[i] : NULL;
+		*rid = NULL;
 	} else if (x->fused) {
 		*values = fused_key_column(x, f->tbl_idx, f->col_idx);
 		*nullbits = NULL;
@@ -31,7 +36,11 @@ void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values,
 
 int pred_slot(struct exec *x, struct pred_prog *p, const struct mdb_expr *f)
 {
-	const int st = f->kind == MDB_EX_COUNT ? -2 : f->tbl_idx, sc = f->kind == MDB_EX_COUNT ? -2 : f->col_idx;
+	/* slot keys: (table, column) of a field; -2 COUNT(*); -3 - i the statement's i-th aggregate */
+	const int ak = f->kind == MDB_EX_AGG ? -3 - agg_index(x, f) : 0;
+	const int st = f->kind == MDB_EX_COUNT ? -2 : f->kind == MDB_EX_AGG ? ak : f->tbl_idx, sc = f->kind == MDB_EX_COUNT ? -2 : f->kind == MDB_EX_AGG ? ak : f->col_idx;
+	if (f->kind == MDB_EX_AGG && agg_index(x, f) < 0)
+		return -1;
 	for (int i = 0; i < p->ncols; i++)
 		if (p->slot_tbl[i] == st && p->slot_col[i] == sc)
 			return i;
@@ -214,7 +223,8 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 		return pred_emit(p, e->op == 0 ? MDB_P_AND : (e->op == 1 ? MDB_P_OR : MDB_P_XOR), 0, 0, 0, 0, 0);
 	case MDB_EX_CMP: {
 		const struct mdb_expr *l = e->kids[0], *r = e->kids[1];
-		const bool lcol = l->kind == MDB_EX_FIELD || l->kind == MDB_EX_COUNT, rcol = r->kind == MDB_EX_FIELD || r->kind == MDB_EX_COUNT;
+		const bool lcol = l->kind == MDB_EX_FIELD || l->kind == MDB_EX_COUNT || l->kind == MDB_EX_AGG;
+		const bool rcol = r->kind == MDB_EX_FIELD || r->kind == MDB_EX_COUNT || r->kind == MDB_EX_AGG;
 		if (lcol && rcol) {
 			if (l->kind == MDB_EX_FIELD && l->type == MDB_CT_TINYINT && e->op != MDB_CMP_EQ && e->op != MDB_CMP_NE)
 				return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
@@ -222,7 +232,7 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 			b = pred_slot(x, p, r);
 			if (a < 0 || b < 0)
 				return -1;
-			return pred_emit(p, MDB_P_CMP_COL_COL, e->op, (l->kind == MDB_EX_FIELD && l->type == MDB_CT_DOUBLE) ? MDB_T_DOUBLE : MDB_T_INT64,
+			return pred_emit(p, MDB_P_CMP_COL_COL, e->op, (l->kind != MDB_EX_COUNT && l->type == MDB_CT_DOUBLE) ? MDB_T_DOUBLE : MDB_T_INT64,
 					 a, b, 0);
 		}
 		if (lcol || rcol) {
@@ -236,8 +246,8 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 			if (a < 0)
 				return -1;
 			return pred_emit(p, lcol ? MDB_P_CMP_COL_CONST : MDB_P_CMP_CONST_COL, e->op,
-					 (f->kind == MDB_EX_FIELD && f->type == MDB_CT_DOUBLE) ? MDB_T_DOUBLE : MDB_T_INT64, a, 0,
-					 lit_bits_for(v, f->kind == MDB_EX_FIELD ? f->type : MDB_CT_INTEGER));
+					 (f->kind != MDB_EX_COUNT && f->type == MDB_CT_DOUBLE) ? MDB_T_DOUBLE : MDB_T_INT64, a, 0,
+					 lit_bits_for(v, f->kind != MDB_EX_COUNT ? f->type : MDB_CT_INTEGER));	/* (an aggregate: its result's type) */
 		}
 		return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, const_cmp(e->op, l, r));
 	}

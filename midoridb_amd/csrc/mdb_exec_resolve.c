@@ -13,8 +13,87 @@ bool field_eq(const struct mdb_expr *a, const struct mdb_expr *b)
 	return a->kind == MDB_EX_FIELD && b->kind == MDB_EX_FIELD && a->tbl_idx == b->tbl_idx && a->col_idx == b->col_idx;
 }
 
-/* a bare name that is a select-list alias stands for the aliased item: a column (any clause) or COUNT(*) (HAVING); names of real columns win */
-static void subst_alias(const struct mdb_select *s, struct mdb_expr *e, bool count_ok)
+/* SUM / MIN / MAX / AVG: the function's name and the column type of its result over a column of type coltype */
+const char *mdb_agg_name(int op)
+{
+	return op == MDB_AGG_SUM ? "SUM" : op == MDB_AGG_MIN ? "MIN" : op == MDB_AGG_MAX ? "MAX" : "AVG";
+}
+
+int mdb_agg_result_type(int op, int coltype)
+{
+	if (op == MDB_AGG_AVG)
+		return MDB_CT_DOUBLE;
+	if (op == MDB_AGG_SUM)
+		return coltype == MDB_CT_DOUBLE ? MDB_CT_DOUBLE : MDB_CT_INTEGER;
+	return coltype;
+}
+
+bool agg_eq(const struct mdb_expr *a, const struct mdb_expr *b)
+{
+	return a->kind == MDB_EX_AGG && b->kind == MDB_EX_AGG && a->op == b->op && a->tbl_idx == b->tbl_idx && a->col_idx == b->col_idx;
+}
+
+/* an aggregate as the parser left it (kid[0] = its column): the column is resolved and the type rules are applied - no function over VARCHAR
+ * (the cells are dictionary ids, which are not in string order), no SUM / AVG over DATE / DATETIME */
+static int resolve_agg(struct mdb_select *s, struct mdb_expr *e, char *err, size_t errlen)
+{
+	int rc;
+	struct mdb_expr *c;
+
+	if (e->nkids != 1 || (e->kids[0]->kind != MDB_EX_NAME && e->kids[0]->kind != MDB_EX_FIELD)) {
+		ERR("%s takes one column\n", mdb_agg_name(e->op));
+		return -MIDORIDB_ERROR;
+	}
+	c = e->kids[0];
+	if ((rc = resolve_expr(s, c, err, errlen)))
+		return rc;
+	if (c->type == MDB_CT_VARCHAR) {
+		ERR("%s over the VARCHAR column '%.100s.%.100s' is not supported: its cells are dictionary ids, which are not in string order\n",
+		    mdb_agg_name(e->op), c->tbl, c->col);
+		return -MIDORIDB_ERROR;
+	}
+	if ((e->op == MDB_AGG_SUM || e->op == MDB_AGG_AVG) && (c->type == MDB_CT_DATE || c->type == MDB_CT_DATETIME)) {
+		ERR("%s over the %s column '%.100s.%.100s' is not supported: only MIN and MAX of a point in time mean something\n", mdb_agg_name(e->op),
+		    c->type == MDB_CT_DATE ? "DATE" : "DATETIME", c->tbl, c->col);
+		return -MIDORIDB_ERROR;
+	}
+	mdb_copy_name(e->tbl, c->tbl);
+	mdb_copy_name(e->col, c->col);
+	e->tbl_idx = c->tbl_idx;
+	e->col_idx = c->col_idx;
+	e->type = mdb_agg_result_type(e->op, c->type);
+	return MIDORIDB_OK;
+}
+
+/* the aggregates under a HAVING / ORDER BY expression that repeat their function and column (an alias has been replaced by its item already):
+ * each must be one of the select list's - the executor computes those and nothing else */
+static int resolve_agg_refs(struct mdb_select *s, struct mdb_expr *e, const char *clause, char *err, size_t errlen)
+{
+	int rc;
+
+	if (!e)
+		return MIDORIDB_OK;
+	if (e->kind == MDB_EX_AGG) {
+		bool found = false;
+		if (e->nkids && (rc = resolve_agg(s, e, err, errlen)))
+			return rc;
+		for (int i = 0; i < s->nsel && !found; i++)
+			found = agg_eq(s->sel[i], e);
+		if (!found) {
+			ERR("%s(%.100s.%.100s) in the %s clause must also stand in the select list\n", mdb_agg_name(e->op), e->tbl, e->col, clause);
+			return -MIDORIDB_ERROR;
+		}
+		return MIDORIDB_OK;
+	}
+	for (int i = 0; i < e->nkids; i++)
+		if ((rc = resolve_agg_refs(s, e->kids[i], clause, err, errlen)))
+			return rc;
+	return MIDORIDB_OK;
+}
+
+/* a bare name that is a select-list alias stands for the aliased item: a column (any clause), COUNT(*) (HAVING: count_ok) or an aggregate (HAVING,
+ * ORDER BY: agg_ok); names of real columns win */
+static void subst_alias(const struct mdb_select *s, struct mdb_expr *e, bool count_ok, bool agg_ok)
 {
 	if (!e)
 		return;
@@ -38,12 +117,22 @@ static void subst_alias(const struct mdb_select *s, struct mdb_expr *e, bool cou
 				e->kind = MDB_EX_COUNT;
 				e->op = to->op;
 				e->ival = to->ival;
+			} else if (to->kind == MDB_EX_AGG && agg_ok) {	/* (resolved; the copy has no kid) */
+				e->kind = MDB_EX_AGG;
+				e->op = to->op;
+				mdb_copy_name(e->tbl, to->tbl);
+				mdb_copy_name(e->col, to->col);
+				e->tbl_idx = to->tbl_idx;
+				e->col_idx = to->col_idx;
+				e->type = to->type;
 			}
 			return;
 		}
 	}
+	if (e->kind == MDB_EX_AGG)
+		return;		/* (the argument of an aggregate is a column, never an alias) */
 	for (int i = 0; i < e->nkids; i++)
-		subst_alias(s, e->kids[i], count_ok);
+		subst_alias(s, e->kids[i], count_ok, agg_ok);
 }
 
 int resolve_expr(struct mdb_select *s, struct mdb_expr *e, char *err, size_t errlen)
@@ -116,7 +205,7 @@ bool is_having_clause(const char *clause)
 int operand_type(const struct mdb_expr *o, const struct mdb_expr *other, bool dml)
 {
 	switch (o->kind) {
-	case MDB_EX_FIELD: return o->type;
+	case MDB_EX_FIELD: case MDB_EX_AGG: return o->type;	/* (an aggregate: its result's type) */
 	case MDB_EX_INT: case MDB_EX_COUNT: return MDB_CT_INTEGER;
 	case MDB_EX_FLOAT: return MDB_CT_DOUBLE;
 	case MDB_EX_BOOL: return MDB_CT_TINYINT;
@@ -140,7 +229,7 @@ int check_predicate_x(const struct mdb_expr *e, const char *clause, bool dml, ch
 		const struct mdb_expr *l = e->kids[0], *r = e->kids[1];
 		for (int i = 0; i < 2; i++) {
 			const struct mdb_expr *o = e->kids[i];
-			if (o->kind == MDB_EX_COUNT && is_having_clause(clause))
+			if ((o->kind == MDB_EX_COUNT || o->kind == MDB_EX_AGG) && is_having_clause(clause))
 				continue;
 			if (o->kind != MDB_EX_FIELD && o->kind != MDB_EX_INT && o->kind != MDB_EX_FLOAT && o->kind != MDB_EX_NULL &&
 			    o->kind != MDB_EX_BOOL && o->kind != MDB_EX_STRING) {
@@ -211,6 +300,9 @@ int check_predicate_x(const struct mdb_expr *e, const char *clause, bool dml, ch
 	case MDB_EX_COUNT:
 		ERR("COUNT function can't be used in the %s-clause\n", clause);
 		return -MIDORIDB_ERROR;
+	case MDB_EX_AGG:
+		ERR("%s function can't be used in the %s-clause\n", mdb_agg_name(e->op), clause);
+		return -MIDORIDB_ERROR;
 	case MDB_EX_LIKE:
 		/* upstream parses LIKE, checks its operands (semantic_select.c) and then evaluates it - and NOT LIKE - to TRUE for every
 		 * row, NULL cells included (executor_select.c:1027-1074: no case for it): a defect, not a semantics to keep.  Here it
@@ -242,6 +334,16 @@ bool expr_has_count(const struct mdb_expr *e)
 	return false;
 }
 
+bool expr_has_agg(const struct mdb_expr *e)
+{
+	if (e->kind == MDB_EX_AGG)
+		return true;
+	for (int i = 0; i < e->nkids; i++)
+		if (expr_has_agg(e->kids[i]))
+			return true;
+	return false;
+}
+
 /* every field under e appears in the select list ("SELECT list is not in <clause> clause", the reference's
  * wording, semantic_select.c:1836-1852, 1965-1985) */
 int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, const char *clause, char *err, size_t errlen)
@@ -256,8 +358,8 @@ int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, 
 			return -MIDORIDB_ERROR;
 		}
 	}
-	if (e->kind == MDB_EX_COUNT)
-		return MIDORIDB_OK;
+	if (e->kind == MDB_EX_COUNT || e->kind == MDB_EX_AGG)
+		return MIDORIDB_OK;	/* (an aggregate's column need not be selected: the aggregate itself must be, resolve_agg_refs) */
 	for (int i = 0; i < e->nkids; i++)
 		if ((rc = fields_in_select_list(s, e->kids[i], clause, err, errlen)))
 			return rc;
@@ -315,7 +417,7 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		if (e->kind != MDB_EX_ALIAS || e->nkids != 1)
 			continue;
 		struct mdb_expr *kid = e->kids[0];
-		if (kid->kind != MDB_EX_NAME && kid->kind != MDB_EX_FIELD && kid->kind != MDB_EX_COUNT)
+		if (kid->kind != MDB_EX_NAME && kid->kind != MDB_EX_FIELD && kid->kind != MDB_EX_COUNT && kid->kind != MDB_EX_AGG)
 			continue;	/* (an aliased expression: rejected below like the expression itself) */
 		if (!s->sel_alias && !(s->sel_alias = calloc((size_t)s->nsel, sizeof(*s->sel_alias)))) {
 			ERR("out of memory\n");
@@ -331,6 +433,7 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		mdb_expr_free(e);
 		s->sel[i] = kid;
 	}
+	int nagg = 0;
 	for (int i = 0; i < s->nsel; i++) {
 		struct mdb_expr *e = s->sel[i];
 		if (e->kind == MDB_EX_COUNT) {
@@ -339,8 +442,23 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 					return rc;
 			continue;
 		}
+		if (e->kind == MDB_EX_AGG) {
+			/* SUM / MIN / MAX / AVG over one column: an extension (upstream knows COUNT only) */
+			if (++nagg > MDB_AGG_MAX_AGGS) {
+				ERR("more than %d SUM / MIN / MAX / AVG aggregates in one select list are not supported\n", MDB_AGG_MAX_AGGS);
+				return -MIDORIDB_ERROR;
+			}
+			if (cat->dist) {
+				/* (known from the statement alone: every rank leaves here together, before anything is exchanged) */
+				ERR("sharded mode: %s is not executed (SUM / MIN / MAX / AVG run on one GPU)\n", mdb_agg_name(e->op));
+				return -MIDORIDB_ERROR;
+			}
+			if ((rc = resolve_agg(s, e, err, errlen)))
+				return rc;
+			continue;
+		}
 		if (e->kind != MDB_EX_NAME && e->kind != MDB_EX_FIELD) {
-			ERR("only columns and COUNT(*) - with or without an alias - are supported in the select list (expressions are not executed by the reference)\n");
+			ERR("only columns, COUNT(*) and SUM / MIN / MAX / AVG of a column - with or without an alias - are supported in the select list (expressions are not executed by the reference)\n");
 			return -MIDORIDB_ERROR;
 		}
 		if ((rc = resolve_expr(s, e, err, errlen)))
@@ -358,7 +476,7 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		return -MIDORIDB_ERROR;
 	}
 	for (int i = 0; i < s->ngroup; i++) {
-		subst_alias(s, s->group[i], false);
+		subst_alias(s, s->group[i], false, false);
 		if (s->group[i]->kind != MDB_EX_NAME && s->group[i]->kind != MDB_EX_FIELD) {
 			ERR("group-by clauses support only fields and aliases\n");
 			return -MIDORIDB_ERROR;
@@ -370,7 +488,7 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 	{
 		int ncount = 0, nfield = 0;
 		for (int i = 0; i < s->nsel; i++) {
-			if (s->sel[i]->kind == MDB_EX_COUNT) {
+			if (s->sel[i]->kind == MDB_EX_COUNT || s->sel[i]->kind == MDB_EX_AGG) {	/* (an aggregate stands where COUNT(*) may) */
 				ncount++;
 				continue;
 			}
@@ -395,12 +513,14 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		}
 		/* ---- DISTINCT / HAVING / ORDER BY / LIMIT: parsed and checked but never executed upstream (SURVEY 8a
 		 *      D7); executed here with SQL semantics (8f row 4), under the reference's own semantic rules */
-		if (s->distinct && (s->ngroup || ncount)) {
+		if (s->distinct && (s->ngroup || ncount) && !nagg) {	/* (with an aggregate DISTINCT runs over the grouped stream, select_tail) */
 			ERR("DISTINCT can't be combined with GROUP BY / COUNT on the MI355X path\n");
 			return -MIDORIDB_ERROR;
 		}
 		if (s->having) {
-			subst_alias(s, s->having, true);
+			subst_alias(s, s->having, true, true);
+			if ((rc = resolve_agg_refs(s, s->having, "HAVING", err, errlen)))
+				return rc;
 			if ((rc = resolve_expr(s, s->having, err, errlen)) || (rc = check_predicate(s->having, "having", err, errlen)))
 				return rc;
 			/* fields must come from the SELECT list (check_having_clause_inselect, semantic_select.c:1953-2001) */
@@ -410,6 +530,10 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 				ERR("COUNT in the having-clause requires a GROUP BY clause on the MI355X path\n");
 				return -MIDORIDB_ERROR;
 			}
+			if (nagg && !s->ngroup) {
+				ERR("HAVING over an ungrouped aggregate is not supported on the MI355X path\n");
+				return -MIDORIDB_ERROR;
+			}
 			if (ncount && !s->ngroup) {
 				ERR("HAVING over an ungrouped COUNT is not supported on the MI355X path\n");
 				return -MIDORIDB_ERROR;
@@ -417,7 +541,12 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		}
 		for (int i = 0; i < s->norder; i++) {
 			struct mdb_expr *o = s->order[i];
-			subst_alias(s, o, false);
+			subst_alias(s, o, false, true);
+			if (o->kind == MDB_EX_AGG) {	/* an aggregate of the select list, repeated or by its alias: ordered by its result column */
+				if ((rc = resolve_agg_refs(s, o, "ORDER BY", err, errlen)))
+					return rc;
+				continue;
+			}
 			if (o->kind == MDB_EX_COUNT) {		/* check_orderby_clause_count, semantic_select.c:1755-1795 */
 				ERR("COUNT function can't be used in the orderby-clause\n");
 				return -MIDORIDB_ERROR;

@@ -43,6 +43,20 @@ int select_tail(struct exec *x, int has_count)
 					tbl0 = t;
 				nk++;
 			}
+		/* (DISTINCT beside SUM / MIN / MAX / AVG - the one case in which it meets a grouped stream: rows are equal when their aggregate
+		 * columns, and COUNT(*) when it is selected, are equal too) */
+		for (int i = 0; x->nagg && i < s->nsel; i++) {
+			if (s->sel[i]->kind != MDB_EX_COUNT && s->sel[i]->kind != MDB_EX_AGG)
+				continue;
+			if (nk == MDB_SORT_MAX_KEYS) {
+				snprintf(x->err, x->errlen, "DISTINCT over more than %d columns is not supported\n", MDB_SORT_MAX_KEYS);
+				return -MIDORIDB_ERROR;
+			}
+			bind_operand(x, s->sel[i], &keys[nk].values, &keys[nk].nullbits, &keys[nk].rid);
+			keys[nk].type = s->sel[i]->kind == MDB_EX_AGG && s->sel[i]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+			keys[nk].desc = 0;
+			nk++;
+		}
 		sel = dalloc(x, x->n * 4);
 		if (!sel)
 			return dev_fail(x, "allocating the DISTINCT selection");
@@ -76,7 +90,7 @@ int select_tail(struct exec *x, int has_count)
 		uint32_t *perm;
 		for (int i = 0; i < s->norder; i++) {
 			bind_operand(x, s->order[i], &keys[i].values, &keys[i].nullbits, &keys[i].rid);
-			keys[i].type = s->order[i]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+			keys[i].type = s->order[i]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;	/* (an aggregate: its result's type) */
 			keys[i].desc = s->order_desc[i];
 		}
 		/* ORDER BY ... LIMIT: only the first offset + count rows of the order are ever looked at - top-k selection instead

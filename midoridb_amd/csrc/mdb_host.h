@@ -126,6 +126,7 @@ struct mdb_catalog {
 	uint64_t joins_eliminated;	/* tables of SELECT statements that were not joined at all: the catalog said every row has exactly one partner (mdb_exec.c) */
 	uint64_t composite_joins;	/* joins of SELECT statements that ran on a packed composite key (mdb_exec.c, composite_join_keys) */
 	uint64_t composite_fused;	/* SELECT statements answered by the fused join + GROUP BY operator on a packed composite key (mdb_exec.c, composite_fused_plan) */
+	uint64_t aggregate_calls[2];	/* mdb_dev_group_aggregate calls of SELECT statements by form: [0] groups in LDS, [1] sorted segments (mdb_exec.c) */
 	uint64_t in_set_lookups;	/* IN / NOT IN lists compiled to one device lookup (mdb_exec_pred.c, pred_compile_in_lookup) */
 	bool groups_any_order;		/* mdb_database_groups_any_order(): GROUP BY over a join need not keep first-occurrence order */
 	bool results_on_device;		/* mdb_database_results_on_device(): SELECT results stay in HBM until a consumer reads them */
@@ -184,6 +185,8 @@ enum mdb_expr_kind {
 	MDB_EX_LIKE,
 	MDB_EX_ARITH,		/* + - * / % NEG: parsed, rejected by the executor like select-list math is ignored upstream */
 	MDB_EX_ALIAS,		/* alias wrapper around kid[0] */
+	MDB_EX_AGG,		/* SUM / MIN / MAX / AVG (col): op = enum mdb_agg_op, kid[0] = the column; resolved: tbl_idx / col_idx / tbl / col are the
+				 * column's, type = the RESULT's column type (mdb_agg_result_type) */
 };
 
 struct mdb_expr {

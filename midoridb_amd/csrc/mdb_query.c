@@ -328,6 +328,18 @@ unsigned long long mdb_database_in_set_lookups(struct database *db)
 	return cat ? cat->in_set_lookups : 0ull;
 }
 
+int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_form, unsigned long long *sorted_form)
+{
+	struct mdb_catalog *cat = db ? db->tables : NULL;
+	if (!cat)
+		return -MIDORIDB_ERROR;
+	if (lds_form)
+		*lds_form = cat->aggregate_calls[0];
+	if (sorted_form)
+		*sorted_form = cat->aggregate_calls[1];
+	return MIDORIDB_OK;
+}
+
 double query_exec_ms(struct result_set *res)
 {
 	return res && res->table ? ((struct mdb_result *)res->table)->exec_ms : 0.0;

@@ -24,7 +24,7 @@
 #include <ctype.h>
 
 enum tk {
-	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_ANDOP, T_OROP, T_ERR
+	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_FAGG, T_ANDOP, T_OROP, T_ERR
 };
 
 static const char *const KEYWORDS[] = {
@@ -229,6 +229,13 @@ static void next(struct parser *p)
 			l->type = T_FCOUNT;
 			return;
 		}
+		/* SUM( MIN( MAX( AVG( - an extension (upstream lexes COUNT( only): a function only with the parenthesis right behind the name,
+		 * as COUNT; a column called `sum` stays a name */
+		if (s[j] == '(' && (strcmp(up, "SUM") == 0 || strcmp(up, "MIN") == 0 || strcmp(up, "MAX") == 0 || strcmp(up, "AVG") == 0)) {
+			l->type = T_FAGG;
+			strcpy(l->text, up);
+			return;
+		}
 		if (strcmp(up, "TRUE") == 0 || strcmp(up, "FALSE") == 0 || strcmp(up, "UNKNOWN") == 0) {
 			l->type = T_BOOL;
 			l->ival = up[0] == 'T' ? 1 : (up[0] == 'F' ? 0 : -1);
@@ -405,6 +412,43 @@ static void parse_primary(struct parser *p)
 			emit(p, "COUNTFIELD");
 		}
 		return;
+	case T_FAGG: {
+		/* SUM(col) | SUM(tbl.col): one column, nothing else (no arithmetic, no DISTINCT) - "NAME col" / "FIELDNAME tbl.col", then "AGG SUM" */
+		char fn[8], first[256];
+		snprintf(fn, sizeof(fn), "%.3s", l->text);
+		if (p->dml) {
+			fail(p, "aggregate function %s can't be used in DELETE / UPDATE", fn);
+			return;
+		}
+		next(p);
+		expect_punct(p, '(');
+		if (p->failed)
+			return;
+		if (p->lx.type != T_NAME) {
+			fail(p, "syntax error, %s takes one column: %s(col) or %s(tbl.col)", fn, fn, fn);
+			return;
+		}
+		strcpy(first, p->lx.text);
+		next(p);
+		if (is_punct(p, '.')) {
+			next(p);
+			if (p->lx.type != T_NAME) {
+				fail(p, "syntax error, expecting column name after '.'");
+				return;
+			}
+			emit(p, "FIELDNAME %s.%s", first, p->lx.text);
+			next(p);
+		} else {
+			emit(p, "NAME %s", first);
+		}
+		if (!is_punct(p, ')')) {
+			fail(p, "syntax error, %s takes one column: %s(col) or %s(tbl.col)", fn, fn, fn);
+			return;
+		}
+		next(p);
+		emit(p, "AGG %s", fn);
+		return;
+	}
 	case T_KW:
 		if (strcmp(l->text, "NULL") == 0) {
 			emit(p, "NULL");

@@ -21,6 +21,8 @@ P_CMP_COL_CONST, P_CMP_CONST_COL, P_CMP_COL_COL, P_ISNULL, P_CONST, P_AND, P_OR,
 P_IN_BITS, P_IN_SET = 9, 10
 CMP_LT, CMP_GT, CMP_NE, CMP_EQ, CMP_LE, CMP_GE = 1, 2, 3, 4, 5, 6
 T_INT64, T_DOUBLE = 0, 1
+AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG = 1, 2, 3, 4     # enum mdb_agg_op
+AGG_IDENTITY = -1                                   # MDB_AGG_IDENTITY: group i is row i
 
 
 class PredInsn(ctypes.Structure):
@@ -44,6 +46,11 @@ class PayloadRight(ctypes.Structure):     # struct mdb_dev_payload_right (includ
 
 class SortKey(ctypes.Structure):
     _fields_ = [("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p), ("type", c_int32), ("desc", c_int32)]
+
+
+class Agg(ctypes.Structure):     # struct mdb_agg (include/mdb_dev.h)
+    _fields_ = [("op", c_int32), ("type", c_int32), ("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p), ("out", c_void_p),
+                ("out_nullbits", c_void_p)]
 
 
 class GatherCol(ctypes.Structure):
@@ -254,6 +261,8 @@ def _bind(lib):
         "mdb_dev_set_insn": ([P, c_int, c_int, POINTER(PredInsn)], c_int),
         "mdb_dev_set_free": ([P, P], c_int),
         "mdb_dev_in_set_lds_values": ([], c_uint64),
+        "mdb_dev_group_aggregate": ([P, POINTER(SortKey), c_int, c_uint64, P, c_uint64, POINTER(Agg), c_int, POINTER(c_uint32)], c_int),
+        "mdb_dev_group_aggregate_lds_groups": ([c_int], c_uint64),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -271,6 +280,7 @@ DEV_SYMBOLS = [
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
     "mdb_set_build", "mdb_set_image_free", "mdb_set_image_contains", "mdb_dev_set_create", "mdb_dev_set_insn", "mdb_dev_set_free", "mdb_dev_in_set_lds_values",
+    "mdb_dev_group_aggregate", "mdb_dev_group_aggregate_lds_groups",
 ]
 
 
@@ -906,6 +916,37 @@ class DeviceCtx:
         self._chk(self.lib.mdb_dev_group_count_multi(self.h, self._sort_keys(keys), len(keys), n, _ptr(first), _ptr(count), n, byref(g)),
                   "group_count_multi")
         return first[:g.value], count[:g.value]
+
+    def group_aggregate(self, keys, n, first, aggs, groups=None):
+        """SUM / MIN / MAX / AVG per group (mdb_dev_group_aggregate).  keys = the group key columns as sort_perm takes them ([]: the whole
+        stream is one group; AGG_IDENTITY: group i is row i), first = int32 tensor of the groups' first stream positions (ascending; None
+        without keys), aggs = [(AGG_SUM | AGG_MIN | AGG_MAX | AGG_AVG, T_INT64 | T_DOUBLE, values, nullbits or None, rid or None), ...]
+        -> (result columns: int64 or float64 tensors of G cells, NULL flags: bool numpy arrays of G, the form that ran: 1 groups in LDS,
+        2 sorted segments, 3 identity)."""
+        identity = isinstance(keys, int) and keys == AGG_IDENTITY
+        nkeys = AGG_IDENTITY if identity else len(keys)
+        G = groups if groups is not None else (n if identity else (first.numel() if first is not None else 1))
+        arr = (Agg * len(aggs))()
+        outs, nbs = [], []
+        for i, (op, ty, v, nb, rid) in enumerate(aggs):
+            as_double = op == AGG_AVG or (ty == T_DOUBLE)
+            out = torch.zeros(max(G, 1), dtype=torch.float64 if as_double else torch.int64, device=self.device)
+            onb = torch.zeros((G + 63) // 64 or 1, dtype=torch.int64, device=self.device)
+            arr[i].op, arr[i].type = op, ty
+            arr[i].values = v.data_ptr()
+            arr[i].nullbits = nb.data_ptr() if nb is not None else None
+            arr[i].rid = rid.data_ptr() if rid is not None else None
+            arr[i].out, arr[i].out_nullbits = out.data_ptr(), onb.data_ptr()
+            outs.append(out)
+            nbs.append(onb)
+        form = c_uint32(0)
+        karr = None if identity or not keys else self._sort_keys(keys)
+        self._chk(self.lib.mdb_dev_group_aggregate(self.h, karr, nkeys, n, _ptr(first), G, arr, len(aggs), byref(form)), "group_aggregate")
+        return ([o[:G] for o in outs], [unpack_nullbits(b.cpu().numpy().view(np.uint64), G) for b in nbs], form.value)
+
+    def group_aggregate_lds_groups(self, naggs):
+        """the largest group count the LDS form of group_aggregate takes for naggs aggregates (mdb_dev_group_aggregate_lds_groups)"""
+        return int(self.lib.mdb_dev_group_aggregate_lds_groups(int(naggs)))
 
     def sort_perm(self, keys, n):
         """ORDER BY: keys = [(values, nullbits or None, rid or None, T_INT64 | T_DOUBLE, desc bool), ...] ->
