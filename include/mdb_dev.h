@@ -374,7 +374,10 @@ int mdb_dev_filter(mdb_dev_ctx *ctx, const struct mdb_pred_insn *prog, int n_ins
  * over the row blocks) - no bitmap pass, no scan, no selection vector.  proj[c].values / nullbits: base columns of the
  * scanned table (no row-id vectors); *proj[c].out_values / *proj[c].out_nullbits: device buffers allocated by the call
  * with room for all n rows, of which the first *out_count hold the result (release with mdb_dev_free; out_nullbits
- * stays NULL for a column without NULL bitmap).  Synchronises. */
+ * stays NULL for a column without NULL bitmap).  The one-pass kernels read two rows per 16-byte load, of the predicate's
+ * column and of every projected one: when a bound column has a row-id vector or is not 16-byte aligned, or a projected
+ * column is not 16-byte aligned, the call takes the bitmap kernel followed by a look-back tail that copies cell by cell -
+ * the same result, still one launch.  Synchronises. */
 struct mdb_project_col {
 	const void *values;
 	const uint64_t *nullbits;

@@ -683,10 +683,12 @@ __device__ static inline void scan_project_body(const int64_t *__restrict__ vals
 				if (p1)
 					a.dst[c][pos1] = (uint64_t)x.y;
 				if (a.dst_null[c]) {	/* (a projected column other than the predicate's may hold NULLs in surviving rows) */
-					const uint64_t nw = a.src_null[c][k0 >> 6] >> (k0 & 63);
-					if (p0 && (nw & 1ull))
+					/* only a lane with a survivor reads the NULL word (k0 is even: one word holds both rows' bits): the span's lanes past
+					 * row n would read beyond the bitmap */
+					const uint64_t *const nwp = a.src_null[c] + (k0 >> 6);
+					if (p0 && ((*nwp >> (k0 & 63)) & 1ull))
 						atomicOr(&a.dst_null[c][pos0 >> 6], 1ull << (pos0 & 63));
-					if (p1 && (nw & 2ull))
+					if (p1 && ((*nwp >> (k0 & 63)) & 2ull))
 						atomicOr(&a.dst_null[c][pos1 >> 6], 1ull << (pos1 & 63));
 				}
 			}
@@ -1070,6 +1072,38 @@ __global__ __launch_bounds__(FILT_THREADS) void k_bits_to_sel(const uint64_t *__
 
 static inline uint32_t filt_blocks(uint64_t n) { return (uint32_t)((n + FILT_TUPLES_PER_BLOCK - 1) / FILT_TUPLES_PER_BLOCK); }
 
+/* base-table stream: EVERY bound column - used by the program or not - without a row-id vector and 16-byte aligned, so that the
+ * kernels with paired 16-byte loads may read it (a program of constants only has no column to stream) */
+static bool filter_direct(const pred_args *p, int n_cols)
+{
+	bool direct = n_cols >= 1;
+	for (int c = 0; c < n_cols; c++)
+		direct = direct && !p->cols[c].rid && ((uintptr_t)p->cols[c].values & 15) == 0;
+	return direct;
+}
+
+/* may scan_project_body write the outputs of `fz`?  It reads every projected column with 16-byte loads of two rows */
+static bool filter_project_aligned(const fp_fused *fz)
+{
+	for (int c = 0; c < fz->cols.ncols; c++)
+		if ((uintptr_t)fz->cols.src[c] & 15)
+			return false;
+	return true;
+}
+
+/* ONE comparison of an INT64 column with a constant */
+static bool filter_is_cmp1(const pred_args *p)
+{
+	return p->n_insns == 1 && p->insn[0].op == MDB_P_CMP_COL_CONST && p->insn[0].type == MDB_T_INT64;
+}
+
+/* does filter_run launch k_scan_project_cmp1 for this program and these outputs?  The one place that decides it: mdb_dev_filter sizes
+ * its look-back words for that kernel's row blocks and relies on it for the positions (filt_fused_tail writes none) */
+static bool filter_takes_scan_cmp1(const pred_args *p, int n_cols, const fp_fused *fz)
+{
+	return filter_direct(p, n_cols) && filter_is_cmp1(p) && filter_project_aligned(fz);
+}
+
 size_t mdb_filter_arena_bytes(uint64_t n)
 {
 	const uint64_t nb = filt_blocks(n) + 1;
@@ -1102,13 +1136,14 @@ static int filter_run(mdb_dev_ctx *ctx, int mode, const pred_args *p, int n_cols
 		}
 	} else {
 		/* base-table streams (no row-id vector, 16-byte aligned columns) take the paired 16-byte-load form */
-		bool direct = n_cols >= 1;	/* (a program of constants only has no column to stream) */
-		for (int c = 0; c < n_cols; c++)
-			direct = direct && !p->cols[c].rid && ((uintptr_t)p->cols[c].values & 15) == 0;
+		const bool direct = filter_direct(p, n_cols);
+		/* the one-pass kernels load the projected columns two rows at a time as well: a projected column 8 bytes off a 16-byte
+		 * boundary sends the call to the bitmap kernel + filt_fused_tail, which copies cell by cell */
+		const bool scan_ok = fuse && filter_project_aligned(fuse);
 		const mdb_pred_insn &i0 = p->insn[0];
 		int tslot = 0;
 		bool tor = false;
-		if (fuse && direct && p->n_insns == 1 && i0.op == MDB_P_CMP_COL_CONST && i0.type == MDB_T_INT64) {
+		if (fuse && filter_takes_scan_cmp1(p, n_cols, fuse)) {
 			/* single pass, rows kept in registers across the look-back */
 			const int64_t *v = (const int64_t *)p->cols[i0.a].values;
 			const uint64_t *nbits = p->cols[i0.a].nullbits;
@@ -1126,7 +1161,7 @@ static int filter_run(mdb_dev_ctx *ctx, int mode, const pred_args *p, int n_cols
 			case MDB_CMP_LE: MDB_LAUNCH(ctx, "scan_project", (k_scan_project_cmp1<MDB_CMP_LE, 8>), nb, SP_THREADS, v, nbits, i0.imm, n, fz); break;
 			default: MDB_LAUNCH(ctx, "scan_project", (k_scan_project_cmp1<MDB_CMP_GE, 8>), nb, SP_THREADS, v, nbits, i0.imm, n, fz); break;
 			}
-		} else if (direct && p->n_insns == 1 && i0.op == MDB_P_CMP_COL_CONST && i0.type == MDB_T_INT64) {
+		} else if (direct && filter_is_cmp1(p)) {
 			const int64_t *v = (const int64_t *)p->cols[i0.a].values;
 			const uint64_t *nbits = p->cols[i0.a].nullbits;
 			switch (i0.cmp) {
@@ -1156,7 +1191,7 @@ static int filter_run(mdb_dev_ctx *ctx, int mode, const pred_args *p, int n_cols
 			} else {
 				MDB_LAUNCH(ctx, "filter_in_set", k_pred_bits_inset<false>, grid, FILT_THREADS, v, nbits, si, n, bits, bc, fz);
 			}
-		} else if (filt_terms ft; fuse && direct && filter_one_column_terms(p, &ft, &tslot, &tor)) {
+		} else if (filt_terms ft; scan_ok && direct && filter_one_column_terms(p, &ft, &tslot, &tor)) {
 			/* ranges / IN lists over one column: the same single pass */
 			const int64_t *v = (const int64_t *)p->cols[tslot].values;
 			const uint64_t *nbits = p->cols[tslot].nullbits;
@@ -1221,14 +1256,14 @@ extern "C" int mdb_dev_filter(mdb_dev_ctx *ctx, const struct mdb_pred_insn *prog
 	 * of bitmap, scan and bitmap -> positions (10^8 rows at 50 %: 0.41 -> 0.30 ms) */
 	/* (term lists - ranges, IN lists - take the three passes here: their evaluation, not the passes, is what costs - 0.43 ms in
 	 * one pass against 0.41 in three at 10^8 rows; mdb_dev_filter_project does use the one-pass term kernel: it saves the gather) */
-	const bool one_pass = n >= (1u << 18) && n_cols >= 1 && p.n_insns == 1 && p.insn[0].op == MDB_P_CMP_COL_CONST && p.insn[0].type == MDB_T_INT64 &&
-			      !p.cols[p.insn[0].a].rid && ((uintptr_t)p.cols[p.insn[0].a].values & 15) == 0;
+	/* (whether the program qualifies is filter_run's decision, over ALL bound columns: one that does not takes the three passes) */
+	fp_fused fz;
+	memset(&fz, 0, sizeof(fz));
+	fz.cols.sel_out = out_sel;
+	const bool one_pass = n >= (1u << 18) && filter_takes_scan_cmp1(&p, n_cols, &fz);
 	if (one_pass) {
 		const uint64_t rows_per_block = (uint64_t)SP_WAVES * FILT_WORDS_PER_WAVE * 64;
 		const uint32_t nblk = (uint32_t)((n + rows_per_block - 1) / rows_per_block);
-		fp_fused fz;
-		memset(&fz, 0, sizeof(fz));
-		fz.cols.sel_out = out_sel;
 		fz.state = (unsigned long long *)mdb_arena_take(ctx, (size_t)nblk * 8 + 64);
 		if (!fz.state)
 			return -MIDORIDB_INTERNAL;
