@@ -282,6 +282,7 @@ __device__ static inline void lw12_barrier(void)
 #define LW12_NSUB 8	/* sub-regions per digit (SH_NSUB of mdb_dev_shard.hip) */
 #define LW12_MAX_CR 31u
 #define LW12_MAX_CL 15u
+#define LW4_EMIT_WORDS ((int)((1u << LW_MAX_REM) / LW_THREADS))	/* k_leaf_wide4's ranged emit: table words a thread keeps between its passes */
 
 /* NX = 1: a further right table on the same key (A JOIN B ON a = b JOIN C ON a = c GROUP BY a: BASELINE configs[4]) - partitioned like the
  * first one; its rows are counted into the (still unused) 4-bit fields, the two counts multiplied into the 5-bit field before the left rows
@@ -817,7 +818,17 @@ __global__ __launch_bounds__(LW_THREADS) void k_leaf_wide12(gc_args a, uint32_t 
  * 4 bytes per key value (right rows in 5 bits above the first left row in 27) + 4 bits of left rows - is 72 KiB where k_leaf_wide's
  * 8 bytes per value are 128: TWO workgroups per CU, one streaming while the other clears or emits, and all 512 digits of the benchmark's
  * variant D resident at once instead of in two rounds.  More than 31 right or 15 left rows of one key are noticed (checksums) and
- * reported - flag 4096: the caller launches k_leaf_wide on the same partitioned tables and remembers the columns. */
+ * reported - flag 4096: the caller launches k_leaf_wide on the same partitioned tables and remembers the columns.
+ * Variant D at the headline (10^8 x 10^8 rows, ranged emit), rocprofv3, profiles/micro/join_leaf_stream/ab.txt: 0.103 -> 0.074 ms.  Ablations of
+ * the 0.103 (same box, builds with parts of the kernel compiled out): launch, clear, barriers and sums alone 0.006; + the right table's count
+ * 0.040 (0.2 GB in 0.034 ms: 5.9 TB/s - the sub-region loop with its four conditional loads and its waits is AT the memory's rate); + the left
+ * probes 0.048; the two streams without a single LDS atomic 0.044.  The other 0.054 was the ranged emit: 0.012 with its record stores compiled
+ * out, 0.014 in the list's form (a digit's records side by side), under 0.001 for the reservations' global atomics.  A digit's 4096 records
+ * go to 1526 ranges, and 4096 scattered stores of 8 bytes a workgroup cost 0.04 ms; staged in the dead table and written a run at a time (the
+ * ranged emit below) 0.025.  Measured and not kept: the digit's words as ONE stream of 16-byte pieces (all 16 counts read once into LDS with
+ * their prefixes, the piece -> sub-region map by seven compares against scalar registers, every load unconditional, a ring of 4 in flight with
+ * s_waitcnt vmcnt(3), the left table's first 8 pieces per thread asked for in front of the barrier: 64 registers, no scratch) - 0.1056 ->
+ * 0.1092 ms with the right stream alone, 0.1121 with the left ring: slower, there was no drain to remove. */
 __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per CU */) void k_leaf_wide4(gc_args a, uint32_t rem, uint32_t shift, uint32_t nsub)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t lw_lds[];
@@ -953,29 +964,53 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 	uint32_t cmax = 0, jsum = 0, last_first = 0, clmax = 0;
 	if (a.rg_rec && base != 0xFFFFFFFFu) {
 		/* the ordering kernel's ranges of 2^rg_shift first row ids are filled here: a digit's groups per range are counted, a place for
-		 * them reserved with one global atomic per (digit, range), and every record written there - ~8 records side by side per run */
-		for (uint32_t s0 = 0; s0 < per_wave; s0 += MDB_WAVE) {
-			const uint32_t sl = s_begin + s0;
-			if (s0 + lane < per_wave && ((s_cl[sl >> 3] >> nib) & 15u))
-				atomicAdd(&s_rg[(s_fc[sl] & 0x07FFFFFFu) >> a.rg_shift], 1u);
+		 * them reserved with one global atomic per (digit, range), and every record written there.  A digit's ~4096 records go to ~1500
+		 * ranges: written from where they are found they are 4096 stores of 8 bytes to as many lines of memory - the stores, not the
+		 * passes over the table, were 0.04 of the kernel's 0.10 ms.  So a thread keeps its up to 16 words of s_fc in registers from the
+		 * counting pass on (s_cl stays where it is); behind the next barrier s_fc is dead and its 4 T bytes stage the records sorted by range (an
+		 * exclusive prefix of the counts: s_rg[r] = the run's next place in its range, low half, and in the stage, high half - one LDS
+		 * atomic hands out both); then thread i writes staged record i: a run's ~3 records leave side by side, one store of 24 bytes.
+		 * Records beyond the stage's T / 2 (a digit with a group for more than half of its key values) are written from where
+		 * they are found, as before. */
+		unsigned long long *const s_stage = reinterpret_cast<unsigned long long *>(s_fc);
+		uint32_t fcr[LW4_EMIT_WORDS];
+		uint32_t total = lane < LW_THREADS / 64 ? s_red32[lane] : 0u;
+#pragma unroll
+		for (int o = 32; o; o >>= 1)
+			total += (uint32_t)__shfl_xor((int)total, o, MDB_WAVE);
+#pragma unroll
+		for (int e = 0; e < LW4_EMIT_WORDS; e++) {
+			const uint32_t s0 = (uint32_t)e * MDB_WAVE, sl = s_begin + s0;
+			const bool live = s0 + lane < per_wave;
+			const uint32_t fc = live ? s_fc[sl] : 0u, cl = live ? (s_cl[sl >> 3] >> nib) & 15u : 0u;
+			fcr[e] = fc;
+			if (cl)
+				atomicAdd(&s_rg[(fc & 0x07FFFFFFu) >> a.rg_shift], 1u);
 		}
 		__syncthreads();
-		for (uint32_t r = threadIdx.x; r < a.rg_n; r += LW_THREADS) {
-			const uint32_t c = s_rg[r];
+		uint32_t before = 0;	/* records of the ranges in front (uniform) */
+		for (uint32_t r0 = 0; r0 < a.rg_n; r0 += LW_THREADS) {
+			const uint32_t r = r0 + threadIdx.x, c = r < a.rg_n ? s_rg[r] : 0u;
+			uint32_t at = 0, sum;
+			if (c)
+				at = atomicAdd(&a.rg_cnt[r], c);	/* (on its way while the prefix is worked out) */
+			const uint32_t loc = before + mdb_block_excl_scan(c, reinterpret_cast<uint32_t *>(s_red), &sum);
+			before += sum;
 			if (!c)
 				continue;
-			uint32_t at = atomicAdd(&a.rg_cnt[r], c);
 			if (at + c > a.rg_cap) {
 				mdb_raise(a.status, GC_ST_RANGE_FULL);	/* a range outgrew its region: the caller takes the record list and its sort */
 				at = a.rg_cap;
 			}
-			s_rg[r] = at;
+			s_rg[r] = at | (loc << 16);	/* (at <= rg_cap <= 2^15 and loc < T <= 2^14: c more of either stay in their halves) */
 		}
-		__syncthreads();
-		for (uint32_t s0 = 0; s0 < per_wave; s0 += MDB_WAVE) {
-			const uint32_t sl = s_begin + s0;
-			const bool live = s0 + lane < per_wave;
-			const uint32_t fc = live ? s_fc[sl] : 0u, cl = live ? (s_cl[sl >> 3] >> nib) & 15u : 0u, cr = fc >> 27;
+		__syncthreads();	/* (every thread has its table words, the last one after the counting pass: s_fc is the stage from here on) */
+		const uint32_t nstage = total < T / 2 ? total : T / 2;
+		uint32_t s_again = s_begin;
+		asm volatile("" : "+v"(s_again));	/* (the addresses worked out again: kept from the counting pass they are 16 registers more than there are) */
+#pragma unroll
+		for (int e = 0; e < LW4_EMIT_WORDS; e++) {
+			const uint32_t s0 = (uint32_t)e * MDB_WAVE, sl = s_again + s0, fc = fcr[e], cl = s0 + lane < per_wave ? (s_cl[sl >> 3] >> nib) & 15u : 0u, cr = fc >> 27;
 			sum_cr += cr;
 			if (!cl)
 				continue;
@@ -984,10 +1019,21 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 			cmax = c > cmax ? c : cmax;
 			clmax = cl > clmax ? cl : clmax;
 			last_first = first > last_first ? first : last_first;
-			const uint32_t at = atomicAdd(&s_rg[r], 1u);
+			const uint32_t both = atomicAdd(&s_rg[r], 0x00010001u), at = both & 0xFFFFu, loc = both >> 16;
+			const unsigned long long rec = ((unsigned long long)first << (64 - a.kbits)) |
+						       (a.keyed_cbits ? ((unsigned long long)((leaf << rem) | sl) << a.keyed_cbits) : 0ull) | c;
+			if (loc < nstage)
+				s_stage[loc] = rec;
+			else if (at < a.rg_cap)
+				a.rg_rec[(size_t)r * a.rg_cap + at] = rec;
+		}
+		__syncthreads();
+		for (uint32_t i = threadIdx.x; i < nstage; i += LW_THREADS) {
+			const unsigned long long rec = s_stage[i];
+			const uint32_t r = (uint32_t)(rec >> (64 - a.kbits)) >> a.rg_shift, end = s_rg[r];	/* (where the run ends, in its range and in the stage) */
+			const uint32_t at = (end & 0xFFFFu) - ((end >> 16) - i);
 			if (at < a.rg_cap)
-				a.rg_rec[(size_t)r * a.rg_cap + at] = ((unsigned long long)first << (64 - a.kbits)) |
-								       (a.keyed_cbits ? ((unsigned long long)((leaf << rem) | sl) << a.keyed_cbits) : 0ull) | c;
+				a.rg_rec[(size_t)r * a.rg_cap + at] = rec;
 		}
 	}
 	for (uint32_t s0 = 0; s0 < ((a.rg_rec && base != 0xFFFFFFFFu) ? 0u : per_wave); s0 += MDB_WAVE) {	/* (per_wave >= 4: tables of 64 values at least; lanes beyond per_wave idle) */
@@ -1071,6 +1117,8 @@ int leaf_wide_launch(mdb_dev_ctx *ctx, const gc_args &a, uint32_t nleaves, uint3
 int leaf_wide4_launch(mdb_dev_ctx *ctx, const gc_args &a, uint32_t nleaves, uint32_t rem, uint32_t shift, uint32_t nsub)
 {
 	const size_t lds4 = ((size_t)4 << rem) + (((size_t)1 << rem) / 2 < 64 ? 64 : ((size_t)1 << rem) / 2) + (a.rg_rec ? (size_t)a.rg_n * 4 : 0);
+	if (a.rg_rec && (a.rg_cap > 0x8000u || rem > LW_MAX_REM))	/* (the ranged emit packs a place in a range and one in a digit into the halves of a word) */
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "one-level direct leaves: ranges beyond the ranged emit's packed places");
 	MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leaf_wide4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
 	MDB_LAUNCH_LDS(ctx, "leaf_join_wide4", k_leaf_wide4, nleaves, LW_THREADS, lds4, a, rem, shift, nsub);
 	return MIDORIDB_OK;
