@@ -97,6 +97,43 @@ def outer_join_rows(dev, res):
                                       "note": "query_execute() with results kept on the device; the statements alternate"}
 
 
+def full_join_rows(dev, res):
+    """outer_complete_full_1e7: mdb_dev_outer_complete_full beside mdb_dev_outer_complete over the same 10^7 pairs, alternating in one
+    run - 10^7 positions on either side, the preserved positions ascending with repeats and gaps, the partner positions in no order
+    (what a hash join delivers); about 0.37 of either side occurs in no pair"""
+    n = 10_000_000
+    g = torch.Generator(device=dev.device)
+    g.manual_seed(6)
+    pp = torch.sort(torch.randint(0, n, (n,), dtype=torch.int32, device=dev.device, generator=g)).values.contiguous()
+    po = torch.randint(0, n, (n,), dtype=torch.int32, device=dev.device, generator=g)
+    left_ms, full_ms = [], []
+    for rep in range(6):                    # (the first turn warms both up and is dropped)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        op, oo = dev.outer_complete(pp, po, n)
+        torch.cuda.synchronize()
+        left_ms.append((time.perf_counter() - t0) * 1e3)
+        rows_left = op.numel()
+        del op, oo
+        t0 = time.perf_counter()
+        op, oo, uo = dev.outer_complete_full(pp, po, n, n)
+        torch.cuda.synchronize()
+        full_ms.append((time.perf_counter() - t0) * 1e3)
+        assert op.numel() == rows_left + uo
+        del op, oo
+    kern = {}
+    for name, fn in (("left", lambda: dev.outer_complete(pp, po, n)), ("full", lambda: dev.outer_complete_full(pp, po, n, n))):
+        dev.prof_enable(True)
+        dev.prof_reset()
+        fn()
+        kern[name] = {k: round(v[1], 4) for k, v in sorted(dev.prof_read().items(), key=lambda kv: -kv[1][1])}
+        dev.prof_enable(False)
+    res["outer_complete_full_1e7"] = {"n_p": n, "n_o": n, "pairs": n, "unmatched_p": rows_left - n, "unmatched_o": uo, "left_ms": min(left_ms[1:]),
+                                      "full_ms": min(full_ms[1:]), "full_over_left": min(full_ms[1:]) / min(left_ms[1:]), "left_ms_all": left_ms[1:],
+                                      "full_ms_all": full_ms[1:], "kernels_ms": kern,
+                                      "note": "wall time per call, both synchronise twice; kernels_ms: one further call each with per-launch events"}
+
+
 def in_set_rows(dev, res):
     """in_set_1e8: WHERE k IN (list) over 10^8 INT64 rows through mdb_dev_filter (bitmap, scan, positions) at about 1 % and about 50 %
     selectivity - a 1000-value list (MDB_P_IN_SET, table in LDS) and a 10^6-value list (table in global memory) beside the two forms that
@@ -186,9 +223,18 @@ def main():
     ap.add_argument("--in-set", action="store_true", help="only the IN-list rows (in_set_1e8: set lookups beside an 8-value term list and one comparison)")
     ap.add_argument("--aggregates", action="store_true", help="only the SUM / MIN / MAX / AVG rows (aggregate_1e8: GROUP BY k, SUM(v) at 4, 1000 and 10^5 "
                                                                "groups with INT64 and DOUBLE v, and SUM(v) without GROUP BY)")
+    ap.add_argument("--full-join", action="store_true", help="only the FULL JOIN completion's row (outer_complete_full_1e7: beside the LEFT completion "
+                                                              "of the same pairs)")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.full_join:
+        full_join_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.aggregates:
         aggregate_rows(dev, res)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

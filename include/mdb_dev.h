@@ -35,7 +35,7 @@
  * A table of 2^32 - 1 rows or more cannot be read through such a vector.  The catalog itself admits
  * rows without a bound (mdb_store.c appends to 64-bit counts; 32-bit row ids are the device layer's);
  * the executor refuses an outer join over a table that large (join_next_table) and
- * mdb_dev_outer_complete refuses the positions.
+ * mdb_dev_outer_complete and mdb_dev_outer_complete_full refuse the positions.
  */
 #ifndef MDB_DEV_H
 #define MDB_DEV_H
@@ -153,6 +153,8 @@ struct mdb_dev_plan_info {
 	uint32_t pairs_identity;	/* mdb_dev_join_pairs matched EVERY left row with exactly one right row (unique right keys, no left row without a
 				 * partner - the primary-key join of BASELINE configs[1]): out_l is 0, 1, 2 ... and the left table's columns of the joined
 				 * stream are its columns as they stand - a caller need not gather them through out_l */
+	uint32_t outer_form;	/* the last outer completion since the last join / GROUP BY operator began: 0 none, 1 one preserved side (LEFT / RIGHT
+				 * [OUTER] JOIN: mdb_dev_outer_complete), 2 both sides preserved (FULL [OUTER] JOIN: mdb_dev_outer_complete_full) */
 };
 int mdb_dev_last_plan(mdb_dev_ctx *ctx, struct mdb_dev_plan_info *out);
 /* The MDB_* environment knobs are read once per process and kept: a process that changes one while it runs calls this. */
@@ -595,7 +597,7 @@ int mdb_dev_join_key_pack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *la
  * lay->ntaken < 2 or lay->empty: an error, nothing is written.  n == 0: nothing happens.  Synchronises. */
 int mdb_dev_join_key_unpack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *lay, const int64_t *keys, uint64_t n, int64_t *const *out_cols);
 
-/* ------------------------------------------------------------------ LEFT / RIGHT OUTER JOIN: outer completion
+/* ------------------------------------------------------------------ LEFT / RIGHT / FULL OUTER JOIN: outer completion
  *
  * The grammar accepts LEFT [OUTER] JOIN and RIGHT [OUTER] JOIN (reference src/parser/midorisql.y:229-233); the reference's
  * executor stops at BUG_ON(join_node->join_type != AST_SEL_JOIN_INNER) (executor_select.c:1094, :1169).  Here the pair
@@ -608,6 +610,17 @@ int mdb_dev_join_key_unpack(mdb_dev_ctx *ctx, const struct mdb_join_key_layout *
  * Streaming: 12 J bytes read, 8 (J + U) written, 9 bytes of bookkeeping per 64 positions; no atomics, no sort.  Synchronises. */
 int mdb_dev_outer_complete(mdb_dev_ctx *ctx, const uint32_t *pairs_p, const uint32_t *pairs_o, uint64_t J, uint64_t n_p,
 			   uint32_t **out_p, uint32_t **out_o, uint64_t *out_count);
+/* FULL [OUTER] JOIN (not in the reference's grammar: `FULL JOIN` is join number 6, `FULL OUTER JOIN` 12, mdb_sql.c) preserves BOTH sides.
+ * The output of mdb_dev_outer_complete(pairs_p, pairs_o, J, n_p) comes first, unchanged - the J + U_p entries in ascending out_p order -
+ * and behind it every position i in [0, n_o) of the OTHER side that occurs nowhere in pairs_o, in ascending i, as (MDB_NO_ROW, i).
+ * *out_count = J + U_p + U_o, *out_unmatched_o = U_o.  pairs_o needs no order.  n_o == 0 is valid (U_o = 0), and so is n_p == 0 with J == 0:
+ * the output is the tail alone; both empty: no output (NULL, NULL, 0).  A partner position at or above n_o fails the call - it is compared,
+ * never used as an index -, as do the positions mdb_dev_outer_complete refuses; n_p, n_o, J and *out_count stay below 2^32 - 1.
+ * Both outputs are allocated once at their final size and the tail is written in place.  On top of mdb_dev_outer_complete: 4 J bytes read
+ * (pairs_o once more), one byte per partner position stored into a flag array of n_o bytes that is cleared once and read twice, 8 U_o bytes
+ * written; plain stores, no atomics, no sort.  Synchronises as often as mdb_dev_outer_complete does (U_o comes back with the run heads). */
+int mdb_dev_outer_complete_full(mdb_dev_ctx *ctx, const uint32_t *pairs_p, const uint32_t *pairs_o, uint64_t J, uint64_t n_p, uint64_t n_o,
+				uint32_t **out_p, uint32_t **out_o, uint64_t *out_count, uint64_t *out_unmatched_o);
 
 /* ------------------------------------------------------------------ GROUP BY key + COUNT(*)
  *

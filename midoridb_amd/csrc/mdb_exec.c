@@ -222,7 +222,7 @@ uint64_t expr_tables(const struct mdb_expr *e)
  * AND-conjuncts of the WHERE clause: push[t][..] = table t's own conjuncts (constants go with table 0),
  * residual[..] = conjuncts that read several tables and stay above the joins.  false = too many to split.
  * Outer joins: WHERE runs after the join, and a table that some join NULL-supplies (T of S LEFT JOIN T; every table of S in S RIGHT
- * JOIN T) has rows in the stream that are not rows of the table - its conjuncts stay above the joins too (they see the NULL cells);
+ * JOIN T; both, T and every table of S, in S FULL JOIN T) has rows in the stream that are not rows of the table - its conjuncts stay above the joins too (they see the NULL cells);
  * a table that every join preserves keeps its push-down (a row the filter drops would be dropped after the joins with all its pairs). */
 
 bool where_split(const struct mdb_select *s, struct where_split *w)
@@ -243,6 +243,8 @@ bool where_split(const struct mdb_select *s, struct where_split *w)
 			null_supplied |= 1ull << t;
 		else if (mdb_join_is_right(s->join_type[t]))
 			null_supplied |= (1ull << t) - 1;
+		else if (mdb_join_is_full(s->join_type[t]))
+			null_supplied |= (2ull << t) - 1;
 	}
 	for (int i = 0; i < n; i++) {
 		const uint64_t m = expr_tables(all[i]);
@@ -857,9 +859,12 @@ static int composite_fused_plan(struct exec *x, const struct where_split *ws, bo
 	return 0;
 }
 
-/* S LEFT / RIGHT [OUTER] JOIN T ON c (S = the stream of the tables joined so far, T = table t).  SQL's meaning, in the emission order of
+/* S LEFT / RIGHT / FULL [OUTER] JOIN T ON c (S = the stream of the tables joined so far, T = table t).  SQL's meaning, in the emission order of
  * the inner join: the pairs for which the WHOLE ON expression is true, and every row of the PRESERVED side (LEFT: S, RIGHT: T) without
- * such a pair once, the other side's tables at MDB_NO_ROW (their cells read as NULL); rows come preserved-side-major.  None of the inner
+ * such a pair once, the other side's tables at MDB_NO_ROW (their cells read as NULL); rows come preserved-side-major.
+ * FULL preserves both sides and runs in the LEFT orientation: the LEFT JOIN's rows in their order, then T's rows without a pair in T's row
+ * order, S's tables at MDB_NO_ROW (mdb_dev_outer_complete_full).  Neither side may be thinned in front of the pair operator: where_split pushes
+ * no WHERE conjunct below a FULL join, and an ON conjunct over T alone stays a residual on the pairs (it makes rows unmatched, on both sides).  None of the inner
  * join's shortcuts apply (join elimination, carried payload cells, "the right key IS the left key": it is NULL where there is no row).
  * Order of work: T filtered by its pushed WHERE conjuncts (where_split pushes them only when every join preserves T) and, for LEFT, by
  * the ON conjuncts that read T alone (they decide matching, and T is not preserved: a T row that fails them matches nothing) ->
@@ -869,7 +874,8 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 {
 	struct mdb_select *s = x->s;
 	struct mdb_table *rt = s->tabs[t].t;
-	const bool left = mdb_join_is_left(s->join_type[t]);
+	const bool full = mdb_join_is_full(s->join_type[t]);
+	const bool left = full || mdb_join_is_left(s->join_type[t]);	/* the orientation: S on the left of the pair operator, S-major pairs */
 	struct mdb_expr *conj[32];
 	const struct mdb_expr *tconj[PUSH_MAX + 32], *resid[32];
 	int nconj = 0, key = -1, ntconj = 0, nresid = 0;
@@ -916,7 +922,7 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 				continue;
 			}
 		}
-		if (left && expr_tables(c) == 1ull << t)
+		if (left && !full && expr_tables(c) == 1ull << t)
 			tconj[ntconj++] = c;
 		else
 			resid[nresid++] = c;
@@ -1018,8 +1024,9 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 	}
 	/* the preserved side's rows without partner, at their places */
 	uint32_t *cp = NULL, *co = NULL;
-	uint64_t total = 0;
-	if (mdb_dev_outer_complete(x->dev, J ? (left ? ps : pt) : NULL, J ? (left ? pt : ps) : NULL, J, n_p, &cp, &co, &total))
+	uint64_t total = 0, u_o = 0;	/* u_o: FULL, T's rows without a pair (they follow the LEFT JOIN's rows) */
+	if (full ? mdb_dev_outer_complete_full(x->dev, J ? ps : NULL, J ? pt : NULL, J, n_p, r_rows, &cp, &co, &total, &u_o)
+		 : mdb_dev_outer_complete(x->dev, J ? (left ? ps : pt) : NULL, J ? (left ? pt : ps) : NULL, J, n_p, &cp, &co, &total))
 		return dev_fail(x, "outer completion");
 	if ((cp && track(x, cp)) || (co && track(x, co)))
 		return -MIDORIDB_NOMEM;
@@ -1038,8 +1045,11 @@ static int outer_join_next_table(struct exec *x, int t, const struct mdb_expr *c
 		ct = NULL;
 	}
 	x->rid[t] = ct;
-	if (total > J)
+	if (total > J + u_o)	/* rows of the preserved side without a pair: the other side's tables are absent there */
 		for (int u = left ? t : 0; u < (left ? t + 1 : t); u++)
+			x->may_be_absent[u] = true;
+	if (u_o)
+		for (int u = 0; u < t; u++)
 			x->may_be_absent[u] = true;
 	x->joined_rows = total;
 	return MIDORIDB_OK;

@@ -103,9 +103,11 @@ struct where_split {
 	int nresidual;
 };
 
-/* join types as the parser numbers them (mdb_sql.c: LEFT 2, RIGHT 4, + 6 with OUTER; the reference's grammar, midorisql.y:229-233) */
+/* join types as the parser numbers them (mdb_sql.c: LEFT 2, RIGHT 4, FULL 6, + 6 with OUTER; the reference's grammar, midorisql.y:229-233) */
 static inline bool mdb_join_is_left(int jt) { return jt == 2 || jt == 8; }
 static inline bool mdb_join_is_right(int jt) { return jt == 4 || jt == 10; }
+/* FULL [OUTER]: this grammar's own, numbered like the others - LEFT 2 + RIGHT 4, + 6 with OUTER */
+static inline bool mdb_join_is_full(int jt) { return jt == 6 || jt == 12; }
 
 extern __thread const struct mdb_strdict *stmt_dict;	/* the statement's string dictionary (VARCHAR literals) */
 

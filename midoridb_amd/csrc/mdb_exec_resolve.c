@@ -399,9 +399,9 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 						return -MIDORIDB_ERROR;
 					}
 		}
-		/* 1 INNER; 2 / 8 LEFT [OUTER], 4 / 10 RIGHT [OUTER] (the reference aborts on them, executor_select.c:1094: here SQL's meaning) */
-		if (s->join_type[t] != 1 && !mdb_join_is_left(s->join_type[t]) && !mdb_join_is_right(s->join_type[t])) {
-			ERR("join type %d is not executed: INNER, LEFT [OUTER] and RIGHT [OUTER] JOIN are\n", s->join_type[t]);
+		/* 1 INNER; 2 / 8 LEFT [OUTER], 4 / 10 RIGHT [OUTER], 6 / 12 FULL [OUTER] (the reference aborts on them, executor_select.c:1094: here SQL's meaning) */
+		if (s->join_type[t] != 1 && !mdb_join_is_left(s->join_type[t]) && !mdb_join_is_right(s->join_type[t]) && !mdb_join_is_full(s->join_type[t])) {
+			ERR("join type %d is not executed: INNER, LEFT [OUTER], RIGHT [OUTER] and FULL [OUTER] JOIN are\n", s->join_type[t]);
 			return -MIDORIDB_ERROR;
 		}
 		if (s->join_type[t] != 1 && cat->dist) {

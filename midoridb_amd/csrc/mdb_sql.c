@@ -29,7 +29,7 @@ enum tk {
 
 static const char *const KEYWORDS[] = {
 	"AND", "AS", "ASC", "AUTO_INCREMENT", "BY", "CREATE", "DATE", "DATETIME", "DELETE", "DESC", "DISTINCT",
-	"DOUBLE", "EXISTS", "FROM", "GROUP", "HAVING", "IF", "IN", "INDEX", "INNER", "INSERT", "INT",
+	"DOUBLE", "EXISTS", "FROM", "FULL", "GROUP", "HAVING", "IF", "IN", "INDEX", "INNER", "INSERT", "INT",
 	"INT4", "INTEGER", "INTO", "IS", "JOIN", "KEY", "LEFT", "LIKE", "LIMIT", "MOD", "NOT", "NULL",
 	"ON", "OR", "ORDER", "OUTER", "PRIMARY", "RIGHT", "SELECT", "SET", "TABLE", "TINYINT", "UNIQUE", "UPDATE",
 	"VALUE", "VALUES", "VARCHAR", "VARCHARACTER", "WHERE", "XOR", NULL
@@ -578,8 +578,8 @@ static void parse_table_reference(struct parser *p)
 		if (is_kw(p, "INNER") || is_kw(p, "JOIN")) {
 			accept_kw(p, "INNER");
 			jt = 1;
-		} else if (is_kw(p, "LEFT") || is_kw(p, "RIGHT")) {
-			jt = is_kw(p, "LEFT") ? 2 : 4;
+		} else if (is_kw(p, "LEFT") || is_kw(p, "RIGHT") || is_kw(p, "FULL")) {
+			jt = is_kw(p, "LEFT") ? 2 : is_kw(p, "RIGHT") ? 4 : 6;	/* (FULL: LEFT + RIGHT; not in the reference's grammar) */
 			next(p);
 			if (accept_kw(p, "OUTER"))
 				jt += 6;

@@ -77,7 +77,7 @@ class PlanInfo(ctypes.Structure):
     """struct mdb_dev_plan_info: what the last join / GROUP BY operator did"""
     _fields_ = [(k, ctypes.c_uint32) for k in ("key_form", "key_bits", "levels", "digits", "minmax_pruned", "semijoin", "any_order", "ranged_order",
                                                 "multi_one_pass", "retries", "samples", "from_stats", "payload_form", "group_form", "arena_mib", "small_form", "keys_are_left_column", "counts_all_one", "groups_as_bits", "payload_tables",
-                                                "pairs_identity")]
+                                                "pairs_identity", "outer_form")]
 
 
 JOIN_KEY_MAX_COLS = 4     # MDB_JOIN_KEY_MAX_COLS
@@ -151,7 +151,7 @@ def explain(op, left, right=None, further_rows=(), as_sample=False, left_nulls_b
         rc = fn(byref(rq), byref(info))
     if rc != 0:
         raise RuntimeError(f"mdb_dev_explain_{op} failed ({rc})")
-    return {k: int(getattr(info, k)) for k, _ in PlanInfo._fields_ if k != "pairs_identity"}    # (a fact of a run's output, not of a plan)
+    return {k: int(getattr(info, k)) for k, _ in PlanInfo._fields_ if k not in ("pairs_identity", "outer_form")}    # (facts of a run, not of a plan)
 
 
 class Counters(ctypes.Structure):
@@ -231,6 +231,7 @@ def _bind(lib):
         "mdb_dev_join_key_pack": ([P, POINTER(JoinKeyLayout), POINTER(JoinKeyCol), c_uint64, P, P, POINTER(c_uint64)], c_int),
         "mdb_dev_join_key_unpack": ([P, POINTER(JoinKeyLayout), P, c_uint64, POINTER(c_void_p)], c_int),
         "mdb_dev_outer_complete": ([P, P, P, c_uint64, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64)], c_int),
+        "mdb_dev_outer_complete_full": ([P, P, P, c_uint64, c_uint64, c_uint64, POINTER(P), POINTER(P), POINTER(c_uint64), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64)], c_int),
         "mdb_dev_join_keys_ordered": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), POINTER(c_uint64), POINTER(c_int)], c_int),
         "mdb_dev_join_payload": ([P, P, P, c_uint64, P, P, c_uint64, POINTER(P), c_int, POINTER(P)], c_int),
@@ -275,7 +276,7 @@ DEV_SYMBOLS = [
     "mdb_dev_ctx_create", "mdb_dev_ctx_destroy", "mdb_dev_ctx_set_stream", "mdb_dev_last_error", "mdb_dev_sync",
     "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
     "mdb_dev_host_alloc", "mdb_dev_host_free", "mdb_dev_h2d", "mdb_dev_d2h", "mdb_dev_prof_enable", "mdb_dev_prof_reset", "mdb_dev_prof_read", "mdb_dev_prof_symbols", "mdb_dev_filter",
-    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_key_layout", "mdb_dev_join_key_pack", "mdb_dev_join_key_unpack", "mdb_dev_outer_complete", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
+    "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_key_layout", "mdb_dev_join_key_pack", "mdb_dev_join_key_unpack", "mdb_dev_outer_complete", "mdb_dev_outer_complete_full", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
@@ -712,6 +713,18 @@ class DeviceCtx:
         if not cnt.value:
             return (torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.int32, device=self.device))
         return self._adopt(pp, cnt.value, torch.int32), self._adopt(po, cnt.value, torch.int32)
+
+    def outer_complete_full(self, pairs_p, pairs_o, n_p, n_o):
+        """FULL OUTER JOIN's completion: what outer_complete(pairs_p, pairs_o, n_p) returns and, behind it, (NO_ROW, i) for every i in
+        [0, n_o) that pairs_o never names, in ascending i (mdb_dev_outer_complete_full) -> (out_p, out_o, unmatched_o): int32 tensors
+        over the library's buffers (NO_ROW reads as -1) and the length of that tail."""
+        J = 0 if pairs_p is None else pairs_p.numel()
+        pp, po, cnt, uo = c_void_p(), c_void_p(), c_uint64(), c_uint64()
+        self._chk(self.lib.mdb_dev_outer_complete_full(self.h, _ptr(pairs_p) if J else None, _ptr(pairs_o) if J else None, J, n_p, n_o,
+                                                       byref(pp), byref(po), byref(cnt), byref(uo)), "outer_complete_full")
+        if not cnt.value:
+            return (torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.int32, device=self.device), 0)
+        return self._adopt(pp, cnt.value, torch.int32), self._adopt(po, cnt.value, torch.int32), int(uo.value)
 
     def join_keys(self, keys_l, null_l, keys_r, null_r):
         """the join's key column alone, every key once per joined row, in unspecified order (mdb_dev_join_keys)"""
