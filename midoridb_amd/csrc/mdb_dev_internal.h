@@ -45,100 +45,108 @@ struct mdb_part_result {
 	uint32_t nleaves;
 	uint32_t bits_total;
 	bool w32;		/* hv holds 4-byte words (narrow form without row ids) */
-	bool w16;		/* ... 2-byte words: the hash bits below the first level's digit (mdb_part_filter.out16) */
-	uint64_t *pay[2];	/* mdb_part_filter.npay: the payload cells, laid out like hv (the cell of hv[i] is pay[c][i]) */
-	uint32_t nsub;		/* != 0: first level only (mdb_part_filter.level0_only) - nleaves = 2^bits1 digits, digit d's rows lie in nsub
+	bool w16;		/* ... 2-byte words: the hash bits below the first level's digit (mdb_part_request.out16) */
+	uint64_t *pay[2];	/* mdb_part_request.npay: the payload cells, laid out like hv (the cell of hv[i] is pay[c][i]) */
+	uint32_t nsub;		/* != 0: first level only (mdb_part_request.level0_only) - nleaves = 2^bits1 digits, digit d's rows lie in nsub
 				 * regions: region r = d * nsub + s at [r * leaf_cap, r * leaf_cap + min(count, leaf_cap)), its count at
 				 * leaf_cnt[s * nleaves + d] */
 };
 
-/* bytes of arena needed by mdb_partition_table() */
-size_t mdb_partition_arena_bytes(uint64_t n, int bits1, int bits2, bool want_rid, bool fast, int npay = 0 /* mdb_part_filter.npay */);
-
-/* Partition one key column into 2^(bits1+bits2) leaves by the top bits of fmix64(key), dropping
- * NULL keys.  stable = keep input order inside every leaf (slower ballot ranking; requires want_rid),
- * otherwise the order inside a leaf is unspecified.  fast = skip the second level's histogram pass: every
- * leaf gets a fixed-capacity region and runs are placed with atomic cursors; if a leaf overflows, MDB_ST_REGION_FULL
- * is raised and the caller must redo the operator with fast = false.  All temporaries and
- * outputs are carved from the arena (caller has called mdb_arena_begin with enough room).  No host sync.
- * narrow (want_rid must be false): every key is expected within 2^31 of narrow_base - a key outside raises
- * MDB_ST_KEY_OUTSIDE and the caller redoes the operator wide.  1: hv[i] = fmix32(key) << 32 | row id, 2: hv is an array of 4-byte words fmix32(key) - only in the
- * two-level fast layout, see mdb_partition_w32_applies(). */
-/* Semi-join filter of the second partition level: a bitmap of the hashed key values the OTHER table holds, one bit per
- * 2^coarse adjacent values, laid out by first-level digit: digit d owns words [d * words, d * words + words).  The
- * second level's workgroup loads its digit's slice into LDS (into the staging buffer, before it is needed) and drops the
- * rows whose bit is clear before they are ranked and written. */
-struct mdb_part_filter {
+/* One partition request: what to partition, into how many leaves, in which form, and what the first and the second level do to the rows
+ * on their way.  Callers zero the record and set the fields they mean by name; mdb_partition_table reads the key column's fields,
+ * mdb_partition_raw the raw words', both the plan and the fields below them. */
+struct mdb_part_request {
+	/* ---- the key column (mdb_partition_table) */
+	const int64_t *keys;	/* 16-byte aligned on the device (8 bytes do for int32 keys and for the selective first level) */
+	const uint64_t *nullbits;	/* NULL keys are dropped (NULL: the column has none) */
+	uint64_t n;		/* rows - or words of the raw list */
+	bool keys32;		/* `keys` points to int32 values */
+	/* ---- the plan: 2^(bits1 + bits2) leaves by the top bits of the hashed key (bits2 = 0: one level) */
+	int bits1, bits2;
+	bool want_rid;		/* row ids travel beside the words (mdb_part_result.rid) */
+	bool stable;		/* keep input order inside every leaf (slower ballot ranking; needs want_rid and the exact layout), otherwise the
+				 * order inside a leaf is unspecified */
+	bool fast;		/* no histogram passes: every leaf is a fixed-capacity region, runs are placed with atomic cursors (two levels, or
+				 * level0_only); a region that overflows raises MDB_ST_REGION_FULL and the caller redoes the operator with fast = false,
+				 * the exact histogram layout */
+	int narrow;		/* (want_rid must be false) every key is expected within 2^31 of narrow_base - a key outside raises MDB_ST_KEY_OUTSIDE
+				 * and the caller redoes the operator wide.  1: hv[i] = fmix32(key) << 32 | row id; 2: hv is an array of 4-byte words
+				 * fmix32(key) - only in the histogram-free layout of both levels, see mdb_partition_w32_applies() */
+	int64_t narrow_base;	/* narrow: the keys are taken relative to this value (centre of their 2^32 window; compact form: its low end) */
+	uint32_t narrow_kbits;	/* compact narrow form: keys in [narrow_base, narrow_base + 2^narrow_kbits), hash32 = mdb_mixk(key - narrow_base,
+				 * narrow_kbits) << (32 - narrow_kbits): below the bits1 + bits2 partition bits only narrow_kbits - bits1 - bits2
+				 * bits tell keys apart */
+	/* ---- ready-made 64-bit sort keys instead of a column (mdb_partition_raw: no hashing, no NULLs) */
+	const uint64_t *raw_hv;
+	uint32_t leaf_cap;	/* != 0: rows per leaf region of the fast layout (the caller guarantees that no leaf holds more) */
+	uint32_t digits0_used;	/* how many of the 2^bits1 first-level digits can occur at all (0 = every one): sizes the fast first-level regions */
+	uint64_t digit0_rows;	/* the words are row ids and a first-level digit spans that many of them (0: not so): the fast first-level regions
+				 * are sized for the most a digit can hold instead of the average */
+	bool zero_is_gap;	/* zero words are gaps of a chunked list, not words */
+	int fold32;		/* two fast levels only, with zero_is_gap.  1: the first level folds every 8-byte record w into the 4-byte word
+				 * (w >> 32) | (uint32_t)w - the caller knows that the two parts share no bit - and everything after it moves 4-byte
+				 * words (mdb_part_result.w32); 2: raw_hv already holds 4-byte words */
+	/* ---- semi-join filter of the SECOND level (left side of a join in the compact narrow form, two fast levels): a bitmap of the hashed
+	 * key values the OTHER table holds, one bit per 2^coarse adjacent values, laid out by first-level digit: digit d owns words
+	 * [d * words, d * words + words).  The second level's workgroup loads its digit's slice into LDS and drops the rows whose bit is
+	 * clear before they are ranked and written. */
 	const uint32_t *bits;	/* NULL: no bitmap */
 	uint32_t words;		/* per first-level digit: a power of two, 4 ... 8192 (32 KiB) */
 	uint32_t shift;		/* bit index (before masking to the slice) = hash32 >> shift */
-	/* min-max pruning at the FIRST level (compact narrow form): the right table's call passes minmax_out (two words the caller
+	/* ---- min-max pruning at the FIRST level (narrow forms): the right table's call passes minmax_out (two words the caller
 	 * initialised to 0xFFFFFFFF, 0: smallest / largest key - window base seen), the left table's call, later on the same
 	 * stream, passes the same words as range_in and drops the rows outside */
 	uint32_t *minmax_out;
 	uint32_t *minmax_tiles;	/* with minmax_out: scratch of mdb_part_minmax_words(n) words (a pair per first-level tile, reduced after the launch) */
 	const uint32_t *range_in;
-	/* the same in the 64-bit form (mdb_partition_table with narrow = 0): the right table (no row ids) leaves [lo, hi] of its keys as
-	 * two signed 64-bit words in minmax64_out (scratch: minmax64_tiles, mdb_part_minmax_words(n) * 2 uint32 words), the left table
-	 * (with row ids) reads them through range64_in */
+	/* the same in the 64-bit form (narrow = 0): the right table (no row ids) leaves [lo, hi] of its keys as two signed 64-bit words in
+	 * minmax64_out (scratch: minmax64_tiles, mdb_part_minmax_words(n) * 2 uint32 words), the left table (with row ids) reads them
+	 * through range64_in */
 	long long *minmax64_out;
 	unsigned long long *minmax64_tiles;
 	const long long *range64_in;
-	/* narrow = 1 (hash | row id words), histogram-free layout, one level (level0_only) or two: up to two 8-byte payload columns of the
-	 * table travel with the rows (mdb_part_result.pay) - a join that carries the right table's payload to the leaf instead of
-	 * gathering it afterwards */
+	bool selective;		/* with range_in, compact narrow form: the caller KNOWS (the last join over these columns, or the caller's statistics)
+				 * that few rows lie inside the range: the first level runs its selective instance (k_part_scatter<pf_key_cf_sel>) */
+	bool expect_pruned;	/* with range_in / range64_in: the caller expects most rows to be dropped (key sample): the second level's grid is
+				 * then sized by the tiles that exist (a 4-byte read-back + synchronisation) instead of by the table */
+	/* ---- payload: narrow = 1, histogram-free layout, one level (level0_only) or two: up to two 8-byte columns of the table travel with
+	 * the rows (mdb_part_result.pay) - a join that carries the right table's payload to the leaf instead of gathering it afterwards */
 	const void *pay_in[2];
 	int npay;
-	/* first level, any form: keep only the rows whose KEY lies in [keep_lo, keep_hi] (keep_on) - the other table's global key
-	 * range, known before an exchange (mdb_dev_partition_by_dest_pruned) */
+	/* ---- key ranges of the first level, any form (mdb_dev_partition_by_dest_pruned): keep only the rows whose KEY lies in
+	 * [keep_lo, keep_hi] - the other table's global key range, known before an exchange */
 	bool keep_on;
 	int64_t keep_lo, keep_hi;
-	bool own_on;		/* ... and verify that every key of THIS table lies in [own_lo, own_hi] (a promised range: PART_ST_OWN_RANGE_BROKEN otherwise) */
+	bool own_on;		/* ... and verify that every key of THIS table lies in [own_lo, own_hi] (a promised range; an error otherwise) */
 	int64_t own_lo, own_hi;
+	/* ---- first level only */
+	bool level0_only;	/* stop after the histogram-free first level (compact narrow form, bits2 = 0, fast): the consumer reads the digits'
+				 * sub-regions itself (mdb_part_result.nsub; k_leaf_wide in mdb_dev_leaf_wide.hip) */
 	bool loose;		/* with level0_only: regions of 1.5 x (instead of 1.25 x) the average size - a column of some 10^4 - 10^5 distinct
 				 * values puts a few dozen of them, with thousands of rows each, into a region */
-	bool out16;		/* with level0_only, right side of the compact narrow form: 2-byte words (mdb_part_result.w16) when the hash bits
-				 * below the digit fit 16 bits */
-	bool level0_only;	/* stop after the histogram-free first level (bits2 = 0): the consumer reads the digits' sub-regions itself
-				 * (mdb_part_result.nsub; k_leaf_wide in mdb_dev_join.hip) */
-	uint32_t region_cap;	/* with level0_only, != 0: words per first-level region (a multiple of 64) instead of 1.25 x the average + 1024 */
+	bool out16;		/* with level0_only and narrow = 2: 2-byte words (mdb_part_result.w16) when the hash bits below the digit fit 16 bits */
+	uint32_t region_cap;	/* with level0_only, != 0: words per first-level region (a multiple of 64) instead of 1.25 x the average + 1024 -
+				 * the sharded operator, whose ranks must agree on it */
 	uint32_t *cursor0_ext;	/* != NULL: the first level's region cursors live here (cursor0_ext_words of them at least), ALREADY ZERO - the caller's
 				 * one memset covers them (ctx->d_status + MDB_ZERO_BLK_OFF) - instead of an arena block and a memset of its own */
 	uint32_t cursor0_ext_words;
-	bool selective;		/* with range_in, compact narrow form: the caller KNOWS (the last join over these columns, or the caller's statistics) that
-				 * few rows lie inside the range: the first level runs its selective instance (k_part_scatter<pf_key_cf_sel>) */
-	bool expect_pruned;	/* with range_in: the caller expects most rows to be dropped (key sample): the second level's grid is then
-				 * sized by the tiles that exist (a 4-byte read-back + synchronisation) instead of by the table */
 };
 static inline size_t mdb_part_minmax_words(uint64_t n) { return (size_t)((n + MDB_TILE - 1) / MDB_TILE + 8) * 2; }
 
-int mdb_partition_table(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n,
-			int bits1, int bits2, bool want_rid, bool stable, bool fast, mdb_part_result *out, int narrow = 0,
-			bool keys32 = false,	/* keys32: `keys` points to int32 values */
-			int64_t narrow_base = 0,	/* narrow: the keys are taken relative to this value (centre of their 2^32 window) */
-			uint32_t narrow_kbits = 0,	/* compact narrow form: keys in [narrow_base, narrow_base + 2^narrow_kbits), hash32 =
-							 * mdb_mixk(key - narrow_base, narrow_kbits) << (32 - narrow_kbits): below the
-							 * bits1 + bits2 partition bits only narrow_kbits - bits1 - bits2 bits tell keys apart */
-			const struct mdb_part_filter *flt = NULL);	/* semi-join filter at the second level (left side of a join in the
-									 * compact narrow form only), see struct mdb_part_filter */
-
-/* arena bytes of a first-level-only partition (mdb_part_filter.level0_only) of n rows by bits1 bits */
-size_t mdb_partition_level0_arena_bytes(uint64_t n, int bits1, bool loose = false /* mdb_part_filter.loose */, int npay = 0 /* mdb_part_filter.npay */);
-
-/* whether narrow = 2 is available for a table of n rows */
+/* Partition rq.keys into 2^(bits1 + bits2) leaves by the top bits of fmix64(key), dropping NULL keys.  All temporaries and outputs are
+ * carved from the arena (the caller has called mdb_arena_begin with enough room: mdb_partition_arena_bytes, or
+ * mdb_partition_level0_arena_bytes for level0_only).  No host sync, except with expect_pruned. */
+int mdb_partition_table(mdb_dev_ctx *ctx, const mdb_part_request &rq, mdb_part_result *out);
+/* ... what it needs of the arena.  Sized for a less specific request than the one that runs (8-byte words where narrow = 2 moves 4). */
+size_t mdb_partition_arena_bytes(uint64_t n, int bits1, int bits2, bool want_rid, bool fast, int npay = 0);
+size_t mdb_partition_level0_arena_bytes(uint64_t n, int bits1, bool loose = false, int npay = 0);
+/* whether narrow = 2 is served for a table of n rows: the histogram-free layout of both levels, with every region index in 32 bits */
 bool mdb_partition_w32_applies(uint64_t n, int bits1, int bits2, bool fast);
 
-/* fast = fixed-capacity regions + cursors (a region overflow raises MDB_ST_REGION_FULL: the caller must check it
- * after the consumer kernel and redo with fast = false, the exact histogram layout) */
-/* digits0_used: how many of the 2^bits1 first-level digits can occur at all (0 = every one) - sizes the fast regions */
-/* digit0_rows: the words are row ids and a first-level digit spans that many of them (0: not so) - sizes the fast first-level regions for
- * the most a digit can hold instead of the average */
+/* MSD radix partition of rq.raw_hv by the top bits1 + bits2 bits of the words; with two levels and fast the last one uses the
+ * fixed-capacity layout with rq.leaf_cap rows per leaf.  Orders GROUP BY results by first row id, and sorts (mdb_dev_sort.hip). */
+int mdb_partition_raw(mdb_dev_ctx *ctx, const mdb_part_request &rq, mdb_part_result *out);
 size_t mdb_partition_raw_arena_bytes(uint64_t n, int bits1, int bits2, uint32_t leaf_cap, bool fast, uint32_t digits0_used, uint64_t digit0_rows = 0);
-int mdb_partition_raw(mdb_dev_ctx *ctx, const uint64_t *hv, uint64_t n, int bits1, int bits2, uint32_t leaf_cap, bool fast,
-		      uint32_t digits0_used, mdb_part_result *out, bool zero_is_gap = true,	/* zero words are gaps of a chunked list */
-		      int fold32 = 0,	/* 1: the 8-byte records are folded into 4-byte words by the first level; 2: `hv` already holds 4-byte words */	/* the first level folds every 8-byte word w into the 4-byte word (w >> 32) | (uint32_t)w - the caller knows
-					 * that the two parts share no bit - and everything after it moves 4-byte words (out->w32; two fast levels only) */
-		      uint64_t digit0_rows = 0);
 
 /* one stable least-significant-digit radix pass over (key, row id) pairs: digit = (key >> shift) & (2^bits - 1),
  * bits <= 8.  hist = scratch of mdb_sort_pass_hist_words(n) uint32, scan_tmp = mdb_scan_scratch_words(of that). */

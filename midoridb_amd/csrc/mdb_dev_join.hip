@@ -1371,6 +1371,33 @@ static bool gc_lw_bad(mdb_dev_ctx *ctx, const gc_state *st)
 	return ctx->vd[VD_LW_BAD].serve(st->keys_l, st->n_l, NULL, st->n_r_cap, MDB_BAD_SERVES);
 }
 
+/* the partition request of one of the operator's tables: the plan of this attempt, the key form (mdb_part_request.narrow) and its window */
+static mdb_part_request gc_table_request(const gc_state *st, const int64_t *keys, const uint64_t *nulls, uint64_t n, int narrow)
+{
+	mdb_part_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.keys = keys;
+	rq.nullbits = nulls;
+	rq.n = n;
+	rq.keys32 = st->keys32;
+	rq.bits1 = st->b1;
+	rq.bits2 = st->b2;
+	rq.fast = st->fast;
+	rq.narrow = narrow;
+	rq.narrow_base = st->direct ? st->key_lo : st->base;
+	rq.narrow_kbits = st->direct ? st->key_bits : 0u;
+	return rq;
+}
+
+/* the left table's first-level cursors in the status block's counter area, which an unsplit call has cleared (the right table's lie in front of them) */
+static void gc_left_cursors(mdb_dev_ctx *ctx, const gc_state *st, mdb_part_request *rq)
+{
+	if (st->own_call) {
+		rq->cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF + MDB_ZERO_BLK_SLOT;
+		rq->cursor0_ext_words = MDB_ZERO_BLK_SLOT;
+	}
+}
+
 /* first half: size and claim the scratch arena, clear the status words, partition the left table */
 static int gc_begin(mdb_dev_ctx *ctx, gc_state *st)
 {
@@ -1531,17 +1558,13 @@ static int gc_begin(mdb_dev_ctx *ctx, gc_state *st)
 		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	}
 	if (!st->defer_l && !st->defer_l64 && !st->wide12) {
-		mdb_part_filter lflt;
-		memset(&lflt, 0, sizeof(lflt));
-		lflt.level0_only = st->one_level;
-		lflt.loose = st->one_level && st->fast1;
-		if (st->own_call) {
-			lflt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF + MDB_ZERO_BLK_SLOT;
-			lflt.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
-		}
-		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, !st->narrow, false, st->fast, &st->pl,
-					 st->narrow ? 1 : 0, st->keys32, st->direct ? st->key_lo : st->base, st->direct ? st->key_bits : 0u,
-					 st->one_level ? &lflt : NULL);
+		mdb_part_request rq = gc_table_request(st, st->keys_l, st->null_l, st->n_l, st->narrow ? 1 : 0);
+		rq.want_rid = !st->narrow;
+		rq.level0_only = st->one_level;
+		rq.loose = st->one_level && st->fast1;
+		if (st->one_level)
+			gc_left_cursors(ctx, st, &rq);
+		rc = mdb_partition_table(ctx, rq, &st->pl);
 		if (rc)
 			return rc;
 	}
@@ -1704,29 +1727,26 @@ static int gc_partition_right(mdb_dev_ctx *ctx, gc_run *g)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "right table larger than announced at begin()");
 	if (st->narrow && !st->one_level && !mdb_partition_w32_applies(g->r.n, st->b1, st->b2, st->fast))
 		return GC_RETRY_WIDE;	/* split form: the left side was prepared narrow for a right table of another size */
-	mdb_part_filter rflt;
-	memset(&rflt, 0, sizeof(rflt));
-	rflt.level0_only = st->one_level;
-	rflt.out16 = st->one_level && !mdb_knob_off("MDB_WORDS16");
-	if (st->own_call) {
-		rflt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF;
-		rflt.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
+	mdb_part_request rq = gc_table_request(st, g->r.keys, g->r.nulls, g->r.n, st->narrow ? 2 : 0);
+	rq.level0_only = st->one_level;
+	rq.out16 = st->one_level && !mdb_knob_off("MDB_WORDS16");
+	if (st->own_call && (st->defer_l || st->one_level || st->defer_l64)) {
+		rq.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF;
+		rq.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
 	}
 	if (st->defer_l) {
-		rflt.minmax_out = ctx->d_status + GC_STW_MINMAX;
-		rflt.minmax_tiles = (uint32_t *)mdb_arena_take(ctx, mdb_part_minmax_words(g->r.n) * 4);
-		if (!rflt.minmax_tiles)
+		rq.minmax_out = ctx->d_status + GC_STW_MINMAX;
+		rq.minmax_tiles = (uint32_t *)mdb_arena_take(ctx, mdb_part_minmax_words(g->r.n) * 4);
+		if (!rq.minmax_tiles)
 			return -MIDORIDB_INTERNAL;
 	}
 	if (st->defer_l64) {
-		rflt.minmax64_out = reinterpret_cast<long long *>(ctx->d_status + GC_STW_MINMAX64);
-		rflt.minmax64_tiles = (unsigned long long *)mdb_arena_take(ctx, mdb_part_minmax_words(g->r.n) * 8);
-		if (!rflt.minmax64_tiles)
+		rq.minmax64_out = reinterpret_cast<long long *>(ctx->d_status + GC_STW_MINMAX64);
+		rq.minmax64_tiles = (unsigned long long *)mdb_arena_take(ctx, mdb_part_minmax_words(g->r.n) * 8);
+		if (!rq.minmax64_tiles)
 			return -MIDORIDB_INTERNAL;
 	}
-	return mdb_partition_table(ctx, g->r.keys, g->r.nulls, g->r.n, st->b1, st->b2, false, false, st->fast, &g->pr, st->narrow ? 2 : 0, st->keys32,
-				   st->direct ? st->key_lo : st->base, st->direct ? st->key_bits : 0u,
-				   (st->defer_l || st->one_level || st->defer_l64) ? &rflt : NULL);
+	return mdb_partition_table(ctx, rq, &g->pr);
 }
 
 /* stage 1c: the further right tables, partitioned exactly like the first: same window, same bits, 4-byte words.  Their keys outside the window are
@@ -1740,13 +1760,13 @@ static int gc_partition_extras(mdb_dev_ctx *ctx, gc_run *g)
 	h[1] = st->key_bits >= 32u ? 0xFFFFFFFFu : ((1u << st->key_bits) - 1u);
 	MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status + GC_STW_WINDOW, h, 8, hipMemcpyHostToDevice, ctx->stream));
 	for (int x = 0; x < st->nextra; x++) {
-		mdb_part_filter xf;
-		memset(&xf, 0, sizeof(xf));
-		xf.range_in = ctx->d_status + GC_STW_WINDOW;
 		if (!mdb_partition_w32_applies(st->xn[x], st->b1, st->b2, st->fast))
 			return GC_NOT_SERVED;
-		int rc = mdb_partition_table(ctx, st->xkeys[x], st->xnull[x], st->xn[x], st->b1, st->b2, false, false, st->fast, &g->px[x], 2, st->keys32,
-					     st->key_lo, st->key_bits, &xf);
+		mdb_part_request rq = gc_table_request(st, st->xkeys[x], st->xnull[x], st->xn[x], 2);
+		rq.narrow_base = st->key_lo;
+		rq.narrow_kbits = st->key_bits;
+		rq.range_in = ctx->d_status + GC_STW_WINDOW;
+		int rc = mdb_partition_table(ctx, rq, &g->px[x]);
 		if (rc)
 			return rc;
 		if (!g->px[x].w32 || !g->px[x].leaf_cap || !g->px[x].leaf_cnt || g->px[x].nleaves != (1u << (st->b1 + st->b2)))
@@ -1762,26 +1782,22 @@ static bool gc_learned_selective(const mdb_dev_ctx *ctx, const int64_t *keys_l, 
 static int gc_partition_left(mdb_dev_ctx *ctx, gc_run *g, bool form64)
 {
 	gc_state *st = g->st;
-	mdb_part_filter flt;
-	memset(&flt, 0, sizeof(flt));
+	mdb_part_request rq = gc_table_request(st, st->keys_l, st->null_l, st->n_l, form64 ? 0 : 1);
 	int rc;
 	if (form64) {
-		flt.range64_in = reinterpret_cast<const long long *>(ctx->d_status + GC_STW_MINMAX64);
-		flt.expect_pruned = st->by_span;
-		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, true, false, st->fast, &st->pl, 0, st->keys32, st->base, 0u, &flt);
+		rq.want_rid = true;
+		rq.range64_in = reinterpret_cast<const long long *>(ctx->d_status + GC_STW_MINMAX64);
+		rq.expect_pruned = st->by_span;
+		rc = mdb_partition_table(ctx, rq, &st->pl);
 	} else if (!st->semijoin) {
-		flt.range_in = ctx->d_status + GC_STW_MINMAX;
-		flt.expect_pruned = st->by_span && !st->one_level;
+		rq.range_in = ctx->d_status + GC_STW_MINMAX;
+		rq.expect_pruned = st->by_span && !st->one_level;
 		/* (a key sample's guess keeps the general first level: what the last join over these columns delivered, or the caller's statistics) */
-		flt.selective = st->selective && (gc_learned_selective(ctx, st->keys_l, st->n_l, g->r.keys, g->r.n) ||
-						  (ctx->cs_on && !ctx->explain_as_sample && ctx->cs_kl == st->keys_l && ctx->cs_has_r && ctx->cs_kr == g->r.keys));
-		flt.level0_only = st->one_level;
-		if (st->own_call) {
-			flt.cursor0_ext = ctx->d_status + MDB_ZERO_BLK_OFF + MDB_ZERO_BLK_SLOT;
-			flt.cursor0_ext_words = MDB_ZERO_BLK_SLOT;
-		}
-		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, false, false, st->fast, &st->pl, 1, st->keys32,
-					 st->direct ? st->key_lo : st->base, st->direct ? st->key_bits : 0u, &flt);
+		rq.selective = st->selective && (gc_learned_selective(ctx, st->keys_l, st->n_l, g->r.keys, g->r.n) ||
+						 (ctx->cs_on && !ctx->explain_as_sample && ctx->cs_kl == st->keys_l && ctx->cs_has_r && ctx->cs_kr == g->r.keys));
+		rq.level0_only = st->one_level;
+		gc_left_cursors(ctx, st, &rq);
+		rc = mdb_partition_table(ctx, rq, &st->pl);
 	} else {
 		/* the right table's hashed keys as a bitmap, then the left table through it */
 		const mdb_part_result &pr = g->pr;
@@ -1795,13 +1811,14 @@ static int gc_partition_left(mdb_dev_ctx *ctx, gc_run *g, bool form64)
 		const uint32_t groups = (pr.nleaves + LB_WAVES - 1) / LB_WAVES, resident = 16u * (uint32_t)ctx->num_cus;
 		MDB_LAUNCH(ctx, "leaf_bitmap", k_leaf_bitmap, groups < resident ? groups : resident, LB_WAVES * MDB_WAVE,
 			   reinterpret_cast<const uint32_t *>(pr.hv), pr.leaf_cnt, pr.leaf_cap, pr.nleaves, rem, coarse, 32u - st->key_bits, bits);
-		flt.range_in = ctx->d_status + GC_STW_MINMAX;
-		flt.expect_pruned = st->by_span;
-		flt.bits = bits;
-		flt.words = 1u << (st->key_bits - (uint32_t)st->b1 - coarse - 5u);
-		flt.shift = 32u - st->key_bits + coarse;
-		rc = mdb_partition_table(ctx, st->keys_l, st->null_l, st->n_l, st->b1, st->b2, false, false, st->fast, &st->pl, 1, st->keys32, st->key_lo, st->key_bits,
-					 &flt);
+		rq.narrow_base = st->key_lo;
+		rq.narrow_kbits = st->key_bits;
+		rq.range_in = ctx->d_status + GC_STW_MINMAX;
+		rq.expect_pruned = st->by_span;
+		rq.bits = bits;
+		rq.words = 1u << (st->key_bits - (uint32_t)st->b1 - coarse - 5u);
+		rq.shift = 32u - st->key_bits + coarse;
+		rc = mdb_partition_table(ctx, rq, &st->pl);
 	}
 	if (!rc)
 		g->pl = st->pl;
@@ -2781,7 +2798,7 @@ static int group_count_common(mdb_dev_ctx *ctx, gc_request *rq)
 	 * and be redone anyway - start with the exact layout */
 	/* ... unless there are still some 10^4 - 10^5 of them (3500 distinct among 4096 sampled: about 1.3 * 10^4 in the column) and
 	 * the one-level form applies: its 256 or 512 first-level regions hold 50 values or more each; sized at 1.5 x the average
-	 * (mdb_part_filter.loose) they take the variation of that number */
+	 * (mdb_part_request.loose) they take the variation of that number */
 	bool fast1 = false;
 	if (!has_r && ctx->vd[VD_DISTINCT].holds(keys_l, n_l, NULL, 0) && ctx->gh_distinct < 4050u) {
 		if (ctx->gh_distinct >= 3500u)

@@ -160,7 +160,7 @@ __device__ static inline void gc_leaf_range(const uint32_t *off, const uint32_t 
 
 #define LW_THREADS 1024
 #define LW_MIN_REM 6u		/* tables of 64 entries at least (key windows from 2^15 values: that few values per first-level region - their
-				 * number varies by 13 % - need the looser regions of mdb_part_filter.loose) */
+				 * number varies by 13 % - need the looser regions of mdb_part_request.loose) */
 #define LW_EMIT_REM 11u		/* from here on every thread owns at least one 32-bit word of halves in the emit pass */
 #define LW_MAX_REM 14u
 #define LW_UNROLL 4

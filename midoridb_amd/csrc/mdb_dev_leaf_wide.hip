@@ -23,7 +23,7 @@ __device__ static inline uint4 lw_load_nt(const void *p)
  * Key windows of at most 2^23 values (a dimension table's keys; after R-based pruning the benchmark's variant D: 6.25 * 10^6
  * right keys) need 11 bits of partitioning before k_leaf_direct's 2^12-entry tables fit - two scatter levels, the second one
  * a full read + write of both tables for 3 or 4 bits.  Here the tables are partitioned ONCE, by 9 bits (histogram-free first
- * level, mdb_part_filter.level0_only), and one 1024-thread workgroup joins a whole digit: 2^rem entries, rem <= 14, with the
+ * level, mdb_part_request.level0_only), and one 1024-thread workgroup joins a whole digit: 2^rem entries, rem <= 14, with the
  * row counts as 16-BIT halves of 32-bit LDS words (8 bytes per entry instead of 12: 128 KiB at rem = 14).  A count that
  * outgrows its half carries into (or out of) the neighbour - every such accident makes the sum of the halves SMALLER than the
  * number of adds, which the emit pass checks: status bit 10, the operator is redone with two levels (and their hot-key path).

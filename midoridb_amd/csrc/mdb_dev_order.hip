@@ -290,6 +290,19 @@ static uint64_t order_sparse_most_slots(uint32_t kbits)
 	return 4 * order_sparse_most_records(kbits);
 }
 
+/* the record list as raw words of the partition: zero words are the gaps of its chunks */
+static mdb_part_request order_request(const unsigned long long *rec, uint64_t list_len, int sb1, int sb2)
+{
+	mdb_part_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.raw_hv = (const uint64_t *)rec;
+	rq.n = list_len;
+	rq.bits1 = sb1;
+	rq.bits2 = sb2;
+	rq.zero_is_gap = true;
+	return rq;
+}
+
 /* Order a record list ((row id << (64 - kbits)) | payload, zero words = gaps) by row id and deliver it:
  * histogram-free regions first; if one overflows (the gaps of the list can bunch the records of one XCD's tile
  * range) the exact layout redoes the sort.  Synchronises. */
@@ -317,7 +330,10 @@ int order_records(mdb_dev_ctx *ctx, const unsigned long long *rec, uint64_t list
 		if ((n_rec ? n_rec : list_len) <= (uint64_t)(OS_MAX_REC - 1024) * 2 / 3 * used_leaves &&
 		    (n_rec ? n_rec : list_len) <= order_sparse_most_records(kbits) && list_len <= order_sparse_most_slots(kbits)) {
 			mdb_part_result ps;
-			rc = mdb_partition_raw(ctx, (const uint64_t *)rec, list_len, s1, s2, 0, true, order_digits0(n_l, kbits, s1), &ps, true, 0);
+			mdb_part_request rq = order_request(rec, list_len, s1, s2);
+			rq.fast = true;
+			rq.digits0_used = order_digits0(n_l, kbits, s1);
+			rc = mdb_partition_raw(ctx, rq, &ps);
 			if (rc)
 				return rc;
 			if (ps.leaf_cap && !ps.w32) {
@@ -362,8 +378,13 @@ int order_records(mdb_dev_ctx *ctx, const unsigned long long *rec, uint64_t list
 	}
 	for (int sort_fast = 1; sort_fast >= 0; sort_fast--) {
 		mdb_part_result ps;
-		rc = mdb_partition_raw(ctx, (const uint64_t *)rec, list_len, sb1, sb2, ord_range, sort_fast != 0, order_digits0(n_l, kbits, sb1),
-				       &ps, true, (rec32 && sort_fast != 0) ? (in32 ? 2 : 1) : 0, (uint64_t)1 << (kbits - (uint32_t)sb1));
+		mdb_part_request rq = order_request(rec, list_len, sb1, sb2);
+		rq.fast = sort_fast != 0;
+		rq.leaf_cap = ord_range;
+		rq.digits0_used = order_digits0(n_l, kbits, sb1);
+		rq.digit0_rows = (uint64_t)1 << (kbits - (uint32_t)sb1);
+		rq.fold32 = (rec32 && sort_fast != 0) ? (in32 ? 2 : 1) : 0;
+		rc = mdb_partition_raw(ctx, rq, &ps);
 		if (rc)
 			return rc;
 		ord_args oa;

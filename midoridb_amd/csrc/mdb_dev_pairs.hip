@@ -427,6 +427,28 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_pairs_emit(pj_args a)
 	}
 }
 
+/* the partition request of one table of a pair join: histogram-free layout unless the caller says otherwise */
+static mdb_part_request pj_request(const int64_t *keys, const uint64_t *nulls, uint64_t n, int b1, int b2)
+{
+	mdb_part_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.keys = keys;
+	rq.nullbits = nulls;
+	rq.n = n;
+	rq.bits1 = b1;
+	rq.bits2 = b2;
+	rq.fast = true;
+	return rq;
+}
+
+/* ... in the compact narrow form with hash | row id words: keys in [lo, lo + 2^kbits) */
+static void pj_compact(mdb_part_request *rq, int64_t lo, uint32_t kbits)
+{
+	rq->narrow = 1;
+	rq->narrow_base = lo;
+	rq->narrow_kbits = kbits;
+}
+
 /* 0 = done, 1 = not applicable (overflow: use the general path), 2 = a key outside the window met the narrow form (call
  * again with narrow = false), 3 = a right key occurs more than once (not a unique-key join this way round), < 0 = error */
 static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
@@ -446,10 +468,17 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
 		return rc;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	mdb_part_result pl, pr;
-	rc = mdb_partition_table(ctx, keys_r, null_r, n_r, b1, b2, !narrow, false, true, &pr, narrow ? 1 : 0, false, base);
+	mdb_part_request rq = pj_request(keys_r, null_r, n_r, b1, b2);
+	rq.want_rid = !narrow;
+	rq.narrow = narrow ? 1 : 0;
+	rq.narrow_base = base;
+	rc = mdb_partition_table(ctx, rq, &pr);
 	if (rc)
 		return rc;
-	rc = mdb_partition_table(ctx, keys_l, null_l, n_l, b1, b2, !narrow, false, true, &pl, narrow ? 1 : 0, false, base);
+	rq.keys = keys_l;
+	rq.nullbits = null_l;
+	rq.n = n_l;
+	rc = mdb_partition_table(ctx, rq, &pl);
 	if (rc)
 		return rc;
 	unsigned long long *rec = (unsigned long long *)mdb_arena_take(ctx, rec_cap * 8);
@@ -519,7 +548,7 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
  * The primary-key join of BASELINE configs[1] (10^7 x 10^7 rows, 4 result columns).  Through the path above it is two
  * partition levels per table, a hashed leaf table, one 8-byte record per pair and an ordering sort of the records by left row
  * id: 0.46 ms of kernels before the projection.  When the key sample offers a compact window of at most 2^24 values (the
- * k-bit bijection of the compact narrow form) both tables are partitioned ONCE by 9 bits (mdb_part_filter.level0_only) and
+ * k-bit bijection of the compact narrow form) both tables are partitioned ONCE by 9 bits (mdb_part_request.level0_only) and
  * one 1024-thread workgroup joins a whole digit: a table of 2^(k-9) <= 2^15 LDS words indexed by the remaining hash bits
  * holds right row id + 1 - plain stores, no atomics: that the right keys are unique is checked afterwards (the number of
  * occupied entries must equal the number of right rows; otherwise status bit 5 and the caller takes the other paths).  A
@@ -737,14 +766,17 @@ static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	if (rc)
 		return rc;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
-	mdb_part_filter flt;
-	memset(&flt, 0, sizeof(flt));
-	flt.level0_only = true;
 	mdb_part_result pl, pr;
-	rc = mdb_partition_table(ctx, keys_r, null_r, n_r, b1, 0, false, false, true, &pr, 1, false, lo, kbits, &flt);
+	mdb_part_request rq = pj_request(keys_r, null_r, n_r, b1, 0);
+	pj_compact(&rq, lo, kbits);
+	rq.level0_only = true;
+	rc = mdb_partition_table(ctx, rq, &pr);
 	if (rc)
 		return rc;
-	rc = mdb_partition_table(ctx, keys_l, null_l, n_l, b1, 0, false, false, true, &pl, 1, false, lo, kbits, &flt);
+	rq.keys = keys_l;
+	rq.nullbits = null_l;
+	rq.n = n_l;
+	rc = mdb_partition_table(ctx, rq, &pl);
 	if (rc)
 		return rc;
 	uint32_t *match = (uint32_t *)mdb_arena_take(ctx, n_l * 4);
@@ -1143,18 +1175,19 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 		if (rc)
 			return rc;
 		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
-		mdb_part_filter rflt;
-		memset(&rflt, 0, sizeof(rflt));
-		rflt.npay = npay;
-		for (int c = 0; c < npay; c++)
-			rflt.pay_in[c] = pay_in[c];
 		mdb_part_result pl, pr;
 		memset(&pl, 0, sizeof(pl));
 		memset(&pr, 0, sizeof(pr));
-		rc = mdb_partition_table(ctx, keys_r, null_r, n_r, b1, b2, false, false, true, &pr, 1, false, win.lo, kbits, &rflt);
+		mdb_part_request lrq = pj_request(keys_l, null_l, n_l, b1, b2), rrq = pj_request(keys_r, null_r, n_r, b1, b2);
+		pj_compact(&lrq, win.lo, kbits);
+		pj_compact(&rrq, win.lo, kbits);
+		rrq.npay = npay;
+		for (int c = 0; c < npay; c++)
+			rrq.pay_in[c] = pay_in[c];
+		rc = mdb_partition_table(ctx, rrq, &pr);
 		if (rc)
 			return rc;
-		rc = mdb_partition_table(ctx, keys_l, null_l, n_l, b1, b2, false, false, true, &pl, 1, false, win.lo, kbits, NULL);
+		rc = mdb_partition_table(ctx, lrq, &pl);
 		if (rc)
 			return rc;
 		if (!pl.leaf_cap || !pr.leaf_cap || !pl.leaf_cnt || !pr.leaf_cnt || pl.nleaves != pr.nleaves || pl.w32 || pr.w32 || !pr.pay[0] ||
@@ -1212,20 +1245,20 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	if (rc)
 		return rc;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
-	mdb_part_filter flt, rflt;
-	memset(&flt, 0, sizeof(flt));
-	flt.level0_only = true;
-	rflt = flt;
-	rflt.npay = npay;
-	for (int c = 0; c < npay; c++)
-		rflt.pay_in[c] = pay_in[c];
 	mdb_part_result pl, pr;
 	memset(&pl, 0, sizeof(pl));
 	memset(&pr, 0, sizeof(pr));
-	rc = mdb_partition_table(ctx, keys_r, null_r, n_r, b1, 0, false, false, true, &pr, 1, false, win.lo, kbits, &rflt);
+	mdb_part_request lrq = pj_request(keys_l, null_l, n_l, b1, 0), rrq = pj_request(keys_r, null_r, n_r, b1, 0);
+	pj_compact(&lrq, win.lo, kbits);
+	pj_compact(&rrq, win.lo, kbits);
+	lrq.level0_only = rrq.level0_only = true;
+	rrq.npay = npay;
+	for (int c = 0; c < npay; c++)
+		rrq.pay_in[c] = pay_in[c];
+	rc = mdb_partition_table(ctx, rrq, &pr);
 	if (rc)
 		return rc;
-	rc = mdb_partition_table(ctx, keys_l, null_l, n_l, b1, 0, false, false, true, &pl, 1, false, win.lo, kbits, &flt);
+	rc = mdb_partition_table(ctx, lrq, &pl);
 	if (rc)
 		return rc;
 	if (!pl.nsub || pl.nsub != pr.nsub || pl.nleaves != pr.nleaves || pl.w32 || pr.w32 || !pr.pay[0] || (npay > 1 && !pr.pay[1]))
@@ -1669,7 +1702,11 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 		rc = mdb_aux_begin(ctx, &main_stream);	/* the right table is partitioned on the auxiliary stream (when enabled) */
 		if (rc)
 			return rc;
-		rc = mdb_partition_table(ctx, keys_r, null_r, n_r, b1, b2, true, !fast, fast != 0, &pr);
+		mdb_part_request rq = pj_request(keys_r, null_r, n_r, b1, b2);
+		rq.want_rid = true;
+		rq.fast = fast != 0;
+		rq.stable = !fast;
+		rc = mdb_partition_table(ctx, rq, &pr);
 		{
 			int rc2 = mdb_aux_end(ctx, main_stream);
 			if (rc)
@@ -1677,7 +1714,11 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 			if (rc2)
 				return rc2;
 		}
-		rc = mdb_partition_table(ctx, keys_l, null_l, n_l, b1, b2, true, false, fast != 0, &pl);
+		rq.keys = keys_l;
+		rq.nullbits = null_l;
+		rq.n = n_l;
+		rq.stable = false;
+		rc = mdb_partition_table(ctx, rq, &pl);
 		if (rc)
 			return rc;
 		if ((rc = mdb_aux_join(ctx)))

@@ -81,7 +81,7 @@ struct mdb_level_args {
 	uint32_t narrow_kbits;		/* compact narrow form: every key must lie in [narrow_base, narrow_base + 2^narrow_kbits); the 32-bit
 					 * hash is mixk(key - narrow_base) in the TOP narrow_kbits bits of the field, zeros below */
 	uint32_t keys32;		/* level 0: `keys` is an array of int32 (keys that crossed xGMI in the 4-byte wire format) */
-	/* semi-join filter (second level, left side of a join in the compact narrow form; struct mdb_part_filter): the slice of
+	/* semi-join filter (second level, left side of a join in the compact narrow form; mdb_part_request.bits): the slice of
 	 * first-level digit td.seg is words [seg * filter_words, ...); a row whose bit (hash32 >> filter_shift, masked to the
 	 * slice) is clear can join nothing and is dropped before it is ranked */
 	const uint32_t *filter;
@@ -1524,17 +1524,6 @@ void mdb_choose_bits(uint64_t n, uint32_t target, int *bits1, int *bits2)
 
 static inline uint32_t grid8(uint32_t tiles) { return ((tiles + 7u) / 8u) * 8u; }
 
-#define PART_F_STABLE 1u	/* keep input order inside every leaf (ballot ranking) */
-#define PART_F_FAST 2u		/* no histogram passes: fixed-capacity regions + atomic cursors (two-level partitions only) */
-#define PART_F_NARROW 4u	/* narrow form: words = fmix32(key) in both halves (mdb_level_args.narrow = 2) */
-#define PART_F_NARROW_RID 8u	/* narrow form with the row id in the low half of the word (narrow = 1; no row-id arrays) */
-#define PART_F_KEYS32 16u	/* the key column is int32 */
-#define PART_F_NO_GAPS 32u	/* raw words: a zero word is a word like any other, not a gap of the input list */
-#define PART_F_IN32 128u	/* with PART_F_FOLD32: the raw list already holds 4-byte words (nothing to fold) */
-#define PART_F_FOLD32 64u	/* raw 8-byte records are folded into 4-byte words by the first level (two-level fast layout only) */
-#define PART_F_LOOSE 1024u	/* first-level regions of 1.5 x (instead of 1.25 x) the average: few values per region, many rows per value */
-#define PART_F_OUT16 512u	/* with PART_F_STOP0 and 4-byte words: the first level writes 2-byte words (hash bits below the digit) */
-#define PART_F_STOP0 256u	/* first level only (histogram-free layout), bits2 = 0: the consumer walks the digits' sub-regions */
 #define PART_NSUB 8u		/* sub-regions per first-level digit in the FAST form */
 
 /* capacity of one leaf region of the FAST form: 1.5 x the average leaf + 1024, rounded up to 64 */
@@ -1544,507 +1533,615 @@ static inline uint32_t part_fast_cap(uint64_t n, uint32_t nleaves)
 	return (uint32_t)(((avg + avg / 2 + 1024) + 63) & ~63ull);
 }
 
-static int partition_impl(part_carver &cv, const int64_t *keys, const uint64_t *nullbits, uint64_t n, int bits1, int bits2,
-			  bool want_rid, uint32_t flags, uint32_t mode, uint32_t n_dest, bool inverse_out, uint64_t *final_hv_out,
-			  const uint64_t *raw_hv, uint32_t cap_override, mdb_part_result *out, uint32_t *final_rid_out = NULL,
-			  uint32_t digits0_used = 0, bool keys32_out = false, int64_t narrow_base = 0, uint32_t narrow_kbits = 0,
-			  const mdb_part_filter *flt = NULL, uint64_t raw_digit_rows = 0)
+/* a request and what only the destination partition (mdb_dev_partition_by_dest_pruned) adds to one */
+struct part_xrequest : mdb_part_request {
+	uint32_t mode;		/* enum mdb_digit_mode of the first level */
+	uint32_t n_dest;	/* MDB_DIGIT_MOD: its digits */
+	bool inverse_out;	/* the last level writes the original keys (the inverse hash of the words) ... */
+	bool keys32_out;	/* ... as 4-byte integers */
+	uint64_t *final_hv_out;	/* the caller's buffers: the last level writes straight into them */
+	uint32_t *final_rid_out;
+	explicit part_xrequest(const mdb_part_request &rq) : mdb_part_request(rq), mode(MDB_DIGIT_RADIX), n_dest(0), inverse_out(false), keys32_out(false), final_hv_out(NULL), final_rid_out(NULL) {}
+};
+
+/* ---- the layout of a request: which levels, which form each takes, how large the regions are.  Pure - no context, no arena, no device */
+struct part_layout {
+	int nlevels;
+	uint32_t R[2];		/* digits per level */
+	uint32_t nleaves;	/* leaves of the whole partition */
+	bool stop0;		/* first level only: the consumer walks the digits' sub-regions */
+	bool out16;		/* ... whose words are the 16 hash bits below the digit */
+	bool fast;		/* histogram-free last level (or only level, with stop0): one fixed-capacity region per leaf */
+	bool fast0;		/* ... and first level: PART_NSUB fixed-capacity sub-regions per digit */
+	bool fold32;		/* raw 8-byte records leave the first level as 4-byte words */
+	bool w32;		/* 4-byte words from the first level's output on */
+	int npay;		/* payload columns that travel with the words */
+	uint32_t fast_cap;	/* words per leaf region */
+	uint32_t cap0;		/* words per first-level sub-region */
+	uint32_t nreg0;		/* first-level sub-regions (their cursors) ... */
+	uint32_t nreg0_used;	/* ... and those of digits that can occur (their words): regions of digits that cannot occur are not allocated */
+	bool selective_ok;	/* the selective first level can serve the request (MDB_SELECTIVE_L0 and the caller's hint decide: part_selective) */
+	bool w32_unserved;	/* 4-byte words were asked for and the layout has none */
+	bool stop0_unserved;	/* level0_only was asked for and the layout is another */
+};
+
+static part_layout part_layout_of(const part_xrequest &x)
 {
-	mdb_dev_ctx *ctx = cv.ctx;
-	const bool dry = cv.dry;
-	const bool stable = flags & PART_F_STABLE;
-	const int nlevels = bits2 > 0 ? 2 : 1;
-	const bool stop0 = (flags & PART_F_STOP0) && nlevels == 1;
-	const bool out16 = stop0 && (flags & PART_F_OUT16) && (flags & PART_F_NARROW) && narrow_kbits && narrow_kbits - (uint32_t)bits1 <= 16u;
-	const uint32_t Rl[2] = { mode == MDB_DIGIT_MOD ? n_dest : (1u << bits1), 1u << bits2 };
-	const uint32_t nt0 = n ? (uint32_t)((n + MDB_TILE - 1) / MDB_TILE) : 1u;
-	/* FAST applies to the second level only, and only while leaf * cap stays a 32-bit index */
-	const uint32_t nleaves_total = nlevels == 2 ? Rl[0] * Rl[1] : Rl[0];
-	const uint32_t fast_cap = cap_override ? cap_override : part_fast_cap(n, nleaves_total);
-	const bool fast = (flags & PART_F_FAST) && !stable && (nlevels == 2 || stop0) && !final_hv_out &&
-			  (uint64_t)nleaves_total * fast_cap < 0xFFFFFFFFull;
+	part_layout y;
+	memset(&y, 0, sizeof(y));
+	const uint32_t kbits = x.narrow ? x.narrow_kbits : 0u;
+	y.nlevels = x.bits2 > 0 ? 2 : 1;
+	y.stop0 = x.level0_only && y.nlevels == 1;
+	y.out16 = y.stop0 && x.out16 && x.narrow == 2 && kbits && kbits - (uint32_t)x.bits1 <= 16u;
+	y.R[0] = x.mode == MDB_DIGIT_MOD ? x.n_dest : (1u << x.bits1);
+	y.R[1] = 1u << x.bits2;
+	/* FAST applies to the last level only, and only while leaf * cap stays a 32-bit index */
+	y.nleaves = y.nlevels == 2 ? y.R[0] * y.R[1] : y.R[0];
+	y.fast_cap = x.leaf_cap ? x.leaf_cap : part_fast_cap(x.n, y.nleaves);
+	y.fast = x.fast && !x.stable && (y.nlevels == 2 || y.stop0) && !x.final_hv_out && (uint64_t)y.nleaves * y.fast_cap < 0xFFFFFFFFull;
 	/* ... and, with it, to the first level: PART_NSUB fixed-capacity sub-regions per digit */
-	const uint32_t nreg0 = Rl[0] * PART_NSUB;
+	y.nreg0 = y.R[0] * PART_NSUB;
 	/* raw sort keys need not cover the whole first digit range (row ids below n < 2^kbits): the regions are
 	 * sized for the digits that can occur */
-	const uint32_t nreg0_used = (digits0_used && digits0_used < Rl[0] ? digits0_used : Rl[0]) * PART_NSUB;
-	uint64_t avg0 = (n + nreg0_used - 1) / nreg0_used;
-	/* raw sort keys that are ROW IDS (the ordering of group records by first row): a first-level digit spans raw_digit_rows ids and every id
-	 * occurs once at most, so min(n, raw_digit_rows) words is the most a digit can receive - and receives, where the first rows bunch
+	y.nreg0_used = (x.digits0_used && x.digits0_used < y.R[0] ? x.digits0_used : y.R[0]) * PART_NSUB;
+	uint64_t avg0 = (x.n + y.nreg0_used - 1) / y.nreg0_used;
+	/* raw sort keys that are ROW IDS (the ordering of group records by first row): a first-level digit spans digit0_rows ids and every id
+	 * occurs once at most, so min(n, digit0_rows) words is the most a digit can receive - and receives, where the first rows bunch
 	 * (single-table GROUP BY over random duplicates: most groups' first rows lie in the first tenth of the table).  Regions sized for
 	 * that never send the sort to its exact layout; the list's order has nothing to do with the row ids, so a digit's words spread
 	 * evenly over its sub-regions */
-	if (raw_digit_rows) {
-		const uint64_t most = n < raw_digit_rows ? n : raw_digit_rows, per_sub = (most + PART_NSUB - 1) / PART_NSUB;
+	if (x.fast && x.digit0_rows) {
+		const uint64_t most = x.n < x.digit0_rows ? x.n : x.digit0_rows, per_sub = (most + PART_NSUB - 1) / PART_NSUB;
 		if (per_sub > avg0)
 			avg0 = per_sub;
 	}
-	/* (flt->region_cap: the caller fixes the capacity of a first-level region itself - the sharded operator, whose ranks must
-	 * agree on it: the regions ARE the transfer blocks, mdb_dev_shard.hip) */
-	const uint32_t cap0 = (flt && flt->region_cap) ? flt->region_cap
-						       : (uint32_t)((((flags & PART_F_LOOSE) ? avg0 * 3 / 2 : avg0 * 5 / 4) + 1024 + 63) & ~63ull);
-	const bool fast0 = fast && mode == MDB_DIGIT_RADIX && (uint64_t)nreg0_used * cap0 < 0xFFFFFFFFull;
+	y.cap0 = x.region_cap ? x.region_cap : (uint32_t)((((x.level0_only && x.loose) ? avg0 * 3 / 2 : avg0 * 5 / 4) + 1024 + 63) & ~63ull);
+	y.fast0 = y.fast && x.mode == MDB_DIGIT_RADIX && (uint64_t)y.nreg0_used * y.cap0 < 0xFFFFFFFFull;
 	/* narrow form without row ids (right side of a join): 4-byte words from the first level's output on; only built for
 	 * the histogram-free layout of both levels (callers ask mdb_partition_w32_applies() first) */
-	const bool fold32 = (flags & PART_F_FOLD32) && raw_hv && fast0 && fast;
-	const bool w32 = ((flags & PART_F_NARROW) && fast0 && fast) || fold32;
-	if ((flags & (PART_F_NARROW | PART_F_FOLD32)) && !w32 && !dry)
-		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "4-byte partition words need the two-level fast layout");
-	if ((flags & PART_F_STOP0) && !(stop0 && fast0) && !dry)
-		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "first-level-only partition: histogram-free layout, one level");
+	y.fold32 = x.fold32 && x.raw_hv && y.fast0 && y.fast;
+	y.w32 = (x.narrow == 2 && y.fast0 && y.fast) || y.fold32;
+	y.w32_unserved = (x.narrow == 2 || x.fold32) && !y.w32;
+	y.stop0_unserved = x.level0_only && !(y.stop0 && y.fast0);
+	/* payload cells beside the words: one buffer per level, laid out like that level's words */
+	y.npay = (y.fast0 && !y.w32 && (y.stop0 || (y.fast && y.nlevels == 2))) ? x.npay : 0;
+	/* the pruned left table of the compact narrow form (hash | row id words over an int64 column, no NULL bitmap): k_part_scatter<pf_key_cf_sel> */
+	y.selective_ok = y.fast0 && x.range_in && !x.nullbits && !x.raw_hv && !x.want_rid && !y.w32 && !y.npay && !x.minmax64_out && x.narrow == 1 && kbits &&
+			 !x.keys32;
+	return y;
+}
 
-	uint64_t *hv_buf[2] = { NULL, NULL };
-	uint32_t *rid_buf[2] = { NULL, NULL };
-	for (int l = 0; l < nlevels; l++) {
-		const uint64_t elems = (fast && l == 1) ? (uint64_t)nleaves_total * fast_cap
-				       : ((fast0 && l == 0) ? (uint64_t)nreg0_used * cap0 : (n ? n : 1));	/* regions of digits that cannot occur are not allocated */
-		if (l == nlevels - 1 && final_hv_out)
-			hv_buf[l] = final_hv_out;	/* last level writes straight into the caller's buffer */
-		else
-			hv_buf[l] = (uint64_t *)cv.take(elems * (w32 ? 4 : 8));
-		if (want_rid)
-			rid_buf[l] = (l == nlevels - 1 && final_rid_out) ? final_rid_out : (uint32_t *)cv.take(elems * 4);
-	}
-	/* payload cells beside the words (mdb_part_filter.npay): one buffer per level, laid out like that level's words */
-	uint64_t *pay_buf[2] = { NULL, NULL }, *pay_buf1[2] = { NULL, NULL };
-	const int npay = (flt && fast0 && !w32 && (stop0 || (fast && nlevels == 2))) ? flt->npay : 0;
-	for (int c = 0; c < npay && c < 2; c++) {
-		pay_buf[c] = (uint64_t *)cv.take((uint64_t)nreg0_used * cap0 * 8);
-		if (!stop0)
-			pay_buf1[c] = (uint64_t *)cv.take((uint64_t)nleaves_total * fast_cap * 8);
-	}
-	/* the pruned left table of the compact narrow form (hash | row id words over an int64 column, no NULL bitmap) when the caller expects a
-	 * selective join: k_part_scatter<pf_key_cf_sel> (MDB_SELECTIVE_L0=0: never, 2: whatever the caller expects) */
-	const long long sel_knob = dry ? 0 : mdb_knob_int("MDB_SELECTIVE_L0", 1);
-	const bool sel0 = !dry && fast0 && flt && flt->range_in && !nullbits && !raw_hv && !want_rid && !w32 && !npay && !flt->minmax64_out &&
-			  (flags & PART_F_NARROW_RID) && narrow_kbits && !(flags & PART_F_KEYS32) && (sel_knob == 2 || (sel_knob != 0 && flt->selective));
-	/* ... which reads a column from any 8-byte boundary; every other first level loads pairs of keys from where the column starts */
-	if (!dry && keys && !(flags & PART_F_KEYS32) && ((uintptr_t)keys & 15) && !sel0)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "key columns must be 16-byte aligned on the device (8-byte for int32 keys)");
+/* ---- the knobs of the first level's choice of instance, read once per run */
+struct part_knobs {
+	long long selective_l0;	/* MDB_SELECTIVE_L0 - 0: never the selective first level, 1: where the caller knows the join is selective, 2: whatever it expects */
+	long long tile2_min;	/* MDB_TILE2_MIN - rows from which the tiles of 2 x MDB_TILE rows are taken (default 2^25; tests: the form on small tables) */
+	long long tile4_min;	/* MDB_TILE4_MIN - the same for the tiles of 4 x MDB_TILE rows */
+	bool tile2_off;		/* MDB_TILE2=0: MDB_TILE rows everywhere */
+	bool tile4_off;		/* MDB_TILE4=0: no tiles of 4 x MDB_TILE rows */
+};
 
-	/* segments of the current level */
-	uint32_t S = 1;
-	uint32_t *seg_start = (uint32_t *)cv.take(2 * 4);
-	uint32_t *tb = (uint32_t *)cv.take(2 * 4);
-	if (cv.failed)
+static part_knobs part_knobs_read(void)
+{
+	part_knobs kn;
+	kn.selective_l0 = mdb_knob_int("MDB_SELECTIVE_L0", 1);
+	kn.tile2_min = mdb_knob_int("MDB_TILE2_MIN", 0);
+	kn.tile4_min = mdb_knob_int("MDB_TILE4_MIN", 0);
+	kn.tile2_off = mdb_knob_off("MDB_TILE2") != 0;
+	kn.tile4_off = mdb_knob_off("MDB_TILE4") != 0;
+	return kn;
+}
+
+/* ... whether the selective first level runs - which reads a column from any 8-byte boundary; every other first level loads pairs of keys
+ * from where the column starts */
+static bool part_selective(const part_xrequest &x, const part_layout &y, const part_knobs &kn)
+{
+	return y.selective_ok && (kn.selective_l0 == 2 || (kn.selective_l0 != 0 && x.selective));
+}
+
+/* ---- one kernel launch of a level, as the ladders below choose it */
+typedef void (*part_kernel)(mdb_level_args);
+enum part_reduce { PART_RED_NONE = 0, PART_RED_MINMAX, PART_RED_MINMAX64 };	/* the per-tile (min, max) pairs a first level left behind, reduced after it */
+struct part_launch {
+	const char *name;	/* profiler name */
+	part_kernel kernel;	/* NULL: no instance serves the request */
+	uint32_t threads;
+	uint32_t rows;		/* rows per tile */
+	bool span16;		/* first level: tiles are counted from the 16-byte boundary at or below the first key */
+	part_reduce reduce;
+};
+
+template <typename F>
+static part_launch part_scatter(const char *name, uint32_t rows = MDB_TILE, uint32_t threads = PART_THREADS)
+{
+	const part_launch pl = { name, k_part_scatter<F>, threads, rows, false, PART_RED_NONE };
+	return pl;
+}
+
+/* the histogram-free first level.  Tables of 2^25 rows and more: tiles of 2 x MDB_TILE rows in the instances that have them, and of
+ * 4 x MDB_TILE rows, 1024 threads, for the 2-byte words of an int64 column without a NULL bitmap (MDB_TILE2=0 asks for MDB_TILE rows
+ * everywhere: not these either) */
+static part_launch part_first_launch(const part_xrequest &x, const part_layout &y, const part_knobs &kn, const mdb_level_args &a)
+{
+	const uint32_t rows2 = PART_TMUL * MDB_TILE;
+	/* compact narrow form over an int64 column: the instances that know so at compile time */
+	const bool cf = a.narrow && a.narrow_kbits && !x.keys32 && x.mode == MDB_DIGIT_RADIX && !x.raw_hv && !x.want_rid;
+	const bool t2 = x.n >= (kn.tile2_min > 0 ? (uint64_t)kn.tile2_min : (1ull << 25)) && !kn.tile2_off;
+	const bool t4 = cf && !x.nullbits && x.n >= (kn.tile4_min > 0 ? (uint64_t)kn.tile4_min : (1ull << 25)) && !kn.tile4_off && !kn.tile2_off;
+	if (x.raw_hv)
+		return (y.fold32 && t2) ? part_scatter<pf_word_raw_w32_t2>("sort_scatter_l0_w32", rows2)
+		       : y.fold32 ? part_scatter<pf_word_raw_w32>("sort_scatter_l0_w32") : part_scatter<pf_word_raw>("sort_scatter_l0");
+	if (y.w32) {
+		part_launch pl = !y.out16 ? (cf ? part_scatter<pf_key_w32_cf>("part_scatter_l0_w32") : part_scatter<pf_key_w32>("part_scatter_l0_w32"))
+				 : t4 ? part_scatter<pf_key_w32_out16_cf_t4>("part_scatter_l0_w32", PART_T4_TILE, PART_T4_THREADS)
+				 : (cf && t2) ? part_scatter<pf_key_w32_out16_cf_t2>("part_scatter_l0_w32", rows2)
+				 : cf ? part_scatter<pf_key_w32_out16_cf>("part_scatter_l0_w32")
+				      : part_scatter<pf_key_w32_out16>("part_scatter_l0_w32");
+		pl.reduce = a.minmax_out ? PART_RED_MINMAX : PART_RED_NONE;	/* (every tile of the launch leaves its pair) */
+		return pl;
+	}
+	if (y.npay) {	/* (payload cells travel with the compact narrow form's hash | row id words only) */
+		part_launch pl = part_scatter<pf_key_cf_pay>("part_scatter_l0_pay");
+		if (!cf || a.narrow != 1u)
+			pl.kernel = NULL;
+		return pl;
+	}
+	if (x.want_rid)		/* (64-bit form, left table, min-max pruning: the first) */
+		return a.range64_in ? part_scatter<pf_key_rid_r64>("part_scatter_l0_rid_pruned") : part_scatter<pf_key_rid>("part_scatter_l0_rid");
+	if (a.minmax64_out) {			/* 64-bit form, right table: its key range recorded */
+		part_launch pl = part_scatter<pf_key_mm64>("part_scatter_l0");
+		pl.reduce = PART_RED_MINMAX64;
+		return pl;
+	}
+	if (part_selective(x, y, kn)) {
+		part_launch pl = t2 ? part_scatter<pf_key_cf_sel_t2>("part_scatter_l0_pruned", rows2) : part_scatter<pf_key_cf_sel>("part_scatter_l0_pruned");
+		pl.span16 = true;
+		return pl;
+	}
+	/* (the same instances under two names: a pruned pass's bytes differ - most rows are read, not written) */
+	const char *name = a.range_in ? "part_scatter_l0_pruned" : "part_scatter_l0";
+	return (cf && t2) ? part_scatter<pf_key_cf_t2>(name, rows2) : cf ? part_scatter<pf_key_cf>(name) : part_scatter<pf_key>(name);
+}
+
+/* tiles of a first level's launch over `span` rows.  (Kept as it was: over an empty table only the instances of MDB_TILE rows that
+ * count from the first key run one - empty - tile; the others get a grid of none) */
+static uint32_t part_first_tiles(const part_launch &pl, uint64_t span)
+{
+	const uint32_t t = (uint32_t)((span + pl.rows - 1) / pl.rows);
+	return (t || pl.rows != MDB_TILE || pl.span16) ? t : 1u;
+}
+
+/* the histogram-free last level: one cursor per leaf, runs placed with global atomics */
+static part_launch part_last_launch(const part_xrequest &x, const part_layout &y, const mdb_level_args &a)
+{
+	return y.npay ? part_scatter<pf_word_pay>("part_scatter_l1_pay")
+	       : x.want_rid ? part_scatter<pf_word_rid>("part_scatter_l1_rid")
+	       : (x.raw_hv && y.fold32) ? part_scatter<pf_word_raw_w32>("sort_scatter_l1_w32")
+	       : x.raw_hv ? part_scatter<pf_word_raw>("sort_scatter_l1")
+	       : y.w32 ? part_scatter<pf_word_w32>("part_scatter_l1_w32")
+	       : a.filter ? part_scatter<pf_word_semi>("part_scatter_l1_semi")
+			  : part_scatter<pf_word>("part_scatter_l1");
+}
+
+/* the exact layout: a level's histogram kernel, and its scatter kernel */
+static part_launch part_hist_launch(const part_xrequest &x, int level)
+{
+	part_launch pl = { "part_hist_l1", k_part_hist<false>, PART_THREADS, MDB_TILE, false, PART_RED_NONE };
+	if (level == 0 && x.raw_hv) {
+		pl.name = "sort_hist_l0";
+		pl.kernel = k_part_hist<false, true>;
+	} else if (level == 0) {
+		pl.name = x.mode == MDB_DIGIT_MOD ? "dest_hist" : "part_hist_l0";
+		pl.kernel = k_part_hist<true>;
+	}
+	return pl;
+}
+
+static part_launch part_exact_launch(const part_xrequest &x, int level, const mdb_level_args &a)
+{
+	if (level != 0)
+		return x.stable ? part_scatter<pf_word_rid_stable_hist>("part_scatter_l1_stable")
+		       : x.want_rid ? part_scatter<pf_word_rid_hist>("part_scatter_l1") : part_scatter<pf_word_hist>("part_scatter_l1");
+	return x.raw_hv ? part_scatter<pf_word_hist_raw>("sort_scatter_l0")
+	       : x.stable ? part_scatter<pf_key_rid_stable_hist>("part_scatter_l0_stable")
+	       : (a.inverse_out && x.want_rid) ? part_scatter<pf_key_rid_hist_dest>("dest_scatter")
+	       : a.inverse_out ? part_scatter<pf_key_hist_dest>("dest_scatter")
+	       : x.want_rid ? part_scatter<pf_key_rid_hist>("part_scatter_l0")
+			    : part_scatter<pf_key_hist>("part_scatter_l0");
+}
+
+/* ---- what the levels hand on to each other.  The sizing pass (cv.dry) and the real one walk the same functions with the same carver:
+ * they cannot disagree about what is taken from the arena */
+struct part_walk {
+	part_carver cv;
+	uint64_t *hv_buf[2];	/* per level: its output words, row ids ... */
+	uint32_t *rid_buf[2];
+	uint64_t *pay_buf[2], *pay_buf1[2];	/* ... and payload cells (first level, last level) */
+	uint32_t S;		/* segments of the current level's input */
+	uint32_t *seg_start, *tb;	/* exact layout: their starts and tile bases */
+	const mdb_tile_desc *tiles;	/* tile descriptors of the current level's input (NULL: level 0, computed arithmetically) ... */
+	uint32_t ntiles;	/* ... and their number (an upper bound from level 1 on) */
+	int used_bits;		/* hash bits consumed so far */
+	uint32_t *leaf_cnt;	/* fast layout: the leaf cursors (with stop0: the first level's) */
+};
+
+/* the levels' output buffers and the first level's segment words */
+static void part_carve_outputs(const part_xrequest &x, const part_layout &y, part_walk &w)
+{
+	for (int l = 0; l < y.nlevels; l++) {
+		const uint64_t elems = (y.fast && l == 1) ? (uint64_t)y.nleaves * y.fast_cap
+				       : ((y.fast0 && l == 0) ? (uint64_t)y.nreg0_used * y.cap0 : (x.n ? x.n : 1));
+		const bool last = l == y.nlevels - 1;
+		w.hv_buf[l] = (last && x.final_hv_out) ? x.final_hv_out : (uint64_t *)w.cv.take(elems * (y.w32 ? 4 : 8));
+		if (x.want_rid)
+			w.rid_buf[l] = (last && x.final_rid_out) ? x.final_rid_out : (uint32_t *)w.cv.take(elems * 4);
+	}
+	for (int c = 0; c < y.npay && c < 2; c++) {
+		w.pay_buf[c] = (uint64_t *)w.cv.take((uint64_t)y.nreg0_used * y.cap0 * 8);
+		if (!y.stop0)
+			w.pay_buf1[c] = (uint64_t *)w.cv.take((uint64_t)y.nleaves * y.fast_cap * 8);
+	}
+	w.seg_start = (uint32_t *)w.cv.take(2 * 4);
+	w.tb = (uint32_t *)w.cv.take(2 * 4);
+}
+
+/* the kernel arguments of level `l`, but for what belongs to the level's form (cursors and capacities, histogram, payload buffers) */
+static mdb_level_args part_level_args(const part_xrequest &x, const part_layout &y, int l, const part_walk &w)
+{
+	mdb_dev_ctx *ctx = w.cv.ctx;
+	mdb_level_args a;
+	memset(&a, 0, sizeof(a));
+	a.keys = x.keys;
+	a.nullbits = x.nullbits;
+	a.n = x.n;
+	a.hv_in = l ? w.hv_buf[l - 1] : x.raw_hv;	/* raw_hv: level 0 reads ready-made 64-bit sort keys */
+	a.skip_zero = (l == 0 && x.raw_hv && x.zero_is_gap) ? 1u : 0u;
+	a.fold64 = (y.fold32 && l == 0 && x.fold32 != 2) ? 1u : 0u;
+	a.rid_in = l ? w.rid_buf[l - 1] : NULL;
+	a.tiles = w.tiles;
+	a.hv_out = w.hv_buf[l];
+	a.rid_out = w.rid_buf[l];
+	a.ntiles = w.ntiles;
+	a.R = y.R[l];
+	a.mode = l == 0 ? x.mode : (uint32_t)MDB_DIGIT_RADIX;
+	a.inverse_out = (x.inverse_out && l == y.nlevels - 1) ? (x.keys32_out ? 2u : 1u) : 0u;
+	a.narrow = (l == 0 && (x.narrow == 1 || x.narrow == 2)) ? (uint32_t)x.narrow : 0u;
+	a.status = ctx ? ctx->d_status : NULL;
+	a.keys32 = x.keys32 ? 1u : 0u;
+	a.narrow_base = x.narrow ? x.narrow_base : 0;
+	a.narrow_kbits = a.narrow ? x.narrow_kbits : 0u;
+	a.own_on = (l == 0 && x.own_on) ? 1u : 0u;
+	a.own_lo = x.own_lo;
+	a.own_hi = x.own_hi;
+	a.keep_on = (l == 0 && x.keep_on) ? 1u : 0u;
+	a.keep_lo = x.keep_lo;
+	a.keep_hi = x.keep_hi;
+	a.minmax_out = (l == 0 && x.minmax_out) ? x.minmax_tiles : NULL;	/* per-tile pairs, reduced after the launch */
+	a.minmax_final = a.minmax_out ? x.minmax_out : NULL;
+	a.range_in = l == 0 ? x.range_in : NULL;
+	a.minmax64_out = (l == 0 && x.minmax64_out) ? x.minmax64_tiles : NULL;
+	a.range64_in = l == 0 ? x.range64_in : NULL;
+	a.filter = l == 1 ? x.bits : NULL;
+	a.filter_words = x.words;
+	a.filter_shift = x.shift;
+	if (a.mode == MDB_DIGIT_RADIX) {
+		const int b = l == 0 ? x.bits1 : x.bits2;
+		a.shift = (uint32_t)((y.w32 ? 32 : 64) - w.used_bits - b);
+		a.mbits = (uint32_t)b;
+	} else {
+		uint32_t mb = 1;
+		while ((1u << mb) < a.R)
+			mb++;
+		a.shift = 0;
+		a.mbits = mb;
+	}
+	return a;
+}
+
+/* the first level's launch, and the reduction of the key range it recorded */
+static int part_first_run(mdb_dev_ctx *ctx, const part_xrequest &x, const part_layout &y, const part_knobs &kn, const part_walk &w, mdb_level_args &a)
+{
+	const part_launch pl = part_first_launch(x, y, kn, a);
+	if (!pl.kernel)
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "payload cells travel with the compact narrow form's hash | row id words only");
+	if (!x.raw_hv && y.w32 && y.out16)
+		a.out16_shift = 32u - a.narrow_kbits;
+	if (!x.raw_hv && y.npay) {
+		a.npay = (uint32_t)y.npay;
+		for (int c = 0; c < y.npay; c++) {
+			a.pay_in[c] = reinterpret_cast<const uint64_t *>(x.pay_in[c]);
+			a.pay_out[c] = w.pay_buf[c];
+		}
+	}
+	/* (the selective instance counts positions from the aligned address below the first key) */
+	a.ntiles = part_first_tiles(pl, x.n + (pl.span16 ? (((uintptr_t)x.keys >> 3) & 1u) : 0u));
+	MDB_LAUNCH(ctx, pl.name, pl.kernel, grid8(a.ntiles), pl.threads, a);
+	if (pl.reduce == PART_RED_MINMAX)
+		MDB_LAUNCH(ctx, "part_minmax", k_part_minmax_reduce, MM_GROUPS, MM_THREADS, (const uint32_t *)a.minmax_out, a.ntiles, x.minmax_out);
+	if (pl.reduce == PART_RED_MINMAX64)
+		MDB_LAUNCH(ctx, "part_minmax", k_part_minmax64_reduce, 1, 1024, (const unsigned long long *)a.minmax64_out, a.ntiles, x.minmax64_out);
+	return MIDORIDB_OK;
+}
+
+/* histogram-free first level: PART_NSUB sub-regions per digit, then the tile descriptors of the level behind it */
+static int part_level_first(const part_xrequest &x, const part_layout &y, const part_knobs *kn, part_walk &w)
+{
+	mdb_dev_ctx *ctx = w.cv.ctx;
+	const bool dry = w.cv.dry;
+	const bool cursor_ext = !dry && x.cursor0_ext && y.nreg0 <= x.cursor0_ext_words;
+	uint32_t *cursor0 = cursor_ext ? x.cursor0_ext : (uint32_t *)w.cv.take((size_t)y.nreg0 * 4);
+	uint32_t *reg_nt = (uint32_t *)w.cv.take(((size_t)y.nreg0 + 1) * 4);
+	const uint32_t next_tiles = (uint32_t)(x.n / MDB_TILE) + y.nreg0 + 1;
+	mdb_tile_desc *next_desc = y.stop0 ? NULL : (mdb_tile_desc *)w.cv.take((size_t)next_tiles * sizeof(mdb_tile_desc));
+	if (w.cv.failed)
 		return -MIDORIDB_INTERNAL;
-	if (!dry && !fast0)	/* the FAST first level has no parent segments to describe */
-		MDB_LAUNCH(ctx, "part_seg0", k_part_seg0, 1, 64, seg_start, tb, (uint32_t)n, nt0);
-
-	uint32_t ntiles = nt0;
-	const mdb_tile_desc *tiles = NULL;
-	uint32_t *leaf_cnt = NULL;
-	int used_bits = 0;
-	for (int l = 0; l < nlevels; l++) {
-		const uint32_t R = Rl[l];
-		const uint32_t nchild = S * R;
-		const bool fast_level = fast && l == 1;
-		mdb_level_args a;
-		memset(&a, 0, sizeof(a));
-		a.keys = keys;
-		a.nullbits = nullbits;
-		a.n = n;
-		a.hv_in = l ? hv_buf[l - 1] : raw_hv;	/* raw_hv: level 0 reads ready-made 64-bit sort keys */
-		a.skip_zero = (l == 0 && raw_hv && !(flags & PART_F_NO_GAPS)) ? 1u : 0u;
-		a.fold64 = (fold32 && l == 0 && !(flags & PART_F_IN32)) ? 1u : 0u;
-		a.rid_in = l ? rid_buf[l - 1] : NULL;
-		a.tiles = tiles;
-		a.hv_out = hv_buf[l];
-		a.rid_out = rid_buf[l];
-		a.ntiles = ntiles;
-		a.R = R;
-		a.mode = l == 0 ? mode : MDB_DIGIT_RADIX;
-		a.inverse_out = (inverse_out && l == nlevels - 1) ? (keys32_out ? 2u : 1u) : 0u;
-		a.narrow = l == 0 ? ((flags & PART_F_NARROW_RID) ? 1u : ((flags & PART_F_NARROW) ? 2u : 0u)) : 0u;
-		a.status = ctx ? ctx->d_status : NULL;
-		a.keys32 = (flags & PART_F_KEYS32) ? 1u : 0u;
-		a.narrow_base = narrow_base;
-		a.narrow_kbits = a.narrow ? narrow_kbits : 0u;
-		a.own_on = (flt && l == 0 && flt->own_on) ? 1u : 0u;
-		a.own_lo = flt ? flt->own_lo : 0;
-		a.own_hi = flt ? flt->own_hi : 0;
-		a.keep_on = (flt && l == 0 && flt->keep_on) ? 1u : 0u;
-		a.keep_lo = flt ? flt->keep_lo : 0;
-		a.keep_hi = flt ? flt->keep_hi : 0;
-		a.minmax_out = (flt && l == 0 && flt->minmax_out) ? flt->minmax_tiles : NULL;	/* per-tile pairs, reduced after the launch */
-		a.minmax_final = a.minmax_out ? flt->minmax_out : NULL;
-		a.range_in = (flt && l == 0) ? flt->range_in : NULL;
-		a.minmax64_out = (flt && l == 0 && flt->minmax64_out) ? flt->minmax64_tiles : NULL;
-		a.range64_in = (flt && l == 0) ? flt->range64_in : NULL;
-		a.filter = (flt && l == 1) ? flt->bits : NULL;
-		a.filter_words = flt ? flt->words : 0u;
-		a.filter_shift = flt ? flt->shift : 0u;
-		if (a.mode == MDB_DIGIT_RADIX) {
-			const int b = l == 0 ? bits1 : bits2;
-			a.shift = (uint32_t)((w32 ? 32 : 64) - used_bits - b);
-			a.mbits = (uint32_t)b;
-		} else {
-			uint32_t mb = 1;
-			while ((1u << mb) < R)
-				mb++;
-			a.shift = 0;
-			a.mbits = mb;
+	if (!dry) {
+		mdb_level_args a = part_level_args(x, y, 0, w);
+		a.cursor = cursor0;
+		a.cap = y.cap0;
+		a.nsub = PART_NSUB;
+		if (!cursor_ext)
+			MDB_HIP(ctx, hipMemsetAsync(cursor0, 0, (size_t)y.nreg0 * 4, ctx->stream));
+		const int rc = part_first_run(ctx, x, y, *kn, w, a);
+		if (rc)
+			return rc;
+		if (!y.stop0) {
+			MDB_LAUNCH(ctx, "part_region_tiles", k_part_region_tiles_scan, 1, 1024, cursor0, y.nreg0, y.cap0, PART_NSUB, reg_nt);
+			MDB_LAUNCH(ctx, "part_build_tiles", k_part_build_tiles_regions, (next_tiles + 255) / 256, 256, cursor0, reg_nt, y.nreg0, y.cap0,
+				   PART_NSUB, next_desc, next_tiles);
 		}
+	}
+	if (y.stop0) {
+		w.leaf_cnt = cursor0;
+		return MIDORIDB_OK;
+	}
+	uint32_t real_tiles = next_tiles;
+	if (!dry && (x.range_in || x.range64_in) && x.expect_pruned) {
+		/* min-max pruning may have dropped most rows: the second level is launched for the tiles that exist (one
+		 * 4-byte read-back and a synchronisation, ~15 us) - 26 000 workgroups that find an empty descriptor and leave
+		 * cost 0.09 ms at 10^8 rows */
+		uint64_t *h = ctx->h_pinned;
+		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_PART_TILES], reg_nt + y.nreg0, 4, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		const uint32_t got = (uint32_t)h[MDB_HP_PART_TILES];
+		real_tiles = got < next_tiles ? (got ? got : 1u) : next_tiles;
+	}
+	w.used_bits += x.bits1;
+	w.seg_start = NULL;
+	w.tb = NULL;
+	w.S = y.R[0];
+	w.tiles = next_desc;
+	w.ntiles = real_tiles;
+	return MIDORIDB_OK;
+}
 
-		if (fast0 && l == 0) {
-			/* histogram-free first level */
-			const bool cursor_ext = !dry && flt && flt->cursor0_ext && nreg0 <= flt->cursor0_ext_words;
-			uint32_t *cursor0 = cursor_ext ? flt->cursor0_ext : (uint32_t *)cv.take((size_t)nreg0 * 4);
-			uint32_t *reg_nt = (uint32_t *)cv.take(((size_t)nreg0 + 1) * 4);
-			const uint32_t next_tiles = (uint32_t)(n / MDB_TILE) + nreg0 + 1;
-			mdb_tile_desc *next_desc = stop0 ? NULL : (mdb_tile_desc *)cv.take((size_t)next_tiles * sizeof(mdb_tile_desc));
-			if (cv.failed)
-				return -MIDORIDB_INTERNAL;
-			if (!dry) {
-				/* compact narrow form over an int64 column: the instances that know so at compile time */
-				const bool cf = a.narrow && narrow_kbits && !(flags & PART_F_KEYS32) && mode == MDB_DIGIT_RADIX && !raw_hv && !want_rid;
-				a.cursor = cursor0;
-				a.cap = cap0;
-				a.nsub = PART_NSUB;
-				a.status = ctx->d_status;
-				if (!cursor_ext)
-					MDB_HIP(ctx, hipMemsetAsync(cursor0, 0, (size_t)nreg0 * 4, ctx->stream));
-				/* tables of 2^25 rows and more: tiles of 2 x MDB_TILE rows in the instances that have them (MDB_TILE2=0: never) */
-				const long long t2min = mdb_knob_int("MDB_TILE2_MIN", 0);	/* (tests: the form on small tables) */
-				const bool t2 = n >= (t2min > 0 ? (uint64_t)t2min : (1ull << 25)) &&
-						!mdb_knob_off("MDB_TILE2");
-				const uint32_t ntiles2 = (uint32_t)((n + (uint64_t)PART_TMUL * MDB_TILE - 1) / ((uint64_t)PART_TMUL * MDB_TILE));
-				if (raw_hv && fold32 && t2) {
-					a.ntiles = ntiles2;
-					MDB_LAUNCH(ctx, "sort_scatter_l0_w32", (k_part_scatter<pf_word_raw_w32_t2>), grid8(ntiles2), PART_THREADS, a);
-				} else if (raw_hv && fold32) {
-					MDB_LAUNCH(ctx, "sort_scatter_l0_w32", (k_part_scatter<pf_word_raw_w32>), grid8(ntiles), PART_THREADS, a);
-				} else if (raw_hv) {
-					MDB_LAUNCH(ctx, "sort_scatter_l0", (k_part_scatter<pf_word_raw>), grid8(ntiles), PART_THREADS, a);
-				} else if (w32) {
-					if (out16) {
-						a.out16_shift = 32u - narrow_kbits;
-						/* ... and of 4 x MDB_TILE rows, 1024 threads, for an int64 column without a NULL bitmap (MDB_TILE4=0: never; MDB_TILE2=0
-						 * asks for MDB_TILE rows everywhere: not these either) */
-						const long long t4min = mdb_knob_int("MDB_TILE4_MIN", 0);	/* (tests: the form on small tables) */
-						const bool t4 = cf && !nullbits && n >= (t4min > 0 ? (uint64_t)t4min : (1ull << 25)) && !mdb_knob_off("MDB_TILE4") &&
-								!mdb_knob_off("MDB_TILE2");
-						if (t4) {
-							a.ntiles = (uint32_t)((n + PART_T4_TILE - 1) / PART_T4_TILE);
-							MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_out16_cf_t4>),
-								   grid8(a.ntiles), PART_T4_THREADS, a);
-						} else if (cf && t2) {
-							a.ntiles = ntiles2;
-							MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_out16_cf_t2>),
-								   grid8(ntiles2), PART_THREADS, a);
-						} else if (cf) {
-							MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_out16_cf>),
-								   grid8(ntiles), PART_THREADS, a);
-						} else {
-							MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_out16>),
-								   grid8(ntiles), PART_THREADS, a);
-						}
-					} else if (cf) {
-						MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32_cf>),
-							   grid8(ntiles), PART_THREADS, a);
-					} else {
-						MDB_LAUNCH(ctx, "part_scatter_l0_w32", (k_part_scatter<pf_key_w32>), grid8(ntiles), PART_THREADS, a);
-					}
-					if (a.minmax_out)
-						MDB_LAUNCH(ctx, "part_minmax", k_part_minmax_reduce, MM_GROUPS, MM_THREADS, (const uint32_t *)a.minmax_out, a.ntiles, flt->minmax_out);	/* (every tile of the launch has left its pair) */
-				} else if (npay) {
-					if (!cf || a.narrow != 1u)
-						return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "payload cells travel with the compact narrow form's hash | row id words only");
-					a.npay = (uint32_t)npay;
-					for (int c = 0; c < npay; c++) {
-						a.pay_in[c] = reinterpret_cast<const uint64_t *>(flt->pay_in[c]);
-						a.pay_out[c] = pay_buf[c];
-					}
-					MDB_LAUNCH(ctx, "part_scatter_l0_pay", (k_part_scatter<pf_key_cf_pay>), grid8(ntiles), PART_THREADS, a);
-				} else if (want_rid && a.range64_in) {	/* 64-bit form, left table, min-max pruning */
-					MDB_LAUNCH(ctx, "part_scatter_l0_rid_pruned", (k_part_scatter<pf_key_rid_r64>), grid8(ntiles), PART_THREADS, a);
-				} else if (want_rid) {
-					MDB_LAUNCH(ctx, "part_scatter_l0_rid", (k_part_scatter<pf_key_rid>), grid8(ntiles), PART_THREADS, a);
-				} else if (a.minmax64_out) {		/* 64-bit form, right table: its key range recorded */
-					MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key_mm64>), grid8(ntiles), PART_THREADS, a);
-					MDB_LAUNCH(ctx, "part_minmax", k_part_minmax64_reduce, 1, 1024, (const unsigned long long *)a.minmax64_out, ntiles,
-						   flt->minmax64_out);
-				} else if (sel0) {
-					const uint64_t span = n + (((uintptr_t)keys >> 3) & 1u);	/* (positions from the aligned address below the first key) */
-					const uint32_t trows = t2 ? PART_TMUL * MDB_TILE : MDB_TILE;
-					a.ntiles = (uint32_t)((span + trows - 1) / trows);
-					if (t2)
-						MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf_sel_t2>), grid8(a.ntiles), PART_THREADS, a);
-					else
-						MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf_sel>), grid8(a.ntiles), PART_THREADS, a);
-				} else if (a.range_in && cf && t2) {
-					a.ntiles = ntiles2;
-					MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf_t2>), grid8(ntiles2), PART_THREADS, a);
-				} else if (a.range_in && cf) {	/* (the same instance under another name: its bytes differ - most rows are read, not written) */
-					MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key_cf>),
-						   grid8(ntiles), PART_THREADS, a);
-				} else if (a.range_in) {
-					MDB_LAUNCH(ctx, "part_scatter_l0_pruned", (k_part_scatter<pf_key>), grid8(ntiles), PART_THREADS, a);
-				} else if (cf && t2) {
-					a.ntiles = ntiles2;
-					MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key_cf_t2>), grid8(ntiles2), PART_THREADS, a);
-				} else if (cf) {
-					MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key_cf>), grid8(ntiles),
-						   PART_THREADS, a);
-				} else {
-					MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key>), grid8(ntiles), PART_THREADS, a);
-				}
-				if (!stop0) {
-					MDB_LAUNCH(ctx, "part_region_tiles", k_part_region_tiles_scan, 1, 1024, cursor0, nreg0, cap0, PART_NSUB, reg_nt);
-					MDB_LAUNCH(ctx, "part_build_tiles", k_part_build_tiles_regions, (next_tiles + 255) / 256, 256, cursor0, reg_nt, nreg0,
-						   cap0, PART_NSUB, next_desc, next_tiles);
-				}
+/* histogram-free last level: one fixed-capacity region and one cursor per leaf */
+static int part_level_last(const part_xrequest &x, const part_layout &y, part_walk &w)
+{
+	mdb_dev_ctx *ctx = w.cv.ctx;
+	const uint32_t nchild = w.S * y.R[1];
+	w.leaf_cnt = (uint32_t *)w.cv.take((size_t)nchild * 4);
+	if (w.cv.failed)
+		return -MIDORIDB_INTERNAL;
+	if (!w.cv.dry) {
+		mdb_level_args a = part_level_args(x, y, 1, w);
+		a.cursor = w.leaf_cnt;
+		a.cap = y.fast_cap;
+		MDB_HIP(ctx, hipMemsetAsync(w.leaf_cnt, 0, (size_t)nchild * 4, ctx->stream));
+		if (y.npay) {
+			a.npay = (uint32_t)y.npay;
+			for (int c = 0; c < y.npay; c++) {
+				a.pay_in[c] = w.pay_buf[c];
+				a.pay_out[c] = w.pay_buf1[c];
 			}
-			if (stop0) {
-				if (out) {
-					out->hv = hv_buf[0];
-					out->rid = NULL;
-					out->leaf_off = NULL;
-					out->leaf_cnt = cursor0;
-					out->leaf_cap = cap0;
-					out->nleaves = R;
-					out->bits_total = (uint32_t)bits1;
-					out->w32 = w32;
-					out->w16 = out16 && w32;
-					out->nsub = PART_NSUB;
-					out->pay[0] = pay_buf[0];
-					out->pay[1] = pay_buf[1];
-				}
-				return MIDORIDB_OK;
-			}
-			uint32_t real_tiles = next_tiles;
-			if (!dry && flt && (flt->range_in || flt->range64_in) && flt->expect_pruned) {
-				/* min-max pruning may have dropped most rows: the second level is launched for the tiles that exist (one
-				 * 4-byte read-back and a synchronisation, ~15 us) - 26 000 workgroups that find an empty descriptor and leave
-				 * cost 0.09 ms at 10^8 rows */
-				uint64_t *h = ctx->h_pinned;
-				MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_PART_TILES], reg_nt + nreg0, 4, hipMemcpyDeviceToHost, ctx->stream));
-				MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-				const uint32_t got = (uint32_t)h[MDB_HP_PART_TILES];
-				real_tiles = got < next_tiles ? (got ? got : 1u) : next_tiles;
-			}
-			used_bits += bits1;
-			seg_start = NULL;
-			tb = NULL;
-			S = R;
-			tiles = next_desc;
-			ntiles = real_tiles;
-			continue;
 		}
-		if (fast_level) {
-			/* histogram-free last level: one cursor per leaf, runs placed with global atomics */
-			leaf_cnt = (uint32_t *)cv.take((size_t)nchild * 4);
-			if (cv.failed)
-				return -MIDORIDB_INTERNAL;
-			if (!dry) {
-				a.cursor = leaf_cnt;
-				a.cap = fast_cap;
-				a.status = ctx->d_status;
-				MDB_HIP(ctx, hipMemsetAsync(leaf_cnt, 0, (size_t)nchild * 4, ctx->stream));
-				if (npay) {
-					a.npay = (uint32_t)npay;
-					for (int c = 0; c < npay; c++) {
-						a.pay_in[c] = pay_buf[c];
-						a.pay_out[c] = pay_buf1[c];
-					}
-					MDB_LAUNCH(ctx, "part_scatter_l1_pay", (k_part_scatter<pf_word_pay>), grid8(ntiles), PART_THREADS, a);
-				} else if (want_rid) {
-					MDB_LAUNCH(ctx, "part_scatter_l1_rid", (k_part_scatter<pf_word_rid>), grid8(ntiles),
-						   PART_THREADS, a);
-				} else if (raw_hv && fold32) {
-					MDB_LAUNCH(ctx, "sort_scatter_l1_w32", (k_part_scatter<pf_word_raw_w32>), grid8(ntiles),
-						   PART_THREADS, a);
-				} else if (raw_hv) {
-					MDB_LAUNCH(ctx, "sort_scatter_l1", (k_part_scatter<pf_word_raw>), grid8(ntiles),
-						   PART_THREADS, a);
-				} else if (w32) {
-					MDB_LAUNCH(ctx, "part_scatter_l1_w32", (k_part_scatter<pf_word_w32>), grid8(ntiles),
-						   PART_THREADS, a);
-				} else if (a.filter) {
-					MDB_LAUNCH(ctx, "part_scatter_l1_semi", (k_part_scatter<pf_word_semi>),
-						   grid8(ntiles), PART_THREADS, a);
-				} else {
-					MDB_LAUNCH(ctx, "part_scatter_l1", (k_part_scatter<pf_word>), grid8(ntiles),
-						   PART_THREADS, a);
-				}
-			}
-			used_bits += bits2;
-			S = nchild;
-			seg_start = NULL;
-			break;
-		}
+		const part_launch pl = part_last_launch(x, y, a);
+		MDB_LAUNCH(ctx, pl.name, pl.kernel, grid8(w.ntiles), pl.threads, a);
+	}
+	w.used_bits += x.bits2;
+	w.S = nchild;
+	w.seg_start = NULL;
+	return MIDORIDB_OK;
+}
 
-		const uint64_t hlen = (uint64_t)ntiles * R + 1;
-		uint32_t *hist = (uint32_t *)cv.take(hlen * 4);
-		uint32_t *scan_tmp = (uint32_t *)cv.take(mdb_scan_scratch_words(hlen) * 4);
-		uint32_t *child_start = (uint32_t *)cv.take(((size_t)nchild + 1) * 4);
-		uint32_t *child_nt = (uint32_t *)cv.take(((size_t)nchild + 1) * 4);
-		uint32_t *child_scan_tmp = (uint32_t *)cv.take(mdb_scan_scratch_words((uint64_t)nchild + 1) * 4);
-		/* tile descriptors of the NEXT level (upper bound: every child adds at most two partial tiles) */
-		const uint32_t next_tiles = (uint32_t)(n / MDB_TILE) + 2 * nchild + 1;
-		mdb_tile_desc *next_desc = NULL;
-		if (l + 1 < nlevels)
-			next_desc = (mdb_tile_desc *)cv.take((size_t)next_tiles * sizeof(mdb_tile_desc));
-		if (cv.failed)
-			return -MIDORIDB_INTERNAL;
-
-		if (!dry) {
-			a.hist = hist;
-			MDB_HIP(ctx, hipMemsetAsync(hist, 0, hlen * 4, ctx->stream));
-			if (l == 0 && raw_hv) {
-				MDB_LAUNCH(ctx, "sort_hist_l0", (k_part_hist<false, true>), grid8(ntiles), PART_THREADS, a);
-			} else if (l == 0) {
-				MDB_LAUNCH(ctx, mode == MDB_DIGIT_MOD ? "dest_hist" : "part_hist_l0", k_part_hist<true>, grid8(ntiles), PART_THREADS, a);
-			} else {
-				MDB_LAUNCH(ctx, "part_hist_l1", k_part_hist<false>, grid8(ntiles), PART_THREADS, a);
-			}
-			int rc = mdb_scan_u32_inplace(ctx, hist, hlen, scan_tmp);
+/* exact level `l`: histogram, scan, scatter; the children's starts, and the tile descriptors of the level behind it */
+static int part_level_exact(const part_xrequest &x, const part_layout &y, int l, part_walk &w)
+{
+	mdb_dev_ctx *ctx = w.cv.ctx;
+	const uint32_t R = y.R[l], nchild = w.S * R, ntiles = w.ntiles;
+	const uint64_t hlen = (uint64_t)ntiles * R + 1;
+	uint32_t *hist = (uint32_t *)w.cv.take(hlen * 4);
+	uint32_t *scan_tmp = (uint32_t *)w.cv.take(mdb_scan_scratch_words(hlen) * 4);
+	uint32_t *child_start = (uint32_t *)w.cv.take(((size_t)nchild + 1) * 4);
+	uint32_t *child_nt = (uint32_t *)w.cv.take(((size_t)nchild + 1) * 4);
+	uint32_t *child_scan_tmp = (uint32_t *)w.cv.take(mdb_scan_scratch_words((uint64_t)nchild + 1) * 4);
+	/* tile descriptors of the NEXT level (upper bound: every child adds at most two partial tiles) */
+	const uint32_t next_tiles = (uint32_t)(x.n / MDB_TILE) + 2 * nchild + 1;
+	const bool more = l + 1 < y.nlevels;
+	mdb_tile_desc *next_desc = more ? (mdb_tile_desc *)w.cv.take((size_t)next_tiles * sizeof(mdb_tile_desc)) : NULL;
+	if (w.cv.failed)
+		return -MIDORIDB_INTERNAL;
+	if (!w.cv.dry) {
+		mdb_level_args a = part_level_args(x, y, l, w);
+		a.hist = hist;
+		MDB_HIP(ctx, hipMemsetAsync(hist, 0, hlen * 4, ctx->stream));
+		const part_launch ph = part_hist_launch(x, l);
+		MDB_LAUNCH(ctx, ph.name, ph.kernel, grid8(ntiles), ph.threads, a);
+		int rc = mdb_scan_u32_inplace(ctx, hist, hlen, scan_tmp);
+		if (rc)
+			return rc;
+		const part_launch ps = part_exact_launch(x, l, a);
+		MDB_LAUNCH(ctx, ps.name, ps.kernel, grid8(ntiles), ps.threads, a);
+		MDB_LAUNCH(ctx, "part_children", k_part_children, (nchild + 1 + 255) / 256, 256, hist, w.tb, w.S, R, child_start, child_nt);
+		if (more) {
+			rc = mdb_scan_u32_inplace(ctx, child_nt, (uint64_t)nchild + 1, child_scan_tmp);
 			if (rc)
 				return rc;
-			if (l == 0 && raw_hv) {
-				MDB_LAUNCH(ctx, "sort_scatter_l0", (k_part_scatter<pf_word_hist_raw>), grid8(ntiles), PART_THREADS, a);
-			} else if (stable && l == 0) {
-				MDB_LAUNCH(ctx, "part_scatter_l0_stable", (k_part_scatter<pf_key_rid_stable_hist>), grid8(ntiles), PART_THREADS, a);
-			} else if (stable) {
-				MDB_LAUNCH(ctx, "part_scatter_l1_stable", (k_part_scatter<pf_word_rid_stable_hist>), grid8(ntiles), PART_THREADS, a);
-			} else if (l == 0 && a.inverse_out && want_rid) {
-				MDB_LAUNCH(ctx, "dest_scatter", (k_part_scatter<pf_key_rid_hist_dest>), grid8(ntiles), PART_THREADS, a);
-			} else if (l == 0 && a.inverse_out) {
-				MDB_LAUNCH(ctx, "dest_scatter", (k_part_scatter<pf_key_hist_dest>), grid8(ntiles), PART_THREADS, a);
-			} else if (l == 0 && want_rid) {
-				MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key_rid_hist>), grid8(ntiles), PART_THREADS, a);
-			} else if (l == 0) {
-				MDB_LAUNCH(ctx, "part_scatter_l0", (k_part_scatter<pf_key_hist>), grid8(ntiles), PART_THREADS, a);
-			} else if (want_rid) {
-				MDB_LAUNCH(ctx, "part_scatter_l1", (k_part_scatter<pf_word_rid_hist>), grid8(ntiles), PART_THREADS, a);
-			} else {
-				MDB_LAUNCH(ctx, "part_scatter_l1", (k_part_scatter<pf_word_hist>), grid8(ntiles), PART_THREADS, a);
-			}
-			MDB_LAUNCH(ctx, "part_children", k_part_children, (nchild + 1 + 255) / 256, 256, hist, tb, S, R, child_start,
-				   child_nt);
-			if (l + 1 < nlevels) {
-				rc = mdb_scan_u32_inplace(ctx, child_nt, (uint64_t)nchild + 1, child_scan_tmp);
-				if (rc)
-					return rc;
-				MDB_LAUNCH(ctx, "part_build_tiles", k_part_build_tiles, (next_tiles + 255) / 256, 256, child_start,
-					   child_nt, nchild, Rl[l + 1], next_desc, next_tiles);
-			}
+			MDB_LAUNCH(ctx, "part_build_tiles", k_part_build_tiles, (next_tiles + 255) / 256, 256, child_start, child_nt, nchild, y.R[l + 1],
+				   next_desc, next_tiles);
 		}
-		used_bits += (l == 0 ? bits1 : bits2);
-		seg_start = child_start;
-		tb = child_nt;
-		S = nchild;
-		tiles = next_desc;
-		ntiles = next_tiles;
 	}
-	if (out) {
-		out->hv = hv_buf[nlevels - 1];
-		out->rid = rid_buf[nlevels - 1];
-		out->leaf_off = seg_start;
-		out->leaf_cnt = leaf_cnt;
-		out->leaf_cap = fast ? fast_cap : 0;
-		out->nleaves = S;
-		out->bits_total = (uint32_t)used_bits;
-		out->w32 = w32;
-		out->w16 = false;
-		out->nsub = 0;
-		out->pay[0] = nlevels == 2 ? pay_buf1[0] : NULL;
-		out->pay[1] = nlevels == 2 ? pay_buf1[1] : NULL;
-	}
+	w.used_bits += (l == 0 ? x.bits1 : x.bits2);
+	w.seg_start = child_start;
+	w.tb = child_nt;
+	w.S = nchild;
+	w.tiles = next_desc;
+	w.ntiles = next_tiles;
 	return MIDORIDB_OK;
+}
+
+static void part_result_fill(const part_xrequest &x, const part_layout &y, const part_walk &w, mdb_part_result *out)
+{
+	const bool digits = y.stop0 && y.fast0;	/* the first level's sub-regions are the result */
+	const int last = y.nlevels - 1;
+	out->hv = w.hv_buf[last];
+	out->rid = digits ? NULL : w.rid_buf[last];
+	out->leaf_off = digits ? NULL : w.seg_start;
+	out->leaf_cnt = w.leaf_cnt;
+	out->leaf_cap = digits ? y.cap0 : (y.fast ? y.fast_cap : 0);
+	out->nleaves = digits ? y.R[0] : w.S;
+	out->bits_total = digits ? (uint32_t)x.bits1 : (uint32_t)w.used_bits;
+	out->w32 = y.w32;
+	out->w16 = digits && y.out16 && y.w32;
+	out->nsub = digits ? PART_NSUB : 0;
+	for (int c = 0; c < 2; c++)
+		out->pay[c] = digits ? w.pay_buf[c] : (y.nlevels == 2 ? w.pay_buf1[c] : NULL);
+}
+
+/* one walk over the levels of a request: the real one, or - kn = NULL - the sizing pass: nothing is launched, *bytes is what the real
+ * one would take from the arena */
+static int part_run(mdb_dev_ctx *ctx, const part_xrequest &x, const part_knobs *kn, mdb_part_result *out, size_t *bytes = NULL)
+{
+	const bool dry = kn == NULL;
+	const part_layout y = part_layout_of(x);
+	part_walk w;
+	memset(&w, 0, sizeof(w));
+	w.cv.ctx = ctx;
+	w.cv.dry = dry;
+	w.S = 1;
+	w.ntiles = x.n ? (uint32_t)((x.n + MDB_TILE - 1) / MDB_TILE) : 1u;
+	if (y.w32_unserved && !dry)
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "4-byte partition words need the two-level fast layout");
+	if (y.stop0_unserved && !dry)
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "first-level-only partition: histogram-free layout, one level");
+	if (!dry && x.keys && !x.keys32 && ((uintptr_t)x.keys & 15) && !part_selective(x, y, *kn))
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "key columns must be 16-byte aligned on the device (8-byte for int32 keys)");
+	part_carve_outputs(x, y, w);
+	if (w.cv.failed)
+		return -MIDORIDB_INTERNAL;
+	if (!dry && !y.fast0)	/* the FAST first level has no parent segments to describe */
+		MDB_LAUNCH(ctx, "part_seg0", k_part_seg0, 1, 64, w.seg_start, w.tb, (uint32_t)x.n, w.ntiles);
+	for (int l = 0; l < y.nlevels; l++) {
+		const int rc = (y.fast0 && l == 0) ? part_level_first(x, y, kn, w) : (y.fast && l == 1) ? part_level_last(x, y, w) : part_level_exact(x, y, l, w);
+		if (rc)
+			return rc;
+	}
+	if (out)
+		part_result_fill(x, y, w, out);
+	if (bytes)
+		*bytes = w.cv.bytes;
+	return MIDORIDB_OK;
+}
+
+/* arena bytes of a request */
+static size_t part_bytes(const part_xrequest &x)
+{
+	size_t bytes = 0;
+	(void)part_run(NULL, x, NULL, NULL, &bytes);
+	return bytes;
+}
+
+static int part_execute(mdb_dev_ctx *ctx, const part_xrequest &x, mdb_part_result *out)
+{
+	const part_knobs kn = part_knobs_read();
+	return part_run(ctx, x, &kn, out);
+}
+
+/* what the sizing functions have in common */
+static mdb_part_request part_sizing_request(uint64_t n, int bits1, int bits2, bool fast)
+{
+	mdb_part_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.n = n;
+	rq.bits1 = bits1;
+	rq.bits2 = bits2;
+	rq.fast = fast;
+	return rq;
 }
 
 size_t mdb_partition_arena_bytes(uint64_t n, int bits1, int bits2, bool want_rid, bool fast, int npay)
 {
-	part_carver cv = { NULL, true, 0, false };
-	mdb_part_filter flt;
-	memset(&flt, 0, sizeof(flt));
-	flt.npay = npay;
-	(void)partition_impl(cv, NULL, NULL, n, bits1, bits2, want_rid, fast ? PART_F_FAST : 0u, MDB_DIGIT_RADIX, 0, false, NULL, NULL, 0, NULL, NULL, 0, false,
-			     0, 0u, npay ? &flt : NULL);
-	return cv.bytes + 4096 + (size_t)npay * 1024;
+	mdb_part_request rq = part_sizing_request(n, bits1, bits2, fast);
+	rq.want_rid = want_rid;
+	rq.npay = npay;
+	return part_bytes(part_xrequest(rq)) + 4096 + (size_t)npay * 1024;
 }
 
 size_t mdb_partition_level0_arena_bytes(uint64_t n, int bits1, bool loose, int npay)
 {
-	part_carver cv = { NULL, true, 0, false };
-	mdb_part_filter flt;
-	memset(&flt, 0, sizeof(flt));
-	flt.level0_only = true;
-	flt.npay = npay;
-	(void)partition_impl(cv, NULL, NULL, n, bits1, 0, false, PART_F_FAST | PART_F_STOP0 | (loose ? PART_F_LOOSE : 0u), MDB_DIGIT_RADIX, 0, false, NULL,
-			     NULL, 0, NULL, NULL, 0, false, 0, 0u, npay ? &flt : NULL);
-	return cv.bytes + 4096 + (size_t)npay * 512;
+	mdb_part_request rq = part_sizing_request(n, bits1, 0, true);
+	rq.level0_only = true;
+	rq.loose = loose;
+	rq.npay = npay;
+	return part_bytes(part_xrequest(rq)) + 4096 + (size_t)npay * 512;
 }
 
 bool mdb_partition_w32_applies(uint64_t n, int bits1, int bits2, bool fast)
 {
-	part_carver cv = { NULL, true, 0, false };
-	mdb_part_result res;
-	memset(&res, 0, sizeof(res));
-	(void)partition_impl(cv, NULL, NULL, n, bits1, bits2, false, (fast ? PART_F_FAST : 0u) | PART_F_NARROW, MDB_DIGIT_RADIX, 0, false, NULL,
-			     NULL, 0, &res);
-	return res.w32;
+	mdb_part_request rq = part_sizing_request(n, bits1, bits2, fast);
+	rq.narrow = 2;
+	return part_layout_of(part_xrequest(rq)).w32;
 }
 
-int mdb_partition_table(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, int bits1, int bits2,
-			bool want_rid, bool stable, bool fast, mdb_part_result *out, int narrow, bool keys32, int64_t narrow_base,
-			uint32_t narrow_kbits, const mdb_part_filter *flt)
+static int part_request_check(mdb_dev_ctx *ctx, const mdb_part_request &rq)
 {
-	const bool stop0 = flt && flt->level0_only;
-	if (stop0 && (!narrow || !narrow_kbits || want_rid || stable || !fast || bits2 != 0 || flt->bits))
+	const bool stop0 = rq.level0_only, stable = rq.stable, want_rid = rq.want_rid, fast = rq.fast;
+	const int narrow = rq.narrow, bits2 = rq.bits2;
+	const uint32_t narrow_kbits = rq.narrow_kbits;
+	if (stop0 && (!narrow || !narrow_kbits || want_rid || stable || !fast || bits2 != 0 || rq.bits))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "first-level-only partition: compact narrow form, bits2 = 0, no bitmap");
-	if (flt && flt->bits && (narrow != 1 || !narrow_kbits || want_rid || stable || !fast || bits2 <= 0 || flt->words < 4 || flt->words > MDB_TILE * 2 ||
-				 (flt->words & (flt->words - 1))))
+	if (rq.bits && (narrow != 1 || !narrow_kbits || want_rid || stable || !fast || bits2 <= 0 || rq.words < 4 || rq.words > MDB_TILE * 2 ||
+			(rq.words & (rq.words - 1))))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "semi-join filter: left side of the compact narrow form, two fast levels, slices of 4 ... 8192 words");
-	if (flt && (flt->minmax_out || flt->range_in) && (!narrow || want_rid || stable || !fast || (bits2 <= 0 && !stop0) ||
-							  (flt->minmax_out && (narrow != 2 || !flt->minmax_tiles))))
+	if ((rq.minmax_out || rq.range_in) && (!narrow || want_rid || stable || !fast || (bits2 <= 0 && !stop0) || (rq.minmax_out && (narrow != 2 || !rq.minmax_tiles))))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "min-max pruning: narrow forms, two fast levels");
-	if (flt && (flt->minmax64_out || flt->range64_in) && (narrow || stable || !fast || bits2 <= 0 || (flt->minmax64_out && (want_rid || !flt->minmax64_tiles)) ||
-							      (flt->range64_in && !want_rid)))
+	if ((rq.minmax64_out || rq.range64_in) && (narrow || stable || !fast || bits2 <= 0 || (rq.minmax64_out && (want_rid || !rq.minmax64_tiles)) ||
+						   (rq.range64_in && !want_rid)))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "min-max pruning, 64-bit form: two fast levels, the right table without and the left with row ids");
-	if (flt && flt->npay && (narrow != 1 || !narrow_kbits || want_rid || stable || !fast || flt->npay < 0 || flt->npay > 2 || (bits2 <= 0 && !stop0)))
+	if (rq.npay && (narrow != 1 || !narrow_kbits || want_rid || stable || !fast || rq.npay < 0 || rq.npay > 2 || (bits2 <= 0 && !stop0)))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "payload cells: compact narrow form with hash | row id words, histogram-free layout, at most two columns");
-	if (narrow_kbits && (!narrow || narrow_kbits < 8 || narrow_kbits > 32 || (uint32_t)(bits1 + bits2) > narrow_kbits))
+	if (narrow_kbits && (!narrow || narrow_kbits < 8 || narrow_kbits > 32 || (uint32_t)(rq.bits1 + bits2) > narrow_kbits))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "compact narrow form: bad window width");
 	if (narrow && (stable || want_rid))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "narrow partitioning carries row ids inside the word");
-	if (n >= 0xFFFFFFFFull)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "table of %llu rows exceeds the 32-bit row-id limit of one GPU shard",
-				   (unsigned long long)n);
-	part_carver cv = { ctx, false, 0, false };
+	if (rq.n >= 0xFFFFFFFFull)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "table of %llu rows exceeds the 32-bit row-id limit of one GPU shard", (unsigned long long)rq.n);
 	if (stable && !want_rid)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "stable partitioning is only built with row ids");
-	if ((uintptr_t)keys & 7)	/* (int64 columns: 16 bytes, unless the selective first level takes them - partition_impl) */
+	if ((uintptr_t)rq.keys & 7)	/* (int64 columns: 16 bytes, unless the selective first level takes them - part_run) */
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "key columns must be 16-byte aligned on the device (8-byte for int32 keys)");
-	return partition_impl(cv, keys, nullbits, n, bits1, bits2, want_rid,
-			      (stable ? PART_F_STABLE : 0u) | (fast ? PART_F_FAST : 0u) | (narrow == 1 ? PART_F_NARROW_RID : 0u) |
-				      (narrow == 2 ? PART_F_NARROW : 0u) | (keys32 ? PART_F_KEYS32 : 0u) | (stop0 ? PART_F_STOP0 : 0u) |
-					      (stop0 && flt->out16 ? PART_F_OUT16 : 0u) | (stop0 && flt->loose ? PART_F_LOOSE : 0u),
-			      MDB_DIGIT_RADIX, 0, false, NULL, NULL, 0, out, NULL, 0, false, narrow ? narrow_base : 0, narrow ? narrow_kbits : 0u, flt);
+	return MIDORIDB_OK;
 }
 
-/* MSD radix partition of ready-made 64-bit sort keys (no hashing, no NULLs) by their top bits1 + bits2
- * bits; with two levels the last one uses the fixed-capacity layout with `leaf_cap` rows per leaf (the
- * caller guarantees no leaf can hold more).  Used to order GROUP BY results by first row id. */
+int mdb_partition_table(mdb_dev_ctx *ctx, const mdb_part_request &rq, mdb_part_result *out)
+{
+	const int rc = part_request_check(ctx, rq);
+	return rc ? rc : part_execute(ctx, part_xrequest(rq), out);
+}
+
 size_t mdb_partition_raw_arena_bytes(uint64_t n, int bits1, int bits2, uint32_t leaf_cap, bool fast, uint32_t digits0_used, uint64_t digit0_rows)
 {
-	part_carver cv = { NULL, true, 0, false };
-	(void)partition_impl(cv, NULL, NULL, n, bits1, bits2, false, fast ? PART_F_FAST : 0u, MDB_DIGIT_RADIX, 0, false, NULL,
-			     (const uint64_t *)16, leaf_cap, NULL, NULL, digits0_used, false, 0, 0, NULL, fast ? digit0_rows : 0);
-	return cv.bytes + 4096;
+	mdb_part_request rq = part_sizing_request(n, bits1, bits2, fast);
+	rq.leaf_cap = leaf_cap;
+	rq.digits0_used = digits0_used;
+	rq.digit0_rows = digit0_rows;
+	return part_bytes(part_xrequest(rq)) + 4096;
 }
 
-int mdb_partition_raw(mdb_dev_ctx *ctx, const uint64_t *hv, uint64_t n, int bits1, int bits2, uint32_t leaf_cap, bool fast,
-		      uint32_t digits0_used, mdb_part_result *out, bool zero_is_gap, int fold32, uint64_t digit0_rows)
+int mdb_partition_raw(mdb_dev_ctx *ctx, const mdb_part_request &rq, mdb_part_result *out)
 {
-	part_carver cv = { ctx, false, 0, false };
-	if (fold32 && (!fast || bits2 <= 0 || !zero_is_gap))
+	if (rq.fold32 && (!rq.fast || rq.bits2 <= 0 || !rq.zero_is_gap))
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "4-byte raw words need the two-level fast layout");
-	return partition_impl(cv, NULL, NULL, n, bits1, bits2, false,
-			      (fast ? PART_F_FAST : 0u) | (zero_is_gap ? 0u : PART_F_NO_GAPS) | (fold32 ? PART_F_FOLD32 : 0u) | (fold32 == 2 ? PART_F_IN32 : 0u),
-			      MDB_DIGIT_RADIX, 0,
-			      false, NULL, hv, leaf_cap, out, NULL, digits0_used, false, 0, 0, NULL, fast ? digit0_rows : 0);
+	return part_execute(ctx, part_xrequest(rq), out);
 }
 
 /* ---- one histogram-free radix level over 4-byte words in caller-described tiles (the receiver's second level of the
@@ -2131,14 +2228,6 @@ extern "C" int mdb_dev_partition_by_dest_pruned(mdb_dev_ctx *ctx, const int64_t 
 						uint32_t n_dest, int keys32, int64_t keep_lo, int64_t keep_hi, int64_t own_lo, int64_t own_hi,
 						void *out_keys, uint32_t *out_rid, uint64_t *out_counts)
 {
-	mdb_part_filter flt;
-	memset(&flt, 0, sizeof(flt));
-	flt.keep_on = keep_lo != INT64_MIN || keep_hi != INT64_MAX;
-	flt.keep_lo = keep_lo;
-	flt.keep_hi = keep_hi;
-	flt.own_on = own_lo != INT64_MIN || own_hi != INT64_MAX;
-	flt.own_lo = own_lo;
-	flt.own_hi = own_hi;
 	if (n_dest == 0 || n_dest > PART_MAX_R)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "partition_by_dest: n_dest must be in [1, %u]", PART_MAX_R);
 	if (n >= 0xFFFFFFFFull)
@@ -2149,21 +2238,34 @@ extern "C" int mdb_dev_partition_by_dest_pruned(mdb_dev_ctx *ctx, const int64_t 
 		out_counts[d] = 0;
 	if (n == 0)
 		return MIDORIDB_OK;
-	/* dry run for the arena size, then the real pass (one level, digit = low32(hash) mod n_dest,
-	 * original keys written back through the inverse hash - as 4-byte integers when the caller knows from the
-	 * column's statistics that every key fits - source row ids beside them when asked for) */
-	const bool want_rid = out_rid != NULL;
-	part_carver dry = { NULL, true, 0, false };
-	(void)partition_impl(dry, NULL, NULL, n, 1, 0, want_rid, 0u, MDB_DIGIT_MOD, n_dest, true, (uint64_t *)out_keys, NULL, 0, NULL, out_rid, 0,
-			     keys32 != 0, 0, 0, &flt);
-	int rc = mdb_arena_begin(ctx, dry.bytes + 4096);
+	/* one exact level, digit = low32(hash) mod n_dest, original keys written back through the inverse hash - as 4-byte integers when the
+	 * caller knows from the column's statistics that every key fits - source row ids beside them when asked for */
+	mdb_part_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.keys = keys;
+	rq.nullbits = nullbits;
+	rq.n = n;
+	rq.bits1 = 1;
+	rq.want_rid = out_rid != NULL;
+	rq.keep_on = keep_lo != INT64_MIN || keep_hi != INT64_MAX;
+	rq.keep_lo = keep_lo;
+	rq.keep_hi = keep_hi;
+	rq.own_on = own_lo != INT64_MIN || own_hi != INT64_MAX;
+	rq.own_lo = own_lo;
+	rq.own_hi = own_hi;
+	part_xrequest x(rq);
+	x.mode = MDB_DIGIT_MOD;
+	x.n_dest = n_dest;
+	x.inverse_out = true;
+	x.keys32_out = keys32 != 0;
+	x.final_hv_out = (uint64_t *)out_keys;
+	x.final_rid_out = out_rid;
+	int rc = mdb_arena_begin(ctx, part_bytes(x) + 4096);
 	if (rc)
 		return rc;
-	part_carver cv = { ctx, false, 0, false };
 	mdb_part_result res;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-	rc = partition_impl(cv, keys, nullbits, n, 1, 0, want_rid, 0u, MDB_DIGIT_MOD, n_dest, true, (uint64_t *)out_keys, NULL, 0, &res, out_rid, 0,
-			    keys32 != 0, 0, 0, &flt);
+	rc = part_execute(ctx, x, &res);
 	if (rc)
 		return rc;
 	uint32_t *h_off = (uint32_t *)ctx->h_pinned;

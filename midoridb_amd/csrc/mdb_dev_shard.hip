@@ -235,13 +235,22 @@ int mdb_scatter4096(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nulls
 int mdb_shard_partition(mdb_dev_ctx *ctx, const mdb_shard_plan *p, int side, const int64_t *keys, const uint64_t *nulls, uint64_t n,
 			const void **regions, const uint32_t **cursors)
 {
-	mdb_part_filter flt;
+	/* the histogram-free first level of the compact narrow form alone, 4- or 2-byte words, regions of the capacity the ranks agreed on */
+	mdb_part_request rq;
 	mdb_part_result res;
-	memset(&flt, 0, sizeof(flt));
+	memset(&rq, 0, sizeof(rq));
 	memset(&res, 0, sizeof(res));
-	flt.level0_only = true;
-	flt.out16 = p->wbytes == 2;
-	flt.region_cap = p->cap[side];
+	rq.keys = keys;
+	rq.nullbits = nulls;
+	rq.n = n;
+	rq.bits1 = SH_D_BITS;
+	rq.fast = true;
+	rq.narrow = 2;
+	rq.narrow_base = p->key_lo;
+	rq.narrow_kbits = p->kbits;
+	rq.level0_only = true;
+	rq.out16 = p->wbytes == 2;
+	rq.region_cap = p->cap[side];
 	if (side != 1) {
 		/* the left table (and any further right table) keeps the rows inside the right table's (global) key range = the
 		 * window: what lies outside joins nothing on any rank */
@@ -249,7 +258,7 @@ int mdb_shard_partition(mdb_dev_ctx *ctx, const mdb_shard_plan *p, int side, con
 		h[0] = 0u;
 		h[1] = (uint32_t)p->l_rel_hi;
 		MDB_HIP(ctx, hipMemcpyAsync(ctx->d_status + SH_RANGE_WORD, h, 8, hipMemcpyHostToDevice, ctx->stream));
-		flt.range_in = ctx->d_status + SH_RANGE_WORD;
+		rq.range_in = ctx->d_status + SH_RANGE_WORD;
 	}
 	if (n == 0) {
 		/* nothing to partition: an all-zero cursor array and a region buffer nobody reads */
@@ -273,7 +282,7 @@ int mdb_shard_partition(mdb_dev_ctx *ctx, const mdb_shard_plan *p, int side, con
 		*cursors = cur;
 		return MIDORIDB_OK;
 	}
-	int rc = mdb_partition_table(ctx, keys, nulls, n, SH_D_BITS, 0, false, false, true, &res, 2, false, p->key_lo, p->kbits, &flt);
+	int rc = mdb_partition_table(ctx, rq, &res);
 	if (rc)
 		return rc;
 	if (!res.nsub || res.nsub != p->nsub || res.leaf_cap != p->cap[side] || !res.w32 || (p->wbytes == 2) != res.w16)

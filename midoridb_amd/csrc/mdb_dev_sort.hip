@@ -401,6 +401,22 @@ static void sort_packed_bits(uint64_t n, int *b1, int *b2)
 	*b2 = b - *b1;
 }
 
+/* the packed words through two histogram-free levels into leaves of SORT_LEAF_CAP words at most; no gaps: the zero word is row 0 of
+ * the smallest value */
+static mdb_part_request sort_packed_request(const uint64_t *words, uint64_t n, int b1, int b2, uint32_t digits0)
+{
+	mdb_part_request rq;
+	memset(&rq, 0, sizeof(rq));
+	rq.raw_hv = words;
+	rq.n = n;
+	rq.bits1 = b1;
+	rq.bits2 = b2;
+	rq.fast = true;
+	rq.leaf_cap = SORT_LEAF_CAP;
+	rq.digits0_used = digits0;
+	return rq;
+}
+
 static size_t sort_packed_arena_bytes(uint64_t n)
 {
 	if (n < SORT_PACK_MIN_ROWS)
@@ -455,7 +471,7 @@ static int sort_perm_packed(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, i
 	}
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	mdb_part_result ps;
-	int rc = mdb_partition_raw(ctx, u, n, b1, b2, SORT_LEAF_CAP, true, digits0, &ps, false);	/* no gaps: the zero word is row 0 of the smallest value */
+	int rc = mdb_partition_raw(ctx, sort_packed_request(u, n, b1, b2, digits0), &ps);
 	if (rc)
 		return rc;
 	if (!ps.leaf_cap)
@@ -527,7 +543,7 @@ int mdb_sort_pairs(mdb_dev_ctx *ctx, const uint32_t *a, const uint32_t *b, uint6
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	MDB_LAUNCH(ctx, "pairs_pack", k_pairs_pack, grid, SORT_THREADS, a, b, n, rb, up, w);
 	mdb_part_result ps;
-	rc = mdb_partition_raw(ctx, w, n, b1, b2, SORT_LEAF_CAP, true, digits0, &ps, false);
+	rc = mdb_partition_raw(ctx, sort_packed_request(w, n, b1, b2, digits0), &ps);
 	if (rc)
 		return rc;
 	if (!ps.leaf_cap)

@@ -228,7 +228,7 @@ def packed_words(keys, n):
         bucket_rows     words per (leaf, bucket): the next 10 bits, 2^(b1 + b2) * 1024 entries
         region_rows     words per first-level sub-region [digit * 8 + sub]: a tile of 4096 consecutive rows goes to sub-region
                         tile // (grid / 8) of each digit (part_tile_of_block, `blockIdx.x % a.nsub`), grid = the tile count rounded up to 8
-        region_cap      cap0 of partition_impl for the digits that can occur"""
+        region_cap      part_layout.cap0 (mdb_dev_partition.hip) for the digits that can occur"""
     assert n >= 1 and len(keys) <= SORT_PACK_MAX_KEYS
     rb = 1
     while rb < 32 and (1 << rb) < n:
@@ -622,7 +622,7 @@ def packed_cases(n):
         return [(v, z, None, False, False), (rng.integers(0, 16, n, dtype=np.int64), None, None, False, True)]
     add("nulls_over_random_bytes", nulls_random_bytes, "packed")
     # a NULL flag that never varies is a constant top bit of the word: half the first-level digits stay empty, the other half receive twice
-    # the average, and a sub-region holds 5/4 of the average + 1024 (cap0 of partition_impl): from ~175 000 rows on the first level
+    # the average, and a sub-region holds 5/4 of the average + 1024 (part_layout.cap0, mdb_dev_partition.hip): from ~175 000 rows on the first level
     # reports MDB_ST_REGION_FULL (at 2^18 rows a leaf overflows as well: 64 leaves in use for 64 x 4096 rows).  A lost fast path
     wasted_bit = "redo"
 
