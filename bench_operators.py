@@ -214,6 +214,73 @@ def aggregate_rows(dev, res, n=100_000_000):
     res["aggregate_1e8"] = out
 
 
+def subquery_rows(dev, res):
+    """subquery_set: the right side of k IN (SELECT ...) as a device set - make_set_from_column (mdb_dev_set_from_column: scan, fill,
+    insert, and the rebuild where the members need a smaller table) beside the route that existed before it for the same cells: the
+    column copied to the host, then make_set (mdb_set_build on one host thread + the upload, mdb_dev_set_create).  Three shapes:
+    10^7 distinct values in 10^7 rows; 10^8 rows over 1000 distinct values (ends in the rebuild and an LDS-size image; the host
+    builder takes at most 2^26 values, so the host route has to drop the duplicates first - numpy.unique - and its plain form is
+    recorded as refused); 10^7 rows through a row-id vector (the host route copies both and indexes there).  The two routes alternate
+    in one run; wall time per call, each call synchronises; kernels_ms from the library's profiler (HIP events), in a call of its
+    own.  bytes_read = the cells (and row ids) the scan and the insertion read once each, bytes_table = the slots filled."""
+    out = {"cases": {}}
+    shapes = (("distinct_1e7", 10_000_000, 0, False), ("dup1000_1e8", 100_000_000, 1000, False), ("rid_1e7", 10_000_000, 0, True))
+    for name, n, modulus, with_rid in shapes:
+        col = dev.gen_keys(n, 0, n, 7, modulus)
+        rid = torch.randperm(n, device=dev.device).to(torch.int32) if with_rid else None
+
+        def on_device():
+            s = dev.make_set_from_column(col, None, rid)
+            info = (int(s.info.members), int(s.info.log2_slots), int(s.info.rebuilt))
+            s.close()
+            return info
+
+        refused = []
+
+        def through_host():
+            vals = col.cpu().numpy()
+            if rid is not None:
+                vals = vals[rid.cpu().numpy()]
+            try:
+                s = dev.make_set(vals)
+            except D.DeviceError:
+                if not refused:
+                    refused.append(True)
+                s = dev.make_set(np.unique(vals))
+            b = s.insn(0)[4]
+            s.close()
+            return b
+
+        dev_ms, host_ms = [], []
+        for turn in range(4):                   # (the first turn warms both up and is dropped)
+            for fn, into in ((on_device, dev_ms), (through_host, host_ms)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got = fn()
+                torch.cuda.synchronize()
+                into.append((time.perf_counter() - t0) * 1e3)
+                if fn is on_device:
+                    info = got
+                else:
+                    assert got == info[1], (got, info)      # both routes end in a table of the same size
+        dev.prof_enable(True)
+        dev.prof_reset()
+        on_device()
+        prof = dev.prof_read()
+        dev.prof_enable(False)
+        first_log2 = min(27, max(4, int(np.ceil(np.log2(max(2 * n, 16))))))
+        out["cases"][name] = {"rows": n, "members": info[0], "log2_slots": info[1], "rebuilt": info[2],
+                              "device_ms": min(dev_ms[1:]), "device_ms_all": dev_ms[1:], "host_route_ms": min(host_ms[1:]),
+                              "host_route_ms_all": host_ms[1:], "host_route_needed_unique": bool(refused),
+                              "host_over_device": min(host_ms[1:]) / min(dev_ms[1:]),
+                              "kernels_ms": {k: round(v[1], 4) for k, v in prof.items() if k.startswith("set_")},
+                              "kernel_launches": {k: v[0] for k, v in prof.items() if k.startswith("set_")},
+                              "bytes_read": 2 * n * (8 + (4 if with_rid else 0)), "bytes_table": 8 * ((1 << first_log2) + (1 << info[1]) * info[2])}
+        del col, rid
+        torch.cuda.empty_cache()
+    res["subquery_set"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04", "operators.json"))
@@ -225,9 +292,18 @@ def main():
                                                                "groups with INT64 and DOUBLE v, and SUM(v) without GROUP BY)")
     ap.add_argument("--full-join", action="store_true", help="only the FULL JOIN completion's row (outer_complete_full_1e7: beside the LEFT completion "
                                                               "of the same pairs)")
+    ap.add_argument("--subquery", action="store_true", help="only the IN (SELECT ...) set builder's row (subquery_set: make_set_from_column at three "
+                                                             "shapes beside the column copied to the host and make_set)")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.subquery:
+        subquery_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.full_join:
         full_join_rows(dev, res)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -264,7 +264,8 @@ enum mdb_pred_op {
 
 /* ------------------------------------------------------------------ device sets (MDB_P_IN_SET)
  *
- * A set is an open-addressing hash table of 8-byte slots, built on the host (mdb_set_build) and uploaded once per statement.
+ * A set is an open-addressing hash table of 8-byte slots, built on the host (mdb_set_build) and uploaded once per statement, or built
+ * on the device from a device column (mdb_dev_set_from_column).
  * The image is an array of 2 + slots 64-bit words, 16-byte aligned:
  *
  *     word 0        the EMPTY marker: a bit pattern the builder has proven absent from the members (it probes candidates against the
@@ -312,6 +313,25 @@ static inline MDB_SET_HD int mdb_set_canonical(int type, uint64_t *bits)
 	return 1;
 }
 
+/* log2 of the slot count for n distinct members: load <= 1/2; <= 1/4 while the table still fits the LDS budget of the filter kernel (a
+ * miss then takes 1.4 probes, not 2.5).  The one sizing rule of the host builder (mdb_set.c) and the device builder (mdb_dev_setbuild.hip) */
+static inline MDB_SET_HD unsigned mdb_set_slots_log2_for(uint64_t n)
+{
+	uint64_t nslots = 1ull << MDB_SET_MIN_LOG2;
+	unsigned log2 = MDB_SET_MIN_LOG2;
+	while (log2 < MDB_SET_MAX_LOG2 && (nslots < 2 * n || (nslots < 4 * n && 2 * nslots <= MDB_SET_LDS_SLOTS))) {
+		nslots <<= 1;
+		log2++;
+	}
+	return log2;
+}
+/* the EMPTY marker's candidates: a full-period sequence, the builders take its first pattern that is not a member */
+#define MDB_SET_MARKER_FIRST 0x8000000000000000ull
+static inline MDB_SET_HD uint64_t mdb_set_marker_next(uint64_t x)
+{
+	return x * 6364136223846793005ull + 1442695040888963407ull;
+}
+
 struct mdb_set_image {
 	uint64_t *words;	/* malloc'ed: marker, slot count, slots (above) */
 	uint64_t slots;
@@ -336,6 +356,24 @@ struct mdb_pred_insn;
 int mdb_dev_set_create(mdb_dev_ctx *ctx, const int64_t *host_values, uint64_t n, int type, mdb_dev_set **set);
 int mdb_dev_set_insn(const mdb_dev_set *set, int slot, int negate, struct mdb_pred_insn *insn);
 int mdb_dev_set_free(mdb_dev_ctx *ctx, mdb_dev_set *set);
+/* The same from a column in DEVICE memory (mdb_dev_setbuild.hip): the right side of  k IN (SELECT ...).  Cell i is values[rid ? rid[i] : i]
+ * (as struct mdb_sort_key and struct mdb_agg read a column); a cell whose NULL bit is set or whose row id is MDB_NO_ROW is skipped, and so is
+ * a NaN cell of MDB_T_DOUBLE.  n = 0 gives the empty set.  The image is one that mdb_set_build could have produced for the same members:
+ * words 0 and 1 are the host builder's (the marker is the first candidate that no valid cell holds, the slot count follows
+ * mdb_set_slots_log2_for(members)), every member sits on its probe path; which of two colliding members comes first is free.  The table is
+ * first sized by the valid cells (capped at 2^MDB_SET_MAX_LOG2 slots) and built again from its occupied slots when the members need a
+ * smaller one (rebuilt = 1).  More than max_members distinct values (0 = MDB_SET_MAX_VALUES, which also caps it): -MIDORIDB_ERROR with a
+ * message naming the count reached and the limit - the insertion stops once the count passes the limit, info->members holds the count at
+ * which it stopped - no set, and the context stays usable.  The call synchronises. */
+struct mdb_dev_set_info {
+	uint64_t cells_null;	/* cells skipped as NULL: NULL bit set, or row id MDB_NO_ROW */
+	uint64_t cells_nan;	/* MDB_T_DOUBLE cells skipped as NaN (mdb_set_canonical) */
+	uint64_t members;	/* distinct canonical values */
+	uint32_t log2_slots;	/* of the final image */
+	uint32_t rebuilt;	/* 1: the first table was larger than the members need and was built again */
+};
+int mdb_dev_set_from_column(mdb_dev_ctx *ctx, const void *values, const uint64_t *nullbits, const uint32_t *rid, uint64_t n,
+			    int type, uint64_t max_members /* 0 = MDB_SET_MAX_VALUES */, mdb_dev_set **set, struct mdb_dev_set_info *info);
 /* the largest number of list values whose table the one-instruction kernel stages in LDS (MDB_SET_LDS_SLOTS / 2); larger sets are
  * probed in global memory (L2 / Infinity Cache) */
 uint64_t mdb_dev_in_set_lds_values(void);

@@ -164,6 +164,10 @@ unsigned long long mdb_database_composite_fused(struct database *db);
  * compile to one comparison per value as before and do not count; with MDB_IN_SET=0 every list does, and a list the device program
  * cannot hold (33 values and more) is refused as "predicate too large". */
 unsigned long long mdb_database_in_set_lookups(struct database *db);
+/* x [NOT] IN (SELECT ...) - an extension: device sets this database's statements have built so far from a subquery's result column, on
+ * the device (mdb_dev_set_from_column, mdb_dev.h): one per subquery of a statement, nested ones included.  mdb_database_in_set_lookups()
+ * does not move for them. */
+unsigned long long mdb_database_subquery_sets(struct database *db);
 /* SUM / MIN / MAX / AVG (an extension: upstream has COUNT only): SELECT statements of this database so far whose aggregates ran through
  * mdb_dev_group_aggregate (mdb_dev.h), by the form the operator took - *lds_form: groups in LDS (integer cells, or MIN / MAX over DOUBLE,
  * one group column or none, few enough groups), *sorted_form: sorted segments (SUM / AVG over DOUBLE, several group columns, many groups,

@@ -1442,13 +1442,7 @@ static int filter_prepare(mdb_dev_ctx *ctx, const struct mdb_pred_insn *prog, in
 
 /* ------------------------------------------------------------------ device sets (MDB_P_IN_SET) */
 
-struct mdb_dev_set {
-	void *d_words;		/* the image (mdb_dev.h) in a buffer of mdb_dev_alloc */
-	uint64_t slots, members;
-	uint32_t log2_slots;
-	int32_t type;
-};
-
+/* (struct mdb_dev_set: mdb_dev_internal.h - the device builder, mdb_dev_setbuild.hip, makes them too) */
 extern "C" uint64_t mdb_dev_in_set_lds_values(void)
 {
 	return MDB_SET_LDS_SLOTS / 2;

@@ -237,6 +237,15 @@ int mdb_expand_keys_by_count(mdb_dev_ctx *ctx, const int64_t *key, const int64_t
 /* group i = row i, COUNT 1 (mdb_dev_dense.hip): a GROUP BY over a column whose statistics say MDB_COL_DISTINCT */
 int mdb_group_identity(mdb_dev_ctx *ctx, uint64_t n, uint32_t *out_first, int64_t *out_count);
 
+/* ---- a set in device memory (MDB_P_IN_SET): made by mdb_dev_set_create (mdb_dev_filter.hip, from host values) and by
+ * mdb_dev_set_from_column (mdb_dev_setbuild.hip, from a device column) */
+struct mdb_dev_set {
+	void *d_words;		/* the image (mdb_dev.h) in a buffer of mdb_dev_alloc */
+	uint64_t slots, members;
+	uint32_t log2_slots;
+	int32_t type;
+};
+
 /* choose level bits so that the average leaf holds about `target` keys */
 void mdb_choose_bits(uint64_t n, uint32_t target, int *bits1, int *bits2);
 

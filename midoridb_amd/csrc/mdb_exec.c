@@ -1457,6 +1457,90 @@ bool keys_only_join(const struct mdb_select *s, const struct mdb_catalog *cat, i
 	return true;
 }
 
+/* ------------------------------------------------------------------ x [NOT] IN (SELECT ...)
+ * Every subquery node under e is evaluated once, inner subqueries first (the nested statement evaluates its own on its way), before the
+ * outer statement's plan is chosen: the nested SELECT runs with its result kept on the device - whatever the database's setting is -,
+ * its one column goes to mdb_dev_set_from_column, the result is freed at once.  The set lives in the node until the outer statement
+ * ends (subqueries_release, on every path out of the statement). */
+int subqueries_eval(struct mdb_catalog *cat, struct mdb_expr *e, char *err, size_t errlen)
+{
+	int rc;
+
+	if (!e)
+		return MIDORIDB_OK;
+	for (int i = 0; i < e->nkids; i++)
+		if ((rc = subqueries_eval(cat, e->kids[i], err, errlen)))
+			return rc;
+	if (e->kind != MDB_EX_ISIN || !e->sub)
+		return MIDORIDB_OK;
+
+	if (e->sub_set) {	/* (a statement that is run again builds its sets again) */
+		mdb_dev_set_free(cat->dev, e->sub_set);
+		e->sub_set = NULL;
+	}
+	struct mdb_result *r = NULL;
+	const bool on_device = cat->results_on_device;
+	cat->results_on_device = true;
+	rc = mdb_exec_select(cat, e->sub, &r, err, errlen);
+	cat->results_on_device = on_device;
+	if (rc)
+		return rc;
+	const void *vals = NULL;
+	const uint64_t *nulls = NULL;
+	void *one = NULL;	/* a result of one row stays on the host (a lone COUNT(*) or MAX(v)): its cell and NULL word, uploaded */
+	struct mdb_dev_set_info info = { 0 };
+	if (r->ncols != 1) {
+		ERR("a subquery must select one column\n");
+		rc = -MIDORIDB_ERROR;
+	} else if (r->nrows && r->d_data && r->d_data[0]) {
+		vals = r->d_data[0];
+		nulls = r->d_nullbits ? r->d_nullbits[0] : NULL;
+	} else if (r->nrows == 1 && r->data && r->data[0]) {
+		const uint64_t cell[2] = { (uint64_t)r->data[0][0], r->nullbits && r->nullbits[0] ? r->nullbits[0][0] & 1u : 0u };
+		if (mdb_dev_alloc(cat->dev, sizeof(cell), &one) || mdb_dev_h2d(cat->dev, one, cell, sizeof(cell))) {
+			ERR("execution phase: IN (SELECT ...): %s\n", mdb_dev_last_error(cat->dev));
+			rc = -MIDORIDB_INTERNAL;
+		}
+		vals = one;
+		nulls = cell[1] ? (const uint64_t *)one + 1 : NULL;
+	} else if (r->nrows) {
+		ERR("execution phase: internal error (IN (SELECT ...): the subquery's column is nowhere)\n");
+		rc = -MIDORIDB_INTERNAL;
+	}
+	if (!rc) {
+		rc = mdb_dev_set_from_column(cat->dev, vals, nulls, NULL, r->nrows, e->kids[0]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64, 0,
+					     &e->sub_set, &info);
+		if (rc && info.members > MDB_SET_MAX_VALUES)
+			ERR("IN (SELECT ...): %llu distinct values, a set takes at most %llu\n", (unsigned long long)info.members,
+			    (unsigned long long)MDB_SET_MAX_VALUES);
+		else if (rc)
+			ERR("execution phase: IN (SELECT ...): %s\n", mdb_dev_last_error(cat->dev));
+	}
+	if (!rc) {
+		e->sub_rows = r->nrows;
+		e->sub_nulls = info.cells_null;
+		e->sub_members = info.members;
+		cat->subquery_sets++;
+	}
+	if (one)
+		mdb_dev_free(cat->dev, one);
+	mdb_result_free(r);
+	stmt_dict = &cat->dict;
+	return rc;
+}
+
+void subqueries_release(struct mdb_catalog *cat, struct mdb_expr *e)
+{
+	if (!e)
+		return;
+	for (int i = 0; i < e->nkids; i++)
+		subqueries_release(cat, e->kids[i]);
+	if (e->sub_set) {
+		mdb_dev_set_free(cat->dev, e->sub_set);
+		e->sub_set = NULL;
+	}
+}
+
 int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_result **out, char *err, size_t errlen)
 {
 	stmt_dict = &cat->dict;
@@ -1476,7 +1560,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	memset(&x, 0, sizeof(x));
 	for (int t = 0; t < MDB_MAX_TABS; t++)
 		x.same_col[t] = -1;
-	if ((rc = resolve_select(cat, s, err, errlen)))
+	if (!s->resolved && (rc = resolve_select(cat, s, err, errlen)))
 		return rc;
 	if ((rc = mdb_catalog_device(cat, err, errlen)))
 		return rc;
@@ -1491,6 +1575,11 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	for (int t = 1; t < s->ntabs; t++)
 		x.has_outer = x.has_outer || s->join_type[t] != 1;
 	mark_needed_all(&x);	/* (which columns the statement reads: the sharded exchange and the join that carries payload cells ask) */
+	/* (the subqueries are part of what the statement costs: their time counts in exec_ms, beside the pipeline's own from t0 on) */
+	const double sub_t0 = now_ms();
+	if ((rc = subqueries_eval(cat, s->where, err, errlen)) || (rc = subqueries_eval(cat, s->having, err, errlen)))
+		goto out;
+	const double sub_ms = (s->where && expr_has_subquery(s->where)) || (s->having && expr_has_subquery(s->having)) ? now_ms() - sub_t0 : 0.0;
 
 	/* ---- result column set in the reference's order (R3): COUNT(*) first if selected, then every column
 	 *      of every FROM table left to right; projected afterwards to the select list */
@@ -2370,7 +2459,7 @@ grouped:
 	res->dict = &cat->dict;
 	mdb_result_legacy_header(res);		/* the reference's struct table in front of the columnar result (include/mdb_legacy.h) ... */
 	mdb_result_legacy_rows(res);		/* ... and, for a small result whose columns are on the host, its rows as datablocks */
-	res->exec_ms = now_ms() - t0;
+	res->exec_ms = now_ms() - t0 + sub_ms;
 	res->joined_rows = x.joined_rows;
 	*out = res;
 	res = NULL;
@@ -2382,6 +2471,8 @@ out:
 	cat->aggregate_calls[0] += (uint64_t)x.agg_calls[0];
 	cat->aggregate_calls[1] += (uint64_t)x.agg_calls[1];
 	shard_cleanup(&x);
+	subqueries_release(cat, s->where);
+	subqueries_release(cat, s->having);
 	free_all(&x);
 	mdb_result_free(res);
 	free(keys);

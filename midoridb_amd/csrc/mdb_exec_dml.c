@@ -244,7 +244,7 @@ int dml_select_rows(struct mdb_catalog *cat, struct mdb_dml *d, struct exec *x, 
 	s->ntabs = 1;
 	if (d->where) {
 		if ((rc = resolve_expr(s, d->where, err, errlen)) || (rc = check_predicate_x(d->where, "where", true, err, errlen)) ||
-		    (rc = dml_check_values(d->where, err, errlen)))
+		    (rc = dml_check_values(d->where, err, errlen)) || (rc = resolve_subqueries(cat, d->where, err, errlen)))
 			return rc;
 		if (dml_value_on_left(d->where)) {
 			ERR("comparisons in DELETE/UPDATE must have the column on the left (the reference evaluates 'value <op> column' "
@@ -264,6 +264,9 @@ int dml_select_rows(struct mdb_catalog *cat, struct mdb_dml *d, struct exec *x, 
 	x->errlen = errlen;
 	x->n = t->nrows;
 	*m = t->nrows;
+	/* IN (SELECT ...): the sets are built before any row changes - a subquery over the statement's own table sees the table as it was */
+	if ((rc = subqueries_eval(cat, d->where, err, errlen)))
+		return rc;
 	if (d->where && t->nrows) {
 		struct pred_prog p;
 		uint32_t *v;
@@ -390,6 +393,7 @@ int mdb_exec_delete(struct mdb_catalog *cat, struct mdb_dml *d, size_t *n_rows_a
 	*n_rows_aff = (size_t)(n_old - n_keep);
 out:
 	free(h_keep);
+	subqueries_release(cat, d->where);
 	free_all(&x);
 	return rc;
 }
@@ -555,6 +559,7 @@ int mdb_exec_update(struct mdb_catalog *cat, struct mdb_dml *d, size_t *n_rows_a
 	*n_rows_aff = (size_t)m;
 out:
 	free(h_sel);
+	subqueries_release(cat, d->where);
 	free_all(&x);
 	return rc;
 }

@@ -124,6 +124,10 @@ const char *mdb_agg_name(int op);
 int mdb_agg_result_type(int op, int coltype);
 int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, const char *clause, char *err, size_t errlen);
 int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, size_t errlen);
+bool expr_has_subquery(const struct mdb_expr *e);
+int resolve_subqueries(struct mdb_catalog *cat, struct mdb_expr *e, char *err, size_t errlen);
+int subqueries_eval(struct mdb_catalog *cat, struct mdb_expr *e, char *err, size_t errlen);
+void subqueries_release(struct mdb_catalog *cat, struct mdb_expr *e);
 int dev_fail(struct exec *x, const char *what);
 int track(struct exec *x, void *p);
 void *dalloc(struct exec *x, size_t bytes);

@@ -212,6 +212,30 @@ static int pred_compile_in_lookup(struct exec *x, struct pred_prog *p, const str
 	return rc;
 }
 
+/* x [NOT] IN (SELECT ...): the subquery has run (subqueries_eval) - e->sub_set is the device set of its column's non-NULL cells,
+ * sub_rows / sub_nulls / sub_members its rows, the NULL cells among them and the distinct values.  SQL's three-valued rules, which are
+ * the list's where they overlap:
+ *   no rows at all            IN false;  NOT IN true for every row, a NULL x included
+ *   rows, some cell NULL      IN the lookup (false without a member);  NOT IN never true
+ *   rows, no NULL             the lookup, negated for NOT IN (a NULL x fails both); without a member (NaN cells only) IN is false and
+ *                             NOT IN is `x IS NOT NULL`
+ * The instruction is the one a long list compiles to: every plan that takes such a list takes this. */
+static int pred_compile_in_subquery(struct pred_prog *p, const struct mdb_expr *e, int a)
+{
+	const int neg = e->op ? 1 : 0;
+	struct mdb_pred_insn in;
+
+	if (!e->sub_rows)
+		return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, neg);
+	if (neg && e->sub_nulls)
+		return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
+	if (!e->sub_members || !e->sub_set)
+		return neg ? pred_emit(p, MDB_P_ISNULL, 1, 0, a, 0, 0) : pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
+	if (mdb_dev_set_insn(e->sub_set, a, neg, &in))
+		return -1;
+	return pred_emit(p, in.op, in.cmp, in.type, in.a, in.b, in.imm);
+}
+
 int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 {
 	int rc = 0, a, b;
@@ -264,6 +288,8 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 		a = pred_slot(x, p, f);
 		if (a < 0)
 			return -1;
+		if (e->sub)
+			return pred_compile_in_subquery(p, e, a);
 		if (e->nkids - 1 > MDB_FILTER_MAX_TERMS && !mdb_knob_off("MDB_IN_SET"))
 			return pred_compile_in_lookup(x, p, e, a);
 		for (int i = 1; i < e->nkids; i++) {

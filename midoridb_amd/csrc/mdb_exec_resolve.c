@@ -366,6 +366,70 @@ int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, 
 	return MIDORIDB_OK;
 }
 
+/* ------------------------------------------------------------------ x [NOT] IN (SELECT ...)
+ * An extension (the reference's grammar has value lists only).  The nested statement hangs beside the node's one kid (mdb_expr.sub), not
+ * among its kids: it is resolved here on its own, against its own FROM tables alone - a correlated reference fails with the inner
+ * statement's ordinary unknown-table / unknown-column error - and must deliver one column of the left operand's type. */
+bool expr_has_subquery(const struct mdb_expr *e)
+{
+	if (!e)
+		return false;
+	if (e->sub)
+		return true;
+	for (int i = 0; i < e->nkids; i++)
+		if (expr_has_subquery(e->kids[i]))
+			return true;
+	return false;
+}
+
+static const char *coltype_name(int type)
+{
+	switch (type) {
+	case MDB_CT_VARCHAR: return "VARCHAR";
+	case MDB_CT_INTEGER: return "INTEGER";
+	case MDB_CT_TINYINT: return "TINYINT";
+	case MDB_CT_DOUBLE: return "DOUBLE";
+	case MDB_CT_DATE: return "DATE";
+	case MDB_CT_DATETIME: return "DATETIME";
+	default: return "?";
+	}
+}
+
+/* every subquery under e (resolved and checked already: the left operands are fields) */
+int resolve_subqueries(struct mdb_catalog *cat, struct mdb_expr *e, char *err, size_t errlen)
+{
+	int rc;
+
+	if (!e)
+		return MIDORIDB_OK;
+	for (int i = 0; i < e->nkids; i++)
+		if ((rc = resolve_subqueries(cat, e->kids[i], err, errlen)))
+			return rc;
+	if (e->kind != MDB_EX_ISIN || !e->sub)
+		return MIDORIDB_OK;
+	if (cat->dist) {
+		/* (known from the statement alone: every rank leaves here together, before anything is exchanged) */
+		ERR("sharded mode: IN (SELECT ...) is not executed (subqueries run on one GPU)\n");
+		return -MIDORIDB_ERROR;
+	}
+	struct mdb_select *q = e->sub;
+	if (q->select_all || q->nsel != 1) {
+		ERR("a subquery must select one column\n");
+		return -MIDORIDB_ERROR;
+	}
+	if (!q->resolved && (rc = resolve_select(cat, q, err, errlen)))
+		return rc;
+	q->resolved = true;
+	const struct mdb_expr *it = q->sel[0];
+	const int have = it->kind == MDB_EX_COUNT ? MDB_CT_INTEGER : it->type, want = e->kids[0]->type;	/* (an aggregate: its result's type) */
+	if (have != want) {
+		ERR("IN (SELECT ...): the column '%.100s.%.100s' is %s, the subquery's column is %s: both sides must have the same type\n",
+		    e->kids[0]->tbl, e->kids[0]->col, coltype_name(want), coltype_name(have));
+		return -MIDORIDB_ERROR;
+	}
+	return MIDORIDB_OK;
+}
+
 int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, size_t errlen)
 {
 	int rc;
@@ -466,10 +530,15 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 	}
 	for (int t = 1; t < s->ntabs; t++)
 		if (s->on[t]) {
+			if (expr_has_subquery(s->on[t])) {
+				ERR("IN (SELECT ...) in JOIN ... ON is not supported: a subquery stands in WHERE or HAVING\n");
+				return -MIDORIDB_ERROR;
+			}
 			if ((rc = resolve_expr(s, s->on[t], err, errlen)) || (rc = check_predicate(s->on[t], "JOIN ON", err, errlen)))
 				return rc;
 		}
-	if (s->where && ((rc = resolve_expr(s, s->where, err, errlen)) || (rc = check_predicate(s->where, "where", err, errlen))))
+	if (s->where && ((rc = resolve_expr(s, s->where, err, errlen)) || (rc = check_predicate(s->where, "where", err, errlen)) ||
+			 (rc = resolve_subqueries(cat, s->where, err, errlen))))
 		return rc;
 	if (s->ngroup > MDB_SORT_MAX_KEYS) {
 		ERR("GROUP BY over more than %d fields is not supported\n", MDB_SORT_MAX_KEYS);
@@ -525,6 +594,8 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 				return rc;
 			/* fields must come from the SELECT list (check_having_clause_inselect, semantic_select.c:1953-2001) */
 			if ((rc = fields_in_select_list(s, s->having, "HAVING", err, errlen)))
+				return rc;
+			if ((rc = resolve_subqueries(cat, s->having, err, errlen)))
 				return rc;
 			if (expr_has_count(s->having) && !s->ngroup) {
 				ERR("COUNT in the having-clause requires a GROUP BY clause on the MI355X path\n");

@@ -128,6 +128,7 @@ struct mdb_catalog {
 	uint64_t composite_fused;	/* SELECT statements answered by the fused join + GROUP BY operator on a packed composite key (mdb_exec.c, composite_fused_plan) */
 	uint64_t aggregate_calls[2];	/* mdb_dev_group_aggregate calls of SELECT statements by form: [0] groups in LDS, [1] sorted segments (mdb_exec.c) */
 	uint64_t in_set_lookups;	/* IN / NOT IN lists compiled to one device lookup (mdb_exec_pred.c, pred_compile_in_lookup) */
+	uint64_t subquery_sets;		/* IN / NOT IN (SELECT ...): device sets built from a subquery's result column (mdb_exec.c, subqueries_eval) */
 	bool groups_any_order;		/* mdb_database_groups_any_order(): GROUP BY over a join need not keep first-occurrence order */
 	bool results_on_device;		/* mdb_database_results_on_device(): SELECT results stay in HBM until a consumer reads them */
 };
@@ -180,7 +181,7 @@ enum mdb_expr_kind {
 	MDB_EX_CMP,		/* op = comparison code 1..6, 2 kids */
 	MDB_EX_LOGOP,		/* op = 0 AND, 1 OR, 2 XOR (reference enum ast_logop_type), 2 kids */
 	MDB_EX_ISNULL,		/* op = negation, 1 kid */
-	MDB_EX_ISIN,		/* op = negation, kid[0] = field, rest = values */
+	MDB_EX_ISIN,		/* op = negation, kid[0] = field, rest = values - or, with `sub`, the one kid and the nested SELECT beside it */
 	MDB_EX_COUNT,		/* COUNT(*) / COUNT(x) */
 	MDB_EX_LIKE,
 	MDB_EX_ARITH,		/* + - * / % NEG: parsed, rejected by the executor like select-list math is ignored upstream */
@@ -201,6 +202,13 @@ struct mdb_expr {
 	int nkids;
 	/* resolution (FIELD): index into the plan's FROM tables and the column index there */
 	int tbl_idx, col_idx, type;
+	/* MDB_EX_ISIN over a subquery: the nested statement, owned by the node (mdb_expr_free) and deliberately NOT among `kids` - the
+	 * outer statement's walkers never descend into it; it is resolved and run on its own.  The executor evaluates it once, before
+	 * the outer statement's plan is chosen (subqueries_eval, mdb_exec.c; subqueries_release ends it): sub_set = the device set of its one column, alive until the outer
+	 * statement ends, sub_rows / sub_nulls / sub_members = its rows, the NULL cells among them, its distinct non-NULL values */
+	struct mdb_select *sub;
+	mdb_dev_set *sub_set;
+	uint64_t sub_rows, sub_nulls, sub_members;
 };
 
 struct mdb_from_tab {
@@ -231,6 +239,7 @@ struct mdb_select {
 	int norder;
 	bool has_limit;
 	int64_t limit_off, limit_cnt;	/* LIMIT cnt | LIMIT off, cnt (midorisql.y:193-196) */
+	bool resolved;			/* a subquery's plan: resolve_select() has run over it (with the outer statement's checks) and is not run again */
 };
 
 struct mdb_create {
@@ -279,6 +288,7 @@ struct mdb_stmt {
 
 int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, size_t errlen);
 void mdb_stmt_free(struct mdb_stmt *st);
+void mdb_select_free(struct mdb_select *s);	/* what the plan owns; not the struct itself */
 void mdb_expr_free(struct mdb_expr *e);
 
 /* ------------------------------------------------------------------ result set */
@@ -294,7 +304,7 @@ struct mdb_result {
 	int64_t **data;			/* host columns, 8-byte values (0 for NULL) */
 	uint64_t **nullbits;		/* host NULL bits per column or NULL */
 	uint64_t nrows;
-	double exec_ms;			/* device pipeline wall time of the SELECT that produced it */
+	double exec_ms;			/* device pipeline wall time of the SELECT that produced it, its IN (SELECT ...) subqueries and their sets included */
 	uint64_t joined_rows;		/* rows produced by the join before aggregation (0 when no join) */
 	const struct mdb_strdict *dict;	/* VARCHAR result cells are ids of this dictionary (the database's) */
 	/* results kept on the device (mdb_database_results_on_device): d_data[c] / d_nullbits[c] are buffers of `dev` owned by the

@@ -16,6 +16,8 @@
 enum {
 	BX_TABLE = 100, BX_JOIN, BX_ONEXPR, BX_WHERE, BX_GROUPBY, BX_HAVING, BX_ORDERBYITEM, BX_ORDERBYLIST,
 	BX_LIMIT, BX_SELECTALL, BX_ASSIGN,
+	BX_SELECT,	/* a finished "SELECT d n": the plan in `sub` - the statement itself, or a subquery's once "SUBQUERY" has wrapped it */
+	BX_SUBQUERY,
 };
 
 static struct mdb_expr *ex_new(int kind)
@@ -46,6 +48,10 @@ void mdb_expr_free(struct mdb_expr *e)
 		mdb_expr_free(e->kids[i]);
 	free(e->kids);
 	free(e->sval);
+	if (e->sub) {
+		mdb_select_free(e->sub);
+		free(e->sub);
+	}
 	free(e);
 }
 
@@ -145,12 +151,10 @@ static int flatten_from(struct mdb_expr *ref, struct mdb_select *s, char *err, s
 	return -MIDORIDB_ERROR;
 }
 
-static int finish_select(struct mdb_expr *root, struct mdb_stmt *out, char *err, size_t errlen)
+static int finish_select(struct mdb_expr *root, struct mdb_select *s, char *err, size_t errlen)
 {
-	struct mdb_select *s = &out->sel;
 	int rc = 0;
 
-	out->kind = MDB_ST_SELECT;
 	s->distinct = (root->op & 2) != 0;
 	for (int i = 0; i < root->nkids && !rc; i++) {
 		struct mdb_expr *k = root->kids[i];
@@ -497,15 +501,64 @@ int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, s
 				FAIL("error while running syntax analysis on query\n");
 			e = ex_new(MDB_EX_ALIAS + 1000);	/* scaffold root */
 			if (e) {
+				/* the plan goes onto the stack: "STMT" takes it as the statement, "SUBQUERY" as the right side of an IN */
+				struct mdb_expr *node = ex_new(BX_SELECT);
 				e->op = x;
-				if (pop_n_into(&st, y, e))
+				if (node)
+					node->sub = calloc(1, sizeof(*node->sub));
+				if (!node || !node->sub) {
+					mdb_expr_free(node);
+					mdb_expr_free(e);
+					goto nomem;
+				}
+				if (pop_n_into(&st, y, e)) {
+					mdb_expr_free(node);
+					e->nkids = 0;	/* (what it took so far is still on the stack, which frees it) */
+					mdb_expr_free(e);
 					FAIL("error while running syntax analysis on query\n");
-				rc = finish_select(e, out, err, errlen);
-				if (rc)
+				}
+				rc = finish_select(e, node->sub, err, errlen);
+				e = node;
+				if (rc) {
+					mdb_expr_free(e);
 					goto out;
-				continue;
+				}
+				rc = -MIDORIDB_ERROR;
+			}
+		} else if (!strcmp(t, "SUBQUERY")) {
+			/* (this project's own token, as ISINSUB / ISNOTINSUB: SURVEY.md Appendix A) */
+			if (st.n < 1 || st.v[st.n - 1]->kind != BX_SELECT)
+				FAIL("error while running syntax analysis on query\n");
+			st.v[st.n - 1]->kind = BX_SUBQUERY;
+			continue;
+		} else if (!strcmp(t, "ISINSUB") || !strcmp(t, "ISNOTINSUB")) {
+			struct mdb_expr *sq;
+			if (st.n < 2 || st.v[st.n - 1]->kind != BX_SUBQUERY || st.v[st.n - 2]->kind >= BX_TABLE)
+				FAIL("error while running syntax analysis on query\n");
+			sq = pop(&st);
+			e = ex_new(MDB_EX_ISIN);
+			if (!e) {
+				mdb_expr_free(sq);
+				goto nomem;
+			}
+			e->op = !strcmp(t, "ISNOTINSUB");
+			e->sub = sq->sub;
+			sq->sub = NULL;
+			mdb_expr_free(sq);
+			if (pop_n_into(&st, 1, e)) {
+				e->nkids = 0;	/* (the field is still on the stack, which frees it) */
+				mdb_expr_free(e);
+				goto nomem;
 			}
 		} else if (!strcmp(t, "STMT")) {
+			if (st.n == 1 && st.v[0]->kind == BX_SELECT && !out->kind) {
+				struct mdb_expr *node = pop(&st);
+				out->sel = *node->sub;
+				free(node->sub);
+				node->sub = NULL;
+				mdb_expr_free(node);
+				out->kind = MDB_ST_SELECT;
+			}
 			done = true;
 			continue;
 		/* ---- DELETE / UPDATE ---- */
@@ -672,26 +725,34 @@ out:
 #undef NEED
 }
 
+void mdb_select_free(struct mdb_select *s)
+{
+	if (!s)
+		return;
+	for (int i = 0; i < s->nsel; i++)
+		mdb_expr_free(s->sel[i]);
+	free(s->sel);
+	free(s->sel_alias);
+	for (int i = 0; i < s->ntabs; i++)
+		mdb_expr_free(s->on[i]);
+	free(s->on);
+	free(s->tabs);
+	free(s->join_type);
+	mdb_expr_free(s->where);
+	for (int i = 0; i < s->ngroup; i++)
+		mdb_expr_free(s->group[i]);
+	free(s->group);
+	mdb_expr_free(s->having);
+	for (int i = 0; i < s->norder; i++)
+		mdb_expr_free(s->order[i]);
+	free(s->order);
+	free(s->order_desc);
+	memset(s, 0, sizeof(*s));
+}
+
 void mdb_stmt_free(struct mdb_stmt *s)
 {
-	for (int i = 0; i < s->sel.nsel; i++)
-		mdb_expr_free(s->sel.sel[i]);
-	free(s->sel.sel);
-	free(s->sel.sel_alias);
-	for (int i = 0; i < s->sel.ntabs; i++)
-		mdb_expr_free(s->sel.on[i]);
-	free(s->sel.on);
-	free(s->sel.tabs);
-	free(s->sel.join_type);
-	mdb_expr_free(s->sel.where);
-	for (int i = 0; i < s->sel.ngroup; i++)
-		mdb_expr_free(s->sel.group[i]);
-	free(s->sel.group);
-	mdb_expr_free(s->sel.having);
-	for (int i = 0; i < s->sel.norder; i++)
-		mdb_expr_free(s->sel.order[i]);
-	free(s->sel.order);
-	free(s->sel.order_desc);
+	mdb_select_free(&s->sel);
 	for (int i = 0; i < s->ins.ntuples; i++) {
 		for (int k = 0; k < s->ins.nvals; k++)
 			mdb_expr_free(s->ins.vals[i][k]);

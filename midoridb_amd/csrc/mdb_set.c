@@ -34,19 +34,6 @@ static int probe_used(const uint64_t *slots, const uint64_t *used, uint64_t nslo
 	return 0;
 }
 
-/* log2 of the slot count for n values: load <= 1/2; <= 1/4 while the table still fits the LDS budget of the filter kernel (a miss
- * then takes 1.4 probes, not 2.5) */
-static unsigned slots_log2_for(uint64_t n)
-{
-	uint64_t nslots = 1ull << MDB_SET_MIN_LOG2;
-	unsigned log2 = MDB_SET_MIN_LOG2;
-	while (nslots < 2 * n || (nslots < 4 * n && 2 * nslots <= MDB_SET_LDS_SLOTS)) {
-		nslots <<= 1;
-		log2++;
-	}
-	return log2;
-}
-
 int mdb_set_build(const int64_t *values, uint64_t n, int type, struct mdb_set_image *out)
 {
 	uint64_t nslots, *words, *slots, *used, empty, run = 0, longest = 0, members = 0;
@@ -57,7 +44,7 @@ int mdb_set_build(const int64_t *values, uint64_t n, int type, struct mdb_set_im
 	memset(out, 0, sizeof(*out));
 	if ((type != 0 && type != 1) || n > MDB_SET_MAX_VALUES || (n && !values))
 		return -MIDORIDB_ERROR;
-	log2 = slots_log2_for(n);
+	log2 = mdb_set_slots_log2_for(n);
 	nslots = 1ull << log2;
 	words = malloc((size_t)(2 + nslots) * 8);
 	used = calloc((size_t)((nslots + 63) / 64), 8);
@@ -83,7 +70,7 @@ int mdb_set_build(const int64_t *values, uint64_t n, int type, struct mdb_set_im
 	/* The table is sized by the DISTINCT values: a list whose duplicates (or NaNs) made this table larger than its members need is
 	 * built again from the members alone - once: they are distinct and canonical, so the second table has the size asked for.  What
 	 * mdb_dev_in_set_lds_values() promises holds for the list's distinct values, however often the list repeats them. */
-	if (slots_log2_for(members) < log2) {
+	if (mdb_set_slots_log2_for(members) < log2) {
 		int64_t *distinct = malloc((size_t)(members ? members : 1) * 8);
 		uint64_t m = 0;
 		int rc;
@@ -102,9 +89,9 @@ int mdb_set_build(const int64_t *values, uint64_t n, int type, struct mdb_set_im
 		return rc;
 	}
 	/* the EMPTY marker: the first pattern of a full-period sequence that is not a member */
-	empty = 0x8000000000000000ull;
+	empty = MDB_SET_MARKER_FIRST;
 	while (probe_used(slots, used, nslots, log2, empty))
-		empty = empty * 6364136223846793005ull + 1442695040888963407ull;
+		empty = mdb_set_marker_next(empty);
 	for (uint64_t i = 0; i < nslots; i++)
 		if (!used_bit(used, i))
 			slots[i] = empty;

@@ -12,6 +12,7 @@
  * reductions, for the statements the SELECT path and its tests need:
  *
  *   SELECT [DISTINCT] exprs FROM refs [WHERE] [GROUP BY] [HAVING] [ORDER BY] [LIMIT] ;
+ *       (in its expressions, and in those of DELETE / UPDATE:  x [NOT] IN ( SELECT ... ), nested up to 8 deep)
  *   CREATE TABLE [IF NOT EXISTS] t (col type [attrs], ...) ;
  *   INSERT [INTO] t [(cols)] VALUES (...), (...) ;
  *
@@ -52,7 +53,10 @@ struct parser {
 	size_t errlen;
 	bool failed;
 	bool dml;		/* inside delete_expr / update_expr: names, literals, logic, comparisons, IS NULL, IN only */
+	int depth;		/* nested SELECTs open: IN (SELECT ...) */
 };
+
+#define MAX_SUBQUERY_DEPTH 8
 
 static void fail(struct parser *p, const char *fmt, ...)
 {
@@ -346,6 +350,27 @@ static void expect_kw(struct parser *p, const char *kw)
 enum { P_OR = 1, P_XOR = 2, P_AND = 3, P_ISIN = 4, P_NOT = 5, P_CMP = 7, P_ADD = 11, P_MUL = 12, P_NEG = 14 };
 
 static void parse_expr(struct parser *p, int min_prec);
+static void parse_select(struct parser *p);
+
+/* IN ( SELECT ... ) - an extension (the reference's grammar knows value lists only, midorisql.y:283-284): the lexer stands on SELECT.
+ * The inner statement's tokens are emitted in place and end in its own "SELECT d n"; "SUBQUERY" wraps it into one stack entry.  Inside
+ * the parentheses the grammar is SELECT's, whatever the outer statement is. */
+static void parse_subquery(struct parser *p)
+{
+	const bool dml = p->dml;
+
+	if (p->depth >= MAX_SUBQUERY_DEPTH) {
+		fail(p, "syntax error, subqueries nested deeper than %d", MAX_SUBQUERY_DEPTH);
+		return;
+	}
+	next(p);
+	p->dml = false;
+	p->depth++;
+	parse_select(p);
+	p->depth--;
+	p->dml = dml;
+	emit(p, "SUBQUERY");
+}
 
 static int parse_val_list(struct parser *p)
 {
@@ -521,6 +546,12 @@ static void parse_expr(struct parser *p, int min_prec)
 				neg = true;
 			if (accept_kw(p, "IN")) {
 				expect_punct(p, '(');
+				if (!p->failed && is_kw(p, "SELECT")) {
+					parse_subquery(p);
+					expect_punct(p, ')');
+					emit(p, neg ? "ISNOTINSUB" : "ISINSUB");
+					continue;
+				}
 				n = parse_val_list(p);
 				expect_punct(p, ')');
 				emit(p, neg ? "ISNOTIN %d" : "ISIN %d", n);

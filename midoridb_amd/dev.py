@@ -36,6 +36,11 @@ class SetImage(ctypes.Structure):
                 ("log2_slots", c_uint32), ("type", c_int32)]
 
 
+class SetInfo(ctypes.Structure):
+    """struct mdb_dev_set_info: what mdb_dev_set_from_column found and built (include/mdb_dev.h)"""
+    _fields_ = [("cells_null", c_uint64), ("cells_nan", c_uint64), ("members", c_uint64), ("log2_slots", c_uint32), ("rebuilt", c_uint32)]
+
+
 class ColBinding(ctypes.Structure):
     _fields_ = [("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p)]
 
@@ -259,6 +264,7 @@ def _bind(lib):
         "mdb_set_image_free": ([POINTER(SetImage)], None),
         "mdb_set_image_contains": ([POINTER(SetImage), c_int64], c_int),
         "mdb_dev_set_create": ([P, P, c_uint64, c_int, POINTER(P)], c_int),
+        "mdb_dev_set_from_column": ([P, P, P, P, c_uint64, c_int, c_uint64, POINTER(P), POINTER(SetInfo)], c_int),
         "mdb_dev_set_insn": ([P, c_int, c_int, POINTER(PredInsn)], c_int),
         "mdb_dev_set_free": ([P, P], c_int),
         "mdb_dev_in_set_lds_values": ([], c_uint64),
@@ -280,7 +286,7 @@ DEV_SYMBOLS = [
     "mdb_dev_group_count", "mdb_dev_group_count_keys", "mdb_dev_join_group_count", "mdb_dev_join_group_count_multi", "mdb_dev_combine_counts", "mdb_dev_join_group_count_begin", "mdb_dev_join_group_count_finish",
     "mdb_dev_join_group_count_i32", "mdb_dev_join_group_count_begin_i32", "mdb_dev_join_group_count_finish_i32",
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
-    "mdb_set_build", "mdb_set_image_free", "mdb_set_image_contains", "mdb_dev_set_create", "mdb_dev_set_insn", "mdb_dev_set_free", "mdb_dev_in_set_lds_values",
+    "mdb_set_build", "mdb_set_image_free", "mdb_set_image_contains", "mdb_dev_set_create", "mdb_dev_set_from_column", "mdb_dev_set_insn", "mdb_dev_set_free", "mdb_dev_in_set_lds_values",
     "mdb_dev_group_aggregate", "mdb_dev_group_aggregate_lds_groups",
 ]
 
@@ -336,8 +342,19 @@ class DeviceSet:
 
     def __init__(self, ctx, values, typ=T_INT64):
         a = np.ascontiguousarray(values, dtype=np.float64 if typ == T_DOUBLE else np.int64).view(np.int64)
-        self._ctx, self.type, self.h = ctx, typ, c_void_p()
+        self._ctx, self.type, self.h, self.info = ctx, typ, c_void_p(), None
         ctx._chk(ctx.lib.mdb_dev_set_create(ctx.h, c_void_p(a.ctypes.data) if a.size else None, a.size, typ, byref(self.h)), "set_create")
+
+    @classmethod
+    def from_column(cls, ctx, values, nulls=None, rid=None, typ=T_INT64, max_members=0):
+        """built on the device from a device column (mdb_dev_set_from_column): values = 8-byte cells, nulls = NULL-bit words or None,
+        rid = int32 row ids or None (then there are rid.numel() cells); .info = the SetInfo of the build"""
+        self = cls.__new__(cls)
+        self._ctx, self.type, self.h, self.info = ctx, typ, c_void_p(), SetInfo()
+        n = rid.numel() if rid is not None else values.numel()
+        ctx._chk(ctx.lib.mdb_dev_set_from_column(ctx.h, _ptr(values) if values.numel() else None, _ptr(nulls), _ptr(rid), n, typ, int(max_members),
+                                                 byref(self.h), byref(self.info)), "set_from_column")
+        return self
 
     def insn(self, slot, negate=False):
         """(op, cmp, type, a, b, imm) testing column slot `slot` against the set"""
@@ -814,6 +831,12 @@ class DeviceCtx:
         """a device set of the given values (int64, or float64 with typ=T_DOUBLE) for P_IN_SET (mdb_dev_set_create) -> DeviceSet: it keeps
         the table alive, and .insn(slot, negate=False) is the instruction tuple for filter() / filter_project()"""
         return DeviceSet(self, values, typ)
+
+    def make_set_from_column(self, values, nulls=None, rid=None, typ=T_INT64, max_members=0):
+        """a device set of the cells of a DEVICE column (int64 or float64 tensor; nulls: NULL-bit words, rid: int32 row ids, both optional)
+        built on the device (mdb_dev_set_from_column) -> DeviceSet with .info (cells_null, cells_nan, members, log2_slots, rebuilt);
+        more than max_members distinct values (0 = the library's limit) raise DeviceError"""
+        return DeviceSet.from_column(self, values, nulls, rid, typ, max_members)
 
     def in_set_lds_values(self):
         """the largest list the one-instruction set kernel stages in LDS (mdb_dev_in_set_lds_values)"""

@@ -41,7 +41,7 @@ QUERY_SYMBOLS = [
     "mdb_query_execute_rpn", "query_column_double", "query_column_is_null", "query_column_count", "query_column_name",
     "query_column_type", "query_row_count", "query_column_data", "query_exec_ms", "query_joined_rows",
     "mdb_table_append_columns", "mdb_table_generate", "mdb_sql_to_rpn", "query_column_text", "mdb_result_text_at",
-    "mdb_database_device", "mdb_database_set_dist", "mdb_database_results_on_device", "mdb_database_groups_any_order", "mdb_database_joins_eliminated", "mdb_database_composite_joins", "mdb_database_composite_fused", "mdb_database_in_set_lookups", "mdb_database_aggregate_calls", "query_column_data_device", "query_column_nulls_device", "mdb_table_generate_shard",
+    "mdb_database_device", "mdb_database_set_dist", "mdb_database_results_on_device", "mdb_database_groups_any_order", "mdb_database_joins_eliminated", "mdb_database_composite_joins", "mdb_database_composite_fused", "mdb_database_in_set_lookups", "mdb_database_subquery_sets", "mdb_database_aggregate_calls", "query_column_data_device", "query_column_nulls_device", "mdb_table_generate_shard",
 ]
 
 
@@ -105,6 +105,8 @@ def _bind(lib):
     lib.mdb_database_composite_fused.restype = ctypes.c_ulonglong
     lib.mdb_database_in_set_lookups.argtypes = [PDB]
     lib.mdb_database_in_set_lookups.restype = ctypes.c_ulonglong
+    lib.mdb_database_subquery_sets.argtypes = [PDB]
+    lib.mdb_database_subquery_sets.restype = ctypes.c_ulonglong
     lib.mdb_database_aggregate_calls.argtypes = [PDB, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
     lib.mdb_database_aggregate_calls.restype = ctypes.c_int
     lib.query_column_data_device.argtypes = [PRS, c_int]
@@ -202,6 +204,11 @@ class DB:
         """IN / NOT IN lists of this database's statements so far that were compiled to one device lookup - lists of more than 8
         values (mdb_database_in_set_lookups)"""
         return int(self.lib.mdb_database_in_set_lookups(ctypes.byref(self.db)))
+
+    def subquery_sets(self):
+        """device sets this database's statements have built so far from the result column of an IN / NOT IN (SELECT ...) subquery - one
+        per subquery, nested ones included (mdb_database_subquery_sets); in_set_lookups() does not rise for them"""
+        return int(self.lib.mdb_database_subquery_sets(ctypes.byref(self.db)))
 
     def aggregate_calls(self):
         """(groups-in-LDS calls, sorted-segments calls): SELECT statements of this database so far whose SUM / MIN / MAX / AVG ran
