@@ -369,7 +369,7 @@ def main():
     def join_payload():
         l, r = dev.join_pairs(a_id, None, b_id, None)
         j = l.numel()
-        # the projection as the executor plans it (mdb_exec.c, projection pass 1): B's join key holds A's value in every joined
+        # the projection as the executor plans it (mdb_exec_result.c: locate_column, projection pass 1): B's join key holds A's value in every joined
         # tuple, so both key columns of SELECT * are ONE gather of A's column through the left row ids (ascending: near-sequential
         # reads); the payload columns are gathered through their own row ids; one launch
         # ... and when every left row found exactly one partner (last_plan()["pairs_identity"]: the primary-key join) the left row ids
@@ -381,7 +381,7 @@ def main():
     algo = 8 * 2 * n2 + 8 * 2 * n2 + 8 * 4 * j      # keys + payload columns read once, 4 result columns written
 
     def join_payload_carried():
-        # the executor's plan since round 4 (mdb_exec.c: join_with_payload): every left row has its one partner, so B's payload cell
+        # the executor's plan since round 4 (mdb_exec_join.c: join_with_payload): every left row has its one partner, so B's payload cell
         # travels through B's one partition level and lands at the left row's place - no partner row ids, no compaction, no random
         # gather; A's columns are read as they stand (copied: the result owns its columns), B's key column is A's
         out = dev.join_payload(a_id, None, b_id, None, [b_f])

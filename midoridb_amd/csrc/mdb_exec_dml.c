@@ -494,7 +494,7 @@ int mdb_exec_update(struct mdb_catalog *cat, struct mdb_dml *d, size_t *n_rows_a
 				goto out;
 			}
 		}
-		/* a device-resident result may hold the column as well (mdb_dev_retain, mdb_exec.c): it keeps the old cells, the table moves on */
+		/* a device-resident result may hold the column as well (mdb_dev_retain, mdb_exec_result.c): it keeps the old cells, the table moves on */
 		for (int pass = 0; pass < 2; pass++) {
 			void **slot = pass ? (void **)&col->d_nullbits : &col->d_data;
 			if (!*slot || !mdb_dev_holders(x.dev, *slot))

@@ -1,7 +1,9 @@
 /*
- * mdb_exec_internal.h - what the files of the executor share (mdb_exec.c: SELECT lowering; mdb_exec_resolve.c: plan normalisation and
- * the semantic checks; mdb_exec_pred.c: predicate programs; mdb_exec_shard.c: sharded mode; mdb_exec_tail.c: HAVING / DISTINCT /
- * ORDER BY / LIMIT; mdb_exec_dml.c: CREATE / INSERT / DELETE / UPDATE).  Nothing here is part of the library's interface.
+ * mdb_exec_internal.h - what the files of the executor share (mdb_exec.c: SELECT lowering - the driver, its plan stages, the stream
+ * helpers; mdb_exec_join.c: one more FROM table into the stream, composite join keys; mdb_exec_result.c: projection and result assembly;
+ * mdb_exec_resolve.c: plan normalisation and the semantic checks; mdb_exec_pred.c: predicate programs; mdb_exec_shard.c: sharded mode;
+ * mdb_exec_tail.c: HAVING / DISTINCT / ORDER BY / LIMIT; mdb_exec_dml.c: CREATE / INSERT / DELETE / UPDATE).  Nothing here is part of the
+ * library's interface.
  */
 #ifndef MDB_EXEC_INTERNAL_H
 #define MDB_EXEC_INTERNAL_H
@@ -22,6 +24,16 @@ struct dbuf_list {
 
 struct where_split;
 
+/* Which plan produced the tuple stream.  STREAM_ROWS: row-id vectors per FROM table (the general plan before it groups in any order, scan +
+ * WHERE + projection).  Every other: the stream is the key column(s) d_fused_key[s] and, but for STREAM_JOIN_KEYS, d_count - no row ids. */
+enum stream_plan {
+	STREAM_ROWS = 0,
+	STREAM_FUSED_CHAIN,	/* the single-key fused join + GROUP BY + COUNT(*) plan, chained over every FROM table (plan_fused_chain) */
+	STREAM_FUSED_COMPOSITE,	/* the same operator on a packed composite key (composite_fused_plan) */
+	STREAM_JOIN_KEYS,	/* the join of two key columns, nothing else selected (plan_keys_only) */
+	STREAM_GROUP_KEYS,	/* the general plan's GROUP BY on one field in its any-order keys form, sharded or not */
+};
+
 struct exec {
 	struct mdb_catalog *cat;
 	mdb_dev_ctx *dev;
@@ -33,7 +45,7 @@ struct exec {
 	bool have_stream;		/* false until the first table is in the stream */
 	uint64_t n;			/* stream length */
 	int64_t *d_count;		/* COUNT(*) column of the stream (after GROUP BY), device */
-	bool fused;			/* north-star plan: the stream is (d_fused_key, d_count), no row ids */
+	enum stream_plan plan;		/* which plan produced the stream (stream_is_keys: it is (d_fused_key, d_count), no row ids) */
 	int64_t *d_fused_key;
 	/* the fused plan on a packed composite key (composite_fused_plan): the stream carries nfused >= 2 key columns d_fused_keys[0 .. nfused)
 	 * (d_fused_key is the first of them) and a map from the fields of the ON equalities to them - both sides of an equality name the
@@ -77,6 +89,8 @@ struct exec {
 	int agg_calls[2];			/* mdb_dev_group_aggregate calls by form: [0] groups in LDS, [1] sorted segments */
 };
 
+static inline bool stream_is_keys(const struct exec *x) { return x->plan != STREAM_ROWS; }
+
 /* which of the statement's aggregates e (MDB_EX_AGG, resolved) is; -1: none */
 static inline int agg_index(const struct exec *x, const struct mdb_expr *e)
 {
@@ -101,6 +115,39 @@ struct where_split {
 	int npush[PUSH_TABS];
 	const struct mdb_expr *residual[64];
 	int nresidual;
+};
+
+/* The result column plan: every column the statement could return - COUNT(*) if selected, the aggregates, then every column of every FROM
+ * table left to right - named, put into the reference's order (R3), and of those the ones that are wanted (result_cols_build / _free) */
+struct result_cols {
+	char (*keys)[MDB_NAME_LEN];	/* candidate k's result column name */
+	int *order;			/* the candidates in the reference's order */
+	int *tbl, *col;			/* candidate k's source: tbl = FROM table and col = its column, or COLSRC_COUNT / COLSRC_AGG(a) */
+	int *src;			/* result column c is candidate src[c] */
+	int nkeys, ncols;
+	int has_count;			/* the select list names COUNT(*) */
+};
+#define COLSRC_COUNT (-1)
+#define COLSRC_AGG(a) (-2 - (a))
+/* which of the statement's aggregates a candidate's source is; -1: none (COUNT(*) or a table column) */
+static inline int colsrc_agg(int tbl) { return tbl <= -2 ? -2 - tbl : -1; }
+
+/* What one SELECT statement's stages share beside the stream (struct exec): the result column plan and the statement's shape, computed
+ * once (select_shape) */
+struct select_stmt {
+	struct result_cols rc;
+	struct where_split ws;
+	bool split_ok;			/* ws holds the WHERE clause's conjuncts (where_split) */
+	bool only_count;		/* SELECT COUNT(*) alone, no GROUP BY */
+	bool has_agg;			/* SUM / MIN / MAX / AVG in the select list */
+	bool fused_chain;		/* the single-key fused plan applies; fkeys[t] = table t's key field of the chain */
+	const struct mdb_expr *fkeys[MDB_MAX_TABS];
+	bool keys_only;			/* the keys-only plan applies; kj[0..1] = the two key fields */
+	const struct mdb_expr *kj[2];
+	int64_t *keys_ordered;		/* ... answered in the reference's order already (keys_only_ordered) */
+	uint64_t keys_ordered_rows;
+	void **direct_vals;		/* scan + WHERE + projection plan: the result columns on the device, final */
+	uint64_t **direct_nulls;
 };
 
 /* join types as the parser numbers them (mdb_sql.c: LEFT 2, RIGHT 4, FULL 6, + 6 with OUTER; the reference's grammar, midorisql.y:229-233) */
@@ -129,6 +176,7 @@ int resolve_subqueries(struct mdb_catalog *cat, struct mdb_expr *e, char *err, s
 int subqueries_eval(struct mdb_catalog *cat, struct mdb_expr *e, char *err, size_t errlen);
 void subqueries_release(struct mdb_catalog *cat, struct mdb_expr *e);
 int dev_fail(struct exec *x, const char *what);
+int dist_fail(struct exec *x, const char *what);
 int track(struct exec *x, void *p);
 void *dalloc(struct exec *x, size_t bytes);
 void free_all(struct exec *x);
@@ -163,10 +211,14 @@ int table_column(struct exec *x, int t, const struct mdb_expr *key, const uint32
 int fused_operand(struct exec *x, int t, const struct mdb_expr *key, const struct mdb_expr *const *conj, int nconj, const void **vals, const uint64_t **nulls, uint64_t *n);
 int join_with_payload(struct exec *x, int t, const struct mdb_expr *kr, const int64_t *vl, const uint64_t *nl, const void *vr, const uint64_t *nr, uint64_t r_rows);
 int join_next_table(struct exec *x, int t, const struct mdb_expr *const *pconj, int npconj);
+bool join_is_total_by_catalog(struct exec *x, const struct mdb_expr *kl, const struct mdb_expr *kr);
+bool only_key_needed(const struct exec *x, int t, int key_col);
+int composite_fused_plan(struct exec *x, const struct where_split *ws, bool only_count);
 int result_column_to_host(mdb_dev_ctx *dev, struct mdb_result *res, int c, const void *d_vals, const uint64_t *d_nulls);
+int project_result(struct exec *x, const struct select_stmt *st, struct mdb_result *res);
 double now_ms(void);
 int fused_chain(struct mdb_select *s, const struct mdb_expr **keys, bool count_only);
-bool keys_only_join(const struct mdb_select *s, const struct mdb_catalog *cat, int has_count, const int *key_tbl, const int *key_col, const int *src, int ncols, const struct mdb_expr **kj);
+bool keys_only_join(const struct mdb_select *s, const struct mdb_catalog *cat, const struct result_cols *rc, bool has_agg, const struct mdb_expr **kj);
 int select_tail(struct exec *x, int has_count);
 int dml_value_on_left(const struct mdb_expr *e);
 int dml_check_values(const struct mdb_expr *e, char *err, size_t errlen);

@@ -22,7 +22,7 @@ void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values,
 		*values = i >= 0 ? x->d_agg[i] : NULL;
 		*nullbits = i >= 0 ? x->d_agg_nulls[i] : NULL;
 		*rid = NULL;
-	} else if (x->fused) {
+	} else if (stream_is_keys(x)) {
 		*values = fused_key_column(x, f->tbl_idx, f->col_idx);
 		*nullbits = NULL;
 		*rid = NULL;

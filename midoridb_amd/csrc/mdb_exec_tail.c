@@ -70,7 +70,7 @@ int select_tail(struct exec *x, int has_count)
 				return dev_fail(x, "allocating the DISTINCT selection");
 			if (keys[0].rid) {
 				int64_t *v = dalloc(x, x->n * 8);
-				const bool want_nb = kn || (!x->fused && x->may_be_absent[tbl0]);	/* ("no row" cells are NULL cells) */
+				const bool want_nb = kn || (!stream_is_keys(x) && x->may_be_absent[tbl0]);	/* ("no row" cells are NULL cells) */
 				uint64_t *nb = want_nb ? dalloc(x, ((x->n + 63) / 64 + 1) * 8) : NULL;
 				if (!v || (want_nb && !nb) || mdb_dev_gather64(x->dev, kv, kn, keys[0].rid, x->n, v, nb))
 					return dev_fail(x, "gathering the DISTINCT column");

@@ -123,9 +123,9 @@ struct mdb_catalog {
 	uint64_t l2g_cap, g2l_cap;
 	int64_t *d_l2g, *d_g2l;
 	uint64_t d_l2g_n, d_g2l_n;	/* entries the device copies hold */
-	uint64_t joins_eliminated;	/* tables of SELECT statements that were not joined at all: the catalog said every row has exactly one partner (mdb_exec.c) */
-	uint64_t composite_joins;	/* joins of SELECT statements that ran on a packed composite key (mdb_exec.c, composite_join_keys) */
-	uint64_t composite_fused;	/* SELECT statements answered by the fused join + GROUP BY operator on a packed composite key (mdb_exec.c, composite_fused_plan) */
+	uint64_t joins_eliminated;	/* tables of SELECT statements that were not joined at all: the catalog said every row has exactly one partner (mdb_exec_join.c) */
+	uint64_t composite_joins;	/* joins of SELECT statements that ran on a packed composite key (mdb_exec_join.c, composite_join_pack) */
+	uint64_t composite_fused;	/* SELECT statements answered by the fused join + GROUP BY operator on a packed composite key (mdb_exec_join.c, composite_fused_plan) */
 	uint64_t aggregate_calls[2];	/* mdb_dev_group_aggregate calls of SELECT statements by form: [0] groups in LDS, [1] sorted segments (mdb_exec.c) */
 	uint64_t in_set_lookups;	/* IN / NOT IN lists compiled to one device lookup (mdb_exec_pred.c, pred_compile_in_lookup) */
 	uint64_t subquery_sets;		/* IN / NOT IN (SELECT ...): device sets built from a subquery's result column (mdb_exec.c, subqueries_eval) */

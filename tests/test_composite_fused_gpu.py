@@ -1,5 +1,5 @@
 """SELECT A.x, A.y, COUNT(*) FROM A JOIN B ON A.x = B.x AND A.y = B.y GROUP BY A.x, A.y  and  SELECT COUNT(*) over the same join through
-DB.query: the fused join + GROUP BY operator on the two tables' PACKED keys (mdb_exec.c: composite_fused_plan; mdb_dev_join_key_pack ->
+DB.query: the fused join + GROUP BY operator on the two tables' PACKED keys (mdb_exec_join.c: composite_fused_plan; mdb_dev_join_key_pack ->
 mdb_dev_join_group_count -> mdb_dev_join_key_unpack).
 
 Every served statement is compared, ORDER INCLUDED, with

@@ -1,5 +1,5 @@
 """ON l.x = r.x AND l.y = r.y [AND ...] through DB.query: the equalities whose columns fit 63 bits together are joined as ONE packed key
-(mdb_exec.c: composite_join_plan / composite_join_pack; mdb_dev_join_key_layout / mdb_dev_join_key_pack).
+(mdb_exec_join.c: composite_join_plan / composite_join_pack; mdb_dev_join_key_layout / mdb_dev_join_key_pack).
 
 Every statement is compared row for row, ORDER INCLUDED, with
   - the same statement under MDB_COMPOSITE_JOIN=0 - the join on the first equality with the others as filters over its pairs -, and
