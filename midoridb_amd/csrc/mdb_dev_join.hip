@@ -1310,11 +1310,6 @@ struct gc_state {
 
 /* one call of the operator as its entry points prepare it: the tables, where the result goes, and the plan so far - the part that
  * group_count_common's retry loop edits between attempts */
-struct gc_table {
-	const int64_t *keys;
-	const uint64_t *nulls;
-	uint64_t n;
-};
 struct gc_out {
 	int64_t *key, *count;
 	uint32_t *first;

@@ -255,6 +255,13 @@ static_assert(sizeof(gc_readback) == GC_RB_BYTES_DN && offsetof(gc_readback, fla
 		      offsetof(gc_readback, dn_exceptions) == 4 * GC_STW_DN_EXC && GC_RB_BYTES == 4 * GC_STW_SAMPLE,
 	      "gc_readback does not lie over the status words");
 
+/* one table of a join call: its key column, the column's NULL bits (or NULL) and its rows */
+struct gc_table {
+	const int64_t *keys;
+	const uint64_t *nulls;
+	uint64_t n;
+};
+
 struct gc_window {
 	uint32_t kbits;		/* 0 = no compact window */
 	int64_t lo;

@@ -427,14 +427,21 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_pairs_emit(pj_args a)
 	}
 }
 
+/* ------------------------------------------------------------------ what the host code of the pair and payload joins shares */
+
+/* the two tables of a call; the call with the sides swapped is pj_sides{ s.r, s.l } */
+struct pj_sides {
+	gc_table l, r;
+};
+
 /* the partition request of one table of a pair join: histogram-free layout unless the caller says otherwise */
-static mdb_part_request pj_request(const int64_t *keys, const uint64_t *nulls, uint64_t n, int b1, int b2)
+static mdb_part_request pj_request(const gc_table &t, int b1, int b2)
 {
 	mdb_part_request rq;
 	memset(&rq, 0, sizeof(rq));
-	rq.keys = keys;
-	rq.nullbits = nulls;
-	rq.n = n;
+	rq.keys = t.keys;
+	rq.nullbits = t.nulls;
+	rq.n = t.n;
 	rq.bits1 = b1;
 	rq.bits2 = b2;
 	rq.fast = true;
@@ -449,35 +456,132 @@ static void pj_compact(mdb_part_request *rq, int64_t lo, uint32_t kbits)
 	rq->narrow_kbits = kbits;
 }
 
+/* ... of the other table, everything else alike */
+static void pj_retarget(mdb_part_request *rq, const gc_table &t)
+{
+	rq->keys = t.keys;
+	rq->nullbits = t.nulls;
+	rq->n = t.n;
+}
+
+/* a form begins: its arena, and the first status_words status words cleared (16: the unique-key and payload forms, 8: the general join) */
+static int pj_begin(mdb_dev_ctx *ctx, size_t arena_bytes, uint32_t status_words)
+{
+	int rc = mdb_arena_begin(ctx, arena_bytes);
+	if (rc)
+		return rc;
+	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, status_words * sizeof(uint32_t), ctx->stream));
+	return MIDORIDB_OK;
+}
+
+/* `bytes` of the status words from word 0 on to the host, and wait: *rb lies over what came back */
+static int pj_read_status(mdb_dev_ctx *ctx, size_t bytes, const gc_readback **rb)
+{
+	uint64_t *h = ctx->h_pinned;
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, bytes, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	*rb = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS]);
+	return MIDORIDB_OK;
+}
+
+namespace {	/* (the owners' member functions stay out of the library's exported names) */
+
+/* a cached device allocation that goes back when its owner goes out of scope (MDB_LAUNCH, MDB_HIP and every other early return included) */
+struct pj_buffer {
+	mdb_dev_ctx *c;
+	void *p;
+	explicit pj_buffer(mdb_dev_ctx *ctx) : c(ctx), p(NULL) {}
+	pj_buffer(const pj_buffer &) = delete;
+	pj_buffer &operator=(const pj_buffer &) = delete;
+	~pj_buffer() { drop(); }
+	void drop()
+	{
+		if (p)
+			(void)mdb_cached_free(c, p);
+		p = NULL;
+	}
+	bool alloc(size_t bytes)
+	{
+		drop();
+		return mdb_cached_alloc(c, bytes, &p) == 0;
+	}
+};
+
+/* the result of a pair join: `count` pairs in two arrays of row ids, the caller's once released */
+struct pj_pairs {
+	pj_buffer bl, br;
+	uint64_t count;
+	explicit pj_pairs(mdb_dev_ctx *ctx) : bl(ctx), br(ctx), count(0) {}
+	uint32_t *l() const { return (uint32_t *)bl.p; }
+	uint32_t *r() const { return (uint32_t *)br.p; }
+	int alloc(uint64_t J)
+	{
+		if (!bl.alloc(J * 4) || !br.alloc(J * 4))
+			return mdb_set_err(bl.c, -MIDORIDB_NOMEM, "cannot allocate %llu join pairs", (unsigned long long)J);
+		return MIDORIDB_OK;
+	}
+	void drop()
+	{
+		bl.drop();
+		br.drop();
+	}
+	void release(uint32_t **out_l, uint32_t **out_r)
+	{
+		*out_l = l();
+		*out_r = r();
+		bl.p = br.p = NULL;
+	}
+};
+
+}	/* namespace */
+
+/* two partitioned tables into a leaf kernel's arguments: the fields every leaf's struct has ... */
+template <typename A>
+static void pj_fill_sides(A *a, const mdb_part_result &pl, const mdb_part_result &pr)
+{
+	a->hv_l = pl.hv;
+	a->cnt_l = pl.leaf_cnt;
+	a->cap_l = pl.leaf_cap;
+	a->hv_r = pr.hv;
+	a->cnt_r = pr.leaf_cnt;
+	a->cap_r = pr.leaf_cap;
+	a->nleaves = pl.nleaves;
+}
+
+/* ... and the row-id arrays and exact offsets of the two-level layouts (pu_args, pj_args) */
+template <typename A>
+static void pj_fill_rid_off(A *a, const mdb_part_result &pl, const mdb_part_result &pr)
+{
+	a->rid_l = pl.rid;
+	a->off_l = pl.leaf_off;
+	a->rid_r = pr.rid;
+	a->off_r = pr.leaf_off;
+}
+
 /* 0 = done, 1 = not applicable (overflow: use the general path), 2 = a key outside the window met the narrow form (call
  * again with narrow = false), 3 = a right key occurs more than once (not a unique-key join this way round), < 0 = error */
-static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-			     const uint64_t *null_r, uint64_t n_r, bool narrow, int64_t base, uint32_t **out_l, uint32_t **out_r,
-			     uint64_t *out_count)
+static int join_pairs_unique(mdb_dev_ctx *ctx, const pj_sides &s, bool narrow, int64_t base, pj_pairs *out)
 {
+	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	int b1, b2, sb1 = 0, sb2 = 0;
 	uint32_t kbits = 0;
 	mdb_choose_bits(n_r, GC_TARGET, &b1, &b2);
 	if ((n_r >> (b1 + b2)) > (uint64_t)GC_SLOTS * 7 / 10 || !order_bits(n_l, &kbits, &sb1, &sb2))
 		return 1;
 	const uint64_t rec_cap = gc_rec_capacity(ctx, n_l);
-	size_t need = mdb_partition_arena_bytes(n_l, b1, b2, true, true) + mdb_partition_arena_bytes(n_r, b1, b2, true, true) +
-		      mdb_align_up(rec_cap * 8) + order_records_arena_bytes(rec_cap, n_l, kbits, sb1, sb2) + 4096;
-	int rc = mdb_arena_begin(ctx, need);
+	int rc = pj_begin(ctx, mdb_partition_arena_bytes(n_l, b1, b2, true, true) + mdb_partition_arena_bytes(n_r, b1, b2, true, true) +
+				       mdb_align_up(rec_cap * 8) + order_records_arena_bytes(rec_cap, n_l, kbits, sb1, sb2) + 4096, 16);
 	if (rc)
 		return rc;
-	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	mdb_part_result pl, pr;
-	mdb_part_request rq = pj_request(keys_r, null_r, n_r, b1, b2);
+	mdb_part_request rq = pj_request(s.r, b1, b2);
 	rq.want_rid = !narrow;
 	rq.narrow = narrow ? 1 : 0;
 	rq.narrow_base = base;
 	rc = mdb_partition_table(ctx, rq, &pr);
 	if (rc)
 		return rc;
-	rq.keys = keys_l;
-	rq.nullbits = null_l;
-	rq.n = n_l;
+	pj_retarget(&rq, s.l);
 	rc = mdb_partition_table(ctx, rq, &pl);
 	if (rc)
 		return rc;
@@ -485,23 +589,14 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
 	if (!rec)
 		return -MIDORIDB_INTERNAL;
 	pu_args a;
-	a.hv_l = pl.hv;
-	a.rid_l = pl.rid;
-	a.off_l = pl.leaf_off;
-	a.cnt_l = pl.leaf_cnt;
-	a.cap_l = pl.leaf_cap;
-	a.hv_r = pr.hv;
-	a.rid_r = pr.rid;
-	a.off_r = pr.leaf_off;
-	a.cnt_r = pr.leaf_cnt;
-	a.cap_r = pr.leaf_cap;
+	pj_fill_sides(&a, pl, pr);
+	pj_fill_rid_off(&a, pl, pr);
 	a.rec = rec;
 	a.rec_count = ctx->d_status + GC_STW_LIST_LEN;	/* (the list kernels share the fused operator's words) */
 	a.rec_valid = ctx->d_status + GC_STW_RECORDS;
 	a.rec_cap = (uint32_t)rec_cap;
 	a.kbits = kbits;
 	a.status = ctx->d_status;
-	a.nleaves = pl.nleaves;
 	{
 		const uint32_t resident = 2u * (uint32_t)ctx->num_cus;
 		const uint32_t grid = pl.nleaves < resident ? pl.nleaves : resident;
@@ -511,10 +606,9 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
 			MDB_LAUNCH(ctx, "leaf_pairs_unique", k_leaf_pairs_unique<false>, grid, GC_THREADS, a);
 		}
 	}
-	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const gc_readback *rb = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS]);
+	const gc_readback *rb;
+	if ((rc = pj_read_status(ctx, GC_RB_BYTES, &rb)))
+		return rc;
 	const uint32_t status = rb->flags;
 	const uint64_t list_len = rb->list_len, J = rb->groups;
 	if (status & MDB_ST_KEY_OUTSIDE)
@@ -523,24 +617,12 @@ static int join_pairs_unique(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint
 		return 3;	/* a right key occurs more than once */
 	if (status & (PJ_ST_TABLE_FULL | MDB_ST_REGION_FULL | MDB_ST_LIST_FULL))
 		return 1;
-	*out_count = J;
+	out->count = J;
 	if (J == 0)
 		return 0;
-	uint32_t *ol = NULL, *orr = NULL;
-	if (mdb_cached_alloc(ctx, J * 4, (void **)&ol) || mdb_cached_alloc(ctx, J * 4, (void **)&orr)) {
-		if (ol)
-			(void)mdb_cached_free(ctx, ol);
-		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "cannot allocate %llu join pairs", (unsigned long long)J);
-	}
-	rc = order_records(ctx, rec, list_len, n_l, kbits, sb1, sb2, ol, NULL, orr, NULL, NULL);
-	if (rc) {
-		(void)mdb_cached_free(ctx, ol);
-		(void)mdb_cached_free(ctx, orr);
+	if ((rc = out->alloc(J)))
 		return rc;
-	}
-	*out_l = ol;
-	*out_r = orr;
-	return 0;
+	return order_records(ctx, rec, list_len, n_l, kbits, sb1, sb2, out->l(), NULL, out->r(), NULL, NULL);
 }
 
 /* ------------------------------------------------------------------ unique right keys in a window of at most 2^24 values: ONE level
@@ -753,29 +835,24 @@ __global__ __launch_bounds__(MC_THREADS) void k_match_emit(const uint32_t *__res
 
 /* 0 = done, 1 = not applicable (a first-level region overflowed), 2 = a key outside the window, 3 = a right key occurs more
  * than once, < 0 = error */
-static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-				  const uint64_t *null_r, uint64_t n_r, uint32_t kbits, int64_t lo, uint32_t **out_l, uint32_t **out_r,
-				  uint64_t *out_count)
+static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const pj_sides &s, uint32_t kbits, int64_t lo, pj_pairs *out)
 {
+	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	const int b1 = 9;
 	const uint32_t rem = kbits - (uint32_t)b1, shift = 32u - kbits;
 	const uint32_t nb = (uint32_t)((n_l + MC_BLOCK - 1) / MC_BLOCK);
-	const size_t need = mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1) + mdb_align_up(n_l * 4) +
-			    mdb_align_up(((size_t)nb + 2) * 4) + mdb_align_up(mdb_scan_scratch_words((uint64_t)nb + 1) * 4) + 8192;
-	int rc = mdb_arena_begin(ctx, need);
+	int rc = pj_begin(ctx, mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1) + mdb_align_up(n_l * 4) +
+				       mdb_align_up(((size_t)nb + 2) * 4) + mdb_align_up(mdb_scan_scratch_words((uint64_t)nb + 1) * 4) + 8192, 16);
 	if (rc)
 		return rc;
-	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	mdb_part_result pl, pr;
-	mdb_part_request rq = pj_request(keys_r, null_r, n_r, b1, 0);
+	mdb_part_request rq = pj_request(s.r, b1, 0);
 	pj_compact(&rq, lo, kbits);
 	rq.level0_only = true;
 	rc = mdb_partition_table(ctx, rq, &pr);
 	if (rc)
 		return rc;
-	rq.keys = keys_l;
-	rq.nullbits = null_l;
-	rq.n = n_l;
+	pj_retarget(&rq, s.l);
 	rc = mdb_partition_table(ctx, rq, &pl);
 	if (rc)
 		return rc;
@@ -788,13 +865,7 @@ static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "one-level unique-key join: the tables are not in the first-level layout");
 	MDB_HIP(ctx, hipMemsetAsync(match, 0, n_l * 4, ctx->stream));
 	pw_args a;
-	a.hv_l = pl.hv;
-	a.hv_r = pr.hv;
-	a.cnt_l = pl.leaf_cnt;
-	a.cnt_r = pr.leaf_cnt;
-	a.cap_l = pl.leaf_cap;
-	a.cap_r = pr.leaf_cap;
-	a.nleaves = pl.nleaves;
+	pj_fill_sides(&a, pl, pr);
 	a.nsub = pl.nsub;
 	a.match = match;
 	a.n_l = (uint32_t)n_l;
@@ -809,30 +880,24 @@ static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	rc = mdb_scan_u32_inplace(ctx, blk, (uint64_t)nb + 1, blk_tmp);
 	if (rc)
 		return rc;
-	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
-	const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
+	const gc_readback *rb;
+	if ((rc = pj_read_status(ctx, GC_RB_BYTES, &rb)))
+		return rc;
+	const uint32_t status = rb->flags;
+	const uint64_t J = rb->joined;
 	if (status & MDB_ST_KEY_OUTSIDE)
 		return 2;
 	if (status & PJ_ST_DUP_RIGHT)
 		return 3;
 	if (status & MDB_ST_REGION_FULL)
 		return 1;
-	*out_count = J;
+	out->count = J;
 	if (J == 0)
 		return 0;
-	uint32_t *ol = NULL, *orr = NULL;
-	if (mdb_cached_alloc(ctx, J * 4, (void **)&ol) || mdb_cached_alloc(ctx, J * 4, (void **)&orr)) {
-		if (ol)
-			(void)mdb_cached_free(ctx, ol);
-		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "cannot allocate %llu join pairs", (unsigned long long)J);
-	}
-	MDB_LAUNCH(ctx, "match_emit", k_match_emit, nb, MC_THREADS, match, (uint32_t)n_l, blk, ol, orr);
+	if ((rc = out->alloc(J)))
+		return rc;
+	MDB_LAUNCH(ctx, "match_emit", k_match_emit, nb, MC_THREADS, match, (uint32_t)n_l, blk, out->l(), out->r());
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	*out_l = ol;
-	*out_r = orr;
 	return 0;
 }
 
@@ -1083,6 +1148,227 @@ __global__ __launch_bounds__(PL_THREADS) void k_leaf_pairs_cell2(pl_args a, uint
 	}
 }
 
+/* ---- mdb_dev_join_payload: guess a key window, run the form it selects, judge what the form found - at most twice */
+
+/* one call: the tables, the right table's carried columns and where the joined rows' cells go */
+struct pay_call {
+	pj_sides s;
+	const void *const *pay_in;
+	void *const *out;
+	int npay;
+};
+
+/* the form a key window selects (payload_applies) */
+struct pay_form {
+	uint32_t form;		/* 3 row order, 2 two levels, 1 one level: mdb_dev_plan_info.payload_form */
+	uint32_t kbits;		/* key bits the form runs with */
+	uint32_t levels;
+	uint64_t expect_j;	/* what the form counts when every left row has found its partner */
+	bool region_full_excused;	/* a region overflow says nothing about the join: not noted against the columns */
+};
+
+/* what a form answers: the status flags and its count; the arena it needs (all that an explained call asks for) */
+struct pay_answer {
+	uint32_t status;
+	uint64_t J;
+	size_t arena;
+};
+
+/* which form a window of 2^win.kbits values and the tables' sizes select; false: none, the call is not served */
+static bool payload_applies(const pay_call &c, const gc_window &win, pay_form *f)
+{
+	const uint64_t n_l = c.s.l.n, n_r = c.s.r.n;
+	/* ---- round 5: both tables sorted tile by tile, the cells placed in the left table's row order without one scattered store per joined
+	 * row (mdb_dev_rowjoin.hip): windows of up to 2^27 values, NULL-free 16-byte-aligned columns */
+	if (mdb_rowjoin_serves(n_l, n_r, win.kbits, c.s.l.keys, c.s.l.nulls, c.s.r.keys, c.s.r.nulls, c.pay_in, c.out, c.npay)) {
+		*f = { 3, win.kbits, 1, (uint64_t)c.npay * n_l, false };
+		return true;
+	}
+	if (win.kbits > 9u + PW_MAX_REM) {
+		/* ---- windows of 2^25 ... 2^30 values: two levels, leaves of 2^12 values */
+		if (win.kbits > 30u)
+			return false;
+		const int b2 = (int)win.kbits - 9 - (int)PL_MAX_REM;
+		if (b2 < 1 || b2 > MDB_MAX_RADIX_BITS || n_l >= 0xF0000000ull || n_r >= 0xF0000000ull)
+			return false;
+		*f = { 2, win.kbits, 2, n_l, true };
+		return true;
+	}
+	/* ---- one level (a dimension table of a few thousand keys: the window may be wider than its keys need) */
+	*f = { 1, win.kbits < 9u + PW_MIN_REM ? 9u + PW_MIN_REM : win.kbits, 1, n_l, false };
+	return true;
+}
+
+/* both tables of a payload form partitioned in the compact narrow form, the right table's cells beside its words (the right table first) */
+static int payload_partition(mdb_dev_ctx *ctx, const pay_call &c, const gc_window &win, uint32_t kbits, int b1, int b2, mdb_part_result *pl,
+			     mdb_part_result *pr)
+{
+	memset(pl, 0, sizeof(*pl));
+	memset(pr, 0, sizeof(*pr));
+	mdb_part_request lrq = pj_request(c.s.l, b1, b2), rrq = pj_request(c.s.r, b1, b2);
+	pj_compact(&lrq, win.lo, kbits);
+	pj_compact(&rrq, win.lo, kbits);
+	lrq.level0_only = rrq.level0_only = b2 == 0;
+	rrq.npay = c.npay;
+	for (int k = 0; k < c.npay; k++)
+		rrq.pay_in[k] = c.pay_in[k];
+	int rc = mdb_partition_table(ctx, rrq, pr);
+	if (rc)
+		return rc;
+	return mdb_partition_table(ctx, lrq, pl);
+}
+
+/* ... and into the leaf's arguments (pp_args, pl_args) */
+template <typename A>
+static void payload_fill(mdb_dev_ctx *ctx, A *a, const pay_call &c, const mdb_part_result &pl, const mdb_part_result &pr)
+{
+	memset(a, 0, sizeof(*a));
+	pj_fill_sides(a, pl, pr);
+	a->npay = (uint32_t)c.npay;
+	for (int k = 0; k < c.npay; k++) {
+		a->pay_r[k] = pr.pay[k];
+		a->out[k] = reinterpret_cast<uint64_t *>(c.out[k]);
+	}
+	a->n_l = (uint32_t)c.s.l.n;
+	a->joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
+	a->status = ctx->d_status;
+}
+
+/* the form's status flags and count to the host */
+static int payload_read(mdb_dev_ctx *ctx, pay_answer *ans)
+{
+	const gc_readback *rb;
+	int rc = pj_read_status(ctx, GC_RB_BYTES, &rb);
+	if (rc)
+		return rc;
+	ans->status = rb->flags;
+	ans->J = rb->joined;
+	return MIDORIDB_OK;
+}
+
+static int payload_row_order(mdb_dev_ctx *ctx, const pay_call &c, const gc_window &win, const pay_form &f, pay_answer *ans)
+{
+	const uint64_t n_l = c.s.l.n, n_r = c.s.r.n;
+	ans->arena = mdb_rowjoin_arena_bytes(n_l, n_r, f.kbits, c.npay) + 8192;
+	if (ctx->explaining)
+		return MIDORIDB_OK;
+	int rc = pj_begin(ctx, ans->arena, 16);
+	if (rc)
+		return rc;
+	rc = mdb_rowjoin_run(ctx, c.s.l.keys, n_l, c.s.r.keys, n_r, c.pay_in, win.lo, f.kbits, c.npay, c.out);
+	if (rc)
+		return rc;
+	if ((rc = payload_read(ctx, ans)))
+		return rc;
+	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
+		fprintf(stderr, "join_payload (row order): k %u status %u J %llu of %llu left rows\n", f.kbits, ans->status, (unsigned long long)ans->J,
+			(unsigned long long)n_l);
+	return MIDORIDB_OK;
+}
+
+static int payload_two_levels(mdb_dev_ctx *ctx, const pay_call &c, const gc_window &win, const pay_form &f, pay_answer *ans)
+{
+	const uint64_t n_l = c.s.l.n, n_r = c.s.r.n;
+	const uint32_t kbits = f.kbits, shift = 32u - kbits;
+	const int b1 = 9, b2 = (int)kbits - 9 - (int)PL_MAX_REM;
+	const uint32_t rem = kbits - (uint32_t)(b1 + b2);
+	ans->arena = mdb_partition_arena_bytes(n_l, b1, b2, false, true) + mdb_partition_arena_bytes(n_r, b1, b2, false, true, c.npay) + 8192;
+	if (ctx->explaining)
+		return MIDORIDB_OK;
+	int rc = pj_begin(ctx, ans->arena, 16);
+	if (rc)
+		return rc;
+	mdb_part_result pl, pr;
+	if ((rc = payload_partition(ctx, c, win, kbits, b1, b2, &pl, &pr)))
+		return rc;
+	if (!pl.leaf_cap || !pr.leaf_cap || !pl.leaf_cnt || !pr.leaf_cnt || pl.nleaves != pr.nleaves || pl.w32 || pr.w32 || !pr.pay[0] ||
+	    (c.npay > 1 && !pr.pay[1]))
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: the tables are not in the two-level fixed-capacity layout");
+	pl_args a;
+	payload_fill(ctx, &a, c, pl, pr);
+	const uint32_t grid = pl.nleaves < 8u * (uint32_t)ctx->num_cus ? pl.nleaves : 8u * (uint32_t)ctx->num_cus;
+	if (c.npay > 1) {
+		MDB_LAUNCH(ctx, "leaf_pairs_payload", k_leaf_pairs_cell2<2>, grid, PL_THREADS, a, rem, shift);
+	} else {
+		MDB_LAUNCH(ctx, "leaf_pairs_payload", k_leaf_pairs_cell2<1>, grid, PL_THREADS, a, rem, shift);
+	}
+	if ((rc = payload_read(ctx, ans)))
+		return rc;
+	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
+		fprintf(stderr, "join_payload (two levels): k %u b2 %d rem %u status %u J %llu of %llu left rows\n", kbits, b2, rem, ans->status,
+			(unsigned long long)ans->J, (unsigned long long)n_l);
+	return MIDORIDB_OK;
+}
+
+static int payload_one_level(mdb_dev_ctx *ctx, const pay_call &c, const gc_window &win, const pay_form &f, pay_answer *ans)
+{
+	const uint64_t n_l = c.s.l.n, n_r = c.s.r.n;
+	const int b1 = 9;
+	const uint32_t kbits = f.kbits, rem = kbits - (uint32_t)b1, shift = 32u - kbits;
+	ans->arena = mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1, false, c.npay) + 8192;
+	if (ctx->explaining)
+		return MIDORIDB_OK;
+	int rc = pj_begin(ctx, ans->arena, 16);
+	if (rc)
+		return rc;
+	mdb_part_result pl, pr;
+	if ((rc = payload_partition(ctx, c, win, kbits, b1, 0, &pl, &pr)))
+		return rc;
+	if (!pl.nsub || pl.nsub != pr.nsub || pl.nleaves != pr.nleaves || pl.w32 || pr.w32 || !pr.pay[0] || (c.npay > 1 && !pr.pay[1]))
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: the tables are not in the first-level layout");
+	pp_args a;
+	payload_fill(ctx, &a, c, pl, pr);
+	a.nsub = pl.nsub;
+	if (pl.nsub > PP_MAX_SUB)
+		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: %u sub-regions per digit", pl.nsub);
+	/* the cells IN the leaf's LDS table: one scattered access per joined row.  Two carried columns: the kernel once per column
+	 * (round 5: 0.51 -> 2 x 0.22 ms at 10^7 rows - the region-lookup leaf paid two scattered accesses per row and cell pair); the second
+	 * launch counts its pairs into a word nobody reads */
+	const uint32_t lowbits = rem < PC_SLOT_BITS ? rem : PC_SLOT_BITS;
+	const size_t lds = ((size_t)8 << lowbits) + ((size_t)1 << lowbits) / 8 + 64;
+	MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leaf_pairs_cell), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	for (int k = 0; k < c.npay; k++) {
+		pp_args ac = a;
+		ac.pay_r[0] = a.pay_r[k];
+		ac.out[0] = a.out[k];
+		ac.npay = 1;
+		if (k)
+			ac.joined = (unsigned long long *)(ctx->d_status + GC_STW_NULL_STATS + 2)	/* (a word nobody reads) */;
+		MDB_LAUNCH_LDS(ctx, "leaf_pairs_payload", k_leaf_pairs_cell, pl.nleaves, PW_THREADS, lds, ac, rem, shift);
+	}
+	if ((rc = payload_read(ctx, ans)))
+		return rc;
+	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
+		fprintf(stderr, "join_payload (one level): k %u rem %u status %u J %llu of %llu left rows\n", kbits, rem, ans->status,
+			(unsigned long long)ans->J, (unsigned long long)n_l);
+	return MIDORIDB_OK;
+}
+
+/* What a form's answer means for the call.  By status bit, first match wins - the same for the three forms but for the last line:
+ *   none, and J as expected            served
+ *   MDB_ST_KEY_OUTSIDE, may_retry      a REMEMBERED window proved wrong: the buffers hold other data than when it was learned (a caller's
+ *                                      allocator handed the same addresses out again) - forget, look at the data itself, once more
+ *   MDB_ST_KEY_OUTSIDE                 a key outside the window after all: the sample is not trusted for a while; not served
+ *   MDB_ST_REGION_FULL, excused        not served, nothing noted (the two-level form alone: f.region_full_excused)
+ *   anything else (J short included)   not such a join: noted against the columns (VD_JP_BAD), not tried again for a while; not served */
+enum pay_verdict { PAY_SERVED, PAY_RETRY, PAY_NOT_SERVED };
+
+static pay_verdict payload_verdict(mdb_dev_ctx *ctx, const pj_sides &s, const pay_answer &ans, uint64_t expect_j, bool region_full_excused,
+				   bool may_retry)
+{
+	if (ans.status == 0 && ans.J == expect_j)
+		return PAY_SERVED;
+	if ((ans.status & MDB_ST_KEY_OUTSIDE) && may_retry) {
+		ctx->forget_guess();
+		return PAY_RETRY;
+	}
+	if (ans.status & MDB_ST_KEY_OUTSIDE)
+		ctx->nh_distrust = 8;
+	else if (!(region_full_excused && (ans.status & MDB_ST_REGION_FULL)))
+		ctx->vd[VD_JP_BAD].note(s.l.keys, s.l.n, s.r.keys, s.r.n);
+	return PAY_NOT_SERVED;
+}
+
 /* 0 = done: every one of the n_l left rows has its partner and out[c][i] = payload cell c of left row i's partner;
  * 1 = not served (some left row without a partner - NULL keys included -, duplicate right keys, no compact window of at most 2^24
  * values, a region overflow ...: mdb_dev_join_pairs answers); < 0 = error.  Synchronises. */
@@ -1095,229 +1381,50 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	for (int c = 0; c < npay; c++)
 		if (!pay_in[c] || !out[c])
 			return -MIDORIDB_ERROR;
-	auto served = [&](uint32_t form, uint32_t kbits, uint32_t levels) {	/* the form that answered, in the plan record */
-		ctx->plan.payload_form = form;
-		ctx->plan.payload_tables = 1;
-		ctx->plan.key_form = 2;
-		ctx->plan.key_bits = kbits;
-		ctx->plan.levels = levels;
-		ctx->plan.digits = 512;
-		return MIDORIDB_OK;
-	};
-	auto explained = [&](uint32_t form, uint32_t kbits, uint32_t levels, size_t arena) {	/* (mdb_dev_explain_join_payload: nothing is launched) */
-		mdb_explain_sampled(ctx);
-		ctx->plan.arena_mib = (uint32_t)((arena + (1u << 20) - 1) >> 20);
-		return served(form, kbits, levels);
-	};
 	if (n_l == 0 || n_r == 0 || n_l >= 0xFFFFFFFFull || n_r >= 0xFFFFFFFFull || n_l + n_r < (1ull << 20) || ld_disabled() ||
 	    mdb_knob_off("MDB_JOIN_PAYLOAD"))
 		return 1;
+	const pay_call call = { { { keys_l, null_l, n_l }, { keys_r, null_r, n_r } }, pay_in, out, npay };
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
 	if (ctx->vd[VD_JP_BAD].serve(keys_l, n_l, keys_r, n_r, MDB_HINT_SERVES))
 		return 1;	/* (these columns were not such a join last time: not tried again for a while) */
 	for (int attempt = 0; attempt < 2; attempt++) {
-	bool narrow = false;
-	int64_t base = 0;
-	gc_window win = { 0, 0, false, false, false, false };
-	int rc = gc_narrow_guess(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &narrow, &base, &win);
-	if (rc)
-		return rc;
-	const bool remembered = ctx->guess_remembered;
-	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
-		fprintf(stderr, "join_payload: narrow %d window 2^%u at %lld (attempt %d, remembered %d)\n", (int)narrow, win.kbits, (long long)win.lo, attempt, (int)remembered);
-	if (!narrow || !win.kbits)
-		return 1;
-	/* ---- round 5: both tables sorted tile by tile, the cells placed in the left table's row order without one scattered store per joined
-	 * row (mdb_dev_rowjoin.hip): windows of up to 2^27 values, NULL-free 16-byte-aligned columns */
-	if (mdb_rowjoin_serves(n_l, n_r, win.kbits, keys_l, null_l, keys_r, null_r, pay_in, out, npay)) {
-		const uint32_t kbits = win.kbits;
-		if (ctx->explaining)
-			return explained(3, kbits, 1, mdb_rowjoin_arena_bytes(n_l, n_r, kbits, npay) + 8192);
-		rc = mdb_arena_begin(ctx, mdb_rowjoin_arena_bytes(n_l, n_r, kbits, npay) + 8192);
+		bool narrow = false;
+		int64_t base = 0;
+		gc_window win = { 0, 0, false, false, false, false };
+		int rc = gc_narrow_guess(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &narrow, &base, &win);
 		if (rc)
 			return rc;
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
-		rc = mdb_rowjoin_run(ctx, keys_l, n_l, keys_r, n_r, pay_in, win.lo, kbits, npay, out);
-		if (rc)
-			return rc;
-		uint64_t *h = ctx->h_pinned;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
-		const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
+		const bool remembered = ctx->guess_remembered;
 		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
-			fprintf(stderr, "join_payload (row order): k %u status %u J %llu of %llu left rows\n", kbits, status, (unsigned long long)J,
-				(unsigned long long)n_l);
-		if (status == 0 && J == (uint64_t)npay * n_l)
-			return served(3, kbits, 1);
-		if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
-			ctx->forget_guess();
-			continue;
-		}
-		if (status & MDB_ST_KEY_OUTSIDE)
-			ctx->nh_distrust = 8;
-		else
-			ctx->vd[VD_JP_BAD].note(keys_l, n_l, keys_r, n_r);
-		return 1;
-	}
-	if (win.kbits > 9u + PW_MAX_REM) {
-		/* ---- windows of 2^25 ... 2^30 values: two levels, leaves of 2^12 values */
-		if (win.kbits > 30u)
+			fprintf(stderr, "join_payload: narrow %d window 2^%u at %lld (attempt %d, remembered %d)\n", (int)narrow, win.kbits, (long long)win.lo,
+				attempt, (int)remembered);
+		pay_form f;
+		if (!narrow || !win.kbits || !payload_applies(call, win, &f))
 			return 1;
-		const uint32_t kbits = win.kbits, shift = 32u - kbits;
-		const int b1 = 9, b2 = (int)kbits - 9 - (int)PL_MAX_REM;
-		const uint32_t rem = kbits - (uint32_t)(b1 + b2);
-		if (b2 < 1 || b2 > MDB_MAX_RADIX_BITS || n_l >= 0xF0000000ull || n_r >= 0xF0000000ull)
-			return 1;
-		if (ctx->explaining)
-			return explained(2, kbits, 2, mdb_partition_arena_bytes(n_l, b1, b2, false, true) + mdb_partition_arena_bytes(n_r, b1, b2, false, true, npay) + 8192);
-		rc = mdb_arena_begin(ctx, mdb_partition_arena_bytes(n_l, b1, b2, false, true) + mdb_partition_arena_bytes(n_r, b1, b2, false, true, npay) + 8192);
+		pay_answer ans = { 0, 0, 0 };
+		rc = f.form == 3 ? payload_row_order(ctx, call, win, f, &ans) :
+		     f.form == 2 ? payload_two_levels(ctx, call, win, f, &ans) : payload_one_level(ctx, call, win, f, &ans);
 		if (rc)
 			return rc;
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
-		mdb_part_result pl, pr;
-		memset(&pl, 0, sizeof(pl));
-		memset(&pr, 0, sizeof(pr));
-		mdb_part_request lrq = pj_request(keys_l, null_l, n_l, b1, b2), rrq = pj_request(keys_r, null_r, n_r, b1, b2);
-		pj_compact(&lrq, win.lo, kbits);
-		pj_compact(&rrq, win.lo, kbits);
-		rrq.npay = npay;
-		for (int c = 0; c < npay; c++)
-			rrq.pay_in[c] = pay_in[c];
-		rc = mdb_partition_table(ctx, rrq, &pr);
-		if (rc)
-			return rc;
-		rc = mdb_partition_table(ctx, lrq, &pl);
-		if (rc)
-			return rc;
-		if (!pl.leaf_cap || !pr.leaf_cap || !pl.leaf_cnt || !pr.leaf_cnt || pl.nleaves != pr.nleaves || pl.w32 || pr.w32 || !pr.pay[0] ||
-		    (npay > 1 && !pr.pay[1]))
-			return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: the tables are not in the two-level fixed-capacity layout");
-		pl_args a;
-		memset(&a, 0, sizeof(a));
-		a.hv_l = pl.hv;
-		a.hv_r = pr.hv;
-		a.npay = (uint32_t)npay;
-		for (int c = 0; c < npay; c++) {
-			a.pay_r[c] = pr.pay[c];
-			a.out[c] = reinterpret_cast<uint64_t *>(out[c]);
-		}
-		a.cnt_l = pl.leaf_cnt;
-		a.cnt_r = pr.leaf_cnt;
-		a.cap_l = pl.leaf_cap;
-		a.cap_r = pr.leaf_cap;
-		a.nleaves = pl.nleaves;
-		a.n_l = (uint32_t)n_l;
-		a.joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
-		a.status = ctx->d_status;
-		const uint32_t grid = pl.nleaves < 8u * (uint32_t)ctx->num_cus ? pl.nleaves : 8u * (uint32_t)ctx->num_cus;
-		if (npay > 1) {
-			MDB_LAUNCH(ctx, "leaf_pairs_payload", k_leaf_pairs_cell2<2>, grid, PL_THREADS, a, rem, shift);
+		if (ctx->explaining) {	/* (mdb_dev_explain_join_payload: nothing was launched) */
+			mdb_explain_sampled(ctx);
+			ctx->plan.arena_mib = (uint32_t)((ans.arena + (1u << 20) - 1) >> 20);
 		} else {
-			MDB_LAUNCH(ctx, "leaf_pairs_payload", k_leaf_pairs_cell2<1>, grid, PL_THREADS, a, rem, shift);
+			const pay_verdict v = payload_verdict(ctx, call.s, ans, f.expect_j, f.region_full_excused, remembered && attempt == 0);
+			if (v == PAY_RETRY)
+				continue;
+			if (v == PAY_NOT_SERVED)
+				return 1;
 		}
-		uint64_t *h = ctx->h_pinned;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
-		const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
-		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
-			fprintf(stderr, "join_payload (two levels): k %u b2 %d rem %u status %u J %llu of %llu left rows\n", kbits, b2, rem, status, (unsigned long long)J,
-				(unsigned long long)n_l);
-		if (status == 0 && J == n_l)
-			return served(2, kbits, 2);
-		if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
-			ctx->forget_guess();
-			continue;
-		}
-		if (status & MDB_ST_KEY_OUTSIDE)
-			ctx->nh_distrust = 8;
-		else if (!(status & MDB_ST_REGION_FULL))	/* (a region overflow says nothing about the join) */
-			ctx->vd[VD_JP_BAD].note(keys_l, n_l, keys_r, n_r);
-		return 1;
-	}
-	const int b1 = 9;
-	/* (a dimension table of a few thousand keys: the window may be wider than its keys need) */
-	const uint32_t kbits = win.kbits < 9u + PW_MIN_REM ? 9u + PW_MIN_REM : win.kbits, rem = kbits - (uint32_t)b1, shift = 32u - kbits;
-	if (ctx->explaining)
-		return explained(1, kbits, 1, mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1, false, npay) + 8192);
-	rc = mdb_arena_begin(ctx, mdb_partition_level0_arena_bytes(n_l, b1) + mdb_partition_level0_arena_bytes(n_r, b1, false, npay) + 8192);
-	if (rc)
-		return rc;
-	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
-	mdb_part_result pl, pr;
-	memset(&pl, 0, sizeof(pl));
-	memset(&pr, 0, sizeof(pr));
-	mdb_part_request lrq = pj_request(keys_l, null_l, n_l, b1, 0), rrq = pj_request(keys_r, null_r, n_r, b1, 0);
-	pj_compact(&lrq, win.lo, kbits);
-	pj_compact(&rrq, win.lo, kbits);
-	lrq.level0_only = rrq.level0_only = true;
-	rrq.npay = npay;
-	for (int c = 0; c < npay; c++)
-		rrq.pay_in[c] = pay_in[c];
-	rc = mdb_partition_table(ctx, rrq, &pr);
-	if (rc)
-		return rc;
-	rc = mdb_partition_table(ctx, lrq, &pl);
-	if (rc)
-		return rc;
-	if (!pl.nsub || pl.nsub != pr.nsub || pl.nleaves != pr.nleaves || pl.w32 || pr.w32 || !pr.pay[0] || (npay > 1 && !pr.pay[1]))
-		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: the tables are not in the first-level layout");
-	pp_args a;
-	memset(&a, 0, sizeof(a));
-	a.hv_l = pl.hv;
-	a.hv_r = pr.hv;
-	a.npay = (uint32_t)npay;
-	for (int c = 0; c < npay; c++) {
-		a.pay_r[c] = pr.pay[c];
-		a.out[c] = reinterpret_cast<uint64_t *>(out[c]);
-	}
-	a.cnt_l = pl.leaf_cnt;
-	a.cnt_r = pr.leaf_cnt;
-	a.cap_l = pl.leaf_cap;
-	a.cap_r = pr.leaf_cap;
-	a.nleaves = pl.nleaves;
-	a.nsub = pl.nsub;
-	a.n_l = (uint32_t)n_l;
-	a.joined = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
-	a.status = ctx->d_status;
-	if (pl.nsub > PP_MAX_SUB)
-		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "join with payload: %u sub-regions per digit", pl.nsub);
-	{
-		/* the cells IN the leaf's LDS table: one scattered access per joined row.  Two carried columns: the kernel once per column
-		 * (round 5: 0.51 -> 2 x 0.22 ms at 10^7 rows - the region-lookup leaf paid two scattered accesses per row and cell pair); the second
-		 * launch counts its pairs into a word nobody reads */
-		const uint32_t lowbits = rem < PC_SLOT_BITS ? rem : PC_SLOT_BITS;
-		const size_t lds = ((size_t)8 << lowbits) + ((size_t)1 << lowbits) / 8 + 64;
-		MDB_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leaf_pairs_cell), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		for (int c = 0; c < npay; c++) {
-			pp_args ac = a;
-			ac.pay_r[0] = a.pay_r[c];
-			ac.out[0] = a.out[c];
-			ac.npay = 1;
-			if (c)
-				ac.joined = (unsigned long long *)(ctx->d_status + GC_STW_NULL_STATS + 2)	/* (a word nobody reads) */;
-			MDB_LAUNCH_LDS(ctx, "leaf_pairs_payload", k_leaf_pairs_cell, pl.nleaves, PW_THREADS, lds, ac, rem, shift);
-		}
-	}
-	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
-	const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
-	if (status == 0 && J == n_l)
-		return served(1, kbits, 1);
-	if ((status & MDB_ST_KEY_OUTSIDE) && remembered && attempt == 0) {
-		/* a REMEMBERED window proved wrong: the buffers hold other data than when it was learned (a caller's allocator handed the
-		 * same addresses out again) - forget, look at the data itself, once more */
-		ctx->forget_guess();
-		continue;
-	}
-	if (status & MDB_ST_KEY_OUTSIDE)	/* a key outside the window after all: the sample is not trusted for a while */
-		ctx->nh_distrust = 8;
-	else
-		ctx->vd[VD_JP_BAD].note(keys_l, n_l, keys_r, n_r);
-	return 1;
+		/* the form that answered, in the plan record */
+		ctx->plan.payload_form = f.form;
+		ctx->plan.payload_tables = 1;
+		ctx->plan.key_form = 2;
+		ctx->plan.key_bits = f.kbits;
+		ctx->plan.levels = f.levels;
+		ctx->plan.digits = 512;
+		return MIDORIDB_OK;
 	}
 	return 1;
 }
@@ -1381,18 +1488,17 @@ extern "C" int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_
 		ctx->plan.arena_mib = (uint32_t)((arena + (1u << 20) - 1) >> 20);
 		return served();
 	}
-	int rc = mdb_arena_begin(ctx, arena);
+	int rc = pj_begin(ctx, arena, 16);
 	if (rc)
 		return rc;
-	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 16 * sizeof(uint32_t), ctx->stream));
 	rc = mdb_rowjoin_run_multi(ctx, keys_l, n_l, rt, nright, key_min, kbits);
 	if (rc)
 		return rc;
-	uint64_t *h = ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, GC_RB_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
-	const uint64_t J = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
+	const gc_readback *rb;
+	if ((rc = pj_read_status(ctx, GC_RB_BYTES, &rb)))
+		return rc;
+	const uint32_t status = rb->flags;
+	const uint64_t J = rb->joined;
 	if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
 		fprintf(stderr, "join_payload_multi (row order): %d tables, %d columns, k %u status %u J %llu of %llu x %d\n", nright, streams, kbits, status,
 			(unsigned long long)J, (unsigned long long)n_l, streams);
@@ -1477,77 +1583,65 @@ __global__ __launch_bounds__(GC_THREADS) void k_tiny_join_pairs(tinyp_args a)
 }
 
 /* 0 = done, 1 = not applicable (too many rows or pairs), < 0 = error */
-static int tiny_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-			   const uint64_t *null_r, uint64_t n_r, uint32_t **out_l, uint32_t **out_r, uint64_t *out_count)
+static int tiny_join_pairs(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
 {
-	if (n_l > TINY_ROWS || n_r > TINY_ROWS)
+	if (s.l.n > TINY_ROWS || s.r.n > TINY_ROWS)
 		return 1;
-	const uint64_t worst = n_l * n_r;
+	const uint64_t worst = s.l.n * s.r.n;
 	const uint32_t cap = worst < TINY_PAIRS_CAP ? (uint32_t)worst : TINY_PAIRS_CAP;
-	uint32_t *ol = NULL, *orr = NULL;
-	if (mdb_cached_alloc(ctx, (size_t)cap * 4, (void **)&ol) || mdb_cached_alloc(ctx, (size_t)cap * 4, (void **)&orr)) {
-		if (ol)
-			(void)mdb_cached_free(ctx, ol);
-		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "cannot allocate %u join pairs", cap);
-	}
+	int rc = out->alloc(cap);
+	if (rc)
+		return rc;
 	tinyp_args a;
-	a.keys_l = keys_l;
-	a.null_l = null_l;
-	a.n_l = (uint32_t)n_l;
-	a.keys_r = keys_r;
-	a.null_r = null_r;
-	a.n_r = (uint32_t)n_r;
-	a.out_l = ol;
-	a.out_r = orr;
+	a.keys_l = s.l.keys;
+	a.null_l = s.l.nulls;
+	a.n_l = (uint32_t)s.l.n;
+	a.keys_r = s.r.keys;
+	a.null_r = s.r.nulls;
+	a.n_r = (uint32_t)s.r.n;
+	a.out_l = out->l();
+	a.out_r = out->r();
 	a.cap = cap;
 	a.status = ctx->d_status;
-	mdb_prof_begin(ctx, "tiny_join_pairs", (const void *)k_tiny_join_pairs);	/* (not MDB_LAUNCH: an error has two buffers to give back) */
-	hipLaunchKernelGGL(k_tiny_join_pairs, dim3(1), dim3(GC_THREADS), 0, ctx->stream, a);
-	mdb_prof_end(ctx);
+	MDB_LAUNCH(ctx, "tiny_join_pairs", k_tiny_join_pairs, 1, GC_THREADS, a);
 	uint32_t *h = (uint32_t *)ctx->h_pinned;
-	hipError_t e = hipMemcpyAsync(h, ctx->d_status, 8, hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(ctx->stream);
-	if (e != hipSuccess || (h[MDB_STW_FLAGS] & TINY_ST_OVER_CAP)) {
-		(void)mdb_cached_free(ctx, ol);
-		(void)mdb_cached_free(ctx, orr);
-		if (e != hipSuccess)
-			return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "tiny join failed: %s", hipGetErrorString(e));
+	MDB_HIP(ctx, hipMemcpyAsync(h, ctx->d_status, 8, hipMemcpyDeviceToHost, ctx->stream));
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (h[MDB_STW_FLAGS] & TINY_ST_OVER_CAP) {
+		out->drop();
 		return 1;	/* more pairs than the small buffers hold: the general path sizes its output exactly */
 	}
-	*out_l = ol;
-	*out_r = orr;
-	*out_count = h[GC_STW_LIST_LEN];
+	out->count = h[GC_STW_LIST_LEN];
 	return 0;
 }
 
 /* the unique-key join with its narrow-form decision and retry; result codes of join_pairs_unique() except 2 */
-static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-				  const uint64_t *null_r, uint64_t n_r, uint32_t **out_l, uint32_t **out_r, uint64_t *out_count)
+static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
 {
+	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	bool narrow = false;
 	int64_t base = 0;
 	gc_window win = { 0, 0, false, false, false, false };
-	int urc = gc_narrow_guess(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &narrow, &base, &win);
+	int urc = gc_narrow_guess(ctx, s.l.keys, s.l.nulls, n_l, s.r.keys, s.r.nulls, n_r, &narrow, &base, &win);
 	if (urc)
 		return urc;
 	/* a compact window of at most 2^24 key values: one partition level, see join_pairs_unique_wide (MDB_ONE_LEVEL=0 switches
 	 * it off).  What it cannot do - a key outside the window after all, a first-level region overflow - goes the usual way */
 	if (narrow && win.kbits >= 9u + PW_MIN_REM && win.kbits <= 9u + PW_MAX_REM && n_l <= PW_MAX_LEFT && n_l + n_r >= (1ull << 20) &&
-	    !ctx->vd[VD_PW_BAD].holds(NULL, 0, keys_r, n_r) && !ld_disabled() &&
+	    !ctx->vd[VD_PW_BAD].holds(NULL, 0, s.r.keys, n_r) && !ld_disabled() &&
 	    !mdb_knob_off("MDB_ONE_LEVEL")) {
-		urc = join_pairs_unique_wide(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, win.kbits, win.lo, out_l, out_r, out_count);
+		urc = join_pairs_unique_wide(ctx, s, win.kbits, win.lo, out);
 		if (urc <= 0 || urc == 3)
 			return urc;
-		ctx->vd[VD_PW_BAD].note(NULL, 0, keys_r, n_r);
+		ctx->vd[VD_PW_BAD].note(NULL, 0, s.r.keys, n_r);
 	}
-	urc = join_pairs_unique(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, narrow, base, out_l, out_r, out_count);
+	urc = join_pairs_unique(ctx, s, narrow, base, out);
 	if (urc == 2) {	/* the sample (or what was remembered about these columns) missed a wide key */
 		if (ctx->narrow_mode == 1) {
 			ctx->nh_distrust = 8;
-			gc_narrow_note(ctx, keys_l, n_l, keys_r, n_r, false);
+			gc_narrow_note(ctx, s.l.keys, n_l, s.r.keys, n_r, false);
 		}
-		urc = join_pairs_unique(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, false, 0, out_l, out_r, out_count);
+		urc = join_pairs_unique(ctx, s, false, 0, out);
 	}
 	return urc;
 }
@@ -1556,81 +1650,180 @@ static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const int64_t *keys_l, const
  * swapped - it delivers the pairs in right-row order - and a stable sort by left row id puts them into the reference's
  * left-major / right-minor order (for one left row the right rows are already ascending).  About half the time of the
  * general count / scan / emit path.  Same result codes as join_pairs_unique(). */
-static int join_pairs_unique_left(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-				  const uint64_t *null_r, uint64_t n_r, uint32_t **out_l, uint32_t **out_r, uint64_t *out_count)
+static int join_pairs_unique_left(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
 {
+	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	if (n_l >= 0x7FFFFFFFull)
 		return 1;
-	uint32_t *sr = NULL, *sl = NULL;	/* swapped call: "left" ids are right rows, "right" ids are left rows */
-	uint64_t J = 0;
-	int rc = join_pairs_unique_auto(ctx, keys_r, null_r, n_r, keys_l, null_l, n_l, &sr, &sl, &J);
+	pj_pairs swapped(ctx);	/* its "left" ids are right rows, its "right" ids are left rows */
+	int rc = join_pairs_unique_auto(ctx, pj_sides{ s.r, s.l }, &swapped);
 	if (rc)
 		return rc;
-	*out_count = J;
+	const uint64_t J = out->count = swapped.count;
 	if (J == 0)
 		return 0;
-	int64_t *wide = NULL;
-	uint32_t *perm = NULL, *ol = NULL, *orr = NULL;
-	rc = -MIDORIDB_NOMEM;
-	if (mdb_cached_alloc(ctx, J * 8, (void **)&wide) || mdb_cached_alloc(ctx, J * 4, (void **)&perm) ||
-	    mdb_cached_alloc(ctx, J * 4, (void **)&ol) || mdb_cached_alloc(ctx, J * 4, (void **)&orr)) {
-		(void)mdb_set_err(ctx, -MIDORIDB_NOMEM, "cannot allocate %llu join pairs", (unsigned long long)J);
-		goto fail;
-	}
+	const uint32_t *sr = swapped.l(), *sl = swapped.r();
+	pj_buffer wide(ctx), perm(ctx);
+	if (!wide.alloc(J * 8) || !perm.alloc(J * 4))
+		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "cannot allocate %llu join pairs", (unsigned long long)J);
+	if ((rc = out->alloc(J)))
+		return rc;
 	/* the pairs as words, sorted: nothing to widen, no permutation to gather through */
-	rc = mdb_sort_pairs(ctx, sl, sr, J, n_l, n_r, ol, orr);
-	if (rc < 0)
-		goto fail;
-	if (rc == 0) {
-		(void)mdb_cached_free(ctx, wide);
-		(void)mdb_cached_free(ctx, perm);
-		(void)mdb_cached_free(ctx, sr);
-		(void)mdb_cached_free(ctx, sl);
-		*out_l = ol;
-		*out_r = orr;
-		return 0;
-	}
+	rc = mdb_sort_pairs(ctx, sl, sr, J, n_l, n_r, out->l(), out->r());
+	if (rc <= 0)
+		return rc;
 	/* few pairs or unevenly spread left rows: stable sort of a permutation by left row id, two gathers */
-	rc = mdb_dev_widen32to64(ctx, (const int32_t *)sl, J, wide);
+	rc = mdb_dev_widen32to64(ctx, (const int32_t *)sl, J, (int64_t *)wide.p);
 	if (rc)
-		goto fail;
-	{
-		struct mdb_sort_key key;
-		memset(&key, 0, sizeof(key));
-		key.values = wide;
-		key.type = MDB_T_INT64;
-		rc = mdb_dev_sort_perm(ctx, &key, 1, J, perm);
-		if (rc)
-			goto fail;
-	}
-	rc = mdb_dev_gather32(ctx, sl, perm, J, ol);
+		return rc < 0 ? rc : -MIDORIDB_INTERNAL;
+	struct mdb_sort_key key;
+	memset(&key, 0, sizeof(key));
+	key.values = wide.p;
+	key.type = MDB_T_INT64;
+	rc = mdb_dev_sort_perm(ctx, &key, 1, J, (uint32_t *)perm.p);
 	if (!rc)
-		rc = mdb_dev_gather32(ctx, sr, perm, J, orr);
+		rc = mdb_dev_gather32(ctx, sl, (const uint32_t *)perm.p, J, out->l());
+	if (!rc)
+		rc = mdb_dev_gather32(ctx, sr, (const uint32_t *)perm.p, J, out->r());
 	if (!rc)
 		rc = mdb_dev_sync(ctx);
-	if (rc)
-		goto fail;
-	(void)mdb_cached_free(ctx, wide);
-	(void)mdb_cached_free(ctx, perm);
-	(void)mdb_cached_free(ctx, sr);
-	(void)mdb_cached_free(ctx, sl);
-	*out_l = ol;
-	*out_r = orr;
-	return 0;
-fail:
-	if (wide)
-		(void)mdb_cached_free(ctx, wide);
-	if (perm)
-		(void)mdb_cached_free(ctx, perm);
-	if (ol)
-		(void)mdb_cached_free(ctx, ol);
-	if (orr)
-		(void)mdb_cached_free(ctx, orr);
-	(void)mdb_cached_free(ctx, sr);
-	(void)mdb_cached_free(ctx, sl);
-	return rc < 0 ? rc : -MIDORIDB_INTERNAL;
+	return rc <= 0 ? rc : -MIDORIDB_INTERNAL;
 }
 
+/* Unique right keys (the usual primary-key join): one record per pair, ordered like group records; unique left keys: the same with
+ * the sides swapped and a stable sort.  What a column turned out to be is remembered (by pointer and length), so that a repeated
+ * query does not pay for failed attempts.  0 = answered, > 0 = duplicates on both sides, or a table / region overflowed: the general
+ * path, < 0 = error */
+static int pairs_unique_side(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+{
+	int urc = 3;
+	bool right_dups = false, left_dups = false, right_unique = false;
+	ctx->dup_sides(s.l.keys, s.l.n, s.r.keys, s.r.n, &left_dups, &right_dups);
+	if (!right_dups) {
+		urc = join_pairs_unique_auto(ctx, s, out);
+		if (urc < 0)
+			return urc;
+		right_unique = urc == 0;
+		if (urc == 3)
+			ctx->dup_side_note(true, s.r.keys, s.r.n);
+	}
+	if (urc == 3 && !left_dups && s.l.n + s.r.n >= SORT_SWAP_MIN_ROWS) {	/* small tables: the general path has fewer launches */
+		urc = join_pairs_unique_left(ctx, s, out);
+		if (urc < 0)
+			return urc;
+		if (urc == 3)
+			ctx->dup_side_note(false, s.l.keys, s.l.n);
+	}
+	/* (unique right keys: a left row has at most one partner; as many pairs as left rows, in left-row order: 0, 1, 2 ...) */
+	if (urc == 0)
+		ctx->plan.pairs_identity = right_unique && out->count == s.l.n;
+	return urc;
+}
+
+/* One attempt of the general join up to the sizes of its output: both tables partitioned - fast: the histogram-free layout, the right
+ * side in arbitrary order; else the exact layout, the right side stable -, the matches of every left row counted and scanned into
+ * offsets.  *a: the leaf's arguments, for the emit; *status: the flags; *J, *total64: the 32-bit and the 64-bit sum of the counts */
+static int pairs_general_count(mdb_dev_ctx *ctx, const pj_sides &s, int b1, int b2, bool fast, pj_args *a, uint32_t *status, uint64_t *J,
+			       uint64_t *total64)
+{
+	const uint64_t n_l = s.l.n, n_r = s.r.n, mlen = n_l + 1;
+	int rc = pj_begin(ctx, mdb_partition_arena_bytes(n_l, b1, b2, true, fast) + mdb_partition_arena_bytes(n_r, b1, b2, true, fast) +
+				       mdb_align_up(mlen * 4) + mdb_align_up(mdb_scan_scratch_words(mlen) * 4) + 4096, 8);
+	if (rc)
+		return rc;
+	mdb_part_result pl, pr;
+	hipStream_t main_stream = NULL;
+	rc = mdb_aux_begin(ctx, &main_stream);	/* the right table is partitioned on the auxiliary stream (when enabled) */
+	if (rc)
+		return rc;
+	mdb_part_request rq = pj_request(s.r, b1, b2);
+	rq.want_rid = true;
+	rq.fast = fast;
+	rq.stable = !fast;
+	rc = mdb_partition_table(ctx, rq, &pr);
+	{
+		int rc2 = mdb_aux_end(ctx, main_stream);
+		if (rc)
+			return rc;
+		if (rc2)
+			return rc2;
+	}
+	pj_retarget(&rq, s.l);
+	rq.stable = false;
+	rc = mdb_partition_table(ctx, rq, &pl);
+	if (rc)
+		return rc;
+	if ((rc = mdb_aux_join(ctx)))
+		return rc;
+	uint32_t *match = (uint32_t *)mdb_arena_take(ctx, mlen * 4);
+	uint32_t *scan_tmp = (uint32_t *)mdb_arena_take(ctx, mdb_scan_scratch_words(mlen) * 4);
+	if (!match || !scan_tmp)
+		return -MIDORIDB_INTERNAL;
+	MDB_HIP(ctx, hipMemsetAsync(match, 0, mlen * 4, ctx->stream));
+
+	pj_fill_sides(a, pl, pr);
+	pj_fill_rid_off(a, pl, pr);
+	a->match = match;
+	a->n_l = (uint32_t)n_l;
+	a->out_l = a->out_r = NULL;
+	a->status = ctx->d_status;
+	a->total64 = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
+	MDB_LAUNCH(ctx, "leaf_pairs_count", k_leaf_pairs_count, pl.nleaves, LEAF_THREADS, *a);
+
+	/* offsets are 32-bit; the 64-bit total written by the count kernel guards against N:M blow-ups */
+	rc = mdb_scan_u32_inplace(ctx, match, mlen, scan_tmp);
+	if (rc)
+		return rc;
+	uint64_t *h = ctx->h_pinned;
+	MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_COUNT], match + n_l, 4, hipMemcpyDeviceToHost, ctx->stream));
+	const gc_readback *rb;
+	if ((rc = pj_read_status(ctx, 4 * GC_STW_NULL_STATS, &rb)))
+		return rc;
+	*J = (uint32_t)h[MDB_HP_COUNT];
+	*status = rb->flags;
+	*total64 = rb->joined;
+	return MIDORIDB_OK;
+}
+
+/* duplicates on both sides: count, scan, emit */
+static int pairs_general(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+{
+	int b1, b2;
+	mdb_choose_bits(s.r.n, PJ_TARGET, &b1, &b2);
+	pj_args a;
+	uint32_t status = 0;
+	uint64_t J = 0, total64 = 0;
+	/* First with the histogram-free partition layout and the right side in arbitrary order (the emit kernel orders
+	 * every key's row ids itself inside one chunk); the exact, stable layout is the fallback when a region
+	 * overflows (skew) or a leaf holds more right rows than one chunk (their order across chunks matters). */
+	for (int fast = 1; fast >= 0; fast--) {
+		int rc = pairs_general_count(ctx, s, b1, b2, fast != 0, &a, &status, &J, &total64);
+		if (rc)
+			return rc;
+		if (fast && (status & (MDB_ST_REGION_FULL | PJ_ST_RIGHT_CHUNKED)))
+			continue;	/* region overflow, or a multi-chunk leaf with unordered right rows */
+		if (status & PJ_ST_TABLE_FULL)
+			return mdb_set_err(ctx, -MIDORIDB_INTERNAL,
+					   "leaf hash table overflow (more than %u distinct keys in one leaf): unsupported key skew", PJ_SLOTS);
+		break;
+	}
+	if (total64 != J)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join produces %llu rows: more than the 2^32-1 a single call can materialise",
+				   (unsigned long long)total64);
+	out->count = J;
+	if (J == 0)
+		return MIDORIDB_OK;
+	int rc = out->alloc(J);
+	if (rc)
+		return rc;
+	a.out_l = out->l();
+	a.out_r = out->r();
+	MDB_LAUNCH(ctx, "leaf_pairs_emit", k_leaf_pairs_emit, a.nleaves, LEAF_THREADS, a);
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return MIDORIDB_OK;
+}
+
+/* tiny, unique side, general: the first that answers */
 extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l,
 				  const int64_t *keys_r, const uint64_t *null_r, uint64_t n_r, uint32_t **out_l, uint32_t **out_r,
 				  uint64_t *out_count)
@@ -1641,147 +1834,17 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	if (n_l == 0 || n_r == 0)
 		return MIDORIDB_OK;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
-	{
-		const int trc = tiny_join_pairs(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, out_l, out_r, out_count);
-		if (trc <= 0)
-			return trc;
-	}
-	/* ---- unique right keys (the usual primary-key join): one record per pair, ordered like group records;
-	 *      unique left keys: the same with the sides swapped and a stable sort.  What a column turned out to be is
-	 *      remembered (by pointer and length), so that a repeated query does not pay for failed attempts. */
-	{
-		uint32_t *ul = NULL, *ur = NULL;
-		uint64_t uj = 0;
-		int urc = 3;
-		bool right_dups = false, left_dups = false;
-		ctx->dup_sides(keys_l, n_l, keys_r, n_r, &left_dups, &right_dups);
-		bool right_unique = false;
-		if (!right_dups) {
-			urc = join_pairs_unique_auto(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &ul, &ur, &uj);
-			if (urc < 0)
-				return urc;
-			right_unique = urc == 0;
-			if (urc == 3)
-				ctx->dup_side_note(true, keys_r, n_r);
-		}
-		if (urc == 3 && !left_dups && n_l + n_r >= SORT_SWAP_MIN_ROWS) {	/* small tables: the general path has fewer launches */
-			urc = join_pairs_unique_left(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &ul, &ur, &uj);
-			if (urc < 0)
-				return urc;
-			if (urc == 3)
-				ctx->dup_side_note(false, keys_l, n_l);
-		}
-		if (urc == 0) {
-			*out_l = ul;
-			*out_r = ur;
-			*out_count = uj;
-			/* (unique right keys: a left row has at most one partner; as many pairs as left rows, in left-row order: 0, 1, 2 ...) */
-			ctx->plan.pairs_identity = right_unique && uj == n_l;
-			return MIDORIDB_OK;
-		}
-		/* duplicates on both sides, or a table / region overflowed: general path below */
-	}
-	int b1, b2;
-	mdb_choose_bits(n_r, PJ_TARGET, &b1, &b2);
-	const uint64_t mlen = n_l + 1;
-	pj_args a;
-	uint64_t J = 0;
-	uint64_t *h = ctx->h_pinned;
-	/* First with the histogram-free partition layout and the right side in arbitrary order (the emit kernel orders
-	 * every key's row ids itself inside one chunk); the exact, stable layout is the fallback when a region
-	 * overflows (skew) or a leaf holds more right rows than one chunk (their order across chunks matters). */
-	for (int fast = 1; fast >= 0; fast--) {
-		size_t need = mdb_partition_arena_bytes(n_l, b1, b2, true, fast != 0) + mdb_partition_arena_bytes(n_r, b1, b2, true, fast != 0) +
-			      mdb_align_up(mlen * 4) + mdb_align_up(mdb_scan_scratch_words(mlen) * 4) + 4096;
-		int rc = mdb_arena_begin(ctx, need);
-		if (rc)
-			return rc;
-		MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 8 * sizeof(uint32_t), ctx->stream));
-		mdb_part_result pl, pr;
-		hipStream_t main_stream = NULL;
-		rc = mdb_aux_begin(ctx, &main_stream);	/* the right table is partitioned on the auxiliary stream (when enabled) */
-		if (rc)
-			return rc;
-		mdb_part_request rq = pj_request(keys_r, null_r, n_r, b1, b2);
-		rq.want_rid = true;
-		rq.fast = fast != 0;
-		rq.stable = !fast;
-		rc = mdb_partition_table(ctx, rq, &pr);
-		{
-			int rc2 = mdb_aux_end(ctx, main_stream);
-			if (rc)
-				return rc;
-			if (rc2)
-				return rc2;
-		}
-		rq.keys = keys_l;
-		rq.nullbits = null_l;
-		rq.n = n_l;
-		rq.stable = false;
-		rc = mdb_partition_table(ctx, rq, &pl);
-		if (rc)
-			return rc;
-		if ((rc = mdb_aux_join(ctx)))
-			return rc;
-		uint32_t *match = (uint32_t *)mdb_arena_take(ctx, mlen * 4);
-		uint32_t *scan_tmp = (uint32_t *)mdb_arena_take(ctx, mdb_scan_scratch_words(mlen) * 4);
-		if (!match || !scan_tmp)
-			return -MIDORIDB_INTERNAL;
-		MDB_HIP(ctx, hipMemsetAsync(match, 0, mlen * 4, ctx->stream));
-
-		a.hv_l = pl.hv;
-		a.rid_l = pl.rid;
-		a.off_l = pl.leaf_off;
-		a.cnt_l = pl.leaf_cnt;
-		a.cap_l = pl.leaf_cap;
-		a.hv_r = pr.hv;
-		a.rid_r = pr.rid;
-		a.off_r = pr.leaf_off;
-		a.cnt_r = pr.leaf_cnt;
-		a.cap_r = pr.leaf_cap;
-		a.match = match;
-		a.n_l = (uint32_t)n_l;
-		a.out_l = a.out_r = NULL;
-		a.status = ctx->d_status;
-		a.total64 = (unsigned long long *)(ctx->d_status + GC_STW_JOINED);
-		a.nleaves = pl.nleaves;
-		MDB_LAUNCH(ctx, "leaf_pairs_count", k_leaf_pairs_count, pl.nleaves, LEAF_THREADS, a);
-
-		/* offsets are 32-bit; the 64-bit total written by the count kernel guards against N:M blow-ups */
-		rc = mdb_scan_u32_inplace(ctx, match, mlen, scan_tmp);
-		if (rc)
-			return rc;
-		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_COUNT], match + n_l, 4, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipMemcpyAsync(&h[MDB_HP_STATUS], ctx->d_status, 4 * GC_STW_NULL_STATS, hipMemcpyDeviceToHost, ctx->stream));
-		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		J = (uint32_t)h[MDB_HP_COUNT];
-		const uint32_t status = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->flags;
-		if (fast && (status & (MDB_ST_REGION_FULL | PJ_ST_RIGHT_CHUNKED)))
-			continue;	/* region overflow, or a multi-chunk leaf with unordered right rows */
-		if (status & PJ_ST_TABLE_FULL)
-			return mdb_set_err(ctx, -MIDORIDB_INTERNAL,
-					   "leaf hash table overflow (more than %u distinct keys in one leaf): unsupported key skew", PJ_SLOTS);
-		break;
-	}
-	const uint64_t total64 = reinterpret_cast<const gc_readback *>(&h[MDB_HP_STATUS])->joined;
-	if (total64 != J)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "join produces %llu rows: more than the 2^32-1 a single call can materialise",
-				   (unsigned long long)total64);
-	if (J == 0)
-		return MIDORIDB_OK;
-	uint32_t *ol = NULL, *orr = NULL;
-	if (mdb_cached_alloc(ctx, J * 4, (void **)&ol) || mdb_cached_alloc(ctx, J * 4, (void **)&orr)) {
-		if (ol)
-			(void)mdb_cached_free(ctx, ol);
-		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "cannot allocate %llu join pairs", (unsigned long long)J);
-	}
-	a.out_l = ol;
-	a.out_r = orr;
-	MDB_LAUNCH(ctx, "leaf_pairs_emit", k_leaf_pairs_emit, a.nleaves, LEAF_THREADS, a);
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	*out_l = ol;
-	*out_r = orr;
-	*out_count = J;
+	const pj_sides sides = { { keys_l, null_l, n_l }, { keys_r, null_r, n_r } };
+	pj_pairs pairs(ctx);
+	int rc = tiny_join_pairs(ctx, sides, &pairs);
+	if (rc > 0)
+		rc = pairs_unique_side(ctx, sides, &pairs);
+	if (rc > 0)
+		rc = pairs_general(ctx, sides, &pairs);
+	if (rc)
+		return rc;
+	*out_count = pairs.count;
+	pairs.release(out_l, out_r);
 	return MIDORIDB_OK;
 }
 
