@@ -586,7 +586,8 @@ int mdb_dev_join_payload_multi(mdb_dev_ctx *ctx, const int64_t *keys_l, const ui
 			       int nright, int64_t key_min, int64_t key_max);
 
 /* Cross join (FROM A, B  ==  JOIN ... ON 1=1, reference optimiser_select.c:395-464):
- * all n_l * n_r pairs in (l, r) order, into caller buffers of that capacity. */
+ * all n_l * n_r pairs in (l, r) order, into caller buffers of that capacity.  An empty side writes nothing; 2^32 pairs
+ * or more (row ids are 32 bits wide) are refused with an error before anything is written. */
 int mdb_dev_cross_pairs(mdb_dev_ctx *ctx, uint64_t n_l, uint64_t n_r, uint32_t *out_l, uint32_t *out_r);
 
 /* ------------------------------------------------------------------ composite equi-join keys

@@ -1351,7 +1351,7 @@ extern "C" int mdb_dev_cross_pairs(mdb_dev_ctx *ctx, uint64_t n_l, uint64_t n_r,
 {
 	if (n_l == 0 || n_r == 0)
 		return MIDORIDB_OK;
-	if (n_l * n_r >= (1ull << 32))
+	if (n_l > 0xFFFFFFFFull / n_r)	/* (by division: the 64-bit product itself can wrap) */
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "cross join of %llu x %llu rows is too large",
 				   (unsigned long long)n_l, (unsigned long long)n_r);
 	MDB_LAUNCH(ctx, "cross_pairs", k_cross_pairs, stream_grid(n_l * n_r), STREAM_THREADS, n_l, n_r, out_l, out_r);

@@ -226,6 +226,7 @@ def _bind(lib):
                                     POINTER(c_uint64)], c_int),
         "mdb_dev_gather32": ([P, P, P, c_uint64, P], c_int),
         "mdb_dev_iota32": ([P, P, c_uint64], c_int),
+        "mdb_dev_map_ids": ([P, P, c_uint64, P, c_uint64, P], c_int),
         "mdb_dev_scatter_set64": ([P, P, P, P, c_uint64, c_int64, c_int], c_int),
         "mdb_dev_sort_perm": ([P, POINTER(SortKey), c_int, c_uint64, P], c_int),
         "mdb_dev_topk_perm": ([P, POINTER(SortKey), c_int, c_uint64, c_uint64, P, POINTER(c_uint64)], c_int),
@@ -910,6 +911,14 @@ class DeviceCtx:
         dst = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
         self._chk(self.lib.mdb_dev_gather32(self.h, _ptr(src), _ptr(idx), n, _ptr(dst)), "gather32")
         return dst[:n]
+
+    def map_ids(self, cells, table, out=None):
+        """out[i] = table[cells[i]], 0 for a cell outside the table (mdb_dev_map_ids); out=cells translates in place"""
+        n = cells.numel()
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        self._chk(self.lib.mdb_dev_map_ids(self.h, _ptr(cells), n, _ptr(table), table.numel(), _ptr(out)), "map_ids")
+        return out[:n]
 
     def scatter_set64(self, dst, dst_nulls, idx, value_bits, set_null=False):
         """UPDATE's device half: dst[idx[k]] = value (all rows when idx is None), NULL bits set or cleared."""
