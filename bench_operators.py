@@ -214,6 +214,49 @@ def aggregate_rows(dev, res, n=100_000_000):
     res["aggregate_1e8"] = out
 
 
+def count_distinct_rows(dev, res, n=100_000_000):
+    """count_distinct_1e8: GROUP BY k, COUNT(DISTINCT v) over 10^8 INT64 rows at 4, 1000 and 10^5 groups, v inside spans of 10^3 and 10^6
+    values (a permutation modulo the span, the range promised as the catalog would) and once full-range without a range.  Per case, wall
+    time per call with its synchronisation after a warm-up call: count_distinct_ms = mdb_dev_group_count_distinct alone in the form it
+    chooses (`form`), sorted_ms = the same call with MDB_COUNT_DISTINCT_BITMAP=0 where the bitmap form ran (what the switch between the
+    forms is judged by), group_count_ms = the shape's GROUP BY k, COUNT(*) that delivers first[] beforehand, workaround_ms =
+    mdb_dev_group_count_multi over (k, v) - the device part of SELECT DISTINCT k, v, what a user runs today before a recount on the host."""
+    out = {"rows": n, "bitmap_bits": dev.count_distinct_bitmap_bits(), "lds_groups": dev.group_count_distinct_lds_groups(), "cases": {}}
+    spans = {"1e3": 1000, "1e6": 1_000_000}
+    vals = {name: dev.gen_keys(n, 0, n, 44, span) for name, span in spans.items()}
+    vals["full"] = torch.mul(dev.gen_payload(n, 0, 11, 0), -7046029254386353131)       # (wraps: every bit of the 64 varies)
+    for groups in (4, 1000, 100_000):
+        keys = dev.gen_keys(n, 0, n, 43, groups)
+        gms, _, (first, cnt) = timed(dev, lambda: dev.group_count(keys, None), reps=3, warmup=1)
+        dkeys = [(keys, None, None, D.T_INT64, False)]
+        for name, v in vals.items():
+            if name == "full" and groups != 1000:
+                continue
+            rng_ = (0, spans[name] - 1) if name in spans else None
+            call = lambda: dev.group_count_distinct(dkeys, n, first, [(D.T_INT64, v, None, None, rng_)])    # noqa: E731
+            ms, kern, got = timed(dev, call, reps=3, warmup=1)
+            case = {"groups": int(first.numel()), "form": got[1][0], "group_count_ms": gms, "count_distinct_ms": ms, "kernels_ms": kern,
+                    "distinct_total": int(got[0][0].sum())}
+            if got[1][0] == 1:
+                os.environ["MDB_COUNT_DISTINCT_BITMAP"] = "0"
+                try:
+                    sms, skern, sgot = timed(dev, call, reps=3, warmup=1)
+                finally:
+                    del os.environ["MDB_COUNT_DISTINCT_BITMAP"]
+                assert sgot[1][0] == 2 and torch.equal(sgot[0][0], got[0][0])
+                case.update({"sorted_ms": sms, "sorted_kernels_ms": skern})
+            wkeys = dkeys + [(v, None, None, D.T_INT64, False)]
+            wms, wkern, wgot = timed(dev, lambda: dev.group_count_multi(wkeys, n), reps=3, warmup=1)
+            case.update({"workaround_ms": wms, "workaround_rows": int(wgot[0].numel()), "workaround_kernels_ms": wkern})
+            assert case["workaround_rows"] == case["distinct_total"]
+            out["cases"][f"span_{name}@{groups}"] = case
+            del got, wgot
+            torch.cuda.empty_cache()
+        del keys, first, cnt
+        torch.cuda.empty_cache()
+    res["count_distinct_1e8"] = out
+
+
 def subquery_rows(dev, res):
     """subquery_set: the right side of k IN (SELECT ...) as a device set - make_set_from_column (mdb_dev_set_from_column: scan, fill,
     insert, and the rebuild where the members need a smaller table) beside the route that existed before it for the same cells: the
@@ -294,9 +337,19 @@ def main():
                                                               "of the same pairs)")
     ap.add_argument("--subquery", action="store_true", help="only the IN (SELECT ...) set builder's row (subquery_set: make_set_from_column at three "
                                                              "shapes beside the column copied to the host and make_set)")
+    ap.add_argument("--count-distinct", action="store_true", help="only the COUNT(DISTINCT col) rows (count_distinct_1e8: GROUP BY k, COUNT(DISTINCT v) at "
+                                                                   "4, 1000 and 10^5 groups and value spans of 10^3, 10^6 and 2^64, per form, beside "
+                                                                   "mdb_dev_group_count_multi over (k, v))")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.count_distinct:
+        count_distinct_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.subquery:
         subquery_rows(dev, res)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

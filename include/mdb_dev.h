@@ -717,7 +717,8 @@ int mdb_dev_group_count_keys(mdb_dev_ctx *ctx, const int64_t *keys, const uint64
  * off -, 2 sorted segments (a stable sort of the stream by the keys, every group one run, folded in an order that depends on n, the
  * permutation and the launch geometry alone), 3 the identity.  No floating-point atomics in any form: the same input gives the same
  * bytes.  Synchronises. */
-enum mdb_agg_op { MDB_AGG_SUM = 1, MDB_AGG_MIN = 2, MDB_AGG_MAX = 3, MDB_AGG_AVG = 4 };
+enum mdb_agg_op { MDB_AGG_SUM = 1, MDB_AGG_MIN = 2, MDB_AGG_MAX = 3, MDB_AGG_AVG = 4,
+		  MDB_AGG_COUNT_DISTINCT = 5	/* COUNT(DISTINCT col): mdb_dev_group_count_distinct below - mdb_dev_group_aggregate refuses it */ };
 #define MDB_AGG_MAX_AGGS 8
 #define MDB_AGG_IDENTITY (-1)
 struct mdb_agg {
@@ -734,6 +735,42 @@ int mdb_dev_group_aggregate(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, i
 /* the largest G the LDS form takes for naggs aggregates (160 KiB of LDS hold the key table at load <= 1/2 and 16 bytes per aggregate
  * and group); 0 for naggs outside 1 ... MDB_AGG_MAX_AGGS */
 uint64_t mdb_dev_group_aggregate_lds_groups(int naggs);
+
+/* ------------------------------------------------------------------ COUNT(DISTINCT col) per group
+ *
+ * An extension, like the aggregates above.  keys, nkeys, n, first and G mean what they mean for mdb_dev_group_aggregate (nkeys == 0: one
+ * group; nkeys == MDB_AGG_IDENTITY: group i is row i; a key that belongs to no group of first[] fails the call).  out[g] of every column =
+ * how many different non-NULL cells the rows of group g hold: a NULL cell - its NULL bit, or a row id of MDB_NO_ROW - is skipped, a group
+ * without a non-NULL cell counts 0 (never NULL).  MDB_T_INT64 cells compare bit for bit, MDB_T_DOUBLE cells as IEEE `==` with -0.0 and +0.0
+ * one value (mdb_set_canonical); NaN cells are outside the contract.
+ *
+ * The group of every row is found once per call (one 8-byte key and G <= mdb_dev_group_count_distinct_lds_groups(): a key -> group table in
+ * LDS; otherwise a stable sort of the stream by the keys, whose runs are the groups).  Then every column takes one of three forms,
+ * reported in out_forms[c] (may be NULL):
+ *   1  bitmap: MDB_T_INT64 cells with has_range set, max - min + 1 not overflowing and G * (span rounded up to 64) at most
+ *      MDB_COUNT_DISTINCT_BITMAP_BITS: every group owns whole 64-bit words, every valid cell marks its bit, a popcount per group.  [min, max]
+ *      is a PROMISE that is checked: a cell outside it sends the column to form 2, never to a wrong count.  MDB_COUNT_DISTINCT_BITMAP=0
+ *      turns the form off.
+ *   2  sorted: one stable sort by (group, value); a position counts when its cell is valid and the position before belongs to another
+ *      group, is NULL or holds another canonical value.
+ *   3  identity (nkeys == MDB_AGG_IDENTITY): 1 for a valid cell, else 0.
+ * Integer atomics only: the same input gives the same bytes.  Synchronises. */
+#define MDB_COUNT_DISTINCT_BITMAP_BITS (1ull << 30)	/* form 1's bitmap at most: 128 MiB, half the Infinity Cache - a memory bound */
+struct mdb_count_distinct {
+	int32_t type;			/* enum mdb_valtype of the cells */
+	int32_t has_range;		/* min / max below are a superset range of the non-NULL cells (MDB_T_INT64 only) */
+	const void *values;		/* as struct mdb_agg */
+	const uint64_t *nullbits;
+	const uint32_t *rid;
+	int64_t min, max;
+	int64_t *out;			/* G counts */
+};
+int mdb_dev_group_count_distinct(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, const uint32_t *first, uint64_t G,
+				 const struct mdb_count_distinct *cols, int ncols, uint32_t *out_forms /* ncols, may be NULL */);
+/* the largest G for which the group of every row is looked up in an LDS table (one 8-byte key) */
+uint64_t mdb_dev_group_count_distinct_lds_groups(void);
+/* MDB_COUNT_DISTINCT_BITMAP_BITS as the library was built */
+uint64_t mdb_dev_count_distinct_bitmap_bits(void);
 
 /* ------------------------------------------------------------------ fused north-star pipeline
  *

@@ -174,6 +174,12 @@ unsigned long long mdb_database_subquery_sets(struct database *db);
  * MDB_AGG_LDS=0).  A GROUP BY over a column measured to hold no value twice answers with the cells themselves and counts in neither.
  * Either pointer may be NULL. */
 int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_form, unsigned long long *sorted_form);
+/* COUNT(DISTINCT col) (an extension as well): the COUNT(DISTINCT) items of this database's SELECT statements so far that
+ * mdb_dev_group_count_distinct (mdb_dev.h) answered, by the form it took for the item's column - *bitmap_form: a bit per value of the
+ * catalog's value range (integer-represented and VARCHAR columns whose range times the number of groups fits
+ * MDB_COUNT_DISTINCT_BITMAP_BITS), *sorted_form: a sort by (group, value) (DOUBLE columns, wide ranges, MDB_COUNT_DISTINCT_BITMAP=0).  All
+ * items of one statement share one operator call.  A GROUP BY answered by the identity counts in neither.  Either pointer may be NULL. */
+int mdb_database_count_distinct_calls(struct database *db, unsigned long long *bitmap_form, unsigned long long *sorted_form);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

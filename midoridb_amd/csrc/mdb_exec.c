@@ -401,29 +401,69 @@ double now_ms(void)
 static int stream_aggregate(struct exec *x, const struct mdb_sort_key *gk, int nk, const uint32_t *first, uint64_t G)
 {
 	struct mdb_agg ag[MDB_AGG_MAX_AGGS];
-	uint32_t form = 0;
+	struct mdb_count_distinct cd[MDB_AGG_MAX_AGGS];
+	uint32_t form = 0, cd_forms[MDB_AGG_MAX_AGGS];
+	int na = 0, ncd = 0;
 
 	for (int i = 0; i < x->nagg; i++) {
 		const int t = x->agg_tbl[i];
-		const struct mdb_column *col = &x->s->tabs[t].t->cols[x->agg_col[i]];
-		ag[i].op = x->agg_op[i];
-		ag[i].type = col->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
-		ag[i].values = col->d_data;
-		ag[i].nullbits = col->d_nullbits;
-		ag[i].rid = x->rid[t];
-		if (!ag[i].values && !(ag[i].values = dalloc(x, 8)))	/* (an empty table under an outer join: every tuple is at "no row", no cell is read) */
+		struct mdb_table *tb = x->s->tabs[t].t;
+		struct mdb_column *col = &tb->cols[x->agg_col[i]];
+		const void *values = col->d_data;
+		if (!values && !(values = dalloc(x, 8)))	/* (an empty table under an outer join: every tuple is at "no row", no cell is read) */
 			return dev_fail(x, "aggregates");
+		const size_t nbytes = ((G + 63) / 64 + 1) * 8;
 		x->d_agg[i] = dalloc(x, G * 8);
-		x->d_agg_nulls[i] = dalloc(x, ((G + 63) / 64 + 1) * 8);
-		ag[i].out = x->d_agg[i];
-		ag[i].out_nullbits = x->d_agg_nulls[i];
+		x->d_agg_nulls[i] = dalloc(x, nbytes);
 		if (!x->d_agg[i] || !x->d_agg_nulls[i])
 			return dev_fail(x, "allocating aggregate columns");
+		if (x->agg_op[i] == MDB_AGG_COUNT_DISTINCT) {
+			/* COUNT(DISTINCT col): the other operator; a count is never NULL.  The catalog's value range - for VARCHAR the ids the
+			 * dictionary has given out - lets the operator take its bitmap form; it is a promise the operator checks */
+			struct mdb_count_distinct *c = &cd[ncd++];
+			int64_t lo = 0, hi = -1;
+			memset(c, 0, sizeof(*c));
+			c->type = col->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+			c->values = values;
+			c->nullbits = col->d_nullbits;
+			c->rid = x->rid[t];
+			if (col->type == MDB_CT_VARCHAR) {
+				lo = 1;
+				hi = (int64_t)x->cat->dict.n;
+			} else if (x->orig_tab[t] || mdb_col_range(x->cat, tb, col, &lo, &hi) != MIDORIDB_OK) {
+				lo = 0;
+				hi = -1;
+			}
+			c->has_range = lo <= hi;
+			c->min = lo;
+			c->max = hi;
+			c->out = x->d_agg[i];
+			if (mdb_dev_memset(x->dev, x->d_agg_nulls[i], 0, nbytes))
+				return dev_fail(x, "clearing the NULL bits of COUNT(DISTINCT)");
+			continue;
+		}
+		ag[na].op = x->agg_op[i];
+		ag[na].type = col->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+		ag[na].values = values;
+		ag[na].nullbits = col->d_nullbits;
+		ag[na].rid = x->rid[t];
+		ag[na].out = x->d_agg[i];
+		ag[na].out_nullbits = x->d_agg_nulls[i];
+		na++;
 	}
-	if (mdb_dev_group_aggregate(x->dev, gk, nk, x->n, first, G, ag, x->nagg, &form))
-		return dev_fail(x, "SUM / MIN / MAX / AVG");
-	if (form == 1 || form == 2)
-		x->agg_calls[form - 1]++;
+	if (na) {
+		if (mdb_dev_group_aggregate(x->dev, gk, nk, x->n, first, G, ag, na, &form))
+			return dev_fail(x, "SUM / MIN / MAX / AVG");
+		if (form == 1 || form == 2)
+			x->agg_calls[form - 1]++;
+	}
+	if (ncd) {
+		if (mdb_dev_group_count_distinct(x->dev, gk, nk, x->n, first, G, cd, ncd, cd_forms))
+			return dev_fail(x, "COUNT(DISTINCT)");
+		for (int c = 0; c < ncd; c++)
+			if (cd_forms[c] == 1 || cd_forms[c] == 2)
+				x->cd_calls[cd_forms[c] - 1]++;
+	}
 	return MIDORIDB_OK;
 }
 
@@ -622,8 +662,8 @@ static int result_cols_build(struct exec *x, struct result_cols *rc)
 		rc->tbl[rc->nkeys++] = COLSRC_COUNT;
 	}
 	for (int a = 0; a < x->nagg; a++) {
-		snprintf(rc->keys[rc->nkeys], MDB_NAME_LEN, "%s(%.56s.%.56s)", mdb_agg_name(x->agg_op[a]), s->tabs[x->agg_tbl[a]].t->name,
-			 s->tabs[x->agg_tbl[a]].t->cols[x->agg_col[a]].name);
+		snprintf(rc->keys[rc->nkeys], MDB_NAME_LEN, "%s%.*s.%.*s)", mdb_agg_open(x->agg_op[a]), x->agg_op[a] == MDB_AGG_COUNT_DISTINCT ? 50 : 56,
+			 s->tabs[x->agg_tbl[a]].t->name, x->agg_op[a] == MDB_AGG_COUNT_DISTINCT ? 50 : 56, s->tabs[x->agg_tbl[a]].t->cols[x->agg_col[a]].name);
 		rc->tbl[rc->nkeys++] = COLSRC_AGG(a);
 	}
 	for (int t = 0; t < s->ntabs; t++)
@@ -1334,6 +1374,8 @@ out:
 	cat->composite_fused += (uint64_t)x.composite_fused;
 	cat->aggregate_calls[0] += (uint64_t)x.agg_calls[0];
 	cat->aggregate_calls[1] += (uint64_t)x.agg_calls[1];
+	cat->count_distinct_calls[0] += (uint64_t)x.cd_calls[0];
+	cat->count_distinct_calls[1] += (uint64_t)x.cd_calls[1];
 	shard_cleanup(&x);
 	subqueries_release(cat, s->where);
 	subqueries_release(cat, s->having);

@@ -87,6 +87,7 @@ struct exec {
 	void *d_agg[MDB_AGG_MAX_AGGS];
 	uint64_t *d_agg_nulls[MDB_AGG_MAX_AGGS];
 	int agg_calls[2];			/* mdb_dev_group_aggregate calls by form: [0] groups in LDS, [1] sorted segments */
+	int cd_calls[2];			/* COUNT(DISTINCT) items answered by mdb_dev_group_count_distinct, by form: [0] bitmap, [1] sorted */
 };
 
 static inline bool stream_is_keys(const struct exec *x) { return x->plan != STREAM_ROWS; }
@@ -168,6 +169,7 @@ bool expr_has_count(const struct mdb_expr *e);
 bool expr_has_agg(const struct mdb_expr *e);
 bool agg_eq(const struct mdb_expr *a, const struct mdb_expr *b);
 const char *mdb_agg_name(int op);
+const char *mdb_agg_open(int op);
 int mdb_agg_result_type(int op, int coltype);
 int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, const char *clause, char *err, size_t errlen);
 int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, size_t errlen);

@@ -13,14 +13,22 @@ bool field_eq(const struct mdb_expr *a, const struct mdb_expr *b)
 	return a->kind == MDB_EX_FIELD && b->kind == MDB_EX_FIELD && a->tbl_idx == b->tbl_idx && a->col_idx == b->col_idx;
 }
 
-/* SUM / MIN / MAX / AVG: the function's name and the column type of its result over a column of type coltype */
+/* SUM / MIN / MAX / AVG / COUNT(DISTINCT): the function's name, how its result column's name begins in front of "<table>.<column>)", and the
+ * column type of its result over a column of type coltype */
 const char *mdb_agg_name(int op)
 {
-	return op == MDB_AGG_SUM ? "SUM" : op == MDB_AGG_MIN ? "MIN" : op == MDB_AGG_MAX ? "MAX" : "AVG";
+	return op == MDB_AGG_SUM ? "SUM" : op == MDB_AGG_MIN ? "MIN" : op == MDB_AGG_MAX ? "MAX" : op == MDB_AGG_AVG ? "AVG" : "COUNT(DISTINCT)";
+}
+
+const char *mdb_agg_open(int op)
+{
+	return op == MDB_AGG_SUM ? "SUM(" : op == MDB_AGG_MIN ? "MIN(" : op == MDB_AGG_MAX ? "MAX(" : op == MDB_AGG_AVG ? "AVG(" : "COUNT(DISTINCT ";
 }
 
 int mdb_agg_result_type(int op, int coltype)
 {
+	if (op == MDB_AGG_COUNT_DISTINCT)
+		return MDB_CT_INTEGER;
 	if (op == MDB_AGG_AVG)
 		return MDB_CT_DOUBLE;
 	if (op == MDB_AGG_SUM)
@@ -34,7 +42,8 @@ bool agg_eq(const struct mdb_expr *a, const struct mdb_expr *b)
 }
 
 /* an aggregate as the parser left it (kid[0] = its column): the column is resolved and the type rules are applied - no function over VARCHAR
- * (the cells are dictionary ids, which are not in string order), no SUM / AVG over DATE / DATETIME */
+ * (the cells are dictionary ids, which are not in string order) but COUNT(DISTINCT), which only asks whether two cells are equal; no SUM / AVG
+ * over DATE / DATETIME */
 static int resolve_agg(struct mdb_select *s, struct mdb_expr *e, char *err, size_t errlen)
 {
 	int rc;
@@ -47,7 +56,7 @@ static int resolve_agg(struct mdb_select *s, struct mdb_expr *e, char *err, size
 	c = e->kids[0];
 	if ((rc = resolve_expr(s, c, err, errlen)))
 		return rc;
-	if (c->type == MDB_CT_VARCHAR) {
+	if (c->type == MDB_CT_VARCHAR && e->op != MDB_AGG_COUNT_DISTINCT) {
 		ERR("%s over the VARCHAR column '%.100s.%.100s' is not supported: its cells are dictionary ids, which are not in string order\n",
 		    mdb_agg_name(e->op), c->tbl, c->col);
 		return -MIDORIDB_ERROR;
@@ -80,7 +89,7 @@ static int resolve_agg_refs(struct mdb_select *s, struct mdb_expr *e, const char
 		for (int i = 0; i < s->nsel && !found; i++)
 			found = agg_eq(s->sel[i], e);
 		if (!found) {
-			ERR("%s(%.100s.%.100s) in the %s clause must also stand in the select list\n", mdb_agg_name(e->op), e->tbl, e->col, clause);
+			ERR("%s%.100s.%.100s) in the %s clause must also stand in the select list\n", mdb_agg_open(e->op), e->tbl, e->col, clause);
 			return -MIDORIDB_ERROR;
 		}
 		return MIDORIDB_OK;
@@ -507,14 +516,17 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 			continue;
 		}
 		if (e->kind == MDB_EX_AGG) {
-			/* SUM / MIN / MAX / AVG over one column: an extension (upstream knows COUNT only) */
+			/* SUM / MIN / MAX / AVG / COUNT(DISTINCT) over one column: an extension (upstream knows COUNT only) */
 			if (++nagg > MDB_AGG_MAX_AGGS) {
 				ERR("more than %d SUM / MIN / MAX / AVG aggregates in one select list are not supported\n", MDB_AGG_MAX_AGGS);
 				return -MIDORIDB_ERROR;
 			}
 			if (cat->dist) {
 				/* (known from the statement alone: every rank leaves here together, before anything is exchanged) */
-				ERR("sharded mode: %s is not executed (SUM / MIN / MAX / AVG run on one GPU)\n", mdb_agg_name(e->op));
+				if (e->op == MDB_AGG_COUNT_DISTINCT)
+					ERR("sharded mode: COUNT(DISTINCT) is not executed (COUNT(DISTINCT col) runs on one GPU)\n");
+				else
+					ERR("sharded mode: %s is not executed (SUM / MIN / MAX / AVG run on one GPU)\n", mdb_agg_name(e->op));
 				return -MIDORIDB_ERROR;
 			}
 			if ((rc = resolve_agg(s, e, err, errlen)))

@@ -127,6 +127,7 @@ struct mdb_catalog {
 	uint64_t composite_joins;	/* joins of SELECT statements that ran on a packed composite key (mdb_exec_join.c, composite_join_pack) */
 	uint64_t composite_fused;	/* SELECT statements answered by the fused join + GROUP BY operator on a packed composite key (mdb_exec_join.c, composite_fused_plan) */
 	uint64_t aggregate_calls[2];	/* mdb_dev_group_aggregate calls of SELECT statements by form: [0] groups in LDS, [1] sorted segments (mdb_exec.c) */
+	uint64_t count_distinct_calls[2];	/* COUNT(DISTINCT col) items of SELECT statements answered by mdb_dev_group_count_distinct, by form: [0] bitmap, [1] sorted (mdb_exec.c) */
 	uint64_t in_set_lookups;	/* IN / NOT IN lists compiled to one device lookup (mdb_exec_pred.c, pred_compile_in_lookup) */
 	uint64_t subquery_sets;		/* IN / NOT IN (SELECT ...): device sets built from a subquery's result column (mdb_exec.c, subqueries_eval) */
 	bool groups_any_order;		/* mdb_database_groups_any_order(): GROUP BY over a join need not keep first-occurrence order */

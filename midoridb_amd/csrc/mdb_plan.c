@@ -456,9 +456,9 @@ int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, s
 			if (e && pop_n_into(&st, 1, e))
 				FAIL("error while running syntax analysis on query\n");
 		} else if (starts(t, "AGG ")) {
-			/* "AGG SUM | MIN | MAX | AVG" behind its column (NAME / FIELDNAME): op = enum mdb_agg_op */
+			/* "AGG SUM | MIN | MAX | AVG | COUNTD" behind its column (NAME / FIELDNAME): op = enum mdb_agg_op (COUNTD: COUNT(DISTINCT col)) */
 			const int fn = !strcmp(t + 4, "SUM") ? MDB_AGG_SUM : !strcmp(t + 4, "MIN") ? MDB_AGG_MIN : !strcmp(t + 4, "MAX") ? MDB_AGG_MAX :
-				       !strcmp(t + 4, "AVG") ? MDB_AGG_AVG : 0;
+				       !strcmp(t + 4, "AVG") ? MDB_AGG_AVG : !strcmp(t + 4, "COUNTD") ? MDB_AGG_COUNT_DISTINCT : 0;
 			if (!fn || st.n < 1 || (st.v[st.n - 1]->kind != MDB_EX_NAME && st.v[st.n - 1]->kind != MDB_EX_FIELD))
 				FAIL("error while running syntax analysis on query\n");
 			e = ex_new(MDB_EX_AGG);

@@ -346,6 +346,18 @@ int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_fo
 	return MIDORIDB_OK;
 }
 
+int mdb_database_count_distinct_calls(struct database *db, unsigned long long *bitmap_form, unsigned long long *sorted_form)
+{
+	struct mdb_catalog *cat = db ? db->tables : NULL;
+	if (!cat)
+		return -MIDORIDB_ERROR;
+	if (bitmap_form)
+		*bitmap_form = cat->count_distinct_calls[0];
+	if (sorted_form)
+		*sorted_form = cat->count_distinct_calls[1];
+	return MIDORIDB_OK;
+}
+
 double query_exec_ms(struct result_set *res)
 {
 	return res && res->table ? ((struct mdb_result *)res->table)->exec_ms : 0.0;

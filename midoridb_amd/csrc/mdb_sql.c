@@ -23,6 +23,7 @@
  */
 #include "mdb_host.h"
 #include <ctype.h>
+#include <strings.h>
 
 enum tk {
 	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_FAGG, T_ANDOP, T_OROP, T_ERR
@@ -423,11 +424,48 @@ static void parse_primary(struct parser *p)
 		next(p);
 		return;
 	case T_FCOUNT:
-		if (p->dml)
+		if (p->dml) {
+			/* (COUNT( stays the syntax error it is in DML; the DISTINCT form gets a text of its own: the lexer stands on the parenthesis) */
+			const char *q = l->s + l->pos + 1;
+			while (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r')
+				q++;
+			if (strncasecmp(q, "DISTINCT", 8) == 0 && !isalnum((unsigned char)q[8]) && q[8] != '_') {
+				fail(p, "COUNT(DISTINCT) can't be used in DELETE / UPDATE");
+				return;
+			}
 			break;
+		}
 		next(p);
 		expect_punct(p, '(');
-		if (is_punct(p, '*')) {
+		if (p->lx.type == T_KW && !strcmp(p->lx.text, "DISTINCT")) {
+			/* COUNT(DISTINCT col) | COUNT(DISTINCT tbl.col): one column and nothing else, as SUM(col) - no descent into parentheses:
+			 * "NAME col" / "FIELDNAME tbl.col", then "AGG COUNTD" */
+			char first[256];
+			next(p);
+			if (p->lx.type != T_NAME) {
+				fail(p, "syntax error, COUNT(DISTINCT col) takes one column: COUNT(DISTINCT col) or COUNT(DISTINCT tbl.col)");
+				return;
+			}
+			strcpy(first, p->lx.text);
+			next(p);
+			if (is_punct(p, '.')) {
+				next(p);
+				if (p->lx.type != T_NAME) {
+					fail(p, "syntax error, expecting column name after '.'");
+					return;
+				}
+				emit(p, "FIELDNAME %s.%s", first, p->lx.text);
+				next(p);
+			} else {
+				emit(p, "NAME %s", first);
+			}
+			if (!is_punct(p, ')')) {
+				fail(p, "syntax error, COUNT(DISTINCT col) takes one column: COUNT(DISTINCT col) or COUNT(DISTINCT tbl.col)");
+				return;
+			}
+			next(p);
+			emit(p, "AGG COUNTD");
+		} else if (is_punct(p, '*')) {
 			next(p);
 			expect_punct(p, ')');
 			emit(p, "COUNTALL");

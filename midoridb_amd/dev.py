@@ -58,6 +58,11 @@ class Agg(ctypes.Structure):     # struct mdb_agg (include/mdb_dev.h)
                 ("out_nullbits", c_void_p)]
 
 
+class CountDistinct(ctypes.Structure):     # struct mdb_count_distinct (include/mdb_dev.h)
+    _fields_ = [("type", c_int32), ("has_range", c_int32), ("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p), ("min", c_int64),
+                ("max", c_int64), ("out", c_void_p)]
+
+
 class GatherCol(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("src_nullbits", c_void_p), ("rid", c_void_p), ("dst", c_void_p), ("dst_nullbits", c_void_p)]
 
@@ -271,6 +276,9 @@ def _bind(lib):
         "mdb_dev_in_set_lds_values": ([], c_uint64),
         "mdb_dev_group_aggregate": ([P, POINTER(SortKey), c_int, c_uint64, P, c_uint64, POINTER(Agg), c_int, POINTER(c_uint32)], c_int),
         "mdb_dev_group_aggregate_lds_groups": ([c_int], c_uint64),
+        "mdb_dev_group_count_distinct": ([P, POINTER(SortKey), c_int, c_uint64, P, c_uint64, POINTER(CountDistinct), c_int, POINTER(c_uint32)], c_int),
+        "mdb_dev_group_count_distinct_lds_groups": ([], c_uint64),
+        "mdb_dev_count_distinct_bitmap_bits": ([], c_uint64),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -289,6 +297,7 @@ DEV_SYMBOLS = [
     "mdb_dev_partition_by_dest", "mdb_dev_partition_by_dest_pruned", "mdb_dev_key_range", "mdb_dev_widen32to64", "mdb_dev_gen_keys", "mdb_dev_gen_payload",
     "mdb_set_build", "mdb_set_image_free", "mdb_set_image_contains", "mdb_dev_set_create", "mdb_dev_set_from_column", "mdb_dev_set_insn", "mdb_dev_set_free", "mdb_dev_in_set_lds_values",
     "mdb_dev_group_aggregate", "mdb_dev_group_aggregate_lds_groups",
+    "mdb_dev_group_count_distinct", "mdb_dev_group_count_distinct_lds_groups", "mdb_dev_count_distinct_bitmap_bits",
 ]
 
 
@@ -988,6 +997,38 @@ class DeviceCtx:
         karr = None if identity or not keys else self._sort_keys(keys)
         self._chk(self.lib.mdb_dev_group_aggregate(self.h, karr, nkeys, n, _ptr(first), G, arr, len(aggs), byref(form)), "group_aggregate")
         return ([o[:G] for o in outs], [unpack_nullbits(b.cpu().numpy().view(np.uint64), G) for b in nbs], form.value)
+
+    def group_count_distinct(self, keys, n, first, cols, groups=None):
+        """COUNT(DISTINCT col) per group (mdb_dev_group_count_distinct).  keys, n, first and groups as group_aggregate takes them; cols =
+        [(T_INT64 | T_DOUBLE, values, nullbits or None, rid or None, (min, max) or None), ...] - the range is a promise about the
+        non-NULL cells that the operator checks -> (counts: int64 tensors of G cells, the form that answered each column: 1 bitmap,
+        2 sorted, 3 identity)."""
+        identity = isinstance(keys, int) and keys == AGG_IDENTITY
+        nkeys = AGG_IDENTITY if identity else len(keys)
+        G = groups if groups is not None else (n if identity else (first.numel() if first is not None else 1))
+        arr = (CountDistinct * len(cols))()
+        outs = []
+        for i, (ty, v, nb, rid, rng) in enumerate(cols):
+            out = torch.full((max(G, 1),), -1, dtype=torch.int64, device=self.device)
+            arr[i].type, arr[i].has_range = ty, 1 if rng is not None else 0
+            arr[i].values = v.data_ptr()
+            arr[i].nullbits = nb.data_ptr() if nb is not None else None
+            arr[i].rid = rid.data_ptr() if rid is not None else None
+            arr[i].min, arr[i].max = (int(rng[0]), int(rng[1])) if rng is not None else (0, 0)
+            arr[i].out = out.data_ptr()
+            outs.append(out)
+        forms = (c_uint32 * len(cols))()
+        karr = None if identity or not keys else self._sort_keys(keys)
+        self._chk(self.lib.mdb_dev_group_count_distinct(self.h, karr, nkeys, n, _ptr(first), G, arr, len(cols), forms), "group_count_distinct")
+        return [o[:G] for o in outs], [int(f) for f in forms]
+
+    def group_count_distinct_lds_groups(self):
+        """the largest group count for which group_count_distinct looks the rows' groups up in LDS (mdb_dev_group_count_distinct_lds_groups)"""
+        return int(self.lib.mdb_dev_group_count_distinct_lds_groups())
+
+    def count_distinct_bitmap_bits(self):
+        """MDB_COUNT_DISTINCT_BITMAP_BITS: the most bits group_count_distinct's bitmap form takes (mdb_dev_count_distinct_bitmap_bits)"""
+        return int(self.lib.mdb_dev_count_distinct_bitmap_bits())
 
     def group_aggregate_lds_groups(self, naggs):
         """the largest group count the LDS form of group_aggregate takes for naggs aggregates (mdb_dev_group_aggregate_lds_groups)"""
