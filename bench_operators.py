@@ -257,6 +257,29 @@ def count_distinct_rows(dev, res, n=100_000_000):
     res["count_distinct_1e8"] = out
 
 
+def window_rows(dev, res, n=100_000_000):
+    """window_1e8: ROW_NUMBER() and SUM(v) OVER (PARTITION BY k ORDER BY o) over 10^8 rows at 4, 1000 and 10^6 partitions - both functions
+    in ONE mdb_dev_window call, wall time per call with its synchronisation -, and beside it mdb_dev_sort_perm alone on the same two keys:
+    the sort is the operator's first step, the difference is what the head bitmaps and the scan passes cost."""
+    out = {"rows": n, "cases": {}}
+    v = dev.gen_payload(n, 0, 11, 0)
+    o = dev.gen_payload(n, 0, 13, 0)
+    outs = [torch.empty(n, dtype=torch.int64, device=dev.device) for _ in range(2)]      # (allocated once: the call's own time is measured)
+    nulls = [torch.empty((n + 63) // 64, dtype=torch.int64, device=dev.device) for _ in range(2)]
+    for parts in (4, 1000, 1_000_000):
+        k = dev.gen_keys(n, 0, n, 43, parts)
+        part = [(k, None, None, D.T_INT64, False)]
+        order = [(o, None, None, D.T_INT64, False)]
+        sms, skern, _ = timed(dev, lambda: dev.sort_perm(part + order, n), reps=3, warmup=1)
+        wms, wkern, got = timed(dev, lambda: dev.window(part, order, n, [(D.WIN_ROW_NUMBER,), (D.WIN_SUM, D.T_INT64, v, None, None)], outs=outs, nulls=nulls),
+                                reps=3, warmup=1)
+        out["cases"][f"row_number_sum@{parts}"] = {"partitions": parts, "form": got[2], "window_ms": wms, "sort_perm_ms": sms, "window_over_sort": wms / sms,
+                                                   "kernels_ms": wkern, "sort_kernels_ms": skern}
+        del k, got
+        torch.cuda.empty_cache()
+    res["window_1e8"] = out
+
+
 def subquery_rows(dev, res):
     """subquery_set: the right side of k IN (SELECT ...) as a device set - make_set_from_column (mdb_dev_set_from_column: scan, fill,
     insert, and the rebuild where the members need a smaller table) beside the route that existed before it for the same cells: the
@@ -340,9 +363,18 @@ def main():
     ap.add_argument("--count-distinct", action="store_true", help="only the COUNT(DISTINCT col) rows (count_distinct_1e8: GROUP BY k, COUNT(DISTINCT v) at "
                                                                    "4, 1000 and 10^5 groups and value spans of 10^3, 10^6 and 2^64, per form, beside "
                                                                    "mdb_dev_group_count_multi over (k, v))")
+    ap.add_argument("--window", action="store_true", help="only the window functions' row (window_1e8: ROW_NUMBER and SUM(v) OVER (PARTITION BY k ORDER BY o) "
+                                                           "at 4, 1000 and 10^6 partitions, beside mdb_dev_sort_perm alone on the same keys)")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.window:
+        window_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.count_distinct:
         count_distinct_rows(dev, res)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -772,6 +772,55 @@ uint64_t mdb_dev_group_count_distinct_lds_groups(void);
 /* MDB_COUNT_DISTINCT_BITMAP_BITS as the library was built */
 uint64_t mdb_dev_count_distinct_bitmap_bits(void);
 
+/* ------------------------------------------------------------------ window functions: ranking and running aggregates OVER
+ *
+ * An extension: the reference's grammar has no OVER clause (src/parser/midorisql.y).  One call computes up to MDB_WIN_MAX_FNS functions that
+ * share ONE window - the same partition keys and the same order keys - for every row of a stream of n < 2^32 - 1 rows; row i reads
+ * values[rid ? rid[i] : i] of every column, as struct mdb_sort_key and struct mdb_agg do.
+ *
+ * The stream is sorted stably by the partition keys (their `desc` is ignored), then by the order keys with their `desc`: NULL sorts before
+ * every value ascending, ties keep the stream order, DOUBLE keys follow IEEE order with -0.0 before +0.0 (mdb_dev_sort_perm).  A PARTITION is
+ * a run of equal partition keys (NULL equals NULL, DOUBLE keys compare by their bits), a PEER GROUP a run of equal order keys inside a
+ * partition, compared the same way: -0.0 and +0.0 in a DOUBLE order key are DIFFERENT peers here, as they are different places in
+ * mdb_dev_sort_perm's order (SQL's `=` would make them one).  norder == 0: the whole partition is one peer group; npart == 0: the whole stream
+ * is one partition.  For the row at sorted position p of a partition that begins at b, with p's peer group [g, e):
+ *
+ *   MDB_WIN_ROW_NUMBER   p - b + 1
+ *   MDB_WIN_RANK         g - b + 1
+ *   MDB_WIN_DENSE_RANK   the peer groups in [b, p]
+ *   MDB_WIN_COUNT        e - b                                     (COUNT(*))
+ *   MDB_WIN_SUM / MIN / MAX / AVG   the function over the non-NULL cells of the sorted positions [b, e)
+ *
+ * - SQL's default frame: up to and including the row's peers, the whole partition without order keys.  A cell is NULL when its NULL bit is
+ * set or its row id is MDB_NO_ROW; where no non-NULL cell lies in [b, e) the result is NULL (out = 0, its bit in out_nullbits set).  The
+ * first four are never NULL and read no column.  SUM: MDB_T_INT64 cells, int64_t, two's complement, WRAPS; MIN / MAX: the cells' own type,
+ * MDB_T_DOUBLE in mdb_dev_sort_perm's order; AVG: MDB_T_INT64 cells, (double)wrapped sum / (double)non-NULL cells, as mdb_dev_group_aggregate.
+ * SUM / AVG over MDB_T_DOUBLE cells are refused (a scan folds in another order than any sequential reference would); NaN cells are outside
+ * the contract.
+ *
+ * The value of the row at stream position i is written to out[i] (int64_t, or double for AVG and for MIN / MAX over MDB_T_DOUBLE); all
+ * (n + 63) / 64 words of out_nullbits are written in full, unused bits 0, nothing beyond them or beyond out[n).  n == 0: nothing is written.
+ * *out_form (may be NULL) = 1 when there are no keys at all (no sort: the stream is one partition of peers), 2 when the stream was sorted.
+ * All functions of a call share the sort, the two bitmaps of partition and peer heads and the scan passes (mdb_dev_window.hip).  Integer
+ * arithmetic and plain stores only: the same input gives the same bytes.  Synchronises.
+ * Scratch, taken from the context's allocator for the length of the call and beside what mdb_dev_sort_perm takes: 4 n bytes for the
+ * permutation (with keys), n / 4 for the bitmaps, 4 n more when a COUNT(*) is among the functions, and 17 n bytes for EVERY SUM / MIN / MAX /
+ * AVG of the call (a running (accumulator, cells) pair per sorted position and a NULL flag per row) - 1.7 GB per such function at 10^8 rows.
+ * Memory that cannot be had fails the call with -MIDORIDB_NOMEM before anything is written; the context stays usable. */
+enum mdb_win_op { MDB_WIN_ROW_NUMBER = 1, MDB_WIN_RANK, MDB_WIN_DENSE_RANK, MDB_WIN_COUNT, MDB_WIN_SUM, MDB_WIN_MIN, MDB_WIN_MAX, MDB_WIN_AVG };
+#define MDB_WIN_MAX_FNS 8
+struct mdb_window_fn {
+	int32_t op;			/* enum mdb_win_op */
+	int32_t type;			/* enum mdb_valtype of the cells (SUM / MIN / MAX / AVG) */
+	const void *values;		/* as struct mdb_agg; unused by the first four functions */
+	const uint64_t *nullbits;
+	const uint32_t *rid;
+	void *out;			/* n cells in STREAM order */
+	uint64_t *out_nullbits;		/* (n + 63) / 64 words, written in full */
+};
+int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part, int npart, const struct mdb_sort_key *order, int norder, uint64_t n,
+		   const struct mdb_window_fn *fns, int nfns, uint32_t *out_form);
+
 /* ------------------------------------------------------------------ fused north-star pipeline
  *
  * SELECT l.key, COUNT(*) FROM L INNER JOIN R ON l.key = r.key GROUP BY l.key

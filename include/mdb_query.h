@@ -180,6 +180,9 @@ int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_fo
  * MDB_COUNT_DISTINCT_BITMAP_BITS), *sorted_form: a sort by (group, value) (DOUBLE columns, wide ranges, MDB_COUNT_DISTINCT_BITMAP=0).  All
  * items of one statement share one operator call.  A GROUP BY answered by the identity counts in neither.  Either pointer may be NULL. */
 int mdb_database_count_distinct_calls(struct database *db, unsigned long long *bitmap_form, unsigned long long *sorted_form);
+/* Window functions, fn(...) OVER (PARTITION BY ... ORDER BY ...) (an extension too): mdb_dev_window (mdb_dev.h) calls of this database's
+ * SELECT statements so far - one per distinct OVER clause of a statement: the items whose windows are equal field for field share a call. */
+unsigned long long mdb_database_window_calls(struct database *db);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

@@ -139,6 +139,18 @@ int stream_apply_sel(struct exec *x, int ntabs_in_stream, const uint32_t *sel, u
 		x->d_agg[i] = nv;
 		x->d_agg_nulls[i] = nb;
 	}
+	for (int i = 0; i < x->nwin; i++) {	/* the window items' columns, with their NULL bits */
+		void *nv;
+		uint64_t *nb;
+		if (!x->d_win[i])
+			continue;
+		nv = dalloc(x, (n_new ? n_new : 1) * 8);
+		nb = dalloc(x, ((n_new + 63) / 64 + 1) * 8);
+		if (!nv || !nb || (n_new && mdb_dev_gather64(x->dev, x->d_win[i], x->d_win_nulls[i], sel, n_new, nv, nb)))
+			return dev_fail(x, "re-mapping a window function's column");
+		x->d_win[i] = nv;
+		x->d_win_nulls[i] = nb;
+	}
 	if (stream_is_keys(x)) {
 		for (int k = 0; k < (x->nfused ? x->nfused : 1); k++) {	/* (a composite key: every key column of the stream) */
 			const int64_t *from = x->nfused ? x->d_fused_keys[k] : x->d_fused_key;
@@ -467,6 +479,77 @@ static int stream_aggregate(struct exec *x, const struct mdb_sort_key *gk, int n
 	return MIDORIDB_OK;
 }
 
+/* Window functions: the plan stage between FROM / WHERE and the tail clauses.  The statement's items whose OVER clauses are equal field for
+ * field share one mdb_dev_window call - one sort, one pair of head bitmaps, one set of scan passes.  Keys and arguments are read through the
+ * stream's row ids, as ORDER BY and DISTINCT read theirs: a tuple without a row of the table (MDB_NO_ROW under an outer join) is a NULL cell
+ * to the operator.  The result columns d_win[] have one row per row of the stream. */
+static void window_key(struct exec *x, const struct mdb_expr *f, int desc, struct mdb_sort_key *k)
+{
+	bind_operand(x, f, &k->values, &k->nullbits, &k->rid);
+	k->type = f->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+	k->desc = desc;
+}
+
+int stream_windows(struct exec *x)
+{
+	bool done[MDB_WIN_MAX_FNS] = { false };
+	const uint64_t n = x->n;
+	void *no_cells = NULL;
+
+	for (int i = 0; i < x->nwin; i++) {
+		x->d_win[i] = dalloc(x, (n ? n : 1) * 8);
+		x->d_win_nulls[i] = dalloc(x, ((n + 63) / 64 + 1) * 8);
+		if (!x->d_win[i] || !x->d_win_nulls[i])
+			return dev_fail(x, "allocating window function columns");
+	}
+	if (!n)
+		return MIDORIDB_OK;
+	for (int i = 0; i < x->nwin; i++) {
+		const struct mdb_expr *lead = x->win_item[i];
+		const int narg0 = lead->op >= MDB_WIN_SUM ? 1 : 0;
+		struct mdb_sort_key part[MDB_SORT_MAX_KEYS], order[MDB_SORT_MAX_KEYS];
+		struct mdb_window_fn fn[MDB_WIN_MAX_FNS];
+		uint32_t form = 0;
+		int nfn = 0;
+		if (done[i])
+			continue;
+		for (int k = 0; k < lead->win_npart; k++)
+			window_key(x, lead->kids[narg0 + k], 0, &part[k]);
+		for (int k = 0; k < lead->win_norder; k++)
+			window_key(x, lead->kids[narg0 + lead->win_npart + k], (lead->win_desc >> k) & 1u, &order[k]);
+		for (int k = 0; k < lead->win_npart + lead->win_norder; k++) {
+			struct mdb_sort_key *key = k < lead->win_npart ? &part[k] : &order[k - lead->win_npart];
+			if (!key->values && !(key->values = no_cells ? no_cells : (no_cells = dalloc(x, 8))))	/* (an empty table under an outer join: every tuple is at "no row") */
+				return dev_fail(x, "window functions");
+		}
+		for (int j = i; j < x->nwin; j++) {
+			const struct mdb_expr *e = x->win_item[j];
+			if (done[j] || !window_same_over(lead, e))
+				continue;
+			done[j] = true;
+			memset(&fn[nfn], 0, sizeof(fn[nfn]));
+			fn[nfn].op = e->op;
+			if (e->op >= MDB_WIN_SUM) {
+				struct mdb_sort_key arg;
+				window_key(x, e->kids[0], 0, &arg);
+				if (!arg.values && !(arg.values = no_cells ? no_cells : (no_cells = dalloc(x, 8))))
+					return dev_fail(x, "window functions");
+				fn[nfn].type = arg.type;
+				fn[nfn].values = arg.values;
+				fn[nfn].nullbits = arg.nullbits;
+				fn[nfn].rid = arg.rid;
+			}
+			fn[nfn].out = x->d_win[j];
+			fn[nfn].out_nullbits = x->d_win_nulls[j];
+			nfn++;
+		}
+		if (mdb_dev_window(x->dev, part, lead->win_npart, order, lead->win_norder, n, fn, nfn, &form))
+			return dev_fail(x, "window functions");
+		x->win_calls++;
+	}
+	return MIDORIDB_OK;
+}
+
 /* The fused plan applies to  T0 JOIN T1 ON k0 = k1 [JOIN T2 ON (k0 | k1) = k2 ...] GROUP BY one of those keys, COUNT(*):
  * every join is an equi-join on the SAME key (each ON clause ties the new table's column to a key column already
  * in the chain); a WHERE clause must be pushable below the joins (where_pushable).  keys[t] = the key field of
@@ -648,7 +731,12 @@ static int result_cols_build(struct exec *x, struct result_cols *rc)
 			x->agg_type[x->nagg] = s->sel[i]->type;
 			x->nagg++;
 		}
-	total = rc->has_count + x->nagg;
+	for (int i = 0; i < s->nsel; i++)
+		if (s->sel[i]->kind == MDB_EX_WINDOW && s->sel[i]->win_idx >= 0 && s->sel[i]->win_idx < MDB_WIN_MAX_FNS) {
+			x->win_item[s->sel[i]->win_idx] = s->sel[i];
+			x->nwin = s->sel[i]->win_idx + 1 > x->nwin ? s->sel[i]->win_idx + 1 : x->nwin;
+		}
+	total = rc->has_count + x->nagg + x->nwin;
 	for (int t = 0; t < s->ntabs; t++)
 		total += s->tabs[t].t->ncols;
 	rc->keys = calloc((size_t)total, sizeof(*rc->keys));
@@ -665,6 +753,13 @@ static int result_cols_build(struct exec *x, struct result_cols *rc)
 		snprintf(rc->keys[rc->nkeys], MDB_NAME_LEN, "%s%.*s.%.*s)", mdb_agg_open(x->agg_op[a]), x->agg_op[a] == MDB_AGG_COUNT_DISTINCT ? 50 : 56,
 			 s->tabs[x->agg_tbl[a]].t->name, x->agg_op[a] == MDB_AGG_COUNT_DISTINCT ? 50 : 56, s->tabs[x->agg_tbl[a]].t->cols[x->agg_col[a]].name);
 		rc->tbl[rc->nkeys++] = COLSRC_AGG(a);
+	}
+	for (int w = 0; w < x->nwin; w++) {	/* a window item: named by its alias, or by its function's text ("SUM(A.v) OVER") */
+		mdb_win_result_name(x->win_item[w], rc->keys[rc->nkeys]);
+		for (int i = 0; s->sel_alias && i < s->nsel; i++)
+			if (s->sel[i] == x->win_item[w] && s->sel_alias[i][0])
+				mdb_copy_name(rc->keys[rc->nkeys], s->sel_alias[i]);
+		rc->tbl[rc->nkeys++] = COLSRC_WIN(w);
 	}
 	for (int t = 0; t < s->ntabs; t++)
 		for (int c = 0; c < s->tabs[t].t->ncols; c++) {
@@ -702,7 +797,8 @@ static void select_shape(struct exec *x, struct select_stmt *st)
 	for (int i = 0; i < s->nsel; i++)
 		st->only_count = st->only_count && s->sel[i]->kind == MDB_EX_COUNT;
 	/* (the fused operator is an inner join and knows COUNT(*) only: a statement with SUM / MIN / MAX / AVG materialises its join) */
-	st->fused_chain = s->ntabs <= PUSH_TABS && !x->has_outer && !st->has_agg && fused_chain(s, st->fkeys, st->only_count) >= 0;
+	/* (nor a window function: it asks for a value per row of the joined stream) */
+	st->fused_chain = s->ntabs <= PUSH_TABS && !x->has_outer && !st->has_agg && !st->has_win && fused_chain(s, st->fkeys, st->only_count) >= 0;
 	if (st->fused_chain && !cat->dist && st->split_ok) {
 		/* join elimination: when the catalog says every right table of the chain is a complete primary key over the first table's key range,
 		 * the fused join + GROUP BY operator has nothing to find out - the general plan drops those joins (join_next_table) and groups the
@@ -717,7 +813,7 @@ static void select_shape(struct exec *x, struct select_stmt *st)
 		st->fused_chain = false;	/* a conjunct reads several tables: it has to see the joined rows */
 	if (st->fused_chain && cat->dist && s->ntabs > 2 && st->fkeys[0]->type == MDB_CT_VARCHAR)
 		st->fused_chain = false;	/* (sharded chains over VARCHAR keys: the general plan exchanges the rows by their strings' common ids) */
-	st->keys_only = !x->has_outer && keys_only_join(s, cat, &st->rc, st->has_agg, st->kj);
+	st->keys_only = !x->has_outer && !st->has_win && keys_only_join(s, cat, &st->rc, st->has_agg, st->kj);
 }
 
 /* ------------------------------------------------------------------ plan stages */
@@ -979,7 +1075,7 @@ static int plan_keys_only(struct exec *x, const struct select_stmt *st)
 
 static bool filter_project_applies(const struct select_stmt *st, const struct mdb_select *s)
 {
-	return s->ntabs == 1 && s->where && st->split_ok && !st->ws.nresidual && st->ws.npush[0] && !s->ngroup && !st->rc.has_count && !st->has_agg &&
+	return s->ntabs == 1 && s->where && st->split_ok && !st->ws.nresidual && st->ws.npush[0] && !s->ngroup && !st->rc.has_count && !st->has_agg && !st->has_win &&
 	       !s->distinct && !s->norder && !s->having && !s->has_limit && s->tabs[0].t->nrows && st->rc.ncols && st->rc.ncols <= MDB_GATHER_MAX_COLS;
 }
 
@@ -1261,6 +1357,8 @@ static int plan_general(struct exec *x, const struct select_stmt *st)
 		return general_group_one(x, st);
 	if (s->ngroup > 1)
 		return general_group_several(x, st);
+	if (st->has_win)	/* (never beside GROUP BY or an aggregate: resolve_select) */
+		return stream_windows(x);
 	/* SUM / MIN / MAX / AVG without GROUP BY: the whole stream is one group (an empty stream: no row, as SELECT COUNT(*) answers it) */
 	return st->has_agg && x->n ? stream_aggregate(x, NULL, 0, NULL, 1) : MIDORIDB_OK;
 }
@@ -1328,6 +1426,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	if ((rc = result_cols_build(&x, &st.rc)))
 		goto out;
 	st.has_agg = x.nagg > 0;
+	st.has_win = x.nwin > 0;
 
 	t0 = now_ms();
 	select_shape(&x, &st);
@@ -1336,7 +1435,7 @@ int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_re
 	/* the plan that produces the stream: the first that applies (composite_fused_plan: 1 = it does not) */
 	if (st.fused_chain)
 		rc = plan_fused_chain(&x, &st);
-	else if (!st.keys_only && st.split_ok && !st.has_agg && (rc = composite_fused_plan(&x, &st.ws, st.only_count)) <= 0)
+	else if (!st.keys_only && st.split_ok && !st.has_agg && !st.has_win && (rc = composite_fused_plan(&x, &st.ws, st.only_count)) <= 0)
 		;
 	else if (st.keys_only)
 		rc = plan_keys_only(&x, &st);
@@ -1376,6 +1475,7 @@ out:
 	cat->aggregate_calls[1] += (uint64_t)x.agg_calls[1];
 	cat->count_distinct_calls[0] += (uint64_t)x.cd_calls[0];
 	cat->count_distinct_calls[1] += (uint64_t)x.cd_calls[1];
+	cat->window_calls += (uint64_t)x.win_calls;
 	shard_cleanup(&x);
 	subqueries_release(cat, s->where);
 	subqueries_release(cat, s->having);

@@ -87,6 +87,14 @@ struct exec {
 	void *d_agg[MDB_AGG_MAX_AGGS];
 	uint64_t *d_agg_nulls[MDB_AGG_MAX_AGGS];
 	int agg_calls[2];			/* mdb_dev_group_aggregate calls by form: [0] groups in LDS, [1] sorted segments */
+	/* window functions: the select list's fn(...) OVER (...) items, win_item[i] the item with win_idx i.  After FROM / WHERE d_win[i] /
+	 * d_win_nulls[i] are their result columns over the stream (stream_windows): row k belongs to row k of the stream and follows it
+	 * through HAVING, DISTINCT, ORDER BY and LIMIT as d_agg[] does.  A statement with one of them takes the general plan only */
+	int nwin;
+	const struct mdb_expr *win_item[MDB_WIN_MAX_FNS];
+	void *d_win[MDB_WIN_MAX_FNS];
+	uint64_t *d_win_nulls[MDB_WIN_MAX_FNS];
+	int win_calls;				/* mdb_dev_window calls: one per distinct OVER clause */
 	int cd_calls[2];			/* COUNT(DISTINCT) items answered by mdb_dev_group_count_distinct, by form: [0] bitmap, [1] sorted */
 };
 
@@ -130,8 +138,11 @@ struct result_cols {
 };
 #define COLSRC_COUNT (-1)
 #define COLSRC_AGG(a) (-2 - (a))
-/* which of the statement's aggregates a candidate's source is; -1: none (COUNT(*) or a table column) */
-static inline int colsrc_agg(int tbl) { return tbl <= -2 ? -2 - tbl : -1; }
+#define COLSRC_WIN(w) (-100 - (w))
+/* which of the statement's aggregates a candidate's source is; -1: none (COUNT(*), a window item or a table column) */
+static inline int colsrc_agg(int tbl) { return tbl <= -2 && tbl > -100 ? -2 - tbl : -1; }
+/* ... which of its window items; -1: none */
+static inline int colsrc_win(int tbl) { return tbl <= -100 ? -100 - tbl : -1; }
 
 /* What one SELECT statement's stages share beside the stream (struct exec): the result column plan and the statement's shape, computed
  * once (select_shape) */
@@ -141,6 +152,7 @@ struct select_stmt {
 	bool split_ok;			/* ws holds the WHERE clause's conjuncts (where_split) */
 	bool only_count;		/* SELECT COUNT(*) alone, no GROUP BY */
 	bool has_agg;			/* SUM / MIN / MAX / AVG in the select list */
+	bool has_win;			/* a window function in the select list: the general plan only */
 	bool fused_chain;		/* the single-key fused plan applies; fkeys[t] = table t's key field of the chain */
 	const struct mdb_expr *fkeys[MDB_MAX_TABS];
 	bool keys_only;			/* the keys-only plan applies; kj[0..1] = the two key fields */
@@ -167,6 +179,11 @@ int check_predicate_x(const struct mdb_expr *e, const char *clause, bool dml, ch
 int check_predicate(const struct mdb_expr *e, const char *clause, char *err, size_t errlen);
 bool expr_has_count(const struct mdb_expr *e);
 bool expr_has_agg(const struct mdb_expr *e);
+bool expr_has_window(const struct mdb_expr *e);
+bool window_same_over(const struct mdb_expr *a, const struct mdb_expr *b);
+const char *mdb_win_name(int op);
+void mdb_win_result_name(const struct mdb_expr *e, char *out);
+int stream_windows(struct exec *x);
 bool agg_eq(const struct mdb_expr *a, const struct mdb_expr *b);
 const char *mdb_agg_name(int op);
 const char *mdb_agg_open(int op);

@@ -22,6 +22,11 @@ void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values,
 		*values = i >= 0 ? x->d_agg[i] : NULL;
 		*nullbits = i >= 0 ? x->d_agg_nulls[i] : NULL;
 		*rid = NULL;
+	} else if (f->kind == MDB_EX_WINDOW) {	/* a result column of mdb_dev_window over the stream (stream_windows) */
+		const int i = f->win_idx >= 0 && f->win_idx < x->nwin ? f->win_idx : -1;
+		*values = i >= 0 ? x->d_win[i] : NULL;
+		*nullbits = i >= 0 ? x->d_win_nulls[i] : NULL;
+		*rid = NULL;
 	} else if (stream_is_keys(x)) {
 		*values = fused_key_column(x, f->tbl_idx, f->col_idx);
 		*nullbits = NULL;
@@ -36,9 +41,12 @@ void bind_operand(struct exec *x, const struct mdb_expr *f, const void **values,
 
 int pred_slot(struct exec *x, struct pred_prog *p, const struct mdb_expr *f)
 {
-	/* slot keys: (table, column) of a field; -2 COUNT(*); -3 - i the statement's i-th aggregate */
-	const int ak = f->kind == MDB_EX_AGG ? -3 - agg_index(x, f) : 0;
-	const int st = f->kind == MDB_EX_COUNT ? -2 : f->kind == MDB_EX_AGG ? ak : f->tbl_idx, sc = f->kind == MDB_EX_COUNT ? -2 : f->kind == MDB_EX_AGG ? ak : f->col_idx;
+	/* slot keys: (table, column) of a field; -2 COUNT(*); -3 - i the statement's i-th aggregate; -100 - i its i-th window item */
+	const int ak = f->kind == MDB_EX_AGG ? -3 - agg_index(x, f) : f->kind == MDB_EX_WINDOW ? -100 - f->win_idx : 0;
+	const bool computed = f->kind == MDB_EX_AGG || f->kind == MDB_EX_WINDOW;
+	const int st = f->kind == MDB_EX_COUNT ? -2 : computed ? ak : f->tbl_idx, sc = f->kind == MDB_EX_COUNT ? -2 : computed ? ak : f->col_idx;
+	if (f->kind == MDB_EX_WINDOW && (f->win_idx < 0 || f->win_idx >= x->nwin))
+		return -1;
 	if (f->kind == MDB_EX_AGG && agg_index(x, f) < 0)
 		return -1;
 	for (int i = 0; i < p->ncols; i++)
@@ -247,8 +255,8 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 		return pred_emit(p, e->op == 0 ? MDB_P_AND : (e->op == 1 ? MDB_P_OR : MDB_P_XOR), 0, 0, 0, 0, 0);
 	case MDB_EX_CMP: {
 		const struct mdb_expr *l = e->kids[0], *r = e->kids[1];
-		const bool lcol = l->kind == MDB_EX_FIELD || l->kind == MDB_EX_COUNT || l->kind == MDB_EX_AGG;
-		const bool rcol = r->kind == MDB_EX_FIELD || r->kind == MDB_EX_COUNT || r->kind == MDB_EX_AGG;
+		const bool lcol = l->kind == MDB_EX_FIELD || l->kind == MDB_EX_COUNT || l->kind == MDB_EX_AGG || l->kind == MDB_EX_WINDOW;
+		const bool rcol = r->kind == MDB_EX_FIELD || r->kind == MDB_EX_COUNT || r->kind == MDB_EX_AGG || r->kind == MDB_EX_WINDOW;
 		if (lcol && rcol) {
 			if (l->kind == MDB_EX_FIELD && l->type == MDB_CT_TINYINT && e->op != MDB_CMP_EQ && e->op != MDB_CMP_NE)
 				return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);

@@ -74,6 +74,112 @@ static int resolve_agg(struct mdb_select *s, struct mdb_expr *e, char *err, size
 	return MIDORIDB_OK;
 }
 
+/* ------------------------------------------------------------------ window functions: fn(...) OVER (PARTITION BY ... ORDER BY ...)
+ * An extension.  The function's text as its result column is named without an alias: "ROW_NUMBER() OVER", "SUM(A.v) OVER" */
+const char *mdb_win_name(int op)
+{
+	static const char *const names[] = { "?", "ROW_NUMBER", "RANK", "DENSE_RANK", "COUNT", "SUM", "MIN", "MAX", "AVG" };
+	return op >= MDB_WIN_ROW_NUMBER && op <= MDB_WIN_AVG ? names[op] : names[0];
+}
+
+/* the aggregate function a window function folds with (enum mdb_agg_op), 0: a ranking function or COUNT(*) */
+static int win_agg_op(int op)
+{
+	return op == MDB_WIN_SUM ? MDB_AGG_SUM : op == MDB_WIN_MIN ? MDB_AGG_MIN : op == MDB_WIN_MAX ? MDB_AGG_MAX : op == MDB_WIN_AVG ? MDB_AGG_AVG : 0;
+}
+
+/* the result column's name of a resolved window item without an alias: the function's text as aggregates are named, then " OVER" */
+void mdb_win_result_name(const struct mdb_expr *e, char *out /* [MDB_NAME_LEN] */)
+{
+	if (e->op >= MDB_WIN_SUM)
+		snprintf(out, MDB_NAME_LEN, "%s(%.56s.%.56s) OVER", mdb_win_name(e->op), e->tbl, e->col);
+	else
+		snprintf(out, MDB_NAME_LEN, "%s OVER", e->op == MDB_WIN_COUNT ? "COUNT(*)" : e->op == MDB_WIN_ROW_NUMBER ? "ROW_NUMBER()" :
+						       e->op == MDB_WIN_RANK ? "RANK()" : "DENSE_RANK()");
+}
+
+bool expr_has_window(const struct mdb_expr *e)
+{
+	if (!e)
+		return false;
+	if (e->kind == MDB_EX_WINDOW)
+		return true;
+	for (int i = 0; i < e->nkids; i++)
+		if (expr_has_window(e->kids[i]))
+			return true;
+	return false;
+}
+
+/* two resolved window items share one operator call when their OVER clauses are equal field for field */
+bool window_same_over(const struct mdb_expr *a, const struct mdb_expr *b)
+{
+	const int na = a->op >= MDB_WIN_SUM ? 1 : 0, nb = b->op >= MDB_WIN_SUM ? 1 : 0;
+	if (a->win_npart != b->win_npart || a->win_norder != b->win_norder || a->win_desc != b->win_desc)
+		return false;
+	for (int k = 0; k < a->win_npart + a->win_norder; k++)
+		if (!field_eq(a->kids[na + k], b->kids[nb + k]))
+			return false;
+	return true;
+}
+
+/* a window item as the parser left it: its fields are resolved and the type rules of resolve_agg are applied to its argument - no function
+ * over VARCHAR, no SUM / AVG over DATE / DATETIME, and no SUM / AVG over DOUBLE (a scan sums in another order than any sequential reference
+ * would) -; PARTITION BY takes a column of any type (cells compare as in GROUP BY), ORDER BY what the statement's ORDER BY takes */
+static int resolve_window(struct mdb_select *s, struct mdb_expr *e, char *err, size_t errlen)
+{
+	const int narg = e->op >= MDB_WIN_SUM ? 1 : 0;
+	int rc;
+
+	if (e->op < MDB_WIN_ROW_NUMBER || e->op > MDB_WIN_AVG || e->win_npart < 0 || e->win_norder < 0 || e->nkids != narg + e->win_npart + e->win_norder) {
+		ERR("error while running syntax analysis on query\n");
+		return -MIDORIDB_ERROR;
+	}
+	for (int k = 0; k < e->nkids; k++) {
+		if (e->kids[k]->kind != MDB_EX_NAME && e->kids[k]->kind != MDB_EX_FIELD) {
+			ERR("%s ... OVER takes columns: col or tbl.col\n", mdb_win_name(e->op));
+			return -MIDORIDB_ERROR;
+		}
+		if ((rc = resolve_expr(s, e->kids[k], err, errlen)))
+			return rc;
+	}
+	if (e->win_npart + e->win_norder > MDB_SORT_MAX_KEYS) {
+		ERR("%s ... OVER: more than %d PARTITION BY and ORDER BY fields together are not supported\n", mdb_win_name(e->op), MDB_SORT_MAX_KEYS);
+		return -MIDORIDB_ERROR;
+	}
+	for (int k = 0; k < e->win_norder; k++) {
+		const struct mdb_expr *o = e->kids[narg + e->win_npart + k];
+		if (o->type == MDB_CT_VARCHAR) {	/* cells are dictionary ids: equality only, no collation order */
+			ERR("ORDER BY over the VARCHAR column '%s.%s' inside OVER is not supported on the MI355X path\n", o->tbl, o->col);
+			return -MIDORIDB_ERROR;
+		}
+	}
+	e->type = MDB_CT_INTEGER;
+	if (narg) {
+		const struct mdb_expr *c = e->kids[0];
+		if (c->type == MDB_CT_VARCHAR) {
+			ERR("%s ... OVER over the VARCHAR column '%.100s.%.100s' is not supported: its cells are dictionary ids, which are not in string order\n",
+			    mdb_win_name(e->op), c->tbl, c->col);
+			return -MIDORIDB_ERROR;
+		}
+		if ((e->op == MDB_WIN_SUM || e->op == MDB_WIN_AVG) && (c->type == MDB_CT_DATE || c->type == MDB_CT_DATETIME)) {
+			ERR("%s ... OVER over the %s column '%.100s.%.100s' is not supported: only MIN and MAX of a point in time mean something\n",
+			    mdb_win_name(e->op), c->type == MDB_CT_DATE ? "DATE" : "DATETIME", c->tbl, c->col);
+			return -MIDORIDB_ERROR;
+		}
+		if ((e->op == MDB_WIN_SUM || e->op == MDB_WIN_AVG) && c->type == MDB_CT_DOUBLE) {
+			ERR("%s ... OVER over the DOUBLE column '%.100s.%.100s' is not supported: a scan would sum in another order than a sequential reference does\n",
+			    mdb_win_name(e->op), c->tbl, c->col);
+			return -MIDORIDB_ERROR;
+		}
+		mdb_copy_name(e->tbl, c->tbl);
+		mdb_copy_name(e->col, c->col);
+		e->tbl_idx = c->tbl_idx;
+		e->col_idx = c->col_idx;
+		e->type = mdb_agg_result_type(win_agg_op(e->op), c->type);
+	}
+	return MIDORIDB_OK;
+}
+
 /* the aggregates under a HAVING / ORDER BY expression that repeat their function and column (an alias has been replaced by its item already):
  * each must be one of the select list's - the executor computes those and nothing else */
 static int resolve_agg_refs(struct mdb_select *s, struct mdb_expr *e, const char *clause, char *err, size_t errlen)
@@ -126,6 +232,11 @@ static void subst_alias(const struct mdb_select *s, struct mdb_expr *e, bool cou
 				e->kind = MDB_EX_COUNT;
 				e->op = to->op;
 				e->ival = to->ival;
+			} else if (to->kind == MDB_EX_WINDOW && agg_ok) {	/* (resolved; the copy has no kid and stands for the item's result column) */
+				e->kind = MDB_EX_WINDOW;
+				e->op = to->op;
+				e->win_idx = to->win_idx;
+				e->type = to->type;
 			} else if (to->kind == MDB_EX_AGG && agg_ok) {	/* (resolved; the copy has no kid) */
 				e->kind = MDB_EX_AGG;
 				e->op = to->op;
@@ -138,7 +249,7 @@ static void subst_alias(const struct mdb_select *s, struct mdb_expr *e, bool cou
 			return;
 		}
 	}
-	if (e->kind == MDB_EX_AGG)
+	if (e->kind == MDB_EX_AGG || e->kind == MDB_EX_WINDOW)
 		return;		/* (the argument of an aggregate is a column, never an alias) */
 	for (int i = 0; i < e->nkids; i++)
 		subst_alias(s, e->kids[i], count_ok, agg_ok);
@@ -214,7 +325,7 @@ bool is_having_clause(const char *clause)
 int operand_type(const struct mdb_expr *o, const struct mdb_expr *other, bool dml)
 {
 	switch (o->kind) {
-	case MDB_EX_FIELD: case MDB_EX_AGG: return o->type;	/* (an aggregate: its result's type) */
+	case MDB_EX_FIELD: case MDB_EX_AGG: case MDB_EX_WINDOW: return o->type;	/* (an aggregate, a window item: its result's type) */
 	case MDB_EX_INT: case MDB_EX_COUNT: return MDB_CT_INTEGER;
 	case MDB_EX_FLOAT: return MDB_CT_DOUBLE;
 	case MDB_EX_BOOL: return MDB_CT_TINYINT;
@@ -238,8 +349,12 @@ int check_predicate_x(const struct mdb_expr *e, const char *clause, bool dml, ch
 		const struct mdb_expr *l = e->kids[0], *r = e->kids[1];
 		for (int i = 0; i < 2; i++) {
 			const struct mdb_expr *o = e->kids[i];
-			if ((o->kind == MDB_EX_COUNT || o->kind == MDB_EX_AGG) && is_having_clause(clause))
+			if ((o->kind == MDB_EX_COUNT || o->kind == MDB_EX_AGG || o->kind == MDB_EX_WINDOW) && is_having_clause(clause))
 				continue;
+			if (o->kind == MDB_EX_WINDOW) {
+				ERR("a window function can't be used in the %s-clause: name its alias in HAVING or ORDER BY\n", clause);
+				return -MIDORIDB_ERROR;
+			}
 			if (o->kind != MDB_EX_FIELD && o->kind != MDB_EX_INT && o->kind != MDB_EX_FLOAT && o->kind != MDB_EX_NULL &&
 			    o->kind != MDB_EX_BOOL && o->kind != MDB_EX_STRING) {
 				ERR("expressions in %s clause must compare columns with literal values\n", clause);
@@ -367,7 +482,7 @@ int fields_in_select_list(const struct mdb_select *s, const struct mdb_expr *e, 
 			return -MIDORIDB_ERROR;
 		}
 	}
-	if (e->kind == MDB_EX_COUNT || e->kind == MDB_EX_AGG)
+	if (e->kind == MDB_EX_COUNT || e->kind == MDB_EX_AGG || e->kind == MDB_EX_WINDOW)
 		return MIDORIDB_OK;	/* (an aggregate's column need not be selected: the aggregate itself must be, resolve_agg_refs) */
 	for (int i = 0; i < e->nkids; i++)
 		if ((rc = fields_in_select_list(s, e->kids[i], clause, err, errlen)))
@@ -490,7 +605,7 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		if (e->kind != MDB_EX_ALIAS || e->nkids != 1)
 			continue;
 		struct mdb_expr *kid = e->kids[0];
-		if (kid->kind != MDB_EX_NAME && kid->kind != MDB_EX_FIELD && kid->kind != MDB_EX_COUNT && kid->kind != MDB_EX_AGG)
+		if (kid->kind != MDB_EX_NAME && kid->kind != MDB_EX_FIELD && kid->kind != MDB_EX_COUNT && kid->kind != MDB_EX_AGG && kid->kind != MDB_EX_WINDOW)
 			continue;	/* (an aliased expression: rejected below like the expression itself) */
 		if (!s->sel_alias && !(s->sel_alias = calloc((size_t)s->nsel, sizeof(*s->sel_alias)))) {
 			ERR("out of memory\n");
@@ -506,9 +621,25 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		mdb_expr_free(e);
 		s->sel[i] = kid;
 	}
-	int nagg = 0;
+	int nagg = 0, nwin = 0;
 	for (int i = 0; i < s->nsel; i++) {
 		struct mdb_expr *e = s->sel[i];
+		if (e->kind == MDB_EX_WINDOW) {
+			/* fn(...) OVER (...): an extension (upstream has no OVER clause) */
+			if (nwin == MDB_WIN_MAX_FNS) {
+				ERR("more than %d window functions in one select list are not supported\n", MDB_WIN_MAX_FNS);
+				return -MIDORIDB_ERROR;
+			}
+			if (cat->dist) {
+				/* (known from the statement alone: every rank leaves here together, before anything is exchanged) */
+				ERR("sharded mode: %s ... OVER is not executed (window functions run on one GPU)\n", mdb_win_name(e->op));
+				return -MIDORIDB_ERROR;
+			}
+			if ((rc = resolve_window(s, e, err, errlen)))
+				return rc;
+			e->win_idx = nwin++;
+			continue;
+		}
 		if (e->kind == MDB_EX_COUNT) {
 			for (int k = 0; k < e->nkids; k++)
 				if ((rc = resolve_expr(s, e->kids[k], err, errlen)))
@@ -533,6 +664,10 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 				return rc;
 			continue;
 		}
+		if (expr_has_window(e)) {
+			ERR("a window function inside an expression is not supported: fn(...) OVER (...) stands alone in the select list, with or without an alias\n");
+			return -MIDORIDB_ERROR;
+		}
 		if (e->kind != MDB_EX_NAME && e->kind != MDB_EX_FIELD) {
 			ERR("only columns, COUNT(*) and SUM / MIN / MAX / AVG of a column - with or without an alias - are supported in the select list (expressions are not executed by the reference)\n");
 			return -MIDORIDB_ERROR;
@@ -540,6 +675,19 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		if ((rc = resolve_expr(s, e, err, errlen)))
 			return rc;
 	}
+	/* two window items without an alias that would name their result columns alike (their windows may differ: the name does not say) */
+	for (int i = 0; nwin > 1 && i < s->nsel; i++)
+		for (int k = 0; k < i; k++) {
+			char a[MDB_NAME_LEN], b[MDB_NAME_LEN];
+			if (s->sel[i]->kind != MDB_EX_WINDOW || s->sel[k]->kind != MDB_EX_WINDOW || (s->sel_alias && (s->sel_alias[i][0] || s->sel_alias[k][0])))
+				continue;
+			mdb_win_result_name(s->sel[i], a);
+			mdb_win_result_name(s->sel[k], b);
+			if (strcmp(a, b) == 0) {
+				ERR("duplicate column name: '%s'\n", a);
+				return -MIDORIDB_ERROR;
+			}
+		}
 	for (int t = 1; t < s->ntabs; t++)
 		if (s->on[t]) {
 			if (expr_has_subquery(s->on[t])) {
@@ -568,7 +716,18 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 	/* S4: with GROUP BY or COUNT, every plain select field must be a GROUP BY field */
 	{
 		int ncount = 0, nfield = 0;
+		if (nwin && s->ngroup) {
+			ERR("a window function beside GROUP BY is not supported on the MI355X path\n");
+			return -MIDORIDB_ERROR;
+		}
+		for (int i = 0; nwin && i < s->nsel; i++)
+			if (s->sel[i]->kind == MDB_EX_COUNT || s->sel[i]->kind == MDB_EX_AGG) {
+				ERR("a window function beside COUNT(*) or an aggregate without OVER is not supported on the MI355X path\n");
+				return -MIDORIDB_ERROR;
+			}
 		for (int i = 0; i < s->nsel; i++) {
+			if (s->sel[i]->kind == MDB_EX_WINDOW)
+				continue;	/* (a value per row, like a field; no field of the statement has to be selected for it) */
 			if (s->sel[i]->kind == MDB_EX_COUNT || s->sel[i]->kind == MDB_EX_AGG) {	/* (an aggregate stands where COUNT(*) may) */
 				ncount++;
 				continue;
@@ -625,6 +784,8 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		for (int i = 0; i < s->norder; i++) {
 			struct mdb_expr *o = s->order[i];
 			subst_alias(s, o, false, true);
+			if (o->kind == MDB_EX_WINDOW)	/* a window item by its alias: ordered by its result column */
+				continue;
 			if (o->kind == MDB_EX_AGG) {	/* an aggregate of the select list, repeated or by its alias: ordered by its result column */
 				if ((rc = resolve_agg_refs(s, o, "ORDER BY", err, errlen)))
 					return rc;

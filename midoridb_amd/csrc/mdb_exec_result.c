@@ -122,7 +122,8 @@ static int result_column_open(const struct exec *x, const struct result_cols *rc
 	memcpy(res->colname[c], rc->keys[key], MDB_NAME_LEN);
 	for (int i = 0; s->sel_alias && !s->select_all && i < s->nsel; i++) {
 		const struct mdb_expr *e = s->sel[i];
-		const bool is_item = colsrc_agg(tbl) >= 0  ? e->kind == MDB_EX_AGG && agg_index(x, e) == colsrc_agg(tbl)
+		const bool is_item = colsrc_win(tbl) >= 0  ? e->kind == MDB_EX_WINDOW && e->win_idx == colsrc_win(tbl)
+				     : colsrc_agg(tbl) >= 0  ? e->kind == MDB_EX_AGG && agg_index(x, e) == colsrc_agg(tbl)
 				     : tbl == COLSRC_COUNT ? e->kind == MDB_EX_COUNT
 							   : e->kind == MDB_EX_FIELD && e->tbl_idx == tbl && e->col_idx == rc->col[key];
 		if (s->sel_alias[i][0] && is_item) {
@@ -199,6 +200,19 @@ static int locate_column(struct exec *x, const struct select_stmt *st, struct md
 			}
 			pj->d_vals[c] = x->d_agg[a];
 			pj->d_nulls[c] = x->d_agg_nulls[a];
+		}
+		return MIDORIDB_OK;
+	}
+	if (colsrc_win(tbl) >= 0) {	/* a window item: a typed column with its NULL bitmap, one row per row of the stream */
+		const int w = colsrc_win(tbl);
+		res->coltype[c] = x->win_item[w]->type;
+		if (pj->out_rows) {
+			if (!x->d_win[w]) {
+				snprintf(x->err, x->errlen, "execution phase: internal error (window function not computed)\n");
+				return -MIDORIDB_INTERNAL;
+			}
+			pj->d_vals[c] = x->d_win[w];
+			pj->d_nulls[c] = x->d_win_nulls[w];
 		}
 		return MIDORIDB_OK;
 	}

@@ -45,15 +45,15 @@ int select_tail(struct exec *x, int has_count)
 			}
 		/* (DISTINCT beside SUM / MIN / MAX / AVG - the one case in which it meets a grouped stream: rows are equal when their aggregate
 		 * columns, and COUNT(*) when it is selected, are equal too) */
-		for (int i = 0; x->nagg && i < s->nsel; i++) {
-			if (s->sel[i]->kind != MDB_EX_COUNT && s->sel[i]->kind != MDB_EX_AGG)
+		for (int i = 0; (x->nagg || x->nwin) && i < s->nsel; i++) {	/* (... and so are a window item's columns) */
+			if (s->sel[i]->kind != MDB_EX_COUNT && s->sel[i]->kind != MDB_EX_AGG && s->sel[i]->kind != MDB_EX_WINDOW)
 				continue;
 			if (nk == MDB_SORT_MAX_KEYS) {
 				snprintf(x->err, x->errlen, "DISTINCT over more than %d columns is not supported\n", MDB_SORT_MAX_KEYS);
 				return -MIDORIDB_ERROR;
 			}
 			bind_operand(x, s->sel[i], &keys[nk].values, &keys[nk].nullbits, &keys[nk].rid);
-			keys[nk].type = s->sel[i]->kind == MDB_EX_AGG && s->sel[i]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
+			keys[nk].type = s->sel[i]->kind != MDB_EX_COUNT && s->sel[i]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;
 			keys[nk].desc = 0;
 			nk++;
 		}

@@ -128,6 +128,7 @@ struct mdb_catalog {
 	uint64_t composite_fused;	/* SELECT statements answered by the fused join + GROUP BY operator on a packed composite key (mdb_exec_join.c, composite_fused_plan) */
 	uint64_t aggregate_calls[2];	/* mdb_dev_group_aggregate calls of SELECT statements by form: [0] groups in LDS, [1] sorted segments (mdb_exec.c) */
 	uint64_t count_distinct_calls[2];	/* COUNT(DISTINCT col) items of SELECT statements answered by mdb_dev_group_count_distinct, by form: [0] bitmap, [1] sorted (mdb_exec.c) */
+	uint64_t window_calls;		/* mdb_dev_window calls of SELECT statements: one per distinct OVER clause of a statement (mdb_exec.c, stream_windows) */
 	uint64_t in_set_lookups;	/* IN / NOT IN lists compiled to one device lookup (mdb_exec_pred.c, pred_compile_in_lookup) */
 	uint64_t subquery_sets;		/* IN / NOT IN (SELECT ...): device sets built from a subquery's result column (mdb_exec.c, subqueries_eval) */
 	bool groups_any_order;		/* mdb_database_groups_any_order(): GROUP BY over a join need not keep first-occurrence order */
@@ -189,6 +190,10 @@ enum mdb_expr_kind {
 	MDB_EX_ALIAS,		/* alias wrapper around kid[0] */
 	MDB_EX_AGG,		/* SUM / MIN / MAX / AVG (col): op = enum mdb_agg_op, kid[0] = the column; resolved: tbl_idx / col_idx / tbl / col are the
 				 * column's, type = the RESULT's column type (mdb_agg_result_type) */
+	MDB_EX_WINDOW,		/* fn(...) OVER (PARTITION BY ... ORDER BY ...): op = enum mdb_win_op; kids = the argument of SUM / MIN / MAX / AVG (none
+				 * for the other four), then win_npart partition fields, then win_norder order fields (bit i of win_desc: order field
+				 * i is DESC); resolved: tbl_idx / col_idx / tbl / col are the argument's, type = the RESULT's column type, win_idx =
+				 * which of the statement's window items it is.  A copy that stands for the item by its alias (HAVING, ORDER BY) has no kids */
 };
 
 struct mdb_expr {
@@ -203,6 +208,8 @@ struct mdb_expr {
 	int nkids;
 	/* resolution (FIELD): index into the plan's FROM tables and the column index there */
 	int tbl_idx, col_idx, type;
+	int win_npart, win_norder, win_idx;	/* MDB_EX_WINDOW */
+	uint32_t win_desc;
 	/* MDB_EX_ISIN over a subquery: the nested statement, owned by the node (mdb_expr_free) and deliberately NOT among `kids` - the
 	 * outer statement's walkers never descend into it; it is resolved and run on its own.  The executor evaluates it once, before
 	 * the outer statement's plan is chosen (subqueries_eval, mdb_exec.c; subqueries_release ends it): sub_set = the device set of its one column, alive until the outer

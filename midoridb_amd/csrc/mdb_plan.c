@@ -15,7 +15,7 @@
 /* wrapper node kinds that only live on the builder stack */
 enum {
 	BX_TABLE = 100, BX_JOIN, BX_ONEXPR, BX_WHERE, BX_GROUPBY, BX_HAVING, BX_ORDERBYITEM, BX_ORDERBYLIST,
-	BX_LIMIT, BX_SELECTALL, BX_ASSIGN,
+	BX_LIMIT, BX_SELECTALL, BX_ASSIGN, BX_WINORDER,
 	BX_SELECT,	/* a finished "SELECT d n": the plan in `sub` - the statement itself, or a subquery's once "SUBQUERY" has wrapped it */
 	BX_SUBQUERY,
 };
@@ -466,6 +466,53 @@ int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, s
 				e->op = fn;
 				if (pop_n_into(&st, 1, e))
 					FAIL("error while running syntax analysis on query\n");
+			}
+		} else if (starts(t, "WINORDER ")) {
+			/* an ORDER BY field of an OVER clause behind its column: "WINORDER 0 | 1" (ASC | DESC) */
+			if (st.n < 1 || (st.v[st.n - 1]->kind != MDB_EX_NAME && st.v[st.n - 1]->kind != MDB_EX_FIELD))
+				FAIL("error while running syntax analysis on query\n");
+			e = ex_new(BX_WINORDER);
+			if (e) {
+				e->op = atoi(t + 9) != 0;
+				if (pop_n_into(&st, 1, e))
+					FAIL("error while running syntax analysis on query\n");
+			}
+		} else if (starts(t, "WINDOW ")) {
+			/* "WINDOW fn npart norder" closes a window item: behind the argument of SUM / MIN / MAX / AVG (NAME / FIELDNAME; none for
+			 * the other functions), the npart partition fields and the norder "WINORDER" items.  op = enum mdb_win_op */
+			static const char *const fns[] = { "", "ROW_NUMBER", "RANK", "DENSE_RANK", "COUNT", "SUM", "MIN", "MAX", "AVG" };
+			int fn = 0, narg;
+			if (sscanf(t + 7, "%15s %d %d", a, &x, &y) != 3 || x < 0 || y < 0 || x > 4096 || y > 4096)
+				FAIL("error while running syntax analysis on query\n");
+			for (int k = MDB_WIN_ROW_NUMBER; k <= MDB_WIN_AVG; k++)
+				if (!strcmp(a, fns[k]))
+					fn = k;
+			narg = fn >= MDB_WIN_SUM ? 1 : 0;
+			if (!fn || st.n < narg + x + y)
+				FAIL("error while running syntax analysis on query\n");
+			for (int k = 0; k < narg + x + y; k++) {
+				const int kind = st.v[st.n - (narg + x + y) + k]->kind;
+				if (k < narg + x ? kind != MDB_EX_NAME && kind != MDB_EX_FIELD : kind != BX_WINORDER)
+					FAIL("error while running syntax analysis on query\n");
+			}
+			if (y > 32)
+				FAIL("too many ORDER BY fields in an OVER clause\n");
+			e = ex_new(MDB_EX_WINDOW);
+			if (e) {
+				e->op = fn;
+				e->win_npart = x;
+				e->win_norder = y;
+				e->win_idx = -1;
+				if (pop_n_into(&st, narg + x + y, e))
+					FAIL("error while running syntax analysis on query\n");
+				for (int k = 0; k < y; k++) {	/* unwrap the order items: the field stays, its direction goes into win_desc */
+					struct mdb_expr *w = e->kids[narg + x + k];
+					if (w->op)
+						e->win_desc |= 1u << k;
+					e->kids[narg + x + k] = w->kids[0];
+					w->nkids = 0;
+					mdb_expr_free(w);
+				}
 			}
 		} else if (!strcmp(t, "LIKE") || !strcmp(t, "NOTLIKE")) {
 			e = ex_new(MDB_EX_LIKE);

@@ -334,6 +334,12 @@ unsigned long long mdb_database_subquery_sets(struct database *db)
 	return cat ? cat->subquery_sets : 0ull;
 }
 
+unsigned long long mdb_database_window_calls(struct database *db)
+{
+	struct mdb_catalog *cat = db ? db->tables : NULL;
+	return cat ? cat->window_calls : 0ull;
+}
+
 int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_form, unsigned long long *sorted_form)
 {
 	struct mdb_catalog *cat = db ? db->tables : NULL;

@@ -16,6 +16,22 @@
  *   CREATE TABLE [IF NOT EXISTS] t (col type [attrs], ...) ;
  *   INSERT [INTO] t [(cols)] VALUES (...), (...) ;
  *
+ * Window functions - an extension, in a SELECT list only (the reference's grammar has no OVER clause):
+ *
+ *   ROW_NUMBER() | RANK() | DENSE_RANK() | COUNT(*) | SUM(col) | MIN(col) | MAX(col) | AVG(col)
+ *       OVER ( [PARTITION BY f, ...] [ORDER BY f [ASC|DESC], ...] )          f: col | tbl.col
+ *
+ * emit this project's own tokens, in the style of "AGG SUM":
+ *
+ *   [NAME col | FIELDNAME tbl.col]          the argument of SUM / MIN / MAX / AVG (nothing for the other four)
+ *   NAME | FIELDNAME ...                    the PARTITION BY fields, in order
+ *   NAME | FIELDNAME, WINORDER d ...        every ORDER BY field, wrapped: d = 0 ASC, 1 DESC
+ *   WINDOW fn npart norder                  closes the item: fn = ROW_NUMBER | RANK | DENSE_RANK | COUNT | SUM | MIN | MAX | AVG
+ *
+ * No word becomes reserved for it: ROW_NUMBER / RANK / DENSE_RANK are functions only with the parenthesis right behind the name (as
+ * SUM( is), OVER is a window only behind the `)` of one of the eight functions and in front of `(`, PARTITION only inside that
+ * parenthesis.  `SELECT SUM(v) over FROM A` still aliases the aggregate as `over`.
+ *
  * Operator precedence follows midorisql.y:48-63; literal lexing follows
  * midorisql.l:83-92 (a '-' directly in front of digits belongs to the number).
  * The emitted queue is accepted unchanged by the reference's ast_build_tree()
@@ -26,7 +42,7 @@
 #include <strings.h>
 
 enum tk {
-	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_FAGG, T_ANDOP, T_OROP, T_ERR
+	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_FAGG, T_FWIN, T_ANDOP, T_OROP, T_ERR
 };
 
 static const char *const KEYWORDS[] = {
@@ -55,6 +71,7 @@ struct parser {
 	bool failed;
 	bool dml;		/* inside delete_expr / update_expr: names, literals, logic, comparisons, IS NULL, IN only */
 	int depth;		/* nested SELECTs open: IN (SELECT ...) */
+	bool sel_list;		/* inside the select list of a SELECT: the one place where fn(...) OVER (...) is a window function */
 };
 
 #define MAX_SUBQUERY_DEPTH 8
@@ -241,6 +258,12 @@ static void next(struct parser *p)
 			strcpy(l->text, up);
 			return;
 		}
+		/* ROW_NUMBER( RANK( DENSE_RANK( - the ranking window functions, functions only with the parenthesis right behind the name: a
+		 * column, table or alias called `rank` stays a name (text keeps the spelling: CREATE TABLE rank(...) names a table) */
+		if (s[j] == '(' && (strcmp(up, "ROW_NUMBER") == 0 || strcmp(up, "RANK") == 0 || strcmp(up, "DENSE_RANK") == 0)) {
+			l->type = T_FWIN;
+			return;
+		}
 		if (strcmp(up, "TRUE") == 0 || strcmp(up, "FALSE") == 0 || strcmp(up, "UNKNOWN") == 0) {
 			l->type = T_BOOL;
 			l->ival = up[0] == 'T' ? 1 : (up[0] == 'F' ? 0 : -1);
@@ -358,7 +381,7 @@ static void parse_select(struct parser *p);
  * the parentheses the grammar is SELECT's, whatever the outer statement is. */
 static void parse_subquery(struct parser *p)
 {
-	const bool dml = p->dml;
+	const bool dml = p->dml, sel_list = p->sel_list;
 
 	if (p->depth >= MAX_SUBQUERY_DEPTH) {
 		fail(p, "syntax error, subqueries nested deeper than %d", MAX_SUBQUERY_DEPTH);
@@ -370,7 +393,147 @@ static void parse_subquery(struct parser *p)
 	parse_select(p);
 	p->depth--;
 	p->dml = dml;
+	p->sel_list = sel_list;
 	emit(p, "SUBQUERY");
+}
+
+/* ------------------------------------------------------------------ window functions: fn(...) OVER ( ... )
+ * No word is reserved for them.  The lexer stands behind the `)` of one of the eight functions: OVER opens a window only as the name
+ * `over` with `(` as the next token; with another name behind it, it is a named window, which gets its own error. */
+static const char *skip_blank(const char *q)
+{
+	while (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r')
+		q++;
+	return q;
+}
+
+static bool name_is(const struct lexer *l, const char *word)
+{
+	return l->type == T_NAME && strcasecmp(l->text, word) == 0;
+}
+
+/* 0: no window behind the function (what follows is an alias or the next clause), 1: OVER ( follows, -1: failed (a named window) */
+static int over_follows(struct parser *p)
+{
+	const char *q;
+
+	if (p->failed || !name_is(&p->lx, "over"))
+		return 0;
+	q = skip_blank(p->lx.s + p->lx.pos);
+	if (*q == '(')
+		return 1;
+	if (isalpha((unsigned char)*q) || *q == '`') {
+		char up[16];
+		size_t k = 0;
+		while (k < sizeof(up) - 1 && (isalnum((unsigned char)q[k]) || q[k] == '_')) {
+			up[k] = (char)toupper((unsigned char)q[k]);
+			k++;
+		}
+		up[k] = 0;
+		if (*q == '`' || (!is_keyword(up) && !isalnum((unsigned char)q[k]) && q[k] != '_') || k == sizeof(up) - 1) {
+			fail(p, "syntax error, named windows (OVER name, WINDOW name AS ...) are not supported: write the window out, OVER ( ... )");
+			return -1;
+		}
+	}
+	return 0;
+}
+
+/* the text from q (behind an opening parenthesis) up to its closing one, then OVER ( : does a window clause follow this function call?
+ * A scan of the raw text that knows nothing of string literals or back-quoted names: a parenthesis inside one - COUNT(s = ')') - is
+ * counted like any other.  It only chooses between two error texts for statements that are refused either way (COUNT(col) OVER, DISTINCT
+ * inside a window function) or falls through to the path these forms took before: the worst a mis-scan gives is the other message. */
+static bool over_behind_call(const char *q)
+{
+	int depth = 1;
+	while (*q && depth) {
+		if (*q == '(')
+			depth++;
+		else if (*q == ')')
+			depth--;
+		q++;
+	}
+	if (depth)
+		return false;
+	q = skip_blank(q);
+	if (strncasecmp(q, "over", 4) != 0 || isalnum((unsigned char)q[4]) || q[4] == '_')
+		return false;
+	return *skip_blank(q + 4) == '(';
+}
+
+static bool window_field(struct parser *p)
+{
+	char first[256];
+
+	if (p->lx.type != T_NAME) {
+		fail(p, "syntax error, PARTITION BY and ORDER BY inside OVER take columns: col or tbl.col");
+		return false;
+	}
+	strcpy(first, p->lx.text);
+	next(p);
+	if (is_punct(p, '.')) {
+		next(p);
+		if (p->lx.type != T_NAME) {
+			fail(p, "syntax error, expecting column name after '.'");
+			return false;
+		}
+		emit(p, "FIELDNAME %s.%s", first, p->lx.text);
+		next(p);
+	} else {
+		emit(p, "NAME %s", first);
+	}
+	return !p->failed;
+}
+
+/* the lexer stands on OVER (over_follows() == 1); the function's argument, if it has one, is emitted already */
+static void parse_over(struct parser *p, const char *fn)
+{
+	int npart = 0, norder = 0;
+
+	if (p->dml) {
+		fail(p, "window function %s ... OVER can't be used in DELETE / UPDATE", fn);
+		return;
+	}
+	if (!p->sel_list) {
+		fail(p, "window function %s ... OVER is allowed in the select list only (not in WHERE, ON, GROUP BY, HAVING, ORDER BY or LIMIT)", fn);
+		return;
+	}
+	next(p);
+	expect_punct(p, '(');
+	if (p->failed)
+		return;
+	if (name_is(&p->lx, "partition")) {
+		next(p);
+		expect_kw(p, "BY");
+		do {
+			if (p->failed || !window_field(p))
+				return;
+			npart++;
+		} while (is_punct(p, ',') && (next(p), true));
+	}
+	if (accept_kw(p, "ORDER")) {
+		expect_kw(p, "BY");
+		do {
+			int desc = 0;
+			if (p->failed || !window_field(p))
+				return;
+			if (accept_kw(p, "DESC"))
+				desc = 1;
+			else
+				accept_kw(p, "ASC");
+			emit(p, "WINORDER %d", desc);
+			norder++;
+		} while (is_punct(p, ',') && (next(p), true));
+	}
+	if (name_is(&p->lx, "rows") || name_is(&p->lx, "range") || name_is(&p->lx, "groups")) {
+		fail(p, "syntax error, window frame clauses (ROWS / RANGE / GROUPS) are not supported: the frame is SQL's default, up to the row's peers");
+		return;
+	}
+	if (p->lx.type == T_NAME && !is_punct(p, ')')) {
+		fail(p, "syntax error, unexpected '%s' in OVER ( [PARTITION BY f, ...] [ORDER BY f [ASC|DESC], ...] ): named windows are not supported", p->lx.text);
+		return;
+	}
+	expect_punct(p, ')');
+	emit(p, "WINDOW %s %d %d", fn, npart, norder);
 }
 
 static int parse_val_list(struct parser *p)
@@ -386,6 +549,7 @@ static int parse_val_list(struct parser *p)
 static void parse_primary(struct parser *p)
 {
 	struct lexer *l = &p->lx;
+	const char *behind_paren;
 
 	if (p->failed)
 		return;
@@ -435,8 +599,16 @@ static void parse_primary(struct parser *p)
 			}
 			break;
 		}
+		behind_paren = l->s + l->pos + 1;	/* (COUNT( is lexed with its parenthesis right behind the name) */
 		next(p);
 		expect_punct(p, '(');
+		if (!p->failed && !is_punct(p, '*') && over_behind_call(behind_paren)) {
+			if (p->lx.type == T_KW && !strcmp(p->lx.text, "DISTINCT"))
+				fail(p, "syntax error, DISTINCT inside a window function is not supported: COUNT(DISTINCT col) OVER");
+			else
+				fail(p, "syntax error, COUNT(col) OVER is not supported: COUNT(*) OVER counts the rows of the frame");
+			return;
+		}
 		if (p->lx.type == T_KW && !strcmp(p->lx.text, "DISTINCT")) {
 			/* COUNT(DISTINCT col) | COUNT(DISTINCT tbl.col): one column and nothing else, as SUM(col) - no descent into parentheses:
 			 * "NAME col" / "FIELDNAME tbl.col", then "AGG COUNTD" */
@@ -468,6 +640,15 @@ static void parse_primary(struct parser *p)
 		} else if (is_punct(p, '*')) {
 			next(p);
 			expect_punct(p, ')');
+			{
+				const int ov = over_follows(p);
+				if (ov < 0)
+					return;
+				if (ov) {
+					parse_over(p, "COUNT");
+					return;
+				}
+			}
 			emit(p, "COUNTALL");
 		} else {
 			parse_expr(p, P_OR);
@@ -487,6 +668,10 @@ static void parse_primary(struct parser *p)
 		expect_punct(p, '(');
 		if (p->failed)
 			return;
+		if (p->lx.type == T_KW && !strcmp(p->lx.text, "DISTINCT") && over_behind_call(l->s + l->pos)) {
+			fail(p, "syntax error, DISTINCT inside a window function is not supported: %s(DISTINCT col) OVER", fn);
+			return;
+		}
 		if (p->lx.type != T_NAME) {
 			fail(p, "syntax error, %s takes one column: %s(col) or %s(tbl.col)", fn, fn, fn);
 			return;
@@ -509,7 +694,48 @@ static void parse_primary(struct parser *p)
 			return;
 		}
 		next(p);
+		{
+			const int ov = over_follows(p);
+			if (ov < 0)
+				return;
+			if (ov) {
+				parse_over(p, fn);
+				return;
+			}
+		}
 		emit(p, "AGG %s", fn);
+		return;
+	}
+	case T_FWIN: {
+		/* ROW_NUMBER() | RANK() | DENSE_RANK(): no argument, and nothing without its OVER clause */
+		char fn[16];
+		size_t k = 0;
+		for (; l->text[k] && k < sizeof(fn) - 1; k++)
+			fn[k] = (char)toupper((unsigned char)l->text[k]);
+		fn[k] = 0;
+		if (p->dml) {
+			fail(p, "window function %s ... OVER can't be used in DELETE / UPDATE", fn);
+			return;
+		}
+		next(p);
+		expect_punct(p, '(');
+		if (p->failed)
+			return;
+		if (!is_punct(p, ')')) {
+			fail(p, "syntax error, %s() takes no argument", fn);
+			return;
+		}
+		next(p);
+		{
+			const int ov = over_follows(p);
+			if (ov < 0)
+				return;
+			if (!ov) {
+				fail(p, "syntax error, %s() needs its window: %s() OVER ( [PARTITION BY f, ...] [ORDER BY f [ASC|DESC], ...] )", fn, fn);
+				return;
+			}
+		}
+		parse_over(p, fn);
 		return;
 	}
 	case T_KW:
@@ -679,7 +905,9 @@ static void parse_select(struct parser *p)
 		nsel = 1;
 	} else {
 		do {
+			p->sel_list = true;
 			parse_expr(p, P_OR);
+			p->sel_list = false;
 			parse_opt_alias(p);
 			nsel++;
 		} while (!p->failed && is_punct(p, ',') && (next(p), true));
@@ -713,6 +941,10 @@ static void parse_select(struct parser *p)
 		parse_expr(p, P_OR);
 		emit(p, "HAVING");
 		extra++;
+	}
+	if (name_is(&p->lx, "window")) {
+		fail(p, "syntax error, named windows (OVER name, WINDOW name AS ...) are not supported: write the window out, OVER ( ... )");
+		return;
 	}
 	if (accept_kw(p, "ORDER")) {
 		int n = 0;
@@ -756,6 +988,8 @@ static void parse_create(struct parser *p)
 		expect_kw(p, "EXISTS");
 		ifne = 1;
 	}
+	if (p->lx.type == T_FWIN)	/* (a table called `rank`, its parenthesis right behind the name) */
+		p->lx.type = T_NAME;
 	if (p->lx.type != T_NAME) {
 		fail(p, "syntax error, expecting table name");
 		return;
@@ -887,6 +1121,8 @@ static void parse_insert(struct parser *p)
 	int hascols = 0, ntuples = 0;
 
 	accept_kw(p, "INTO");
+	if (p->lx.type == T_FWIN)	/* (a table called `rank`, its parenthesis right behind the name) */
+		p->lx.type = T_NAME;
 	if (p->lx.type != T_NAME) {
 		fail(p, "syntax error, expecting table name");
 		return;

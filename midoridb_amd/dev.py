@@ -23,6 +23,8 @@ CMP_LT, CMP_GT, CMP_NE, CMP_EQ, CMP_LE, CMP_GE = 1, 2, 3, 4, 5, 6
 T_INT64, T_DOUBLE = 0, 1
 AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG = 1, 2, 3, 4     # enum mdb_agg_op
 AGG_IDENTITY = -1                                   # MDB_AGG_IDENTITY: group i is row i
+WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX, WIN_AVG = 1, 2, 3, 4, 5, 6, 7, 8     # enum mdb_win_op
+WIN_MAX_FNS = 8                                     # MDB_WIN_MAX_FNS
 
 
 class PredInsn(ctypes.Structure):
@@ -61,6 +63,11 @@ class Agg(ctypes.Structure):     # struct mdb_agg (include/mdb_dev.h)
 class CountDistinct(ctypes.Structure):     # struct mdb_count_distinct (include/mdb_dev.h)
     _fields_ = [("type", c_int32), ("has_range", c_int32), ("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p), ("min", c_int64),
                 ("max", c_int64), ("out", c_void_p)]
+
+
+class WindowFn(ctypes.Structure):     # struct mdb_window_fn (include/mdb_dev.h)
+    _fields_ = [("op", c_int32), ("type", c_int32), ("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p), ("out", c_void_p),
+                ("out_nullbits", c_void_p)]
 
 
 class GatherCol(ctypes.Structure):
@@ -279,6 +286,7 @@ def _bind(lib):
         "mdb_dev_group_count_distinct": ([P, POINTER(SortKey), c_int, c_uint64, P, c_uint64, POINTER(CountDistinct), c_int, POINTER(c_uint32)], c_int),
         "mdb_dev_group_count_distinct_lds_groups": ([], c_uint64),
         "mdb_dev_count_distinct_bitmap_bits": ([], c_uint64),
+        "mdb_dev_window": ([P, POINTER(SortKey), c_int, POINTER(SortKey), c_int, c_uint64, POINTER(WindowFn), c_int, POINTER(c_uint32)], c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -298,6 +306,7 @@ DEV_SYMBOLS = [
     "mdb_set_build", "mdb_set_image_free", "mdb_set_image_contains", "mdb_dev_set_create", "mdb_dev_set_from_column", "mdb_dev_set_insn", "mdb_dev_set_free", "mdb_dev_in_set_lds_values",
     "mdb_dev_group_aggregate", "mdb_dev_group_aggregate_lds_groups",
     "mdb_dev_group_count_distinct", "mdb_dev_group_count_distinct_lds_groups", "mdb_dev_count_distinct_bitmap_bits",
+    "mdb_dev_window",
 ]
 
 
@@ -1029,6 +1038,32 @@ class DeviceCtx:
     def count_distinct_bitmap_bits(self):
         """MDB_COUNT_DISTINCT_BITMAP_BITS: the most bits group_count_distinct's bitmap form takes (mdb_dev_count_distinct_bitmap_bits)"""
         return int(self.lib.mdb_dev_count_distinct_bitmap_bits())
+
+    def window(self, part, order, n, fns, outs=None, nulls=None):
+        """Window functions over one window (mdb_dev_window).  part / order = the PARTITION BY / ORDER BY key columns as sort_perm takes
+        them ([]: none), fns = [(WIN_ROW_NUMBER | WIN_RANK | WIN_DENSE_RANK | WIN_COUNT,), ... or (WIN_SUM | WIN_MIN | WIN_MAX | WIN_AVG,
+        T_INT64 | T_DOUBLE, values, nullbits or None, rid or None), ...].  outs / nulls: the callers' own result tensors (n cells of 8 bytes;
+        (n + 63) // 64 int64 words) per function, allocated here when not given -> (result columns in stream order: int64 or float64
+        tensors of n cells, their NULL words: int64 tensors, the form: 1 no keys, 2 sorted)."""
+        arr = (WindowFn * len(fns))()
+        res, words = [], []
+        for i, fn in enumerate(fns):
+            op = fn[0]
+            ty, v, nb, rid = (tuple(fn[1:]) + (None,) * 4)[:4] if len(fn) > 1 else (T_INT64, None, None, None)
+            as_double = op == WIN_AVG or (op in (WIN_MIN, WIN_MAX) and ty == T_DOUBLE)
+            out = outs[i] if outs is not None else torch.zeros(max(n, 1), dtype=torch.float64 if as_double else torch.int64, device=self.device)
+            onb = nulls[i] if nulls is not None else torch.zeros((n + 63) // 64 or 1, dtype=torch.int64, device=self.device)
+            arr[i].op, arr[i].type = op, ty
+            arr[i].values = v.data_ptr() if v is not None else None
+            arr[i].nullbits = nb.data_ptr() if nb is not None else None
+            arr[i].rid = rid.data_ptr() if rid is not None else None
+            arr[i].out, arr[i].out_nullbits = out.data_ptr(), onb.data_ptr()
+            res.append(out)
+            words.append(onb)
+        form = c_uint32(0)
+        self._chk(self.lib.mdb_dev_window(self.h, self._sort_keys(part) if part else None, len(part), self._sort_keys(order) if order else None,
+                                          len(order), n, arr, len(fns), byref(form)), "window")
+        return [o[:n] for o in res], [w[:(n + 63) // 64] for w in words], form.value
 
     def group_aggregate_lds_groups(self, naggs):
         """the largest group count the LDS form of group_aggregate takes for naggs aggregates (mdb_dev_group_aggregate_lds_groups)"""
