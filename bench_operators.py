@@ -280,6 +280,53 @@ def window_rows(dev, res, n=100_000_000):
     res["window_1e8"] = out
 
 
+def setops_rows(dev, res, n_probe=100_000_000, n_build=10_000_000):
+    """setops: 10^8 probe rows x 10^7 build rows over one and over two INT64 columns, wall time per call with its synchronisation after
+    a warm-up call.  rows_semi_ms = mdb_dev_rows_semi alone (every probe row, no DISTINCT in front); distinct_sel_ms = mdb_dev_distinct_sel
+    over the probe side alone, the statement's first step; intersect_ms = the whole
+    SELECT ... INTERSECT SELECT ... through query_execute(), the result kept on the device; and, for one column, in_subquery_ms = the
+    statement that could be written before there were set operations, SELECT DISTINCT k FROM A WHERE k IN (SELECT k FROM B) - the same rows
+    while k holds no NULL.  Column 0: A a permutation of [0, 10^8) modulo 2 * 10^7, B a permutation of [0, 10^7) - half of A's rows are
+    members; column 1: modulo 4 on both sides."""
+    from midoridb_amd.query import DB
+    out = {"probe_rows": n_probe, "build_rows": n_build, "cases": {}}
+    with DB() as db:
+        db.execute("CREATE TABLE A (k INT, k2 INT);")
+        db.execute("CREATE TABLE B (j INT, j2 INT);")
+        db.generate("A", n_probe, 42, [2 * n_build, 4])
+        db.generate("B", n_build, 52, [0, 4])
+        db.results_on_device(True)
+        pk = [dev.gen_keys(n_probe, 0, n_probe, 42, 2 * n_build), dev.gen_keys(n_probe, 0, n_probe, 43, 4)]
+        bk = [dev.gen_keys(n_build, 0, n_build, 52, 0), dev.gen_keys(n_build, 0, n_build, 53, 4)]
+        for ncols, la, lb in ((1, "k", "j"), (2, "k, k2", "j, j2")):
+            probe = [(c, None, None, D.T_INT64, False) for c in pk[:ncols]]
+            build = [(c, None, None, D.T_INT64, False) for c in bk[:ncols]]
+            ms, kern, (sel, info) = timed(dev, lambda: dev.rows_semi(probe, n_probe, build, n_build), reps=2, warmup=1)
+            case = {"columns": ncols, "rows_semi_ms": ms, "rows_semi_hits": int(sel.numel()), "members": info["members"], "log2_slots": info["log2_slots"],
+                    "form": info["form"], "kernels_ms": kern}
+            del sel
+            dms, dkern, first = timed(dev, lambda: dev.distinct_sel(probe, n_probe), reps=1, warmup=1)      # (the statement's first step, alone)
+            case.update({"distinct_sel_ms": dms, "distinct_rows": int(first.numel()), "distinct_kernels_ms": dkern})
+            del first
+            sql = f"SELECT {la} FROM A INTERSECT SELECT {lb} FROM B;"
+            runs = []
+            for _ in range(3):
+                got = db.query_device(sql, copy=False)
+                runs.append(db.last_call_ms)
+            case.update({"intersect_ms": min(runs[1:]), "intersect_ms_all": runs, "intersect_rows": got[3]})
+            if ncols == 1:
+                sub = "SELECT DISTINCT k FROM A WHERE k IN (SELECT j FROM B);"
+                runs = []
+                for _ in range(3):
+                    got = db.query_device(sub, copy=False)
+                    runs.append(db.last_call_ms)
+                case.update({"in_subquery_ms": min(runs[1:]), "in_subquery_ms_all": runs, "in_subquery_rows": got[3]})
+                assert case["in_subquery_rows"] == case["intersect_rows"]
+            out["cases"][f"int64x{ncols}"] = case
+            torch.cuda.empty_cache()
+    res["setops"] = out
+
+
 def subquery_rows(dev, res):
     """subquery_set: the right side of k IN (SELECT ...) as a device set - make_set_from_column (mdb_dev_set_from_column: scan, fill,
     insert, and the rebuild where the members need a smaller table) beside the route that existed before it for the same cells: the
@@ -365,9 +412,19 @@ def main():
                                                                    "mdb_dev_group_count_multi over (k, v))")
     ap.add_argument("--window", action="store_true", help="only the window functions' row (window_1e8: ROW_NUMBER and SUM(v) OVER (PARTITION BY k ORDER BY o) "
                                                            "at 4, 1000 and 10^6 partitions, beside mdb_dev_sort_perm alone on the same keys)")
+    ap.add_argument("--setops", action="store_true", help="only the set operations' row (setops: 10^8 probe rows x 10^7 build rows over one and two "
+                                                           "INT64 columns - mdb_dev_rows_semi alone, the whole INTERSECT statement, and for one column "
+                                                           "SELECT DISTINCT ... WHERE k IN (SELECT ...))")
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
+    if args.setops:
+        setops_rows(dev, res)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     if args.window:
         window_rows(dev, res)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -519,6 +519,45 @@ int mdb_dev_distinct_sel(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int 
 int mdb_dev_group_count_multi(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint32_t *out_first,
 			      int64_t *out_count, uint64_t cap, uint64_t *out_groups);
 
+/* ------------------------------------------------------------------ row sets: UNION [ALL], INTERSECT, EXCEPT
+ *
+ * An extension (the reference's grammar has no set operators).  Whole-row semi- / anti-join: out_sel[0..*out_count) = the ASCENDING
+ * probe positions p for which some build row equals probe row p on every one of the ncols columns (anti != 0: for which none does).
+ * Columns are read as struct mdb_sort_key is read everywhere - cell i is values[rid ? rid[i] : i], NULL by its NULL bit or by a row
+ * id of MDB_NO_ROW; `desc` is ignored - and equality is mdb_dev_distinct_sel's: NULL equals NULL, the value bits under a NULL cell
+ * do not count, MDB_T_INT64 and MDB_T_DOUBLE cells compare by their 64 bits (-0.0 != +0.0, a NaN equals the NaN of the same bits).
+ * probe[c].type must equal build[c].type.  n_build == 0: the empty selection, with anti every position; n_probe == 0: nothing.
+ * out_sel has room for n_probe entries.  -MIDORIDB_ERROR with a message, the context usable afterwards: ncols outside
+ * 1..MDB_ROWS_MAX_COLS, n_build > MDB_ROWS_MAX_BUILD, n_probe > 2^32 - 2, a type mismatch.  Synchronous; the same input gives the
+ * same bytes.
+ *
+ * The build rows go into an open-addressing table in global memory: 2^log2_slots uint32 slots (a power of two, at least 16 and at
+ * least 2 n_build) that hold a build row number and nothing else; linear probing from the top log2_slots bits of a 64-bit row hash
+ * that every bit of every cell reaches (a NULL cell: a constant and its flag).  info (may be NULL): members = the distinct build
+ * rows (where in the table two equal build rows meet is free), form = 1, the one form there is. */
+#define MDB_ROWS_MAX_COLS 16		/* = MDB_SORT_MAX_KEYS */
+#define MDB_ROWS_MAX_BUILD (1ull << 30)
+struct mdb_dev_rows_info {
+	uint64_t members;
+	uint32_t log2_slots;
+	uint32_t form;
+};
+int mdb_dev_rows_semi(mdb_dev_ctx *ctx, const struct mdb_sort_key *probe, uint64_t n_probe, const struct mdb_sort_key *build, uint64_t n_build,
+		      int ncols, int anti, uint32_t *out_sel, uint64_t *out_count, struct mdb_dev_rows_info *info);
+
+/* The column of a UNION: the 8-byte cells of parts[0], parts[1], ... one behind the other in dst.  The NULL bits of part k begin at
+ * bit offset sum(n of the parts before it) - in general no multiple of 64; a part without a bitmap contributes zero bits; every one
+ * of the (sum n + 63) / 64 words of dst_nullbits is written, the bits behind the last row are zero.  dst_nullbits may be NULL when
+ * no part has a bitmap.  At most MDB_CONCAT_MAX_PARTS parts; the whole concatenation is one launch.  Asynchronous on the context's
+ * stream. */
+#define MDB_CONCAT_MAX_PARTS 16
+struct mdb_concat_part {
+	const void *values;
+	const uint64_t *nullbits;	/* or NULL */
+	uint64_t n;
+};
+int mdb_dev_concat64(mdb_dev_ctx *ctx, const struct mdb_concat_part *parts, int nparts, void *dst, uint64_t *dst_nullbits);
+
 /* ------------------------------------------------------------------ INNER JOIN (materialising)
  *
  * Replaces _join_nested_loop_tbl2tbl() for ON l = r (reference

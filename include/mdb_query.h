@@ -183,6 +183,9 @@ int mdb_database_count_distinct_calls(struct database *db, unsigned long long *b
 /* Window functions, fn(...) OVER (PARTITION BY ... ORDER BY ...) (an extension too): mdb_dev_window (mdb_dev.h) calls of this database's
  * SELECT statements so far - one per distinct OVER clause of a statement: the items whose windows are equal field for field share a call. */
 unsigned long long mdb_database_window_calls(struct database *db);
+/* Set operations, SELECT ... UNION [ALL] | INTERSECT | EXCEPT SELECT ... (an extension too): mdb_dev_rows_semi (mdb_dev.h) calls of this
+ * database's compound statements so far - one per INTERSECT / EXCEPT step of a chain, none for UNION [ALL]. */
+unsigned long long mdb_database_setop_calls(struct database *db);
 
 /* mdb_table_generate() for one shard of a table spread over several processes: this process holds rows
  * [first_index, first_index + n) of a table of `domain` rows.  INTEGER column c = perm_{seed+c}(i) mod modulus[c] as above;

@@ -1388,7 +1388,57 @@ static int sharded_finish(struct exec *x, const struct select_stmt *st)
 	return MIDORIDB_OK;
 }
 
+/* The result columns a RESOLVED statement will deliver, without running it and without a device: their number, and result column c's name
+ * and column type - what a compound checks its arms by before any of them runs.  select_signature_free() whatever is returned. */
+int select_signature(struct mdb_select *s, struct select_signature *sig, char *err, size_t errlen)
+{
+	struct exec x;
+	struct result_cols rc;
+	int r;
+
+	memset(&x, 0, sizeof(x));
+	memset(&rc, 0, sizeof(rc));
+	memset(sig, 0, sizeof(*sig));
+	x.s = s;
+	x.err = err;
+	x.errlen = errlen;
+	if (!(r = result_cols_build(&x, &rc))) {
+		sig->ncols = rc.ncols;
+		sig->name = calloc((size_t)(rc.ncols ? rc.ncols : 1), sizeof(*sig->name));
+		sig->type = calloc((size_t)(rc.ncols ? rc.ncols : 1), sizeof(int));
+		sig->at = calloc((size_t)(rc.ncols ? rc.ncols : 1), sizeof(int));
+		if (!sig->name || !sig->type || !sig->at)
+			r = -MIDORIDB_NOMEM;
+		for (int c = 0; !r && c < rc.ncols; c++) {
+			int before = 0;		/* (the columns whose items stand in front of this one's: no two share a place) */
+			result_column_name(&x, &rc, c, sig->name[c]);
+			sig->type[c] = result_column_type(&x, &rc, c);
+			for (int d = 0; d < rc.ncols; d++)
+				before += result_column_list_place(&x, &rc, d) < result_column_list_place(&x, &rc, c);
+			sig->at[before] = c;
+		}
+	}
+	if (r == -MIDORIDB_NOMEM)
+		ERR("out of memory\n");
+	result_cols_free(&rc);
+	return r;
+}
+
+void select_signature_free(struct select_signature *sig)
+{
+	free(sig->name);
+	free(sig->type);
+	free(sig->at);
+	memset(sig, 0, sizeof(*sig));
+}
+
 int mdb_exec_select(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_result **out, char *err, size_t errlen)
+{
+	return s->nset ? exec_setop(cat, s, out, err, errlen) : exec_select_one(cat, s, out, err, errlen);
+}
+
+/* one SELECT: a whole statement, a subquery, or an arm of a compound */
+int exec_select_one(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_result **out, char *err, size_t errlen)
 {
 	stmt_dict = &cat->dict;
 	struct exec x;

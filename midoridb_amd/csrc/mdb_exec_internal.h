@@ -2,7 +2,8 @@
  * mdb_exec_internal.h - what the files of the executor share (mdb_exec.c: SELECT lowering - the driver, its plan stages, the stream
  * helpers; mdb_exec_join.c: one more FROM table into the stream, composite join keys; mdb_exec_result.c: projection and result assembly;
  * mdb_exec_resolve.c: plan normalisation and the semantic checks; mdb_exec_pred.c: predicate programs; mdb_exec_shard.c: sharded mode;
- * mdb_exec_tail.c: HAVING / DISTINCT / ORDER BY / LIMIT; mdb_exec_dml.c: CREATE / INSERT / DELETE / UPDATE).  Nothing here is part of the
+ * mdb_exec_tail.c: HAVING / DISTINCT / ORDER BY / LIMIT; mdb_exec_setop.c: UNION [ALL] / INTERSECT / EXCEPT over the results of several SELECTs;
+ * mdb_exec_dml.c: CREATE / INSERT / DELETE / UPDATE).  Nothing here is part of the
  * library's interface.
  */
 #ifndef MDB_EXEC_INTERNAL_H
@@ -239,6 +240,25 @@ double now_ms(void);
 int fused_chain(struct mdb_select *s, const struct mdb_expr **keys, bool count_only);
 bool keys_only_join(const struct mdb_select *s, const struct mdb_catalog *cat, const struct result_cols *rc, bool has_agg, const struct mdb_expr **kj);
 int select_tail(struct exec *x, int has_count);
+uint64_t order_rows_wanted(uint64_t n, bool has_limit, int64_t limit_off, int64_t limit_cnt);
+int order_perm(mdb_dev_ctx *dev, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint64_t want, uint32_t *perm);
+void limit_window(uint64_t n, int64_t limit_off, int64_t limit_cnt, uint64_t *off, uint64_t *cnt);
+const char *coltype_name(int type);
+void result_column_name(const struct exec *x, const struct result_cols *rc, int c, char *out);
+int result_column_type(const struct exec *x, const struct result_cols *rc, int c);
+/* a compound statement (UNION [ALL] / INTERSECT / EXCEPT; mdb_exec_setop.c) and what it asks of the executor of one SELECT */
+int result_column_list_place(const struct exec *x, const struct result_cols *rc, int c);
+struct select_signature {
+	int ncols;
+	char (*name)[MDB_NAME_LEN];	/* result column c's name and column type */
+	int *type;
+	int *at;			/* at[i] = the result column that the i-th (different) item of the select list delivers: a result's columns stand
+					 * in the reference's order (R3), the arms of a compound correspond by their lists */
+};
+int select_signature(struct mdb_select *s, struct select_signature *sig, char *err, size_t errlen);
+void select_signature_free(struct select_signature *sig);
+int exec_select_one(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_result **out, char *err, size_t errlen);
+int exec_setop(struct mdb_catalog *cat, struct mdb_select *s, struct mdb_result **out, char *err, size_t errlen);
 int dml_value_on_left(const struct mdb_expr *e);
 int dml_check_values(const struct mdb_expr *e, char *err, size_t errlen);
 int dml_select_rows(struct mdb_catalog *cat, struct mdb_dml *d, struct exec *x, struct mdb_select *s, struct mdb_from_tab *tab, bool complement, struct mdb_table **out_t, const uint32_t **sel, uint64_t *m, char *err, size_t errlen);

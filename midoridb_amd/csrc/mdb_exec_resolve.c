@@ -506,7 +506,7 @@ bool expr_has_subquery(const struct mdb_expr *e)
 	return false;
 }
 
-static const char *coltype_name(int type)
+const char *coltype_name(int type)
 {
 	switch (type) {
 	case MDB_CT_VARCHAR: return "VARCHAR";

@@ -113,24 +113,56 @@ static int result_alloc(struct mdb_result *res, struct projection *pj, int ncols
 	return MIDORIDB_OK;
 }
 
-/* result column c's name - its candidate's, or the alias of its select-list item (`item AS name`; the first alias of an item wins) -
- * and, for a result that goes to the host, its host column */
-static int result_column_open(const struct exec *x, const struct result_cols *rc, struct mdb_result *res, const struct projection *pj, int c)
+/* does select-list item e deliver result column c? */
+static bool item_is_column(const struct exec *x, const struct result_cols *rc, int c, const struct mdb_expr *e)
+{
+	const int key = rc->src[c], tbl = rc->tbl[key];
+	return colsrc_win(tbl) >= 0  ? e->kind == MDB_EX_WINDOW && e->win_idx == colsrc_win(tbl)
+	       : colsrc_agg(tbl) >= 0  ? e->kind == MDB_EX_AGG && agg_index(x, e) == colsrc_agg(tbl)
+	       : tbl == COLSRC_COUNT ? e->kind == MDB_EX_COUNT
+				     : e->kind == MDB_EX_FIELD && e->tbl_idx == tbl && e->col_idx == rc->col[key];
+}
+
+/* result column c's name: its candidate's, or the alias of its select-list item (`item AS name`; the first alias of an item wins) */
+void result_column_name(const struct exec *x, const struct result_cols *rc, int c, char *out)
 {
 	const struct mdb_select *s = x->s;
-	const int key = rc->src[c], tbl = rc->tbl[key];
-	memcpy(res->colname[c], rc->keys[key], MDB_NAME_LEN);
-	for (int i = 0; s->sel_alias && !s->select_all && i < s->nsel; i++) {
-		const struct mdb_expr *e = s->sel[i];
-		const bool is_item = colsrc_win(tbl) >= 0  ? e->kind == MDB_EX_WINDOW && e->win_idx == colsrc_win(tbl)
-				     : colsrc_agg(tbl) >= 0  ? e->kind == MDB_EX_AGG && agg_index(x, e) == colsrc_agg(tbl)
-				     : tbl == COLSRC_COUNT ? e->kind == MDB_EX_COUNT
-							   : e->kind == MDB_EX_FIELD && e->tbl_idx == tbl && e->col_idx == rc->col[key];
-		if (s->sel_alias[i][0] && is_item) {
-			mdb_copy_name(res->colname[c], s->sel_alias[i]);
+	memcpy(out, rc->keys[rc->src[c]], MDB_NAME_LEN);
+	for (int i = 0; s->sel_alias && !s->select_all && i < s->nsel; i++)
+		if (s->sel_alias[i][0] && item_is_column(x, rc, c, s->sel[i])) {
+			mdb_copy_name(out, s->sel_alias[i]);
 			break;
 		}
-	}
+}
+
+/* where result column c stands in the statement's select list: the index of the first item that delivers it; for SELECT * its place among
+ * the FROM tables' columns, left to right.  (The result's own column order is the reference's, R3 - not the list's.) */
+int result_column_list_place(const struct exec *x, const struct result_cols *rc, int c)
+{
+	const struct mdb_select *s = x->s;
+	for (int i = 0; !s->select_all && i < s->nsel; i++)
+		if (item_is_column(x, rc, c, s->sel[i]))
+			return i;
+	return rc->src[c];
+}
+
+/* result column c's column type: an aggregate's or a window item's result type, INTEGER for COUNT(*), else its table column's */
+int result_column_type(const struct exec *x, const struct result_cols *rc, int c)
+{
+	const int key = rc->src[c], tbl = rc->tbl[key];
+	if (colsrc_agg(tbl) >= 0)
+		return x->agg_type[colsrc_agg(tbl)];
+	if (colsrc_win(tbl) >= 0)
+		return x->win_item[colsrc_win(tbl)]->type;
+	if (tbl == COLSRC_COUNT)
+		return MDB_CT_INTEGER;
+	return x->s->tabs[tbl].t->cols[rc->col[key]].type;
+}
+
+/* result column c's name and, for a result that goes to the host, its host column */
+static int result_column_open(const struct exec *x, const struct result_cols *rc, struct mdb_result *res, const struct projection *pj, int c)
+{
+	result_column_name(x, rc, c, res->colname[c]);
 	if (!pj->keep) {
 		res->data[c] = mdb_dev_host_alloc((size_t)(pj->out_rows ? pj->out_rows : 1) * 8);	/* pinned when large */
 		if (!res->data[c])
@@ -191,8 +223,8 @@ static int locate_column(struct exec *x, const struct select_stmt *st, struct md
 {
 	struct mdb_select *s = x->s;
 	const int key = st->rc.src[c], tbl = st->rc.tbl[key], a = colsrc_agg(tbl);
+	res->coltype[c] = result_column_type(x, &st->rc, c);
 	if (a >= 0) {	/* SUM / MIN / MAX / AVG: an ordinary typed column with its NULL bitmap - one row without GROUP BY */
-		res->coltype[c] = x->agg_type[a];
 		if (pj->out_rows) {
 			if (!x->d_agg[a]) {
 				snprintf(x->err, x->errlen, "execution phase: internal error (aggregate not computed)\n");
@@ -205,7 +237,6 @@ static int locate_column(struct exec *x, const struct select_stmt *st, struct md
 	}
 	if (colsrc_win(tbl) >= 0) {	/* a window item: a typed column with its NULL bitmap, one row per row of the stream */
 		const int w = colsrc_win(tbl);
-		res->coltype[c] = x->win_item[w]->type;
 		if (pj->out_rows) {
 			if (!x->d_win[w]) {
 				snprintf(x->err, x->errlen, "execution phase: internal error (window function not computed)\n");
@@ -217,7 +248,6 @@ static int locate_column(struct exec *x, const struct select_stmt *st, struct md
 		return MIDORIDB_OK;
 	}
 	if (tbl == COLSRC_COUNT) {
-		res->coltype[c] = MDB_CT_INTEGER;
 		if (pj->count_only) {
 			if (pj->out_rows)
 				res->data[c][0] = (int64_t)x->n;
@@ -232,7 +262,6 @@ static int locate_column(struct exec *x, const struct select_stmt *st, struct md
 	}
 	const int col_idx = st->rc.col[key];
 	struct mdb_column *col = &s->tabs[tbl].t->cols[col_idx];
-	res->coltype[c] = col->type;
 	res->colprec[c] = col->type == MDB_CT_VARCHAR ? col->precision : 0;
 	if (!pj->out_rows || pj->count_only)
 		return MIDORIDB_OK;

@@ -4,6 +4,32 @@
  */
 #include "mdb_exec_internal.h"
 
+/* ---- ORDER BY / LIMIT over n rows: what the statement's tail below and a compound's (mdb_exec_setop.c) share */
+
+/* ORDER BY ... LIMIT: only the first offset + count rows of the order are ever looked at */
+uint64_t order_rows_wanted(uint64_t n, bool has_limit, int64_t limit_off, int64_t limit_cnt)
+{
+	if (has_limit && limit_off >= 0 && limit_cnt >= 0 && (uint64_t)limit_off + (uint64_t)limit_cnt < n)
+		return (uint64_t)limit_off + (uint64_t)limit_cnt;
+	return n;
+}
+
+/* perm[0 .. want) = the first `want` positions of the n rows in the keys' order: top-k selection instead of a sort of all rows when fewer
+ * than all are wanted (mdb_dev_topk_perm falls back to the sort by itself when that does not pay) */
+int order_perm(mdb_dev_ctx *dev, const struct mdb_sort_key *keys, int nkeys, uint64_t n, uint64_t want, uint32_t *perm)
+{
+	if (want < n)
+		return want ? mdb_dev_topk_perm(dev, keys, nkeys, n, want, perm, NULL) : MIDORIDB_OK;
+	return mdb_dev_sort_perm(dev, keys, nkeys, n, perm);
+}
+
+/* LIMIT off, cnt over n rows: the rows [*off, *off + *cnt) */
+void limit_window(uint64_t n, int64_t limit_off, int64_t limit_cnt, uint64_t *off, uint64_t *cnt)
+{
+	*off = (uint64_t)limit_off < n ? (uint64_t)limit_off : n;
+	*cnt = (uint64_t)limit_cnt < n - *off ? (uint64_t)limit_cnt : n - *off;
+}
+
 /* HAVING, DISTINCT, ORDER BY, LIMIT over the finished stream (after FROM / WHERE / GROUP BY) */
 int select_tail(struct exec *x, int has_count)
 {
@@ -93,25 +119,18 @@ int select_tail(struct exec *x, int has_count)
 			keys[i].type = s->order[i]->type == MDB_CT_DOUBLE ? MDB_T_DOUBLE : MDB_T_INT64;	/* (an aggregate: its result's type) */
 			keys[i].desc = s->order_desc[i];
 		}
-		/* ORDER BY ... LIMIT: only the first offset + count rows of the order are ever looked at - top-k selection instead
-		 * of a sort of the whole stream (mdb_dev_topk_perm falls back to the sort by itself when that does not pay) */
-		uint64_t want = x->n;
-		if (s->has_limit && s->limit_off >= 0 && s->limit_cnt >= 0 && (uint64_t)s->limit_off + (uint64_t)s->limit_cnt < x->n)
-			want = (uint64_t)s->limit_off + (uint64_t)s->limit_cnt;
+		const uint64_t want = order_rows_wanted(x->n, s->has_limit, s->limit_off, s->limit_cnt);
 		perm = dalloc(x, (want ? want : 1) * 4);
 		if (!perm)
 			return dev_fail(x, "allocating the ORDER BY permutation");
-		if (want < x->n) {
-			if (want && mdb_dev_topk_perm(x->dev, keys, s->norder, x->n, want, perm, NULL))
-				return dev_fail(x, "ORDER BY ... LIMIT");
-		} else if (mdb_dev_sort_perm(x->dev, keys, s->norder, x->n, perm))
-			return dev_fail(x, "ORDER BY");
+		if (order_perm(x->dev, keys, s->norder, x->n, want, perm))
+			return dev_fail(x, want < x->n ? "ORDER BY ... LIMIT" : "ORDER BY");
 		if ((rc = stream_apply_sel(x, s->ntabs, perm, want)))
 			return rc;
 	}
 	if (s->has_limit) {
-		const uint64_t off = (uint64_t)s->limit_off < x->n ? (uint64_t)s->limit_off : x->n;
-		const uint64_t cnt = (uint64_t)s->limit_cnt < x->n - off ? (uint64_t)s->limit_cnt : x->n - off;
+		uint64_t off, cnt;
+		limit_window(x->n, s->limit_off, s->limit_cnt, &off, &cnt);
 		if (off || cnt < x->n) {
 			uint32_t *idx = dalloc(x, (off + cnt ? off + cnt : 1) * 4);
 			if (!idx || mdb_dev_iota32(x->dev, idx, off + cnt))

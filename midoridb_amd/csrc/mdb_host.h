@@ -129,6 +129,7 @@ struct mdb_catalog {
 	uint64_t aggregate_calls[2];	/* mdb_dev_group_aggregate calls of SELECT statements by form: [0] groups in LDS, [1] sorted segments (mdb_exec.c) */
 	uint64_t count_distinct_calls[2];	/* COUNT(DISTINCT col) items of SELECT statements answered by mdb_dev_group_count_distinct, by form: [0] bitmap, [1] sorted (mdb_exec.c) */
 	uint64_t window_calls;		/* mdb_dev_window calls of SELECT statements: one per distinct OVER clause of a statement (mdb_exec.c, stream_windows) */
+	uint64_t setop_calls;		/* mdb_dev_rows_semi calls of compound statements: one per INTERSECT / EXCEPT step, none for UNION [ALL] (mdb_exec_setop.c) */
 	uint64_t in_set_lookups;	/* IN / NOT IN lists compiled to one device lookup (mdb_exec_pred.c, pred_compile_in_lookup) */
 	uint64_t subquery_sets;		/* IN / NOT IN (SELECT ...): device sets built from a subquery's result column (mdb_exec.c, subqueries_eval) */
 	bool groups_any_order;		/* mdb_database_groups_any_order(): GROUP BY over a join need not keep first-occurrence order */
@@ -248,7 +249,21 @@ struct mdb_select {
 	bool has_limit;
 	int64_t limit_off, limit_cnt;	/* LIMIT cnt | LIMIT off, cnt (midorisql.y:193-196) */
 	bool resolved;			/* a subquery's plan: resolve_select() has run over it (with the outer statement's checks) and is not run again */
+	/* a compound (UNION [ALL] / INTERSECT / EXCEPT; mdb_exec_setop.c): this plan is its FIRST arm, set_arm[0 .. nset) are the arms behind
+	 * it (owned), set_op[i] = enum mdb_setop between what stands left of set_arm[i] and set_arm[i] - evaluated left to right.  The arms'
+	 * own order / limit fields are empty; the compound's are set_order (bare names of the first arm's result columns) and set_limit_* */
+	struct mdb_select **set_arm;
+	int *set_op;
+	int nset;
+	bool set_closed;		/* (builder state: "COMPOUND" has closed the chain) */
+	char (*set_order)[MDB_NAME_LEN];
+	int *set_order_desc;
+	int nset_order;
+	bool set_has_limit;
+	int64_t set_limit_off, set_limit_cnt;
 };
+enum mdb_setop { MDB_SETOP_UNION = 1, MDB_SETOP_UNIONALL, MDB_SETOP_INTERSECT, MDB_SETOP_EXCEPT };
+#define MDB_SETOP_MAX_ARMS 8
 
 struct mdb_create {
 	char name[MDB_NAME_LEN];

@@ -5,7 +5,8 @@
  * src/parser/ast_select.c:1021-1140 for SELECT, ast_create.c / ast_insert.c for DDL/DML): every
  * token either pushes a leaf or pops its operands and pushes the combined node; "SELECT d n" pops
  * its n children (select items, table references, then WHERE / GROUP BY / HAVING / ORDER BY /
- * LIMIT wrappers) and "STMT" ends the statement.  The result is a flat struct mdb_select
+ * LIMIT wrappers) and "STMT" ends the statement ("SETOP op" hangs a finished SELECT into the one below it as the next arm of a compound,
+ * "COMPOUND narms norder nlimit" closes that: this project's own words, mdb_sql.c).  The result is a flat struct mdb_select
  * (left-deep join list) instead of the reference's pointer-linked AST: that is the executor's
  * input contract (SURVEY.md 8b "internal seam 1"), normalised later by mdb_exec.c the way the
  * reference optimiser does (optimiser_select.c:114-238, 395-464).
@@ -18,6 +19,8 @@ enum {
 	BX_LIMIT, BX_SELECTALL, BX_ASSIGN, BX_WINORDER,
 	BX_SELECT,	/* a finished "SELECT d n": the plan in `sub` - the statement itself, or a subquery's once "SUBQUERY" has wrapped it */
 	BX_SUBQUERY,
+	BX_SETORDER,	/* an ORDER BY item of a compound: the result column's name in `col`, op = DESC */
+	BX_SETLIMIT,	/* its LIMIT: the one or two integer literals */
 };
 
 static struct mdb_expr *ex_new(int kind)
@@ -574,9 +577,100 @@ int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, s
 			}
 		} else if (!strcmp(t, "SUBQUERY")) {
 			/* (this project's own token, as ISINSUB / ISNOTINSUB: SURVEY.md Appendix A) */
-			if (st.n < 1 || st.v[st.n - 1]->kind != BX_SELECT)
+			if (st.n < 1 || st.v[st.n - 1]->kind != BX_SELECT || st.v[st.n - 1]->sub->nset)	/* (a subquery is one SELECT, no compound) */
 				FAIL("error while running syntax analysis on query\n");
 			st.v[st.n - 1]->kind = BX_SUBQUERY;
+			continue;
+		} else if (starts(t, "SETOP ")) {
+			/* "SETOP UNION | UNIONALL | INTERSECT | EXCEPT" behind the second of two finished SELECTs: the right one becomes the next arm
+			 * of the left one's compound (this project's own tokens, as WINDOW: mdb_sql.c) */
+			const int op = !strcmp(t + 6, "UNION") ? MDB_SETOP_UNION : !strcmp(t + 6, "UNIONALL") ? MDB_SETOP_UNIONALL :
+				       !strcmp(t + 6, "INTERSECT") ? MDB_SETOP_INTERSECT : !strcmp(t + 6, "EXCEPT") ? MDB_SETOP_EXCEPT : 0;
+			if (!op || st.n < 2 || st.v[st.n - 1]->kind != BX_SELECT || st.v[st.n - 2]->kind != BX_SELECT)
+				FAIL("error while running syntax analysis on query\n");
+			struct mdb_select *l = st.v[st.n - 2]->sub, *r = st.v[st.n - 1]->sub;
+			/* (an arm is a plain SELECT without a tail of its own; the chain is still open) */
+			if (r->nset || r->norder || r->has_limit || l->set_closed || (!l->nset && (l->norder || l->has_limit)))
+				FAIL("error while running syntax analysis on query\n");
+			if (l->nset + 1 >= MDB_SETOP_MAX_ARMS)
+				FAIL("more than %d arms in one set operation\n", MDB_SETOP_MAX_ARMS);
+			for (int k = 0; op == MDB_SETOP_INTERSECT && k < l->nset; k++)
+				if (l->set_op[k] != MDB_SETOP_INTERSECT)
+					FAIL("INTERSECT behind UNION or EXCEPT in one chain is not supported: the standard binds INTERSECT tighter, SQLite reads left "
+					     "to right, and there are no parentheses to say which\n");
+			struct mdb_select **na = realloc(l->set_arm, sizeof(*na) * (size_t)(l->nset + 1));
+			if (na)
+				l->set_arm = na;
+			int *no = realloc(l->set_op, sizeof(int) * (size_t)(l->nset + 1));
+			if (no)
+				l->set_op = no;
+			if (!na || !no)
+				goto nomem;
+			struct mdb_expr *rn = pop(&st);
+			l->set_arm[l->nset] = rn->sub;
+			l->set_op[l->nset++] = op;
+			rn->sub = NULL;
+			mdb_expr_free(rn);
+			continue;
+		} else if (starts(t, "SETORDER ")) {
+			/* an ORDER BY item of a compound behind its result column's bare name: "SETORDER 0 | 1" (ASC | DESC) */
+			if (st.n < 1 || st.v[st.n - 1]->kind != MDB_EX_NAME)
+				FAIL("error while running syntax analysis on query\n");
+			st.v[st.n - 1]->kind = BX_SETORDER;
+			st.v[st.n - 1]->op = atoi(t + 9) != 0;
+			continue;
+		} else if (starts(t, "SETLIMIT ")) {
+			x = atoi(t + 9);
+			if (x < 1 || x > 2)
+				FAIL("error while running syntax analysis on query\n");
+			e = ex_new(BX_SETLIMIT);
+			if (e && pop_n_into(&st, x, e)) {
+				e->nkids = 0;	/* (what it took so far is still on the stack, which frees it) */
+				mdb_expr_free(e);
+				FAIL("error while running syntax analysis on query\n");
+			}
+		} else if (starts(t, "COMPOUND ")) {
+			/* "COMPOUND narms norder nlimit" closes a compound: on the stack its first SELECT (the arms are in it), the norder "SETORDER"
+			 * items and, with nlimit = 1, the "SETLIMIT" item */
+			int z;
+			if (sscanf(t + 9, "%d %d %d", &x, &y, &z) != 3 || x < 2 || x > MDB_SETOP_MAX_ARMS || y < 0 || y > 4096 || z < 0 || z > 1 || st.n < 1 + y + z)
+				FAIL("error while running syntax analysis on query\n");
+			struct mdb_expr *first = st.v[st.n - 1 - y - z];
+			if (first->kind != BX_SELECT || first->sub->nset != x - 1 || first->sub->set_closed)
+				FAIL("error while running syntax analysis on query\n");
+			for (int k = 0; k < y; k++)
+				if (st.v[st.n - y - z + k]->kind != BX_SETORDER)
+					FAIL("error while running syntax analysis on query\n");
+			if (z && st.v[st.n - 1]->kind != BX_SETLIMIT)
+				FAIL("error while running syntax analysis on query\n");
+			if (y > MDB_SORT_MAX_KEYS)
+				FAIL("too many ORDER BY items (max %d)\n", MDB_SORT_MAX_KEYS);
+			struct mdb_select *c = first->sub;
+			if (z) {
+				const struct mdb_expr *lim = st.v[st.n - 1];
+				for (int j = 0; j < lim->nkids; j++)
+					if (lim->kids[j]->kind != MDB_EX_INT || lim->kids[j]->ival < 0)
+						FAIL("LIMIT takes non-negative integer literals\n");
+				c->set_has_limit = true;
+				c->set_limit_off = lim->nkids == 2 ? lim->kids[0]->ival : 0;
+				c->set_limit_cnt = lim->kids[lim->nkids - 1]->ival;
+				mdb_expr_free(pop(&st));
+			}
+			if (y) {
+				c->set_order = calloc((size_t)y, sizeof(*c->set_order));
+				c->set_order_desc = calloc((size_t)y, sizeof(int));
+				if (!c->set_order || !c->set_order_desc)
+					goto nomem;
+				for (int k = 0; k < y; k++) {
+					const struct mdb_expr *it = st.v[st.n - y + k];
+					copy_name(c->set_order[k], it->col);
+					c->set_order_desc[k] = it->op;
+				}
+				c->nset_order = y;
+				for (int k = 0; k < y; k++)
+					mdb_expr_free(pop(&st));
+			}
+			c->set_closed = true;
 			continue;
 		} else if (!strcmp(t, "ISINSUB") || !strcmp(t, "ISNOTINSUB")) {
 			struct mdb_expr *sq;
@@ -598,6 +692,8 @@ int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, s
 				goto nomem;
 			}
 		} else if (!strcmp(t, "STMT")) {
+			if (st.n == 1 && st.v[0]->kind == BX_SELECT && !out->kind && st.v[0]->sub->nset && !st.v[0]->sub->set_closed)
+				FAIL("error while running syntax analysis on query\n");	/* (a chain of SETOPs without its COMPOUND) */
 			if (st.n == 1 && st.v[0]->kind == BX_SELECT && !out->kind) {
 				struct mdb_expr *node = pop(&st);
 				out->sel = *node->sub;
@@ -794,6 +890,14 @@ void mdb_select_free(struct mdb_select *s)
 		mdb_expr_free(s->order[i]);
 	free(s->order);
 	free(s->order_desc);
+	for (int i = 0; i < s->nset; i++) {
+		mdb_select_free(s->set_arm[i]);
+		free(s->set_arm[i]);
+	}
+	free(s->set_arm);
+	free(s->set_op);
+	free(s->set_order);
+	free(s->set_order_desc);
 	memset(s, 0, sizeof(*s));
 }
 

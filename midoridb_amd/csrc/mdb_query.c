@@ -340,6 +340,12 @@ unsigned long long mdb_database_window_calls(struct database *db)
 	return cat ? cat->window_calls : 0ull;
 }
 
+unsigned long long mdb_database_setop_calls(struct database *db)
+{
+	struct mdb_catalog *cat = db ? db->tables : NULL;
+	return cat ? cat->setop_calls : 0ull;
+}
+
 int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_form, unsigned long long *sorted_form)
 {
 	struct mdb_catalog *cat = db ? db->tables : NULL;

@@ -32,6 +32,23 @@
  * SUM( is), OVER is a window only behind the `)` of one of the eight functions and in front of `(`, PARTITION only inside that
  * parenthesis.  `SELECT SUM(v) over FROM A` still aliases the aggregate as `over`.
  *
+ * Set operations - an extension too (the reference's grammar has one SELECT per statement):
+ *
+ *   SELECT ... { (UNION [ALL | DISTINCT] | INTERSECT [DISTINCT] | EXCEPT [DISTINCT]) SELECT ... }
+ *       [ORDER BY name [ASC|DESC], ...] [LIMIT [off,] cnt] ;                 at most 8 arms, evaluated left to right
+ *
+ * Every arm emits what it emits as a statement of its own, "SELECT d n" included; then, in the style of "WINDOW fn npart norder":
+ *
+ *   SETOP UNION | UNIONALL | INTERSECT | EXCEPT     behind every arm but the first: combines the two plans on top of the stack
+ *   NAME col, SETORDER d ...                        every ORDER BY item behind the last arm: a bare result column name, d = 0 ASC, 1 DESC
+ *   NUMBER ..., SETLIMIT n                          LIMIT cnt (n = 1) | LIMIT off, cnt (n = 2)
+ *   COMPOUND narms norder nlimit                    closes the compound: nlimit = 0 | 1 (a SETLIMIT item precedes)
+ *
+ * The RPN of a statement without a set operator is what it was.  No word becomes reserved: union, intersect, except and all are
+ * operators only when the token behind them is SELECT, or ALL / DISTINCT followed by SELECT (setop_follows); everywhere else they stay
+ * names and implicit aliases.  A chain in which INTERSECT stands behind UNION or EXCEPT is refused: the standard binds INTERSECT
+ * tighter, SQLite reads left to right, and there are no parentheses to say which.
+ *
  * Operator precedence follows midorisql.y:48-63; literal lexing follows
  * midorisql.l:83-92 (a '-' directly in front of digits belongs to the number).
  * The emitted queue is accepted unchanged by the reference's ast_build_tree()
@@ -72,9 +89,12 @@ struct parser {
 	bool dml;		/* inside delete_expr / update_expr: names, literals, logic, comparisons, IS NULL, IN only */
 	int depth;		/* nested SELECTs open: IN (SELECT ...) */
 	bool sel_list;		/* inside the select list of a SELECT: the one place where fn(...) OVER (...) is a window function */
+	bool arm;		/* parsing an arm of a compound behind the first: ORDER BY / LIMIT are not the arm's, they close the compound */
+	bool had_tail;		/* the SELECT parsed last had an ORDER BY or LIMIT of its own */
 };
 
 #define MAX_SUBQUERY_DEPTH 8
+#define MAX_SETOP_ARMS 8
 
 static void fail(struct parser *p, const char *fmt, ...)
 {
@@ -375,13 +395,14 @@ enum { P_OR = 1, P_XOR = 2, P_AND = 3, P_ISIN = 4, P_NOT = 5, P_CMP = 7, P_ADD =
 
 static void parse_expr(struct parser *p, int min_prec);
 static void parse_select(struct parser *p);
+static int setop_follows(struct parser *p);
 
 /* IN ( SELECT ... ) - an extension (the reference's grammar knows value lists only, midorisql.y:283-284): the lexer stands on SELECT.
  * The inner statement's tokens are emitted in place and end in its own "SELECT d n"; "SUBQUERY" wraps it into one stack entry.  Inside
  * the parentheses the grammar is SELECT's, whatever the outer statement is. */
 static void parse_subquery(struct parser *p)
 {
-	const bool dml = p->dml, sel_list = p->sel_list;
+	const bool dml = p->dml, sel_list = p->sel_list, arm = p->arm;
 
 	if (p->depth >= MAX_SUBQUERY_DEPTH) {
 		fail(p, "syntax error, subqueries nested deeper than %d", MAX_SUBQUERY_DEPTH);
@@ -389,11 +410,15 @@ static void parse_subquery(struct parser *p)
 	}
 	next(p);
 	p->dml = false;
+	p->arm = false;
 	p->depth++;
 	parse_select(p);
 	p->depth--;
 	p->dml = dml;
 	p->sel_list = sel_list;
+	p->arm = arm;
+	if (!p->failed && setop_follows(p) > 0)
+		fail(p, "syntax error, a set operation (UNION / INTERSECT / EXCEPT) inside IN (SELECT ...) is not supported: a subquery is one SELECT");
 	emit(p, "SUBQUERY");
 }
 
@@ -534,6 +559,71 @@ static void parse_over(struct parser *p, const char *fn)
 	}
 	expect_punct(p, ')');
 	emit(p, "WINDOW %s %d %d", fn, npart, norder);
+}
+
+/* ------------------------------------------------------------------ set operations: UNION [ALL] / INTERSECT / EXCEPT
+ * No word is reserved for them either.  The lexer stands on a name: it is a set operator only when SELECT, or ALL / DISTINCT and then
+ * SELECT, stands behind it in the text.  A scan of the raw text, as over_follows(). */
+enum { SETOP_UNION = 1, SETOP_UNIONALL, SETOP_INTERSECT, SETOP_EXCEPT };
+
+/* the word at q, upper-cased, into up; returns the text behind it (q itself when no word stands there) */
+static const char *word_at(const char *q, char *up, size_t cap)
+{
+	size_t k = 0;
+	if (isalpha((unsigned char)*q))
+		while (isalnum((unsigned char)q[k]) || q[k] == '_') {
+			if (k < cap - 1)
+				up[k] = (char)toupper((unsigned char)q[k]);
+			k++;
+		}
+	up[k < cap - 1 ? k : cap - 1] = 0;
+	return q + k;
+}
+
+static bool paren_select_at(const char *q)
+{
+	char up[16];
+	if (*q != '(')
+		return false;
+	word_at(skip_blank(q + 1), up, sizeof(up));
+	return strcmp(up, "SELECT") == 0;
+}
+
+/* 0: the token is no set operator (a name, an alias, or something else altogether), SETOP_*: it is one, -1: failed (a form that is refused) */
+static int setop_follows(struct parser *p)
+{
+	const char *q;
+	char w1[16], w2[16];
+	int op;
+
+	if (p->failed || p->lx.type != T_NAME)
+		return 0;
+	op = name_is(&p->lx, "union") ? SETOP_UNION : name_is(&p->lx, "intersect") ? SETOP_INTERSECT : name_is(&p->lx, "except") ? SETOP_EXCEPT : 0;
+	if (!op)
+		return 0;
+	q = skip_blank(p->lx.s + p->lx.pos);
+	if (paren_select_at(q))
+		goto paren;
+	q = skip_blank(word_at(q, w1, sizeof(w1)));
+	if (strcmp(w1, "SELECT") == 0)
+		return op;
+	if (strcmp(w1, "ALL") != 0 && strcmp(w1, "DISTINCT") != 0)
+		return 0;
+	if (paren_select_at(q))
+		goto paren;
+	word_at(q, w2, sizeof(w2));
+	if (strcmp(w2, "SELECT") != 0)
+		return 0;
+	if (w1[0] == 'D')
+		return op;
+	if (op == SETOP_UNION)
+		return SETOP_UNIONALL;
+	fail(p, "syntax error, %s ALL is not supported: multiset semantics are not built, %s [DISTINCT] is", op == SETOP_INTERSECT ? "INTERSECT" : "EXCEPT",
+	     op == SETOP_INTERSECT ? "INTERSECT" : "EXCEPT");
+	return -1;
+paren:
+	fail(p, "syntax error, a parenthesised SELECT as an arm of a set operation is not supported: write the arms without parentheses, they are evaluated left to right");
+	return -1;
 }
 
 static int parse_val_list(struct parser *p)
@@ -847,7 +937,7 @@ static void parse_opt_alias(struct parser *p)
 		}
 		emit(p, "ALIAS %s", p->lx.text);
 		next(p);
-	} else if (p->lx.type == T_NAME) {
+	} else if (p->lx.type == T_NAME && !setop_follows(p)) {	/* (union / intersect / except in front of a SELECT: the operator, no alias) */
 		emit(p, "ALIAS %s", p->lx.text);
 		next(p);
 	}
@@ -913,6 +1003,7 @@ static void parse_select(struct parser *p)
 		} while (!p->failed && is_punct(p, ',') && (next(p), true));
 	}
 	if (!accept_kw(p, "FROM")) {
+		p->had_tail = false;
 		emit(p, "SELECT %d %d", opts, nsel);
 		return;
 	}
@@ -946,6 +1037,12 @@ static void parse_select(struct parser *p)
 		fail(p, "syntax error, named windows (OVER name, WINDOW name AS ...) are not supported: write the window out, OVER ( ... )");
 		return;
 	}
+	p->had_tail = false;
+	if (p->arm) {	/* (an arm behind the first: what follows closes the compound, parse_compound) */
+		emit(p, "SELECT %d %d", opts, nsel + ntab + extra);
+		return;
+	}
+	p->had_tail = is_kw(p, "ORDER") || is_kw(p, "LIMIT");
 	if (accept_kw(p, "ORDER")) {
 		int n = 0;
 		expect_kw(p, "BY");
@@ -974,6 +1071,89 @@ static void parse_select(struct parser *p)
 		extra++;
 	}
 	emit(p, "SELECT %d %d", opts, nsel + ntab + extra);
+}
+
+/* The lexer stands behind the first SELECT of a statement: the arms that follow, each behind its operator, and the ORDER BY / LIMIT that
+ * close the compound.  Nothing is emitted for a statement without a set operator. */
+static void parse_compound(struct parser *p)
+{
+	static const char *const opname[] = { "", "UNION", "UNIONALL", "INTERSECT", "EXCEPT" };
+	int narms = 1, norder = 0, nlimit = 0, op;
+	bool loose = false;	/* a UNION or EXCEPT stands in the chain already */
+
+	while ((op = setop_follows(p)) > 0) {
+		if (p->had_tail) {
+			fail(p, "syntax error, ORDER BY / LIMIT in an arm of a set operation that is not the last: they belong behind the last SELECT and order the whole result");
+			return;
+		}
+		if (op == SETOP_INTERSECT && loose) {
+			fail(p, "syntax error, INTERSECT behind UNION or EXCEPT in one chain is not supported: the standard binds INTERSECT tighter, SQLite reads "
+				"left to right, and there are no parentheses to say which - put the INTERSECT first or split the statement");
+			return;
+		}
+		loose = loose || op != SETOP_INTERSECT;
+		if (narms == MAX_SETOP_ARMS) {
+			fail(p, "syntax error, more than %d arms in one set operation", MAX_SETOP_ARMS);
+			return;
+		}
+		next(p);	/* the operator */
+		if (name_is(&p->lx, "all") || is_kw(p, "DISTINCT"))
+			next(p);
+		expect_kw(p, "SELECT");
+		p->arm = true;
+		parse_select(p);
+		p->arm = false;
+		if (p->failed)
+			return;
+		emit(p, "SETOP %s", opname[op]);
+		narms++;
+		if (is_kw(p, "ORDER") || is_kw(p, "LIMIT")) {
+			p->had_tail = true;
+			break;
+		}
+	}
+	if (op < 0 || narms == 1)
+		return;
+	if (accept_kw(p, "ORDER")) {
+		expect_kw(p, "BY");
+		do {
+			int desc = 0;
+			if (p->failed)
+				return;
+			if (p->lx.type != T_NAME || setop_follows(p)) {
+				fail(p, "syntax error, ORDER BY behind a set operation takes result columns of the first SELECT by their bare names: a column's name or an alias");
+				return;
+			}
+			emit(p, "NAME %s", p->lx.text);
+			next(p);
+			if (is_punct(p, '.')) {
+				fail(p, "syntax error, ORDER BY behind a set operation takes result columns of the first SELECT by their bare names: a column's name or an alias");
+				return;
+			}
+			if (accept_kw(p, "DESC"))
+				desc = 1;
+			else
+				accept_kw(p, "ASC");
+			emit(p, "SETORDER %d", desc);
+			norder++;
+		} while (is_punct(p, ',') && (next(p), true));
+	}
+	if (accept_kw(p, "LIMIT")) {
+		parse_expr(p, P_OR);
+		if (is_punct(p, ',')) {
+			next(p);
+			parse_expr(p, P_OR);
+			emit(p, "SETLIMIT 2");
+		} else {
+			emit(p, "SETLIMIT 1");
+		}
+		nlimit = 1;
+	}
+	if (setop_follows(p) > 0) {
+		fail(p, "syntax error, ORDER BY / LIMIT in an arm of a set operation that is not the last: they belong behind the last SELECT and order the whole result");
+		return;
+	}
+	emit(p, "COMPOUND %d %d %d", narms, norder, nlimit);
 }
 
 /* CREATE TABLE (midorisql.y:447-483) */
@@ -1246,8 +1426,11 @@ int mdb_sql_parse(const char *sql, struct mdb_rpn *out, char *err, size_t errlen
 	if (err && errlen)
 		err[0] = 0;
 	next(&p);
-	if (accept_kw(&p, "SELECT"))
+	if (accept_kw(&p, "SELECT")) {
 		parse_select(&p);
+		parse_compound(&p);
+	} else if (is_punct(&p, '(') && paren_select_at(p.lx.s + p.lx.pos - 1))
+		fail(&p, "syntax error, a parenthesised SELECT as an arm of a set operation is not supported: write the arms without parentheses, they are evaluated left to right");
 	else if (accept_kw(&p, "CREATE"))
 		parse_create(&p);
 	else if (accept_kw(&p, "INSERT"))

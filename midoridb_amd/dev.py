@@ -70,6 +70,19 @@ class WindowFn(ctypes.Structure):     # struct mdb_window_fn (include/mdb_dev.h)
                 ("out_nullbits", c_void_p)]
 
 
+class RowsInfo(ctypes.Structure):     # struct mdb_dev_rows_info (include/mdb_dev.h)
+    _fields_ = [("members", c_uint64), ("log2_slots", c_uint32), ("form", c_uint32)]
+
+
+class ConcatPart(ctypes.Structure):     # struct mdb_concat_part (include/mdb_dev.h)
+    _fields_ = [("values", c_void_p), ("nullbits", c_void_p), ("n", c_uint64)]
+
+
+ROWS_MAX_COLS = 16              # MDB_ROWS_MAX_COLS
+ROWS_MAX_BUILD = 1 << 30        # MDB_ROWS_MAX_BUILD
+CONCAT_MAX_PARTS = 16           # MDB_CONCAT_MAX_PARTS
+
+
 class GatherCol(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("src_nullbits", c_void_p), ("rid", c_void_p), ("dst", c_void_p), ("dst_nullbits", c_void_p)]
 
@@ -287,6 +300,8 @@ def _bind(lib):
         "mdb_dev_group_count_distinct_lds_groups": ([], c_uint64),
         "mdb_dev_count_distinct_bitmap_bits": ([], c_uint64),
         "mdb_dev_window": ([P, POINTER(SortKey), c_int, POINTER(SortKey), c_int, c_uint64, POINTER(WindowFn), c_int, POINTER(c_uint32)], c_int),
+        "mdb_dev_rows_semi": ([P, POINTER(SortKey), c_uint64, POINTER(SortKey), c_uint64, c_int, c_int, P, POINTER(c_uint64), POINTER(RowsInfo)], c_int),
+        "mdb_dev_concat64": ([P, POINTER(ConcatPart), c_int, P, P], c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -307,6 +322,7 @@ DEV_SYMBOLS = [
     "mdb_dev_group_aggregate", "mdb_dev_group_aggregate_lds_groups",
     "mdb_dev_group_count_distinct", "mdb_dev_group_count_distinct_lds_groups", "mdb_dev_count_distinct_bitmap_bits",
     "mdb_dev_window",
+    "mdb_dev_rows_semi", "mdb_dev_concat64",
 ]
 
 
@@ -960,6 +976,34 @@ class DeviceCtx:
         m = c_uint64(0)
         self._chk(self.lib.mdb_dev_distinct_sel(self.h, self._sort_keys(keys), len(keys), n, _ptr(sel), byref(m)), "distinct_sel")
         return sel[:m.value]
+
+    def rows_semi(self, probe, n_probe, build, n_build, anti=False, ncols=None):
+        """Whole-row semi- / anti-join (mdb_dev_rows_semi): probe / build = the two sides' columns as sort_perm takes keys, (values,
+        nullbits or None, rid or None, type, desc).  -> (ascending probe positions with (anti: without) an equal build row, info dict).
+        ncols: what the call is told instead of len(probe) (the refusals)"""
+        sel = torch.empty(max(n_probe, 1), dtype=torch.int32, device=self.device)
+        m = c_uint64(0)
+        info = RowsInfo()
+        nc = len(probe) if ncols is None else ncols
+        self._chk(self.lib.mdb_dev_rows_semi(self.h, self._sort_keys(probe) if probe else None, n_probe, self._sort_keys(build) if build else None,
+                                             n_build, nc, 1 if anti else 0, _ptr(sel), byref(m), byref(info)), "rows_semi")
+        return sel[:m.value], {"members": int(info.members), "log2_slots": int(info.log2_slots), "form": int(info.form)}
+
+    def concat64(self, parts, want_nulls=True):
+        """The column of a UNION (mdb_dev_concat64): parts = [(values tensor or None, nullbits tensor or None, n)] -> (cells, NULL words or
+        None); every NULL word is written by the call (the buffer starts as all ones)"""
+        total = sum(n for _, _, n in parts)
+        arr = (ConcatPart * max(len(parts), 1))()
+        for k, (v, nb, n) in enumerate(parts):
+            arr[k].values = v.data_ptr() if v is not None else None
+            arr[k].nullbits = nb.data_ptr() if nb is not None else None
+            arr[k].n = n
+        dst = torch.empty(max(total, 1), dtype=torch.int64, device=self.device)
+        words = (total + 63) // 64
+        dnull = torch.full((max(words, 1),), -1, dtype=torch.int64, device=self.device) if want_nulls else None
+        self._chk(self.lib.mdb_dev_concat64(self.h, arr, len(parts), _ptr(dst), _ptr(dnull)), "concat64")
+        self.sync()
+        return dst[:total], (dnull[:words] if want_nulls else None)
 
     def combine_counts(self, cnt1, first1, idx, cnt2):
         """chained fused joins: (cnt1[idx] * cnt2, first1[idx] (or idx), sum)"""

@@ -41,7 +41,7 @@ QUERY_SYMBOLS = [
     "mdb_query_execute_rpn", "query_column_double", "query_column_is_null", "query_column_count", "query_column_name",
     "query_column_type", "query_row_count", "query_column_data", "query_exec_ms", "query_joined_rows",
     "mdb_table_append_columns", "mdb_table_generate", "mdb_sql_to_rpn", "query_column_text", "mdb_result_text_at",
-    "mdb_database_device", "mdb_database_set_dist", "mdb_database_results_on_device", "mdb_database_groups_any_order", "mdb_database_joins_eliminated", "mdb_database_composite_joins", "mdb_database_composite_fused", "mdb_database_in_set_lookups", "mdb_database_subquery_sets", "mdb_database_aggregate_calls", "mdb_database_count_distinct_calls", "mdb_database_window_calls", "query_column_data_device", "query_column_nulls_device", "mdb_table_generate_shard",
+    "mdb_database_device", "mdb_database_set_dist", "mdb_database_results_on_device", "mdb_database_groups_any_order", "mdb_database_joins_eliminated", "mdb_database_composite_joins", "mdb_database_composite_fused", "mdb_database_in_set_lookups", "mdb_database_subquery_sets", "mdb_database_aggregate_calls", "mdb_database_count_distinct_calls", "mdb_database_window_calls", "mdb_database_setop_calls", "query_column_data_device", "query_column_nulls_device", "mdb_table_generate_shard",
 ]
 
 
@@ -113,6 +113,8 @@ def _bind(lib):
     lib.mdb_database_count_distinct_calls.restype = ctypes.c_int
     lib.mdb_database_window_calls.argtypes = [PDB]
     lib.mdb_database_window_calls.restype = ctypes.c_ulonglong
+    lib.mdb_database_setop_calls.argtypes = [PDB]
+    lib.mdb_database_setop_calls.restype = ctypes.c_ulonglong
     lib.query_column_data_device.argtypes = [PRS, c_int]
     lib.query_column_data_device.restype = c_void_p
     lib.query_column_nulls_device.argtypes = [PRS, c_int]
@@ -234,6 +236,11 @@ class DB:
         """mdb_dev_window calls of this database's SELECT statements so far: one per distinct OVER clause of a statement
         (mdb_database_window_calls)"""
         return int(self.lib.mdb_database_window_calls(ctypes.byref(self.db)))
+
+    def setop_calls(self):
+        """mdb_dev_rows_semi calls of this database's compound statements so far: one per INTERSECT / EXCEPT step, none for
+        UNION [ALL] (mdb_database_setop_calls)"""
+        return int(self.lib.mdb_database_setop_calls(ctypes.byref(self.db)))
 
     def results_on_device(self, on=True):
         """SELECT results stay in HBM until a consumer reads them (mdb_database_results_on_device)"""
