@@ -418,55 +418,17 @@ def main():
     args = ap.parse_args()
     dev = DeviceCtx(0)
     res = {}
-    if args.setops:
-        setops_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
-    if args.window:
-        window_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
-    if args.count_distinct:
-        count_distinct_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
-    if args.subquery:
-        subquery_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
-    if args.full_join:
-        full_join_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
-    if args.aggregates:
-        aggregate_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
-    if args.in_set:
-        in_set_rows(dev, res)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res, indent=1))
-        return
+    # one flag, one group of rows: run it, write the document, print it whole
+    only = (("setops", setops_rows), ("window", window_rows), ("count_distinct", count_distinct_rows), ("subquery", subquery_rows),
+            ("full_join", full_join_rows), ("aggregates", aggregate_rows), ("in_set", in_set_rows))
+    for flag, rows in only:
+        if getattr(args, flag):
+            rows(dev, res)
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+            print(json.dumps(res, indent=1))
+            return
     if args.outer:
         outer_join_rows(dev, res)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)

@@ -8,107 +8,36 @@
  * atomic anywhere, and every floating-point sum is folded in an order that depends on n, the sort permutation and the launch geometry alone.
  *
  * An accumulator is a pair (acc, cnt) of 64-bit words: cnt = non-NULL cells folded, acc = their sum (integers: two's complement, wrapping;
- * DOUBLE: the bits of the sum) or the smallest / largest order-preserving image (the sort operator's: INT64 with the sign bit flipped,
- * DOUBLE by the IEEE total-order trick, so -0.0 lies before +0.0).
+ * DOUBLE: the bits of the sum) or the smallest / largest order-preserving image (mdb_order_image).  Cells, images, the LDS table and the
+ * status flags are mdb_dev_stream.h's.
  *
  *   form 1  groups in LDS.  Every aggregate is order-free (integer cells, or MIN / MAX over DOUBLE), at most one 8-byte group key per row
  *           and G <= mdb_dev_group_aggregate_lds_groups(naggs): every workgroup builds the key -> group table from the keys at first[g]
- *           (open addressing at load <= 1/2, mdb_set_slot_of; the NULL key has a slot of its own), streams its share of the rows and
+ *           (mdb_group_lds_build), streams its share of the rows and
  *           updates accumulators in LDS with 64-bit integer atomics - as many copies of the accumulators as fit (at most AGG_MAX_COPIES),
  *           indexed by thread, so that a handful of groups does not send every lane to one address.  The workgroups' slabs are folded by
  *           k_agg_fold_slabs, a wave per accumulator.  MDB_AGG_LDS=0 turns the form off.
- *   form 2  sorted segments.  mdb_dev_sort_perm over the group keys is stable: every group is one run of rows in stream order, and the
- *           run whose head sits at stream position p is the group g with first[g] == p.  Chunks of AGG_CHUNK sorted positions, one wave
+ *   form 2  sorted segments.  mdb_runs_find (mdb_dev_runs.hip) sorts the stream by the group keys and delivers the runs' heads and their
+ *           groups.  Chunks of AGG_CHUNK sorted positions, one wave
  *           each, a strip of AGG_STRIP positions per lane: a lane folds its strip in order, the wave joins the strips with a segmented
  *           scan (shuffles), runs that begin and end inside a chunk are final there; a run that crosses a chunk boundary is finished by
  *           k_agg_seg_fin from the chunks' (part before the first head, part after the last head) records, in chunk order.
  *   form 3  the identity (nkeys == MDB_AGG_IDENTITY): group i is row i.
  */
 #include "mdb_dev_internal.h"
+#include "mdb_dev_stream.h"
 
 #define AGG_LDS_THREADS 1024
-#define AGG_LDS_BUDGET (160u * 1024u - 1024u)	/* bytes of dynamic LDS a workgroup of form 1 may take (the CU has 160 KiB; 1 KiB stays free) */
 #define AGG_MAX_COPIES 16u
-#define AGG_EMPTY 0xFFFFFFFFu
-#define AGG_CHUNK 1024u				/* sorted positions per wave of form 2 */
+#define AGG_CHUNK MDB_RUNS_CHUNK		/* sorted positions per wave of form 2 */
 #define AGG_STRIP (AGG_CHUNK / MDB_WAVE)	/* ... per lane: 16, a quarter of a word of head bits */
 #define AGG_SEG_THREADS 256
-/* flags of the operator's own status word */
-#define AGG_ST_KEY_MISSING 1u	/* a row's group key is the key of no group / a run's head is nobody's first row: first[] does not belong to these keys */
-#define AGG_ST_RUNS_DIFFER 2u	/* more runs of equal keys than groups */
-static_assert(mdb_flags_distinct({ AGG_ST_KEY_MISSING, AGG_ST_RUNS_DIFFER }), "aggregate: two status flags share a bit");
 static_assert(AGG_STRIP == 16u, "a lane's strip is 16 head bits");
-
-struct agg_col {
-	const uint64_t *values;
-	const uint64_t *nullbits;
-	const uint32_t *rid;
-	int32_t op, type;
-};
-
-struct agg_keys {
-	agg_col k[MDB_SORT_MAX_KEYS];
-	int nkeys;
-};
 
 __host__ __device__ static inline bool agg_is_minmax(int op) { return op == MDB_AGG_MIN || op == MDB_AGG_MAX; }
 
-/* the sort operator's order-preserving image (mdb_dev_sort.hip, sort_image) and its inverse */
-__device__ static inline uint64_t agg_image(uint64_t bits, int type)
-{
-	if (type == MDB_T_DOUBLE)
-		return (bits >> 63) ? ~bits : (bits ^ 0x8000000000000000ull);
-	return bits ^ 0x8000000000000000ull;
-}
-
-__device__ static inline uint64_t agg_unimage(uint64_t u, int type)
-{
-	if (type == MDB_T_DOUBLE)
-		return (u >> 63) ? (u ^ 0x8000000000000000ull) : ~u;
-	return u ^ 0x8000000000000000ull;
-}
-
-/* the cell of stream position sp: false for a NULL cell and for "no row" */
-__device__ static inline bool agg_cell(const agg_col &c, uint64_t sp, uint64_t *bits)
-{
-	uint64_t row = sp;
-	if (c.rid) {
-		const uint32_t r = c.rid[sp];
-		if (r == MDB_NO_ROW)
-			return false;
-		row = r;
-	}
-	if (c.nullbits && mdb_bit_is_set(c.nullbits, row))
-		return false;
-	*bits = c.values[row];
-	return true;
-}
-
-/* the cells of stream positions i and i + 1 (i even; two: both exist): a column read without row ids takes one 16-byte load where its
- * address allows (a column that starts 8 bytes off a 16-byte boundary is read by 8-byte loads) and one look at the NULL word */
-__device__ static inline void agg_cell2(const agg_col &c, uint64_t i, bool two, uint64_t bits[2], bool valid[2])
-{
-	if (c.rid) {
-		valid[0] = agg_cell(c, i, &bits[0]);
-		valid[1] = two && agg_cell(c, i + 1, &bits[1]);
-		return;
-	}
-	const uint64_t *q = c.values + i;
-	if (two && !((uintptr_t)q & 15u)) {
-		const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(q);
-		bits[0] = w.x;
-		bits[1] = w.y;
-	} else {
-		bits[0] = q[0];
-		bits[1] = two ? q[1] : 0;
-	}
-	const uint64_t nw = c.nullbits ? c.nullbits[i >> 6] >> (i & 63) : 0ull;	/* (i is even: i + 1 lies in the same word) */
-	valid[0] = !(nw & 1ull);
-	valid[1] = two && !(nw & 2ull);
-}
-
 /* value -> what is folded */
-__device__ static inline uint64_t agg_to_acc(int op, int type, uint64_t bits) { return agg_is_minmax(op) ? agg_image(bits, type) : bits; }
+__device__ static inline uint64_t agg_to_acc(int op, int type, uint64_t bits) { return agg_is_minmax(op) ? mdb_order_image(bits, type) : bits; }
 
 /* (a, na) then (b, nb): b is folded INTO a, in that order.  An empty side changes nothing (a group's first cell is taken as it is: the sum
  * of {-0.0} is -0.0) */
@@ -148,7 +77,7 @@ __global__ __launch_bounds__(256) void k_agg_finish(const unsigned long long *__
 	uint64_t res = 0;
 	if (cnt) {
 		if (agg_is_minmax(op))
-			res = agg_unimage(acc, type);
+			res = mdb_order_unimage(acc, type);
 		else if (op == MDB_AGG_SUM)
 			res = acc;
 		else if (type == MDB_T_DOUBLE)
@@ -195,21 +124,21 @@ __global__ __launch_bounds__(256) void k_agg_fold_slabs(const unsigned long long
 }
 
 /* ------------------------------------------------------------------ form 3: group i = row i */
-__global__ __launch_bounds__(256) void k_agg_identity(agg_col c, uint64_t n, unsigned long long *__restrict__ rec)
+__global__ __launch_bounds__(256) void k_agg_identity(mdb_stream_col c, uint64_t n, unsigned long long *__restrict__ rec)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
 	if (i >= n)
 		return;
 	uint64_t bits = 0;
-	const bool ok = agg_cell(c, i, &bits);
+	const bool ok = mdb_stream_cell(c, i, &bits);
 	rec[i * 2u] = ok ? agg_to_acc(c.op, c.type, bits) : 0ull;
 	rec[i * 2u + 1u] = ok ? 1ull : 0ull;
 }
 
 /* ------------------------------------------------------------------ form 1: groups in LDS */
 struct agg_lds_args {
-	agg_col a[MDB_AGG_MAX_AGGS];
-	agg_col key;
+	mdb_stream_col a[MDB_AGG_MAX_AGGS];
+	mdb_stream_col key;
 	int naggs, has_key;
 	uint64_t n;
 	const uint32_t *first;
@@ -222,38 +151,16 @@ struct agg_lds_args {
 __global__ __launch_bounds__(AGG_LDS_THREADS) void k_agg_lds(agg_lds_args A)
 {
 	extern __shared__ unsigned long long s_mem[];
-	__shared__ uint32_t s_nullgrp;
 	const uint32_t slots = A.has_key ? 1u << A.log2_slots : 0u, G = A.G;
 	const uint32_t per = (uint32_t)A.naggs * G;
 	unsigned long long *s_acc = s_mem;
-	unsigned long long *s_key = s_acc + (size_t)A.copies * per * 2u;
-	uint32_t *s_grp = reinterpret_cast<uint32_t *>(s_key + slots);
 
 	for (uint32_t i = threadIdx.x; i < A.copies * per; i += AGG_LDS_THREADS) {
 		const int op = A.a[(i % per) / G].op;
 		s_acc[2u * i] = op == MDB_AGG_MIN ? ~0ull : 0ull;
 		s_acc[2u * i + 1u] = 0ull;
 	}
-	for (uint32_t i = threadIdx.x; i < slots; i += AGG_LDS_THREADS)
-		s_grp[i] = AGG_EMPTY;
-	if (threadIdx.x == 0)
-		s_nullgrp = AGG_EMPTY;
-	__syncthreads();
-	if (A.has_key)
-		for (uint32_t g = threadIdx.x; g < G; g += AGG_LDS_THREADS) {
-			uint64_t kb = 0;
-			if (!agg_cell(A.key, A.first[g], &kb)) {
-				s_nullgrp = g;
-				continue;
-			}
-			uint32_t s = (uint32_t)mdb_set_slot_of(kb, A.log2_slots);
-			for (uint32_t step = 0; step < slots; step++, s = (s + 1u) & (slots - 1u))
-				if (atomicCAS(&s_grp[s], AGG_EMPTY, g) == AGG_EMPTY) {	/* (G <= slots / 2: a free slot exists) */
-					s_key[s] = kb;
-					break;
-				}
-		}
-	__syncthreads();
+	const mdb_group_lds T = mdb_group_lds_build(s_acc + (size_t)A.copies * per * 2u, slots, A.log2_slots, A.key, A.first, G, AGG_LDS_THREADS);
 
 	const uint32_t copy = threadIdx.x & (A.copies - 1u);
 	bool missing = false;
@@ -263,44 +170,27 @@ __global__ __launch_bounds__(AGG_LDS_THREADS) void k_agg_lds(agg_lds_args A)
 		bool kv[2] = { true, two };
 		uint32_t grp[2] = { 0u, 0u };
 		if (A.has_key) {
-			agg_cell2(A.key, i, two, kb, kv);
+			mdb_stream_cell2(A.key, i, two, kb, kv);
 #pragma unroll
 			for (int r = 0; r < 2; r++) {
-				uint32_t g = AGG_EMPTY;
-				if (r && !two) {
-					/* (no second row) */
-				} else if (!kv[r]) {
-					g = s_nullgrp;
-				} else {
-					uint32_t s = (uint32_t)mdb_set_slot_of(kb[r], A.log2_slots);
-					for (uint32_t step = 0; step < slots; step++, s = (s + 1u) & (slots - 1u)) {
-						const uint32_t at = s_grp[s];
-						if (at == AGG_EMPTY)
-							break;
-						if (s_key[s] == kb[r]) {
-							g = at;
-							break;
-						}
-					}
-				}
-				grp[r] = g;
-				missing = missing || (g == AGG_EMPTY && (!r || two));
+				grp[r] = r && !two ? MDB_GROUP_NONE : mdb_group_lds_find(T, kb[r], kv[r]);	/* (r && !two: no second row) */
+				missing = missing || (grp[r] == MDB_GROUP_NONE && (!r || two));
 			}
 		}
 		for (int a = 0; a < A.naggs; a++) {
-			const agg_col &c = A.a[a];
+			const mdb_stream_col &c = A.a[a];
 			uint64_t vb[2];
 			bool vv[2];
-			agg_cell2(c, i, two, vb, vv);
+			mdb_stream_cell2(c, i, two, vb, vv);
 #pragma unroll
 			for (int r = 0; r < 2; r++) {
-				if (!vv[r] || grp[r] == AGG_EMPTY)
+				if (!vv[r] || grp[r] == MDB_GROUP_NONE)
 					continue;
 				unsigned long long *at = s_acc + ((size_t)(copy * (uint32_t)A.naggs + (uint32_t)a) * G + grp[r]) * 2u;
 				if (c.op == MDB_AGG_MIN)
-					atomicMin(at, (unsigned long long)agg_image(vb[r], c.type));
+					atomicMin(at, (unsigned long long)mdb_order_image(vb[r], c.type));
 				else if (c.op == MDB_AGG_MAX)
-					atomicMax(at, (unsigned long long)agg_image(vb[r], c.type));
+					atomicMax(at, (unsigned long long)mdb_order_image(vb[r], c.type));
 				else
 					atomicAdd(at, (unsigned long long)vb[r]);
 				atomicAdd(at + 1, 1ull);
@@ -308,10 +198,10 @@ __global__ __launch_bounds__(AGG_LDS_THREADS) void k_agg_lds(agg_lds_args A)
 		}
 	}
 	if (missing)
-		mdb_raise(A.status, AGG_ST_KEY_MISSING);
+		mdb_raise(A.status, MDB_GROUPS_ST_KEY_MISSING);
 	__syncthreads();
 	for (uint32_t i = threadIdx.x; i < per; i += AGG_LDS_THREADS) {
-		const agg_col &c = A.a[i / G];
+		const mdb_stream_col &c = A.a[i / G];
 		uint64_t acc = 0, cnt = 0;
 		for (uint32_t k = 0; k < A.copies; k++)
 			agg_fold(c.op, c.type, acc, cnt, s_acc[2u * ((size_t)k * per + i)], s_acc[2u * ((size_t)k * per + i) + 1u]);
@@ -322,7 +212,7 @@ __global__ __launch_bounds__(AGG_LDS_THREADS) void k_agg_lds(agg_lds_args A)
 
 static size_t agg_lds_bytes(uint32_t slots, uint32_t copies, int naggs, uint64_t G)
 {
-	return (size_t)slots * 12u + (size_t)copies * (size_t)naggs * (size_t)G * 16u;
+	return mdb_group_lds_bytes(slots) + (size_t)copies * (size_t)naggs * (size_t)G * 16u;
 }
 
 extern "C" uint64_t mdb_dev_group_aggregate_lds_groups(int naggs)
@@ -332,9 +222,9 @@ extern "C" uint64_t mdb_dev_group_aggregate_lds_groups(int naggs)
 		return 0;
 	for (uint32_t lg = MDB_SET_MIN_LOG2; lg <= 16u; lg++) {
 		const uint64_t slots = 1ull << lg;
-		if (slots * 12u >= AGG_LDS_BUDGET)
+		if (mdb_group_lds_bytes(slots) >= MDB_GROUP_LDS_BUDGET)
 			break;
-		uint64_t g = (AGG_LDS_BUDGET - slots * 12u) / ((uint64_t)naggs * 16u);
+		uint64_t g = (MDB_GROUP_LDS_BUDGET - mdb_group_lds_bytes(slots)) / ((uint64_t)naggs * 16u);
 		g = g < slots / 2u ? g : slots / 2u;
 		best = g > best ? g : best;
 	}
@@ -343,85 +233,10 @@ extern "C" uint64_t mdb_dev_group_aggregate_lds_groups(int naggs)
 
 /* ------------------------------------------------------------------ form 2: sorted segments */
 
-/* one workgroup per chunk: hb bit p = "sorted position p begins a run" (position 0, or a key column differs from the row before: NULL
- * equals NULL, values by their bits), cnt[chunk] = heads in the chunk */
-__global__ __launch_bounds__(AGG_CHUNK) void k_agg_heads(agg_keys K, const uint32_t *__restrict__ perm, uint64_t n, unsigned long long *__restrict__ hb,
-							  uint32_t *__restrict__ cnt)
-{
-	__shared__ uint32_t s_cnt;
-	if (threadIdx.x == 0)
-		s_cnt = 0;
-	__syncthreads();
-	const uint64_t p = (uint64_t)blockIdx.x * AGG_CHUNK + threadIdx.x;
-	/* every position gathers ITS key cells once; the row before is the lane before (a shuffle) - only a wave's first lane gathers it */
-	const bool in = p < n, first_lane = in && p && mdb_lane() == 0;
-	const uint64_t s1 = in ? (perm ? perm[p] : p) : 0, s0 = first_lane ? (perm ? perm[p - 1] : p - 1) : 0;
-	bool head = in && p == 0;
-	for (int k = 0; k < K.nkeys; k++) {
-		uint64_t b1 = 0;
-		const bool v1 = in && agg_cell(K.k[k], s1, &b1);
-		uint64_t b0 = (uint64_t)__shfl_up((unsigned long long)b1, 1u, MDB_WAVE);
-		bool v0 = __shfl_up((int)v1, 1u, MDB_WAVE) != 0;
-		if (first_lane) {
-			b0 = 0;
-			v0 = agg_cell(K.k[k], s0, &b0);
-		}
-		if (in && p)
-			head = head || v0 != v1 || (v1 && b0 != b1);
-	}
-	const unsigned long long b = __ballot(head);
-	if (mdb_lane() == 0) {
-		hb[p >> 6] = b;
-		if (b)
-			atomicAdd(&s_cnt, (uint32_t)__popcll(b));
-	}
-	__syncthreads();
-	if (threadIdx.x == 0)
-		cnt[blockIdx.x] = s_cnt;
-}
-
-/* rungroup[r] = the group whose first row is the head of run r (base[chunk] = heads before the chunk) */
-__global__ __launch_bounds__(AGG_CHUNK) void k_agg_run_groups(const unsigned long long *__restrict__ hb, const uint32_t *__restrict__ base,
-							       const uint32_t *__restrict__ perm, uint64_t n, const uint32_t *__restrict__ first, uint64_t G,
-							       uint32_t *__restrict__ rungroup, uint32_t *status)
-{
-	const uint64_t p = (uint64_t)blockIdx.x * AGG_CHUNK + threadIdx.x;
-	if (p >= n)
-		return;
-	const unsigned long long w = hb[p >> 6];
-	if (!((w >> (p & 63)) & 1ull))
-		return;
-	uint32_t r = base[blockIdx.x] + (uint32_t)__popcll(w & ((1ull << (p & 63)) - 1ull));
-	for (uint64_t q = (uint64_t)blockIdx.x * (AGG_CHUNK / 64u); q < (p >> 6); q++)
-		r += (uint32_t)__popcll(hb[q]);
-	if (r >= G) {
-		mdb_raise(status, AGG_ST_RUNS_DIFFER);
-		return;
-	}
-	uint32_t g = 0;
-	if (first) {
-		const uint32_t sp = perm ? perm[p] : (uint32_t)p;
-		uint64_t lo = 0, hi = G;
-		while (lo < hi) {
-			const uint64_t mid = (lo + hi) >> 1;
-			if (first[mid] < sp)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		if (lo >= G || first[lo] != sp) {
-			mdb_raise(status, AGG_ST_KEY_MISSING);
-			return;
-		}
-		g = (uint32_t)lo;
-	}
-	rungroup[r] = g;
-}
-
 /* One wave per chunk, one aggregate per launch.  A lane folds its strip in order; what it holds at the strip's end is the part of the run
  * that is open there.  Written: rec[g] for every run that begins and ends inside the chunk; pre[chunk] = the part of the chunk in front of
  * its first head (the whole chunk when it has none), tail[chunk] = the part from its last head on. */
-__global__ __launch_bounds__(AGG_SEG_THREADS) void k_agg_seg(agg_col c, const uint32_t *__restrict__ perm, uint64_t n, uint64_t nchunks,
+__global__ __launch_bounds__(AGG_SEG_THREADS) void k_agg_seg(mdb_stream_col c, const uint32_t *__restrict__ perm, uint64_t n, uint64_t nchunks,
 							      const unsigned long long *__restrict__ hb, const uint32_t *__restrict__ base,
 							      const uint32_t *__restrict__ rungroup, unsigned long long *__restrict__ rec,
 							      unsigned long long *__restrict__ pre, unsigned long long *__restrict__ tail)
@@ -468,7 +283,7 @@ __global__ __launch_bounds__(AGG_SEG_THREADS) void k_agg_seg(agg_col c, const ui
 			acc = cnt = 0;
 		}
 		uint64_t vb = 0;
-		if (agg_cell(c, sp[j], &vb))
+		if (mdb_stream_cell(c, sp[j], &vb))
 			agg_fold(c.op, c.type, acc, cnt, agg_to_acc(c.op, c.type, vb), 1ull);
 	}
 	/* segmented inclusive scan over the lanes: (flag, value) (+) (flag', value') = (flag | flag', flag' ? value' : value + value') */
@@ -553,47 +368,7 @@ __global__ __launch_bounds__(AGG_SEG_THREADS) void k_agg_seg_fin(int op, int typ
 
 /* ------------------------------------------------------------------ host side */
 
-static agg_col agg_col_of(const struct mdb_agg *a)
-{
-	agg_col c;
-	c.values = (const uint64_t *)a->values;
-	c.nullbits = a->nullbits;
-	c.rid = a->rid;
-	c.op = a->op;
-	c.type = a->type;
-	return c;
-}
-
-static agg_col agg_col_of_key(const struct mdb_sort_key *k)
-{
-	agg_col c;
-	c.values = (const uint64_t *)k->values;
-	c.nullbits = k->nullbits;
-	c.rid = k->rid;
-	c.op = 0;
-	c.type = k->type;
-	return c;
-}
-
-struct agg_tmp {
-	mdb_dev_ctx *ctx;
-	void *p[12];
-	int n;
-	explicit agg_tmp(mdb_dev_ctx *c) : ctx(c), n(0) {}
-	~agg_tmp()
-	{
-		for (int i = 0; i < n; i++)
-			(void)mdb_cached_free(ctx, p[i]);
-	}
-	void *take(size_t bytes)
-	{
-		void *q = NULL;
-		if (n == 12 || mdb_cached_alloc(ctx, bytes, &q))
-			return NULL;
-		p[n++] = q;
-		return q;
-	}
-};
+static mdb_stream_col agg_col_of(const struct mdb_agg *a) { return mdb_stream_col_of(a->values, a->nullbits, a->rid, a->op, a->type); }
 
 static int agg_finish_all(mdb_dev_ctx *ctx, const unsigned long long *rec, uint32_t nslab, uint64_t G, const struct mdb_agg *aggs, int naggs)
 {
@@ -604,22 +379,10 @@ static int agg_finish_all(mdb_dev_ctx *ctx, const unsigned long long *rec, uint3
 	return MIDORIDB_OK;
 }
 
-static int agg_status(mdb_dev_ctx *ctx, const uint32_t *d_status, const char *what)
-{
-	uint32_t h = 0;
-	MDB_HIP(ctx, hipMemcpyAsync(&h, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h & AGG_ST_RUNS_DIFFER)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group_aggregate (%s): the keys form more runs than there are groups", what);
-	if (h & AGG_ST_KEY_MISSING)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group_aggregate (%s): a row's key belongs to no group of first[]", what);
-	return MIDORIDB_OK;
-}
-
 static int agg_form_lds(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, const uint32_t *first, uint64_t G,
 			const struct mdb_agg *aggs, int naggs)
 {
-	agg_tmp tmp(ctx);
+	mdb_dev_tmp tmp(ctx);
 	agg_lds_args A;
 	memset(&A, 0, sizeof(A));
 	for (int a = 0; a < naggs; a++)
@@ -627,26 +390,19 @@ static int agg_form_lds(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int n
 	A.naggs = naggs;
 	A.has_key = nkeys == 1;
 	if (A.has_key)
-		A.key = agg_col_of_key(&keys[0]);
+		A.key = mdb_stream_col_of_key(&keys[0]);
 	A.n = n;
 	A.first = first;
 	A.G = (uint32_t)G;
-	uint32_t lg = MDB_SET_MIN_LOG2;
-	while (A.has_key && (1ull << lg) < 2u * G)
-		lg++;
-	A.log2_slots = lg;
-	const uint32_t slots = A.has_key ? 1u << lg : 0u;
+	A.log2_slots = A.has_key ? mdb_group_lds_log2(G) : MDB_SET_MIN_LOG2;
+	const uint32_t slots = A.has_key ? 1u << A.log2_slots : 0u;
 	A.copies = 1;
-	while (A.copies < AGG_MAX_COPIES && agg_lds_bytes(slots, A.copies * 2u, naggs, G) <= AGG_LDS_BUDGET)
+	while (A.copies < AGG_MAX_COPIES && agg_lds_bytes(slots, A.copies * 2u, naggs, G) <= MDB_GROUP_LDS_BUDGET)
 		A.copies *= 2u;
 	const size_t lds = agg_lds_bytes(slots, A.copies, naggs, G);
-	if (lds > AGG_LDS_BUDGET)
+	if (lds > MDB_GROUP_LDS_BUDGET)
 		return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "group_aggregate: %llu groups do not fit the LDS form", (unsigned long long)G);
-	/* two workgroups per CU while their LDS allows, never more workgroups than 8192-row shares */
-	uint64_t grid = (uint64_t)ctx->num_cus * (lds * 2u <= 160u * 1024u ? 2u : 1u);
-	const uint64_t shares = (n + 8191u) / 8192u;
-	grid = grid < shares ? grid : shares;
-	grid = grid ? grid : 1;
+	const uint64_t grid = mdb_group_lds_grid(ctx, lds, n);
 	const uint64_t per = (uint64_t)naggs * G;
 	A.slab = (unsigned long long *)tmp.take(grid * per * 16u);
 	A.status = (uint32_t *)tmp.take(256);
@@ -666,67 +422,29 @@ static int agg_form_lds(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int n
 	int rc = agg_finish_all(ctx, rec, 1u, G, aggs, naggs);
 	if (rc)
 		return rc;
-	return agg_status(ctx, A.status, "groups in LDS");
+	return mdb_groups_status(ctx, A.status, "group_aggregate", "groups in LDS");
 }
 
 static int agg_form_sorted(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, const uint32_t *first, uint64_t G,
 			   const struct mdb_agg *aggs, int naggs)
 {
-	agg_tmp tmp(ctx);
-	const uint64_t nchunks = (n + AGG_CHUNK - 1u) / AGG_CHUNK;
-	uint32_t *perm = NULL;
-	int rc;
-	if (nkeys > 0) {
-		struct mdb_sort_key sk[MDB_SORT_MAX_KEYS];
-		perm = (uint32_t *)tmp.take(n * 4u + 16u);
-		if (!perm)
-			return mdb_set_err(ctx, -MIDORIDB_NOMEM, "group_aggregate: no device memory for the permutation");
-		for (int k = 0; k < nkeys; k++) {
-			sk[k] = keys[k];
-			sk[k].desc = 0;
-		}
-		if ((rc = mdb_dev_sort_perm(ctx, sk, nkeys, n, perm)))
-			return rc;
-	}
-	unsigned long long *hb = (unsigned long long *)tmp.take(nchunks * (AGG_CHUNK / 8u));
-	uint32_t *base = (uint32_t *)tmp.take((nchunks + 1u) * 4u);
-	uint32_t *scan_tmp = (uint32_t *)tmp.take(mdb_scan_scratch_words(nchunks + 1u) * 4u);
-	uint32_t *rungroup = (uint32_t *)tmp.take(G * 4u);
+	mdb_dev_tmp tmp(ctx);
+	mdb_runs R;
+	int rc = mdb_runs_find(ctx, keys, nkeys, n, first, G, "group_aggregate", "sorted segments", tmp, &R);
+	if (rc)
+		return rc;
+	const uint64_t nchunks = R.nchunks;
 	unsigned long long *pre = (unsigned long long *)tmp.take(nchunks * 16u);
 	unsigned long long *tail = (unsigned long long *)tmp.take(nchunks * 16u);
 	unsigned long long *rec = (unsigned long long *)tmp.take((uint64_t)naggs * G * 16u);
-	uint32_t *status = (uint32_t *)tmp.take(256);
-	if (!hb || !base || !scan_tmp || !rungroup || !pre || !tail || !rec || !status)
+	if (!pre || !tail || !rec)
 		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "group_aggregate: no device memory for %llu chunks", (unsigned long long)nchunks);
-	agg_keys K;
-	memset(&K, 0, sizeof(K));
-	K.nkeys = nkeys > 0 ? nkeys : 0;
-	for (int k = 0; k < K.nkeys; k++)
-		K.k[k] = agg_col_of_key(&keys[k]);
-	MDB_HIP(ctx, hipMemsetAsync(status, 0, 4, ctx->stream));
-	MDB_HIP(ctx, hipMemsetAsync(base + nchunks, 0, 4, ctx->stream));
-	/* (a group nobody writes would be read uninitialised by k_agg_finish: the checks below make sure every group has its run) */
-	MDB_LAUNCH(ctx, "agg_heads", k_agg_heads, (uint32_t)nchunks, AGG_CHUNK, K, (const uint32_t *)perm, n, hb, base);
-	if ((rc = mdb_scan_u32_inplace(ctx, base, nchunks + 1u, scan_tmp)))
-		return rc;
-	MDB_LAUNCH(ctx, "agg_run_groups", k_agg_run_groups, (uint32_t)nchunks, AGG_CHUNK, (const unsigned long long *)hb, (const uint32_t *)base,
-		   (const uint32_t *)perm, n, first, G, rungroup, status);
-	{
-		uint32_t runs = 0;
-		MDB_HIP(ctx, hipMemcpyAsync(&runs, base + nchunks, 4, hipMemcpyDeviceToHost, ctx->stream));
-		if ((rc = agg_status(ctx, status, "sorted segments")))
-			return rc;
-		if (runs != G)
-			return mdb_set_err(ctx, -MIDORIDB_ERROR, "group_aggregate (sorted segments): %u runs of equal keys, %llu groups", runs,
-					   (unsigned long long)G);
-	}
 	const uint32_t seg_grid = (uint32_t)((nchunks + (AGG_SEG_THREADS / MDB_WAVE) - 1u) / (AGG_SEG_THREADS / MDB_WAVE));
 	for (int a = 0; a < naggs; a++) {
 		unsigned long long *r = rec + (uint64_t)a * G * 2u;
-		MDB_LAUNCH(ctx, "agg_seg", k_agg_seg, seg_grid, AGG_SEG_THREADS, agg_col_of(&aggs[a]), (const uint32_t *)perm, n, nchunks,
-			   (const unsigned long long *)hb, (const uint32_t *)base, (const uint32_t *)rungroup, r, pre, tail);
-		MDB_LAUNCH(ctx, "agg_seg_fin", k_agg_seg_fin, seg_grid, AGG_SEG_THREADS, (int)aggs[a].op, (int)aggs[a].type, nchunks, (const uint32_t *)base,
-			   (const uint32_t *)rungroup, (const unsigned long long *)pre, (const unsigned long long *)tail, r);
+		MDB_LAUNCH(ctx, "agg_seg", k_agg_seg, seg_grid, AGG_SEG_THREADS, agg_col_of(&aggs[a]), R.perm, n, nchunks, R.hb, R.base, R.rungroup, r, pre, tail);
+		MDB_LAUNCH(ctx, "agg_seg_fin", k_agg_seg_fin, seg_grid, AGG_SEG_THREADS, (int)aggs[a].op, (int)aggs[a].type, nchunks, R.base, R.rungroup,
+			   (const unsigned long long *)pre, (const unsigned long long *)tail, r);
 	}
 	if ((rc = agg_finish_all(ctx, rec, 1u, G, aggs, naggs)))
 		return rc;
@@ -765,7 +483,7 @@ extern "C" int mdb_dev_group_aggregate(mdb_dev_ctx *ctx, const struct mdb_sort_k
 	if (!G)
 		return MIDORIDB_OK;
 	if (!n) {	/* (one group over no row: NULL) */
-		agg_tmp tmp(ctx);
+		mdb_dev_tmp tmp(ctx);
 		unsigned long long *rec = (unsigned long long *)tmp.take((uint64_t)naggs * G * 16u);
 		if (!rec)
 			return mdb_set_err(ctx, -MIDORIDB_NOMEM, "group_aggregate: no device memory");
@@ -777,7 +495,7 @@ extern "C" int mdb_dev_group_aggregate(mdb_dev_ctx *ctx, const struct mdb_sort_k
 		return MIDORIDB_OK;
 	}
 	if (nkeys == MDB_AGG_IDENTITY) {
-		agg_tmp tmp(ctx);
+		mdb_dev_tmp tmp(ctx);
 		unsigned long long *rec = (unsigned long long *)tmp.take((uint64_t)naggs * n * 16u);
 		if (!rec)
 			return mdb_set_err(ctx, -MIDORIDB_NOMEM, "group_aggregate: no device memory");

@@ -22,6 +22,7 @@
  * meet in that XCD's L2.
  */
 #include "mdb_dev_join_internal.h"
+#include "mdb_dev_stream.h"
 #include "mdb_dev_rowjoin.h"
 
 #ifndef BG_TILE_BITS
@@ -55,13 +56,6 @@ __device__ static inline uint32_t bg_tile_of_block(uint32_t b)
 {
 	const uint32_t xcd = b & 7u, k = b >> 3;
 	return ((k / BG_BAND_TILES) * 8u + xcd) * BG_BAND_TILES + (k % BG_BAND_TILES);
-}
-
-/* (the image of mdb_dev_sort.hip's sort_image: order does not matter here, equality does - the same bits as the packed sort's fields) */
-__device__ static inline uint64_t bg_image(uint64_t bits, int is_double, int desc)
-{
-	const uint64_t u = (is_double && (bits >> 63)) ? ~bits : (bits ^ 0x8000000000000000ull);
-	return desc ? ~u : u;
 }
 
 template <bool FULL, bool COMP = false>
@@ -127,7 +121,10 @@ __global__ __launch_bounds__(BG_THREADS) void k_bg_band_sort(bg_sort_args a)
 						const uint32_t r = 2u * ((uint32_t)(jb + jj) * BG_THREADS + threadIdx.x) + (uint32_t)e;
 						const bool live = FULL || r < cnt;
 						const bool isnull = nb && live && mdb_bit_is_set(nb, row0 + r);
-						uint64_t d = bg_image(e ? pre[jj].y : pre[jj].x, a.comp.is_double[c], a.comp.desc[c]) - a.comp.lo[c];
+						const uint64_t cell = e ? pre[jj].y : pre[jj].x;
+						/* (is_double mapped to a type.  `is_double[c] ? MDB_T_DOUBLE : MDB_T_INT64` gives the same image; this form - only a DOUBLE
+						 * cell with its sign bit set differs from INT64 - is kept because it compiles to the registers of the parent's bg_image) */
+						uint64_t d = mdb_order_image(cell, a.comp.is_double[c] && (cell >> 63) ? MDB_T_DOUBLE : MDB_T_INT64, a.comp.desc[c]) - a.comp.lo[c];
 						d = (isnull || !live) ? 0ull : d;
 						bad |= d > a.comp.span[c] ? 1u : 0u;
 						const uint32_t flag = nb ? (uint32_t)(isnull == (a.comp.desc[c] != 0)) : 0u;

@@ -246,6 +246,27 @@ struct mdb_dev_set {
 	int32_t type;
 };
 
+/* ---- the runs of a stream sorted by its group keys (mdb_dev_runs.hip; device side and the types: mdb_dev_stream.h) ----
+ * mdb_dev_sort_perm over the keys (ascending) is stable: every group is one run of rows in stream order, and the run whose head sits at stream
+ * position p is the group g with first[g] == p.  Delivered, in buffers of `tmp`: perm (NULL without keys: the stream is one run), hb - bit p =
+ * "sorted position p begins a run" (position 0, or a key column differs from the row before: NULL equals NULL, values by their bits) -,
+ * base[c] = heads in front of chunk c of MDB_RUNS_CHUNK positions (base[nchunks] = runs) and rungroup[r] = the group of run r.  n, G >= 1.
+ * Fails "<op> (<what>): ..." when first[] does not belong to these keys (more runs than groups, a head that is nobody's first row, another
+ * number of runs than groups) and "<op>: no device memory ..." when `tmp` cannot hold its buffers.  Synchronises once. */
+struct mdb_dev_tmp;
+struct mdb_runs {
+	const uint32_t *perm;
+	const unsigned long long *hb;
+	const uint32_t *base;
+	const uint32_t *rungroup;
+	uint64_t nchunks;
+};
+int mdb_runs_find(mdb_dev_ctx *ctx, const struct mdb_sort_key *keys, int nkeys, uint64_t n, const uint32_t *first, uint64_t G, const char *op,
+		  const char *what, mdb_dev_tmp &tmp, mdb_runs *out);
+/* reads a grouped operator's status word (*word, may be NULL, = all of it: the operator's own flags) and fails "<op> (<what>): ..." for
+ * the MDB_GROUPS_ST_ flags.  Synchronises. */
+int mdb_groups_status(mdb_dev_ctx *ctx, const uint32_t *d_status, const char *op, const char *what, uint32_t *word = NULL);
+
 /* choose level bits so that the average leaf holds about `target` keys */
 void mdb_choose_bits(uint64_t n, uint32_t target, int *bits1, int *bits2);
 

@@ -26,6 +26,7 @@
  * bit offsets that are in general no multiple of 64, in one launch.
  */
 #include "mdb_dev_internal.h"
+#include "mdb_dev_stream.h"
 
 #define ROWS_THREADS 256
 #define ROWS_WAVES (ROWS_THREADS / MDB_WAVE)
@@ -36,33 +37,19 @@
 #define ROWS_NULL_WORD 0x6E756C6C4E554C4Cull	/* what a NULL cell contributes to the row hash instead of the bits under it */
 #define ROWS_SEED 0x9E3779B97F4A7C15ull
 
-struct rows_column {
-	const unsigned long long *values;
-	const unsigned long long *nullbits;
-	const uint32_t *rid;
-};
-
 struct rows_side {
-	rows_column col[MDB_ROWS_MAX_COLS];
+	mdb_stream_col col[MDB_ROWS_MAX_COLS];
 	unsigned long long n;
 	int ncols;
 };
 
-/* cell i of a column: true = NULL (NULL bit or no row), else *bits = its 64 bits */
-__device__ static inline bool rows_cell(const rows_column &c, unsigned long long i, unsigned long long *bits)
+/* cell i of a column (mdb_stream_cell): true = NULL (NULL bit or no row) and *bits = 0, else *bits = its 64 bits */
+__device__ static inline bool rows_cell(const mdb_stream_col &c, unsigned long long i, unsigned long long *bits)
 {
-	unsigned long long row = i;
-	*bits = 0;
-	if (c.rid) {
-		const uint32_t r = c.rid[i];
-		if (r == MDB_NO_ROW)
-			return true;
-		row = r;
-	}
-	if (c.nullbits && mdb_bit_is_set((const uint64_t *)c.nullbits, row))
-		return true;
-	*bits = c.values[row];
-	return false;
+	uint64_t v = 0;
+	const bool isnull = !mdb_stream_cell(c, i, &v);
+	*bits = v;
+	return isnull;
 }
 
 /* The row hash: every cell's word goes through fmix64 - a bijection, so all 64 bits of every column reach every bit of the hash, the top
@@ -252,9 +239,7 @@ static int rows_side_from(mdb_dev_ctx *ctx, const struct mdb_sort_key *k, int nc
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "rows_semi: unknown value type %d of %s column %d", (int)k[c].type, which, c);
 		if (n && !k[c].values)
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "rows_semi: %s column %d has no values", which, c);
-		s->col[c].values = (const unsigned long long *)k[c].values;
-		s->col[c].nullbits = (const unsigned long long *)k[c].nullbits;
-		s->col[c].rid = k[c].rid;
+		s->col[c] = mdb_stream_col_of_key(&k[c]);
 	}
 	return MIDORIDB_OK;
 }

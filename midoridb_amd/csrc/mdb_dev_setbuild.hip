@@ -24,6 +24,7 @@
  * The state block (8 words of device memory) carries the counters; the host reads it after the scan and after each insertion.
  */
 #include "mdb_dev_internal.h"
+#include "mdb_dev_stream.h"
 
 #define SB_THREADS 256
 #define SB_ST_VALID 0
@@ -49,16 +50,10 @@ struct sb_candidates {
 /* the canonical bits of cell i; 0 = a valid member candidate, 1 = NULL (NULL bit or no row), 2 = NaN */
 __device__ static inline int sb_cell(const sb_column &col, unsigned long long i, unsigned long long *bits)
 {
-	unsigned long long row = i;
-	if (col.rid) {
-		const uint32_t r = col.rid[i];
-		if (r == MDB_NO_ROW)
-			return 1;
-		row = r;
-	}
-	if (col.nullbits && mdb_bit_is_set((const uint64_t *)col.nullbits, row))
+	const mdb_stream_col c = { (const uint64_t *)col.values, (const uint64_t *)col.nullbits, col.rid, 0, col.type };
+	uint64_t v = 0;
+	if (!mdb_stream_cell(c, i, &v))
 		return 1;
-	uint64_t v = col.values[row];
 	if (!mdb_set_canonical(col.type, &v))
 		return 2;
 	*bits = v;

@@ -25,19 +25,10 @@
  * tables (at most 14 bits, mdb_dev_groupby.hip) as they load them, written as an 8-byte column otherwise.
  */
 #include "mdb_dev_internal.h"
+#include "mdb_dev_stream.h"
 #include "mdb_dev_rowjoin.h"	/* (mdb_group_count_banded: the band sort reads the columns of a composite key itself) */
 
 #define SORT_THREADS 256
-
-__device__ static inline uint64_t sort_image(uint64_t bits, int type, int desc)
-{
-	uint64_t u;
-	if (type == MDB_T_DOUBLE)
-		u = (bits >> 63) ? ~bits : (bits ^ 0x8000000000000000ull);
-	else
-		u = bits ^ 0x8000000000000000ull;
-	return desc ? ~u : u;
-}
 
 /* mm[0] = min image, mm[1] = max image, mm[2] = 1 when a NULL was seen (all over non-NULL rows) */
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_load(const uint64_t *__restrict__ values, const uint64_t *__restrict__ nullbits,
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_load(const uint64_t *__re
 		if (nullbits && mdb_bit_is_set(nullbits, row)) {
 			anynull = true;
 		} else {
-			u = sort_image(values[row], type, desc);
+			u = mdb_order_image(values[row], type, desc);
 			lo = u < lo ? u : lo;
 			hi = u > hi ? u : hi;
 		}
@@ -143,11 +134,11 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_pack(sort_pack_args a, ui
 				const bool isnull = mdb_bit_is_set(key.nullbits, row);
 				/* ASC: NULLs first (flag 0), DESC: NULLs last (flag 1) - as in the general path */
 				const uint64_t flag = (uint64_t)(isnull == (key.desc != 0));
-				const uint64_t d = isnull ? 0ull : sort_image(values[row], key.type, key.desc) - a.lo[c];
+				const uint64_t d = isnull ? 0ull : mdb_order_image(values[row], key.type, key.desc) - a.lo[c];
 				out = out || d > a.span[c];
 				v = (v << (a.kb[c] + 1)) | (flag << a.kb[c]) | d;
 			} else {
-				const uint64_t d = sort_image(values[row], key.type, key.desc) - a.lo[c];
+				const uint64_t d = mdb_order_image(values[row], key.type, key.desc) - a.lo[c];
 				out = out || d > a.span[c];
 				v = (v << a.kb[c]) | d;
 			}
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_ranges(sort_pack_args a, 
 #pragma unroll
 			for (int c = 0; c < SORT_PACK_MAX_KEYS; c++)
 				if (have[r][c]) {
-					const uint64_t im = sort_image(u[r][c], a.key[c].type, a.key[c].desc);
+					const uint64_t im = mdb_order_image(u[r][c], a.key[c].type, a.key[c].desc);
 					lo[c] = im < lo[c] ? im : lo[c];
 					hi[c] = im > hi[c] ? im : hi[c];
 				}
@@ -595,7 +586,7 @@ __global__ __launch_bounds__(SORT_TINY_THREADS) void k_sort_tiny(sort_tiny_args 
 			const bool isnull = key.nullbits && mdb_bit_is_set(key.nullbits, row);
 			/* ASC: NULLs first (flag 0), DESC: NULLs last (flag 1) - as in the other paths */
 			s_flag[c][k] = (uint8_t)(isnull == (key.desc != 0));
-			s_img[c][k] = isnull ? 0ull : sort_image(((const uint64_t *)key.values)[row], key.type, key.desc);
+			s_img[c][k] = isnull ? 0ull : mdb_order_image(((const uint64_t *)key.values)[row], key.type, key.desc);
 		}
 	}
 	/* workgroup b ranks rows [64 b, 64 b + 64): lane = row i, wave w counts over the rows j = w, w + 16, ... (every lane of a

@@ -6,8 +6,8 @@
  * The stream is sorted once, stably, by the partition keys and then the order keys (mdb_dev_sort_perm): a partition is a run of equal
  * partition keys, a peer group a run of equal order keys inside it.  Everything else is a segmented scan over the sorted positions:
  *
- *   k_win_heads      one thread per sorted position gathers ITS key cells once, the row before is the lane before (a shuffle; a wave's
- *                    first lane gathers it); one ballot per wave and bitmap: ph = partition heads, gh = peer heads (gh contains ph)
+ *   k_win_heads      one thread per sorted position asks mdb_stream_head_of (mdb_dev_stream.h, with the cells and the order images); one
+ *                    ballot per wave and bitmap: ph = partition heads, gh = peer heads (gh contains ph)
  *   k_win_scan<0>    chunks of WIN_CHUNK positions, one workgroup each, a strip of WIN_STRIP positions per thread: every thread folds its
  *                    strip, the strips are scanned by shuffles inside a wave and across the four waves through LDS, the workgroup's
  *                    total is the chunk's summary - the last partition head (b1), the last peer head (g1), the peer heads since the last
@@ -23,32 +23,19 @@
  * DOUBLE cells are refused), plain stores: the same input gives the same bytes.
  */
 #include "mdb_dev_internal.h"
+#include "mdb_dev_stream.h"
 
 #define WIN_THREADS 256u
 #define WIN_STRIP 16u				/* sorted positions per thread: a quarter of a word of head bits */
 #define WIN_CHUNK (WIN_THREADS * WIN_STRIP)	/* ... per workgroup: 4096, 64 words of head bits */
 #define WIN_WORDS (WIN_CHUNK / 64u)
 #define WIN_WAVES (WIN_THREADS / MDB_WAVE)
-/* flags of the operator's own status word */
-#define WIN_ST_PERM_RANGE 1u	/* the sort's permutation names a stream position at or beyond n: that row is skipped, the call fails */
-static_assert(mdb_flags_distinct({ WIN_ST_PERM_RANGE }), "window: two status flags share a bit");
 static_assert(WIN_STRIP == 16u && WIN_CHUNK % 64u == 0, "a thread's strip is 16 head bits of one word");
-
-struct win_col {
-	const uint64_t *values;
-	const uint64_t *nullbits;
-	const uint32_t *rid;
-	int32_t op, type;
-};
-
-struct win_keys {
-	win_col k[MDB_SORT_MAX_KEYS];
-	int npart, nkeys;	/* k[0 .. npart): partition keys, k[npart .. nkeys): order keys */
-};
+/* (the status word holds one flag, MDB_GROUPS_ST_PERM_RANGE of mdb_dev_stream.h) */
 
 #define WIN_MAX_FNS MDB_WIN_MAX_FNS
 struct win_fns {
-	win_col c[WIN_MAX_FNS];
+	mdb_stream_col c[WIN_MAX_FNS];
 	uint64_t *out[WIN_MAX_FNS];		/* n cells in stream order */
 	uint8_t *nf[WIN_MAX_FNS];		/* aggregates: n NULL flags in stream order */
 	unsigned long long *T[WIN_MAX_FNS];	/* aggregates: n running (accumulator, cells) pairs in sorted order */
@@ -68,37 +55,6 @@ struct win_ag {
 
 __host__ __device__ static inline bool win_is_agg(int op) { return op >= MDB_WIN_SUM; }
 __host__ __device__ static inline bool win_is_minmax(int op) { return op == MDB_WIN_MIN || op == MDB_WIN_MAX; }
-
-/* the sort operator's order-preserving image (mdb_dev_sort.hip, sort_image) and its inverse */
-__device__ static inline uint64_t win_image(uint64_t bits, int type)
-{
-	if (type == MDB_T_DOUBLE)
-		return (bits >> 63) ? ~bits : (bits ^ 0x8000000000000000ull);
-	return bits ^ 0x8000000000000000ull;
-}
-
-__device__ static inline uint64_t win_unimage(uint64_t u, int type)
-{
-	if (type == MDB_T_DOUBLE)
-		return (u >> 63) ? (u ^ 0x8000000000000000ull) : ~u;
-	return u ^ 0x8000000000000000ull;
-}
-
-/* the cell of stream position sp: false for a NULL cell and for "no row" */
-__device__ static inline bool win_cell(const win_col &c, uint64_t sp, uint64_t *bits)
-{
-	uint64_t row = sp;
-	if (c.rid) {
-		const uint32_t r = c.rid[sp];
-		if (r == MDB_NO_ROW)
-			return false;
-		row = r;
-	}
-	if (c.nullbits && mdb_bit_is_set(c.nullbits, row))
-		return false;
-	*bits = c.values[row];
-	return true;
-}
 
 /* left then right: right is folded INTO left, in that order; an empty side changes nothing */
 __device__ static inline win_ag win_fold(int op, win_ag l, win_ag r)
@@ -227,38 +183,12 @@ __device__ static inline win_ag win_block_scan_ag(int op, win_ag v, bool hasp, w
  * ph bit p = "sorted position p begins a partition" (position 0, or a partition key differs from the row before: NULL equals NULL, values
  * by their bits), gh bit p = "... a peer group" (a partition head, or an order key differs).  Both bitmaps were cleared by the caller;
  * every wave that holds a position below n writes its word of each. */
-__global__ __launch_bounds__(WIN_THREADS) void k_win_heads(win_keys K, const uint32_t *__restrict__ perm, uint64_t n, unsigned long long *__restrict__ ph,
+__global__ __launch_bounds__(WIN_THREADS) void k_win_heads(mdb_stream_keys K, const uint32_t *__restrict__ perm, uint64_t n, unsigned long long *__restrict__ ph,
 							    unsigned long long *__restrict__ gh, uint32_t *status)
 {
 	const uint64_t p = (uint64_t)blockIdx.x * WIN_THREADS + threadIdx.x;
-	const bool in = p < n, first_lane = in && p && mdb_lane() == 0;
-	uint64_t s1 = in ? (perm ? perm[p] : p) : 0, s0 = first_lane ? (perm ? perm[p - 1] : p - 1) : 0;
-	if (s1 >= n || s0 >= n) {	/* (never read a key cell beyond the stream) */
-		if (in)
-			mdb_raise(status, WIN_ST_PERM_RANGE);
-		s1 = s1 >= n ? 0 : s1;
-		s0 = s0 >= n ? 0 : s0;
-	}
-	bool phead = in && p == 0, ghead = false;
-	for (int k = 0; k < K.nkeys; k++) {
-		uint64_t b1 = 0;
-		const bool v1 = in && win_cell(K.k[k], s1, &b1);
-		uint64_t b0 = (uint64_t)__shfl_up((unsigned long long)b1, 1u, MDB_WAVE);
-		bool v0 = __shfl_up((int)v1, 1u, MDB_WAVE) != 0;
-		if (first_lane) {
-			b0 = 0;
-			v0 = win_cell(K.k[k], s0, &b0);
-		}
-		if (in && p) {
-			const bool differs = v0 != v1 || (v1 && b0 != b1);
-			if (k < K.npart)
-				phead = phead || differs;
-			else
-				ghead = ghead || differs;
-		}
-	}
-	ghead = ghead || phead;
-	const unsigned long long bp = __ballot(phead), bg = __ballot(ghead);
+	const mdb_stream_head h = mdb_stream_head_of(K, perm, n, p, status);
+	const unsigned long long bp = __ballot(h.part), bg = __ballot(h.peer);
 	if (mdb_lane() == 0 && (p & ~63ull) < n) {
 		ph[p >> 6] = bp;
 		gh[p >> 6] = bg;
@@ -317,7 +247,7 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 				sp[j] = 0xFFFFFFFFu;
 			}
 		if (bad)
-			mdb_raise(A.status, WIN_ST_PERM_RANGE);
+			mdb_raise(A.status, MDB_GROUPS_ST_PERM_RANGE);
 	}
 
 	/* ---- the structure: b, g and the peer heads since b */
@@ -380,7 +310,7 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 	/* ---- the aggregates: the running pair of the partition's cells */
 	int slot = 0;
 	for (int f = 0; f < A.F.nfns; f++) {
-		const win_col &col = A.F.c[f];
+		const mdb_stream_col &col = A.F.c[f];
 		if (!win_is_agg(col.op))
 			continue;
 		const bool mm = win_is_minmax(col.op);
@@ -393,9 +323,9 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 			if ((pb >> j) & 1u)
 				acc.acc = acc.cnt = 0;
 			uint64_t vb = 0;
-			if (sp[j] != 0xFFFFFFFFu && win_cell(col, sp[j], &vb)) {
+			if (sp[j] != 0xFFFFFFFFu && mdb_stream_cell(col, sp[j], &vb)) {
 				win_ag one;
-				one.acc = mm ? win_image(vb, col.type) : vb;
+				one.acc = mm ? mdb_order_image(vb, col.type) : vb;
 				one.cnt = 1;
 				acc = win_fold(col.op, acc, one);
 			}
@@ -417,9 +347,9 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 				if ((pb >> j) & 1u)
 					cur.acc = cur.cnt = 0;
 				uint64_t vb = 0;
-				if (sp[j] != 0xFFFFFFFFu && win_cell(col, sp[j], &vb)) {
+				if (sp[j] != 0xFFFFFFFFu && mdb_stream_cell(col, sp[j], &vb)) {
 					win_ag one;
-					one.acc = mm ? win_image(vb, col.type) : vb;
+					one.acc = mm ? mdb_order_image(vb, col.type) : vb;
 					one.cnt = 1;
 					cur = win_fold(col.op, cur, one);
 				}
@@ -541,9 +471,9 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_ends(win_ends_args A)
 		const uint64_t e = above ? p + (uint64_t)__ffsll((long long)above) : (uint64_t)s_nx[w];	/* (p < e <= n) */
 		const uint64_t sp = A.perm ? A.perm[p] : p;
 		if (sp >= n)
-			continue;	/* (k_win_scan has raised WIN_ST_PERM_RANGE) */
+			continue;	/* (k_win_scan has raised MDB_GROUPS_ST_PERM_RANGE) */
 		for (int f = 0; f < A.F.nfns; f++) {
-			const win_col &col = A.F.c[f];
+			const mdb_stream_col &col = A.F.c[f];
 			if (col.op == MDB_WIN_COUNT) {
 				A.F.out[f][sp] = e - (uint64_t)A.B32[p];
 				continue;
@@ -554,7 +484,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_ends(win_ends_args A)
 			uint64_t res = 0;
 			if (v.y) {
 				if (win_is_minmax(col.op))
-					res = win_unimage(v.x, col.type);
+					res = mdb_order_unimage(v.x, col.type);
 				else if (col.op == MDB_WIN_SUM)
 					res = v.x;
 				else
@@ -576,37 +506,6 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_pack(const uint8_t *__restr
 }
 
 /* ------------------------------------------------------------------ host side */
-
-struct win_tmp {
-	mdb_dev_ctx *ctx;
-	void *p[16 + 2 * WIN_MAX_FNS];
-	int n;
-	explicit win_tmp(mdb_dev_ctx *c) : ctx(c), n(0) {}
-	~win_tmp()
-	{
-		for (int i = 0; i < n; i++)
-			(void)mdb_cached_free(ctx, p[i]);
-	}
-	void *take(size_t bytes)
-	{
-		void *q = NULL;
-		if (n == (int)(sizeof(p) / sizeof(p[0])) || mdb_cached_alloc(ctx, bytes ? bytes : 8, &q))
-			return NULL;
-		p[n++] = q;
-		return q;
-	}
-};
-
-static win_col win_col_of_key(const struct mdb_sort_key *k)
-{
-	win_col c;
-	c.values = (const uint64_t *)k->values;
-	c.nullbits = k->nullbits;
-	c.rid = k->rid;
-	c.op = 0;
-	c.type = k->type;
-	return c;
-}
 
 extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part, int npart, const struct mdb_sort_key *order, int norder, uint64_t n,
 			      const struct mdb_window_fn *fns, int nfns, uint32_t *out_form)
@@ -650,10 +549,7 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "window: function %d: no cells, or unknown cell type %d", f, w->type);
 		if (w->type == MDB_T_DOUBLE && !win_is_minmax(w->op))
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "window: function %d: SUM / AVG over DOUBLE cells are not served (a scan's order of summation)", f);
-		F.c[f].values = (const uint64_t *)w->values;
-		F.c[f].nullbits = w->nullbits;
-		F.c[f].rid = w->rid;
-		F.c[f].type = w->type;
+		F.c[f] = mdb_stream_col_of(w->values, w->nullbits, w->rid, w->op, w->type);
 		nslots++;
 	}
 	const uint32_t form = nkeys ? 2u : 1u;
@@ -663,7 +559,7 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 		return MIDORIDB_OK;
 	}
 
-	win_tmp tmp(ctx);
+	mdb_dev_tmp tmp(ctx);
 	const uint64_t nchunks = (n + WIN_CHUNK - 1u) / WIN_CHUNK, words = (n + 63u) / 64u;
 	uint32_t *perm = NULL;
 	int rc;
@@ -695,12 +591,12 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 			return mdb_set_err(ctx, -MIDORIDB_NOMEM, "window: no device memory for the running values of %llu rows", (unsigned long long)n);
 	}
 
-	win_keys K;
+	mdb_stream_keys K;
 	memset(&K, 0, sizeof(K));
 	K.npart = npart;
 	K.nkeys = nkeys;
 	for (int k = 0; k < nkeys; k++)
-		K.k[k] = win_col_of_key(&sk[k]);
+		K.k[k] = mdb_stream_col_of_key(&sk[k]);
 	MDB_HIP(ctx, hipMemsetAsync(status, 0, 4, ctx->stream));
 	MDB_HIP(ctx, hipMemsetAsync(ph, 0, nchunks * WIN_WORDS * 8u * 2u, ctx->stream));
 	MDB_LAUNCH(ctx, "win_heads", k_win_heads, (uint32_t)((n + WIN_THREADS - 1u) / WIN_THREADS), WIN_THREADS, K, (const uint32_t *)perm, n, ph, gh, status);
@@ -760,7 +656,7 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 		uint32_t h = 0;
 		MDB_HIP(ctx, hipMemcpyAsync(&h, status, 4, hipMemcpyDeviceToHost, ctx->stream));
 		MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		if (h & WIN_ST_PERM_RANGE)
+		if (h & MDB_GROUPS_ST_PERM_RANGE)
 			return mdb_set_err(ctx, -MIDORIDB_INTERNAL, "window: the sort's permutation names a row beyond the stream");
 	}
 	if (out_form)

@@ -52,7 +52,7 @@
  * Operator precedence follows midorisql.y:48-63; literal lexing follows
  * midorisql.l:83-92 (a '-' directly in front of digits belongs to the number).
  * The emitted queue is accepted unchanged by the reference's ast_build_tree()
- * (checked in tests/test_sql_frontend.py against oracle/_ref).
+ * (checked in tests/test_cpu_frontend_abi.py against oracle/_ref).
  */
 #include "mdb_host.h"
 #include <ctype.h>

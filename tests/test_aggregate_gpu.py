@@ -73,6 +73,36 @@ def make_stream(rng, n, G, null_key=True):
     return gid, first, keys, knull
 
 
+def run_head_cases():
+    """(n, the sorted positions at which runs begin) for the run finder's 1024-position chunks and 64-position words: one run, a run per row,
+    and three runs whose heads are the last position of a chunk, the first of the next, position 63 / 64 of a word, the stream's last row"""
+    three = {1023: [(0, 63, 64), (0, 64, 1022)], 1024: [(0, 63, 64), (0, 64, 1023)], 1025: [(0, 63, 64), (0, 1023, 1024)],
+             2049: [(0, 1023, 1024), (0, 2047, 2048)]}
+    return [(n, h) for n in (1023, 1024, 1025, 2049) for h in [(0,), tuple(range(n))] + three[n]]
+
+
+def run_head_id(case):
+    n, heads = case
+    return f"{n}-G{len(heads)}" + (f"-{heads[1]}-{heads[2]}" if len(heads) == 3 else "")
+
+
+def stream_with_run_heads(rng, n, heads):
+    """Two key columns whose stable ascending sort has its runs begin at exactly the sorted positions `heads` (heads[0] == 0): the run at
+    heads[s] holds the key (s // 2 - 1, s % 2), the first run's first column is NULL (NULLs sort first).  The rows come in random stream
+    order, so a run's group - groups are numbered by first occurrence - is not its place in the sorted order.
+    -> gid, first[], (cells, nulls) of the two key columns"""
+    G = len(heads)
+    srt = np.repeat(np.arange(G, dtype=np.int64), np.diff(list(heads) + [n]))      # the run of every sorted position
+    rng.shuffle(srt)                                                               # ... of every stream position
+    _, first_of = np.unique(srt, return_index=True)
+    rank = np.empty(G, dtype=np.int64)
+    rank[np.argsort(first_of)] = np.arange(G)
+    k1, k2 = srt // 2 - 1, srt % 2
+    k1null = (srt == 0) & (G >= 2)
+    k1[k1null] = 99                                                                # (what lies under a NULL key does not matter)
+    return rank[srt], np.sort(first_of).astype(np.int32), (k1, k1null), (k2, np.zeros(n, dtype=bool))
+
+
 def int_cells(rng, n):
     v = rng.integers(I64_MIN, I64_MAX, n, dtype=np.int64, endpoint=True)
     small = rng.random(n) < 0.5
@@ -197,6 +227,20 @@ def test_operator_double_cells_bit_exact_in_both_forms(dev, n):
         run_and_check(dev, D, dkeys, n, dfirst, G, gid,
                       [(D.AGG_SUM, D.T_DOUBLE, off), (D.AGG_AVG, D.T_DOUBLE, via), (D.AGG_MIN, D.T_DOUBLE, plain), (D.AGG_MAX, D.T_DOUBLE, via)], 2)
         run_and_check(dev, D, dkeys, n, dfirst, G, gid, [(D.AGG_MIN, D.T_DOUBLE, via), (D.AGG_MAX, D.T_DOUBLE, off)], 1 if G <= lds2 else 2)
+
+
+@pytest.mark.parametrize("case", run_head_cases(), ids=run_head_id)
+def test_operator_sorted_form_run_heads_at_chunk_and_word_edges(dev, case):
+    """the sorted form (a DOUBLE sum) over two key columns, the runs' heads on the run finder's chunk and word edges: bit for bit numpy's"""
+    from midoridb_amd import dev as D
+    n, heads = case
+    rng = np.random.default_rng(2500 + n + len(heads) + heads[-1])
+    gid, first, (k1, k1null), (k2, k2null) = stream_with_run_heads(rng, n, heads)
+    G = len(heads)
+    c1, c2 = Column(dev, D, rng, k1, k1null), Column(dev, D, rng, k2, k2null, misaligned=True)
+    dkeys = [(c1.values, c1.nullbits, None, D.T_INT64, False), (c2.values, c2.nullbits, None, D.T_INT64, False)]
+    vd = Column(dev, D, rng, eighths(rng, n).view(np.int64), null_cells(rng, gid, G, n), misaligned=True)
+    run_and_check(dev, D, dkeys, n, dev.to_dev(first), G, gid, [(D.AGG_SUM, D.T_DOUBLE, vd)], 2)
 
 
 @pytest.mark.parametrize("n", [1, 65, 4097, 2 ** 18 + 1])

@@ -7,7 +7,7 @@ import sqlite3
 import numpy as np
 import pytest
 
-from tests.test_aggregate_gpu import Column, by_name, make_stream, null_cells, sql_rows
+from tests.test_aggregate_gpu import Column, by_name, make_stream, null_cells, run_head_cases, run_head_id, sql_rows, stream_with_run_heads
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +148,25 @@ def test_operator_step_a_lds_table_and_sorted_runs_agree(dev, monkeypatch):
     # twice the same call: the same bytes
     again = run_and_check(dev, D, [k1], n, dfirst, G, gid, cols, [1, 2])
     assert all(x.tobytes() == y.tobytes() for x, y in zip(a, again))
+
+
+@pytest.mark.parametrize("case", run_head_cases(), ids=run_head_id)
+def test_operator_sorted_runs_heads_at_chunk_and_word_edges(dev, monkeypatch, case):
+    """two key columns - sorted runs whatever G is: one run, a run per row, and three runs whose heads are the last position of a
+    1024-position chunk, the first of the next, position 63 / 64 of a word of head bits and the stream's last row (n around one and two
+    chunks).  A ranged and a DOUBLE column, as the forms decide and both sorted: exactly the restatement's counts"""
+    from midoridb_amd import dev as D
+    n, heads = case
+    rng = np.random.default_rng(7600 + n + len(heads) + heads[-1])
+    gid, first, (k1, k1null), (k2, k2null) = stream_with_run_heads(rng, n, heads)
+    G = len(heads)
+    c1, c2 = Column(dev, D, rng, k1, k1null, misaligned=True), Column(dev, D, rng, k2, k2null)
+    dkeys = [(c1.values, c1.nullbits, None, D.T_INT64, False), (c2.values, c2.nullbits, None, D.T_INT64, False)]
+    vnull = null_cells(rng, gid, G, n)
+    v = ranged_cells(rng, n, gid, G, -7, 40, vnull)
+    cols = [(D.T_INT64, Column(dev, D, rng, v, vnull, through_rid=True), (-7, 32)),
+            (D.T_DOUBLE, Column(dev, D, rng, double_cells(rng, n), vnull), None)]
+    both_ways(dev, D, monkeypatch, dkeys, n, dev.to_dev(first), G, gid, cols, [1, 2])
 
 
 def test_operator_long_spans_and_the_bitmap_bound(dev, monkeypatch):
