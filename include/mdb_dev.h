@@ -63,6 +63,16 @@ void mdb_dev_ctx_destroy(mdb_dev_ctx *ctx);
 int mdb_dev_ctx_set_stream(mdb_dev_ctx *ctx, void *stream);
 const char *mdb_dev_last_error(mdb_dev_ctx *ctx);
 int mdb_dev_sync(mdb_dev_ctx *ctx);
+/* Results in stream order.  Default off: every operator's result columns are complete when it returns, whatever stream the caller reads
+ * them on.  On: a caller whose every reader of the result columns is ordered by the context's stream (kernels, asynchronous copies and
+ * allocator reuse on that stream; mdb_dev_sync for the host) lets mdb_dev_join_group_count return as soon as its sizes are known - on
+ * return *out_groups, *out_joined and the plan are final, and the result columns are complete IN THE ORDER OF THE CONTEXT'S STREAM: the
+ * kernel that writes them may still be running.  Input columns must likewise stay untouched until the stream has passed the call.
+ * Only the join whose leaf kernel fills the ordering kernel's ranges uses it (mdb_dev_last_plan: ranged_order); every other operator and
+ * path completes on return as before.  Switching synchronises. */
+int mdb_dev_results_in_stream_order(mdb_dev_ctx *ctx, int on);
+/* 1: the last mdb_dev_join_group_count returned behind its leaf kernel's status, its ordering kernel queued behind the return (tests) */
+int mdb_dev_last_return_was_early(mdb_dev_ctx *ctx);
 /* Number of visible HIP devices (no context needed; <0 on error). */
 int mdb_dev_device_count(void);
 /* Pre-size the internal scratch arena (bytes).  Operators grow it on demand; growing

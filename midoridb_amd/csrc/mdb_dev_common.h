@@ -30,6 +30,9 @@ struct mdb_dev_ctx : mdb_memo_store {
 	bool own_stream;
 	hipStream_t aux_stream;		/* second stream: the two tables of a join are partitioned concurrently */
 	hipEvent_t ev_fork, ev_join;
+	hipEvent_t ev_status;		/* recorded behind a status copy that a kernel is queued behind: the host waits for the copy alone */
+	bool stream_ordered;		/* mdb_dev_results_in_stream_order(): the caller reads result columns in the order of `stream` */
+	bool last_return_early;		/* the last join + GROUP BY returned with its ordering kernel still queued (mdb_dev_last_return_was_early) */
 	bool overlap;			/* false: everything on the main stream (isolated per-kernel timing) */
 	bool last_left_dups_known, last_left_dups;	/* the last join ran through leaf kernels that tell whether a key with partners has several LEFT rows, and whether one has */
 	int narrow_mode;		/* 32-bit hashes for int32-range join keys: 0 never, 1 sampled + verified (default), 2 always try */
@@ -86,8 +89,10 @@ struct mdb_plan_scope {
 	mdb_dev_ctx *c;
 	explicit mdb_plan_scope(mdb_dev_ctx *ctx) : c(ctx)
 	{
-		if (c && c->pl_depth++ == 0)
+		if (c && c->pl_depth++ == 0) {
 			memset(&c->plan, 0, sizeof(c->plan));
+			c->last_return_early = false;
+		}
 	}
 	~mdb_plan_scope()
 	{
@@ -96,6 +101,23 @@ struct mdb_plan_scope {
 			c->ct_retries += c->plan.retries;
 			c->ct_samples += c->plan.samples;
 		}
+	}
+};
+
+/* An operator that calls mdb_dev_join_group_count and then works on its result columns outside the context's stream (mdb_dist.hip's transfer
+ * stream), or whose use of them has not been checked against mdb_dev_results_in_stream_order(): complete on return inside this scope */
+struct mdb_complete_on_return {
+	mdb_dev_ctx *c;
+	bool was;
+	explicit mdb_complete_on_return(mdb_dev_ctx *ctx) : c(ctx), was(ctx && ctx->stream_ordered)
+	{
+		if (c)
+			c->stream_ordered = false;
+	}
+	~mdb_complete_on_return()
+	{
+		if (c)
+			c->stream_ordered = was;
 	}
 };
 

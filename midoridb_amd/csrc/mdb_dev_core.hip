@@ -66,7 +66,8 @@ extern "C" int mdb_dev_ctx_create(int device, void *stream, mdb_dev_ctx **out)
 		ctx->own_stream = false;
 	}
 	ctx->aux_stream = NULL;
-	ctx->ev_fork = ctx->ev_join = NULL;
+	ctx->ev_fork = ctx->ev_join = ctx->ev_status = NULL;
+	ctx->stream_ordered = ctx->last_return_early = false;
 	ctx->pending_op = NULL;
 	ctx->cache_bytes = 0;
 	ctx->narrow_mode = 1;
@@ -78,7 +79,8 @@ extern "C" int mdb_dev_ctx_create(int device, void *stream, mdb_dev_ctx **out)
 	ctx->overlap = false;	/* measured: no gain on one GPU (each kernel already fills the chip), kept for the multi-GPU exchange */
 	if (hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess ||
 	    hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) {
+	    hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess ||
+	    hipEventCreateWithFlags(&ctx->ev_status, hipEventDisableTiming) != hipSuccess) {
 		mdb_dev_ctx_destroy(ctx);
 		return -MIDORIDB_INTERNAL;
 	}
@@ -110,6 +112,8 @@ extern "C" void mdb_dev_ctx_destroy(mdb_dev_ctx *ctx)
 		(void)hipEventDestroy(ctx->ev_fork);
 	if (ctx->ev_join)
 		(void)hipEventDestroy(ctx->ev_join);
+	if (ctx->ev_status)
+		(void)hipEventDestroy(ctx->ev_status);
 	free(ctx->pending_op);
 	for (auto &c : ctx->cache)
 		(void)hipFree(c.first);
@@ -153,6 +157,20 @@ extern "C" int mdb_dev_sync(mdb_dev_ctx *ctx)
 {
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return MIDORIDB_OK;
+}
+
+extern "C" int mdb_dev_results_in_stream_order(mdb_dev_ctx *ctx, int on)
+{
+	if (!ctx)
+		return -MIDORIDB_ERROR;
+	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));	/* (what an earlier call left queued is complete before the contract changes) */
+	ctx->stream_ordered = on != 0;
+	return MIDORIDB_OK;
+}
+
+extern "C" int mdb_dev_last_return_was_early(mdb_dev_ctx *ctx)
+{
+	return ctx && ctx->last_return_early ? 1 : 0;
 }
 
 /* ------------------------------------------------------------------ two-stream fork / join */

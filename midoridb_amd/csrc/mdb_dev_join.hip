@@ -1662,6 +1662,7 @@ struct gc_run {
 	bool ranged;			/* ... that writes its records into the ordering kernel's ranges */
 	uint32_t rg_n;
 	bool ordered_early;		/* order_presorted was launched behind the leaf kernel, before the status came back */
+	bool tail_queued;		/* ... and the host has waited for the status alone: that kernel may still be running (gc_read_status) */
 	unsigned long long *dn_bits;	/* != NULL: the groups leave as one bit per left row */
 	gc_readback *rb;		/* the status words as last read back (ctx->h_pinned + MDB_HP_STATUS) */
 	uint32_t dn_cleared, dn_exceptions;
@@ -2104,16 +2105,35 @@ static int gc_read_back(mdb_dev_ctx *ctx, gc_run *g, size_t bytes)
 {
 	MDB_HIP(ctx, hipMemcpyAsync(g->rb, ctx->d_status, bytes, hipMemcpyDeviceToHost, ctx->stream));
 	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	g->tail_queued = false;		/* (whatever was queued behind an earlier status is complete too) */
 	return MIDORIDB_OK;
 }
 
 /* stage 4: G, J and the status flags come back with one sync; the sort is sized by G ... except where the leaf kernel has filled the ordering kernel's
  * ranges itself: that kernel needs no size, and is launched right behind it (its writes bounded by the caller's capacity; should the status words
- * ask for another path, that path writes the columns again) - the step's only sync then comes after its last kernel */
+ * ask for another path, that path writes the columns again) - the step's only sync then comes after its last kernel.
+ * A caller that reads its result columns in stream order (mdb_dev_results_in_stream_order) does not wait for that kernel at all: the leaf kernel
+ * has written every status word, so the copy goes in front of the ordering kernel and the host waits for an event recorded behind the copy -
+ * the ordering kernel runs while the call returns and the next one is prepared.  Nothing the host reads afterwards is touched by it (no status
+ * of its own, its stores go to the caller's columns alone); whatever a retry path launches queues behind it on the same stream. */
 static int gc_read_status(mdb_dev_ctx *ctx, gc_run *g)
 {
 	int rc;
 	g->ordered_early = false;
+	g->tail_queued = false;
+	if (g->ranged && g->out.cap && ctx->stream_ordered) {
+		MDB_HIP(ctx, hipMemcpyAsync(g->rb, ctx->d_status, GC_RB_BYTES_DN, hipMemcpyDeviceToHost, ctx->stream));
+		MDB_HIP(ctx, hipEventRecord(ctx->ev_status, ctx->stream));
+		rc = gc_order_presorted(ctx, g, g->out.cap);
+		MDB_HIP(ctx, hipEventSynchronize(ctx->ev_status));
+		if (rc)
+			return rc;
+		g->ordered_early = true;
+		g->tail_queued = true;
+		g->dn_cleared = g->rb->dn_cleared;
+		g->dn_exceptions = g->rb->dn_exceptions;
+		return MIDORIDB_OK;
+	}
 	if (g->ranged && g->out.cap) {
 		if ((rc = gc_order_presorted(ctx, g, g->out.cap)))
 			return rc;
@@ -2335,7 +2355,7 @@ static int gc_deliver_records(mdb_dev_ctx *ctx, gc_run *g)
 		if (!rc)
 			MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	} else if (g->ranged && g->ordered_early)
-		rc = MIDORIDB_OK;	/* (done, and waited for with the status words) */
+		rc = MIDORIDB_OK;	/* (launched behind the leaf kernel: waited for with the status words, or queued behind them for a stream-ordered caller) */
 	else if (g->ranged)
 		rc = gc_order_presorted(ctx, g, 0);
 	else
@@ -2424,6 +2444,7 @@ static int gc_finish(mdb_dev_ctx *ctx, gc_state *st, const gc_table &right, cons
 	if (g.G && (rc = g.records ? gc_deliver_records(ctx, &g) : gc_deliver_dense(ctx, &g)))
 		return rc;
 	gc_remember(ctx, &g);
+	ctx->last_return_early = g.tail_queued;
 	return MIDORIDB_OK;
 }
 
@@ -3328,6 +3349,7 @@ extern "C" int mdb_dev_join_group_count_multi(mdb_dev_ctx *ctx, const int64_t *k
 	if (n_right == 1)
 		return mdb_dev_join_group_count(ctx, keys_l, null_l, n_l, keys_r[0], null_r ? null_r[0] : NULL, n_r[0], flags, out_key, out_count, out_first,
 						cap, out_groups, out_joined);
+	mdb_complete_on_return complete_(ctx);	/* (several right tables: complete on return, as the chain below has always been) */
 	if (!n_l)
 		return MIDORIDB_OK;
 	uint64_t smallest = n_l;

@@ -1931,6 +1931,7 @@ extern "C" int mdb_dev_join_keys_ordered(mdb_dev_ctx *ctx, const int64_t *keys_l
 					 const uint64_t *null_r, uint64_t n_r, int64_t **out_key, uint64_t *out_rows, int *served)
 {
 	mdb_plan_scope plan_scope(ctx);
+	mdb_complete_on_return complete_(ctx);
 	if (!ctx || !out_key || !out_rows || !served)
 		return -MIDORIDB_ERROR;
 	*out_key = NULL;
@@ -2003,6 +2004,7 @@ extern "C" int mdb_dev_join_keys(mdb_dev_ctx *ctx, const int64_t *keys_l, const 
 				 const uint64_t *null_r, uint64_t n_r, int64_t **out_key, uint64_t *out_rows)
 {
 	mdb_plan_scope plan_scope(ctx);
+	mdb_complete_on_return complete_(ctx);
 	if (!ctx || !out_key || !out_rows)
 		return -MIDORIDB_ERROR;
 	*out_key = NULL;

@@ -1153,6 +1153,9 @@ static int dist_join_impl(mdb_dist *d, const int64_t *keys_l, const uint64_t *nu
 			  uint32_t **out_first, uint64_t cap, uint64_t *out_groups, uint64_t *out_joined, bool by_key_hash = false)
 {
 	mdb_dev_ctx *ctx = d->ctx;
+	/* (the next call's transfers overwrite the receive buffers on comm_stream, and the local join's group keys are gathered from one of them:
+	 * the local join completes on return here, whatever the context's caller has promised about its own reads) */
+	mdb_complete_on_return complete_(ctx);
 	*out_groups = 0;
 	if (out_joined)
 		*out_joined = 0;

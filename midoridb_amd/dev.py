@@ -217,6 +217,8 @@ def _bind(lib):
         "mdb_dev_ctx_set_stream": ([P, P], c_int),
         "mdb_dev_last_error": ([P], c_char_p),
         "mdb_dev_sync": ([P], c_int),
+        "mdb_dev_results_in_stream_order": ([P, c_int], c_int),
+        "mdb_dev_last_return_was_early": ([P], c_int),
         "mdb_dev_device_count": ([], c_int),
         "mdb_dev_reserve": ([P, c_size_t], c_int),
         "mdb_dev_set_overlap": ([P, c_int], c_int),
@@ -312,6 +314,7 @@ def _bind(lib):
 
 DEV_SYMBOLS = [
     "mdb_dev_ctx_create", "mdb_dev_ctx_destroy", "mdb_dev_ctx_set_stream", "mdb_dev_last_error", "mdb_dev_sync",
+    "mdb_dev_results_in_stream_order", "mdb_dev_last_return_was_early",
     "mdb_dev_device_count", "mdb_dev_reserve", "mdb_dev_set_overlap", "mdb_dev_set_narrow_keys", "mdb_dev_call_stats", "mdb_dev_last_plan", "mdb_dev_reload_knobs", "mdb_dev_counters", "mdb_dev_distinct_scan", "mdb_dev_explain_join_group_count", "mdb_dev_explain_group_count", "mdb_dev_explain_join_payload", "mdb_dev_arena_bytes", "mdb_dev_alloc", "mdb_dev_free", "mdb_dev_memset",
     "mdb_dev_host_alloc", "mdb_dev_host_free", "mdb_dev_h2d", "mdb_dev_d2h", "mdb_dev_prof_enable", "mdb_dev_prof_reset", "mdb_dev_prof_read", "mdb_dev_prof_symbols", "mdb_dev_filter",
     "mdb_dev_gather64", "mdb_dev_gather_cols", "mdb_dev_filter_project", "mdb_dev_double_join_keys", "mdb_dev_gather32", "mdb_dev_iota32", "mdb_dev_scatter_set64", "mdb_dev_sort_perm", "mdb_dev_topk_perm", "mdb_dev_distinct_sel", "mdb_dev_group_count_multi", "mdb_dev_join_pairs", "mdb_dev_join_key_layout", "mdb_dev_join_key_pack", "mdb_dev_join_key_unpack", "mdb_dev_outer_complete", "mdb_dev_outer_complete_full", "mdb_dev_join_keys", "mdb_dev_join_keys_ordered", "mdb_dev_join_payload", "mdb_dev_join_payload_multi", "mdb_dev_cross_pairs", "mdb_dev_alloc_size", "mdb_dev_retain", "mdb_dev_holders", "mdb_dev_map_ids",
@@ -426,6 +429,10 @@ class DeviceCtx:
         if rc != 0:
             raise DeviceError(f"mdb_dev_ctx_create failed with {rc}")
         self.h = h
+        # bound to torch's current stream, every reader of a result tensor (torch kernels, copies, the caching allocator) is ordered by that
+        # stream: the operators may return with their last kernel still queued on it (mdb_dev_results_in_stream_order)
+        if use_torch_stream:
+            self.results_in_stream_order(True)
 
     def close(self):
         if getattr(self, "h", None):
@@ -459,6 +466,15 @@ class DeviceCtx:
 
     def sync(self):
         self._chk(self.lib.mdb_dev_sync(self.h), "sync")
+
+    def results_in_stream_order(self, on=True):
+        """on: result tensors are complete in the order of the context's stream when an operator returns, not necessarily for a reader on
+        another stream (on by default when the context is bound to torch's current stream); off: complete on return"""
+        self._chk(self.lib.mdb_dev_results_in_stream_order(self.h, 1 if on else 0), "results_in_stream_order")
+
+    def last_return_was_early(self):
+        """the last join_group_count returned with its ordering kernel still queued on the stream (mdb_dev_last_return_was_early)"""
+        return bool(self.lib.mdb_dev_last_return_was_early(self.h))
 
     def reserve(self, nbytes):
         self._chk(self.lib.mdb_dev_reserve(self.h, nbytes), "reserve")
