@@ -255,7 +255,7 @@ __host__ __device__ static inline uint32_t mdb_fmix32(uint32_t h)
 /* The same finaliser on k-bit words (8 <= k <= 32): x ^= x >> s and a multiplication by an odd constant modulo 2^k are
  * both bijections of [0, 2^k), so mixk is one, and mixk(0) == 0.  The compact narrow form uses it on key - window base: a
  * key column whose values span fewer than 2^k values hashes into k bits, the radix partition consumes the top bits and what
- * is left below them is small enough to INDEX a per-leaf table in LDS directly (mdb_dev_join.hip, k_leaf_direct). */
+ * is left below them is small enough to INDEX a per-leaf table in LDS directly (mdb_dev_join_leaf.hip, k_leaf_direct). */
 __host__ __device__ static inline uint32_t mdb_mixk(uint32_t x, uint32_t k)
 {
 	const uint32_t mask = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);

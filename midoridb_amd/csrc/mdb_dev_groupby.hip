@@ -258,17 +258,17 @@ int mdb_group_count_direct_comp(mdb_dev_ctx *ctx, const struct mdb_bg_comp *comp
 
 /* 0 = done, 1 = not applicable (use the partitioned path), < 0 = error.  keys_r != NULL: the join form (both key columns
  * inside one window; NULL keys never join) - also the cheap way through joins on a handful of hot values. */
-int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, const int64_t *keys_r,
-			    const uint64_t *null_r, uint64_t n_r, bool null_group, int64_t *out_key, uint32_t *out_first, int64_t *out_count,
-			    uint64_t cap, uint64_t *out_groups, uint64_t *out_joined)
+int group_direct_try(mdb_dev_ctx *ctx, const gc_sides &s, bool null_group, const gc_out &out)
 {
-	if (n + (keys_r ? n_r : 0) < GD_MIN_ROWS || n >= 0xFFFFFFFFull || ((uintptr_t)keys & 15) || ((!out_first || !out_count) && !ctx->explaining))
+	const int64_t *keys = s.l.keys, *keys_r = s.r.keys;
+	const uint64_t n = s.l.n, n_r = s.r.n, cap = out.cap;
+	if (n + (keys_r ? n_r : 0) < GD_MIN_ROWS || n >= 0xFFFFFFFFull || ((uintptr_t)keys & 15) || ((!out.first || !out.count) && !ctx->explaining))
 		return 1;
 	if (keys_r && (n_r >= 0xFFFFFFFFull || ((uintptr_t)keys_r & 15) || n_r == 0))
 		return 1;
 	/* range of a sample of the column(s) (shared with the narrow-form decision of the partitioned path) */
 	int64_t lo = 0, hi = 0;
-	int rc = gc_sample_range(ctx, keys, nullbits, n, keys_r, null_r, n_r, ctx->nh_distrust > 0, &lo, &hi);
+	int rc = gc_sample_range(ctx, s, ctx->nh_distrust > 0, &lo, &hi);
 	if (rc)
 		return rc;
 	if (lo > hi)
@@ -298,7 +298,7 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	gd_args a;
 	memset(&a, 0, sizeof(a));
 	a.keys = keys;
-	a.nullbits = nullbits;
+	a.nullbits = s.l.nulls;
 	a.n = n;
 	a.base = (int64_t)((uint64_t)lo - (uint64_t)((range - span) / 2));
 	a.range = range;
@@ -329,7 +329,7 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	if (keys_r) {
 		gd_args b = a;
 		b.keys = keys_r;
-		b.nullbits = null_r;
+		b.nullbits = s.r.nulls;
 		b.n = n_r;
 		b.g_cnt = g_cnt_r;
 		b.g_first = g_first_r;
@@ -340,35 +340,34 @@ int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 	}
 	MDB_LAUNCH(ctx, "group_direct_emit", k_group_direct_emit, (range + 1 + 255) / 256, 256, a, (const unsigned long long *)g_cnt_r, kbits, rec, rec_n,
 		   d_joined);
-	uint32_t *h32 = (uint32_t *)ctx->h_pinned;
-	MDB_HIP(ctx, hipMemcpyAsync(h32, ctx->d_status, 16, hipMemcpyDeviceToHost, ctx->stream));
-	MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
+	const uint32_t *h32 = NULL;
+	if ((rc = gc_status_head(ctx, &h32)))
+		return rc;
+	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE) {
 		ctx->vd[VD_SAMPLE].clear();	/* the sample missed a value outside its range: not to be reused */
-	if (h32[MDB_STW_FLAGS] & GD_ST_VALUE_OUTSIDE)
 		return 1;	/* a value outside the window: the partitioned path */
+	}
 	ctx->plan.small_form = 2;
 	const uint64_t G = h32[GC_STW_LIST_LEN];
-	const uint64_t joined = (uint64_t)h32[GC_STW_JOINED] | ((uint64_t)h32[GC_STW_JOINED + 1] << 32);
 	if (G > cap)
 		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)cap,
 				   (unsigned long long)G);
-	*out_groups = G;
-	if (out_joined)
-		*out_joined = joined;
+	*out.groups = G;
+	if (out.joined)
+		*out.joined = gc_status_joined(h32);
 	if (G == 0)
 		return 0;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-	rc = mdb_order_records_by_rowid(ctx, rec, G, n, kbits, out_first, out_count);
+	rc = mdb_order_records_by_rowid(ctx, rec, G, n, kbits, out.first, out.count);
 	if (rc)
 		return rc < 0 ? rc : -MIDORIDB_INTERNAL;
-	MDB_LAUNCH(ctx, "group_direct_counts", k_group_direct_counts, (uint32_t)((G + 255) / 256), 256, out_count, G, (const unsigned long long *)a.g_cnt,
+	MDB_LAUNCH(ctx, "group_direct_counts", k_group_direct_counts, (uint32_t)((G + 255) / 256), 256, out.count, G, (const unsigned long long *)a.g_cnt,
 		   (const unsigned long long *)g_cnt_r);
 	rc = mdb_dev_sync(ctx);
 	if (rc)
 		return rc;
-	if (out_key) {
-		rc = mdb_dev_gather64(ctx, keys, NULL, out_first, G, out_key, NULL);
+	if (out.key) {
+		rc = mdb_dev_gather64(ctx, keys, NULL, out.first, G, out.key, NULL);
 		if (!rc)
 			rc = mdb_dev_sync(ctx);
 	}
@@ -585,10 +584,12 @@ __global__ void k_group_hashed_emit(gh_args a, uint32_t kbits, unsigned long lon
 }
 
 /* 0 = done, 1 = not applicable, < 0 = error */
-int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, bool null_group, uint32_t *out_first,
-			    int64_t *out_count, uint64_t cap, uint64_t *out_groups)
+int group_hashed_try(mdb_dev_ctx *ctx, const gc_table &t, bool null_group, const gc_out &out)
 {
-	if (n < GD_MIN_ROWS || n >= 0xFFFFFFFFull || ((uintptr_t)keys & 15) || !out_first || !out_count)
+	const int64_t *keys = t.keys;
+	const uint64_t *nullbits = t.nulls;
+	const uint64_t n = t.n;
+	if (n < GD_MIN_ROWS || n >= 0xFFFFFFFFull || ((uintptr_t)keys & 15) || !out.first || !out.count)
 		return 1;	/* (mdb_dev_explain_group_count passes no outputs: whether a column has few distinct values is no statistic a catalog hands over) */
 	/* distinct values in a sample of the column, remembered like the range sample */
 	uint32_t distinct;
@@ -643,17 +644,17 @@ int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *null
 		return 1;
 	}
 	const uint64_t G = h32[GC_STW_LIST_LEN];
-	if (G > cap)
-		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)cap,
+	if (G > out.cap)
+		return mdb_set_err(ctx, -MIDORIDB_ERROR, "group output capacity %llu too small for %llu groups", (unsigned long long)out.cap,
 				   (unsigned long long)G);
-	*out_groups = G;
+	*out.groups = G;
 	if (G == 0)
 		return 0;
 	MDB_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-	rc = mdb_order_records_by_rowid(ctx, rec, G, n, kbits, out_first, out_count);
+	rc = mdb_order_records_by_rowid(ctx, rec, G, n, kbits, out.first, out.count);
 	if (rc)
 		return rc < 0 ? rc : -MIDORIDB_INTERNAL;
-	MDB_LAUNCH(ctx, "group_direct_counts", k_group_direct_counts, (uint32_t)((G + 255) / 256), 256, out_count, G, (const unsigned long long *)a.g_cnt,
+	MDB_LAUNCH(ctx, "group_direct_counts", k_group_direct_counts, (uint32_t)((G + 255) / 256), 256, out.count, G, (const unsigned long long *)a.g_cnt,
 		   (const unsigned long long *)NULL);
 	return mdb_dev_sync(ctx);
 }

@@ -218,7 +218,7 @@ size_t mdb_scatter4096_arena_bytes(const mdb_dev_ctx *ctx, uint64_t n, bool row_
 int mdb_scatter4096(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nulls, uint64_t n, int64_t key_lo, uint32_t kbits, bool report, uint32_t rel_hi,
 		    uint32_t cap, bool row_words, const char *name, void **regions, uint32_t **cursors);
 
-/* ---- ordering of (row id, payload) records (mdb_dev_join.hip) ----------------------------------
+/* ---- ordering of (row id, payload) records (mdb_dev_order.hip) ---------------------------------
  * rec[i] = (row id << (64 - kbits)) | payload (payload >= 1; zero words are gaps), kbits = bits of a row id as
  * returned by mdb_order_records_arena_bytes(); delivers out_first[] = row ids ascending, out_count[] = payloads. */
 size_t mdb_order_records_arena_bytes(uint64_t cap, uint64_t n_rows, uint32_t *kbits_out);

@@ -2,10 +2,14 @@
  * mdb_dev_join_internal.h - what the translation units of the join / GROUP BY operators share: the leaf-table helpers, the
  * argument block of the fused operator's leaf kernels, the retry codes of its driver, and the host functions that cross the files
  *
- *   mdb_dev_join.hip     fused join + GROUP BY key + COUNT(*) (leaf kernels, planning, retries, split and N-way forms), plain GROUP BY driver
- *   mdb_dev_order.hip    ordering of the group records by first row id
- *   mdb_dev_groupby.hip  plain GROUP BY fast paths (small value range, few distinct values)
- *   mdb_dev_pairs.hip    materialising INNER JOIN
+ *   mdb_dev_join.hip       fused join + GROUP BY key + COUNT(*): the staged driver (plan, retries, split and N-way forms), the entry points, plain GROUP BY driver, mdb_dev_explain_*
+ *   mdb_dev_join_leaf.hip  its per-leaf LDS kernels (hashed tables, direct-address tables, hot keys, the NULL group) and their launchers
+ *   mdb_dev_leaf_wide.hip  ... and the kernels that join a whole first-level digit per workgroup
+ *   mdb_dev_keyform.hip    the key sample and what it decides: narrow form, compact window, pruning hints (for every file below as well)
+ *   mdb_dev_join_small.hip the forms that answer before the staged driver: single workgroup, any order, mdb_dev_group_count_keys
+ *   mdb_dev_order.hip      ordering of the group records by first row id
+ *   mdb_dev_groupby.hip    plain GROUP BY fast paths (small value range, few distinct values)
+ *   mdb_dev_pairs.hip      materialising INNER JOIN
  */
 #ifndef MDB_DEV_JOIN_INTERNAL_H
 #define MDB_DEV_JOIN_INTERNAL_H
@@ -262,6 +266,25 @@ struct gc_table {
 	uint64_t n;
 };
 
+/* the two tables of a call; the call with the sides swapped is gc_sides{ s.r, s.l }.  One column: r = { NULL, NULL, 0 } */
+struct gc_sides {
+	gc_table l, r;
+};
+
+/* where a call's groups go: key / first may be NULL (not wanted), joined as well */
+struct gc_out {
+	int64_t *key, *count;
+	uint32_t *first;
+	uint64_t cap;
+	uint64_t *groups, *joined;
+	void clear() const
+	{
+		*groups = 0;
+		if (joined)
+			*joined = 0;
+	}
+};
+
 struct gc_window {
 	uint32_t kbits;		/* 0 = no compact window */
 	int64_t lo;
@@ -273,6 +296,14 @@ struct gc_window {
 	bool r_based;		/* the compact window covers the RIGHT table's sampled keys only (by_span, unsplit call): the left rows outside
 				 * it are exactly the ones min-max pruning drops - fewer key bits, hence fewer and larger leaves */
 	bool fast1;		/* plain GROUP BY, duplicates in the key sample: the fixed-capacity layout only if the ONE-level form applies */
+};
+
+/* what gc_narrow_guess decides for a call's key columns.  narrow: try the narrow form; base: centre of the 2^32-wide window of key values it
+ * will be tried with (0 = the plain int32 range, whenever the sampled keys lie inside it); win: the compact window the sample offers */
+struct gc_key_form {
+	bool narrow;
+	int64_t base;
+	gc_window win;
 };
 
 #define TINY_ROWS (GC_THREADS * LEAF_BATCH)	/* rows per table up to which ONE workgroup does the whole operator in LDS */
@@ -303,22 +334,71 @@ int order_records(mdb_dev_ctx *ctx, const unsigned long long *rec, uint64_t list
 			 bool keys32 = false, bool rec32 = false, uint32_t keyed_cbits = 0, uint32_t key_bits = 0, int64_t key_lo = 0,
 			 bool in32 = false /* the list already holds 4-byte records */, uint64_t n_rec = 0 /* records in the list (0: unknown) */);
 size_t order_records_arena_bytes(uint64_t cap, uint64_t n_l, uint32_t kbits, int sb1, int sb2);
-int gc_sample_range(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-			   const uint64_t *null_r, uint64_t n_r, bool fresh, int64_t *lo, int64_t *hi, bool keys32 = false);
-void gc_narrow_note(mdb_dev_ctx *ctx, const int64_t *keys_l, uint64_t n_l, const int64_t *keys_r, uint64_t n_r, bool narrow,
-			   int64_t base = 0, uint32_t key_bits = 0, int64_t key_lo = 0);
-int gc_narrow_guess(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-			   const uint64_t *null_r, uint64_t n_r, bool *narrow, int64_t *base, gc_window *win = nullptr, bool keys32 = false,
-			   bool prune_ok = false /* unsplit call: min-max pruning can run */);
-int tiny_group_count(mdb_dev_ctx *ctx, const int64_t *keys_l, const uint64_t *null_l, uint64_t n_l, const int64_t *keys_r,
-			    const uint64_t *null_r, uint64_t n_r, bool has_r, bool null_group, int64_t *out_key, int64_t *out_count,
-			    uint32_t *out_first, uint64_t cap, uint64_t *out_groups, uint64_t *out_joined);
-int group_hashed_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, bool null_group, uint32_t *out_first,
-			    int64_t *out_count, uint64_t cap, uint64_t *out_groups);
-int group_direct_try(mdb_dev_ctx *ctx, const int64_t *keys, const uint64_t *nullbits, uint64_t n, const int64_t *keys_r,
-			    const uint64_t *null_r, uint64_t n_r, bool null_group, int64_t *out_key, uint32_t *out_first, int64_t *out_count,
-			    uint64_t cap, uint64_t *out_groups, uint64_t *out_joined);
 bool ld_disabled(void);
+/* the first four status words - flags, GC_STW_LIST_LEN, GC_STW_JOINED as two halves - copied to the pinned block, waited for: *h points at them */
+int gc_status_head(mdb_dev_ctx *ctx, const uint32_t **h);
+static inline uint64_t gc_status_joined(const uint32_t *h)
+{
+	return (uint64_t)h[GC_STW_JOINED] | ((uint64_t)h[GC_STW_JOINED + 1] << 32);
+}
+
+/* ---- mdb_dev_keyform.hip: the key sample and the key form it decides */
+int gc_sample_range(mdb_dev_ctx *ctx, const gc_sides &s, bool fresh, int64_t *lo, int64_t *hi, bool keys32 = false);
+void gc_compact_window(int64_t lo, int64_t hi, uint32_t *kbits, int64_t *wlo, bool exact = false);
+void gc_narrow_note(mdb_dev_ctx *ctx, const gc_sides &s, bool narrow, int64_t base = 0, uint32_t key_bits = 0, int64_t key_lo = 0);
+bool gc_learned_selective(const mdb_dev_ctx *ctx, const gc_sides &s);
+int gc_narrow_guess(mdb_dev_ctx *ctx, const gc_sides &s, gc_key_form *kf, bool keys32 = false, bool prune_ok = false /* unsplit call: min-max pruning can run */);
+
+/* The forms that take a compact window from the key sample ALONE (any-order join, mdb_dev_group_count_keys, the band / tile sort of
+ * mdb_dev_group_count) and check every key against it on the device: sample, window, form - and on a key outside the window of a REMEMBERED
+ * sample (the column's contents have changed since) the sample is taken again, once; outside a sample just taken: not served, and the next few
+ * calls look at the data itself (nh_distrust).  fresh: as gc_sample_range takes it; of: whose sampled range the window pads; exact_stats: a range
+ * from the caller's statistics is the column's own - no margin.  form(lo, kbits) reports a gc_form_rc or an error (< 0), and so does this. */
+enum gc_form_rc { GC_FORM_DONE = 0, GC_FORM_NOT_SERVED = 1, GC_FORM_KEY_OUTSIDE = 2 };
+enum gc_window_of { GC_WINDOW_BOTH, GC_WINDOW_RIGHT };
+template <typename Form>
+static int gc_windowed_try(mdb_dev_ctx *ctx, const gc_sides &s, bool fresh, gc_window_of of, bool exact_stats, Form form)
+{
+	for (int attempt = 0; attempt < 2; attempt++) {
+		int64_t lo = 0, hi = 0;
+		int rc = gc_sample_range(ctx, s, attempt > 0 || fresh, &lo, &hi);
+		if (rc)
+			return rc;
+		const bool remembered = ctx->vd[VD_SAMPLE].served();
+		const bool right = of == GC_WINDOW_RIGHT;
+		uint32_t kb = 0;
+		int64_t wlo = 0;
+		gc_compact_window(right ? ctx->sr_rlo : lo, right ? ctx->sr_rhi : hi, &kb, &wlo, !right && exact_stats && ctx->plan.from_stats != 0);
+		if (!kb)
+			return GC_FORM_NOT_SERVED;
+		rc = form(wlo, kb);
+		if (rc != GC_FORM_KEY_OUTSIDE)
+			return rc;
+		if (!(remembered && attempt == 0)) {
+			ctx->nh_distrust = 8;	/* a key outside the sampled window: look at the data itself the next few times */
+			return GC_FORM_NOT_SERVED;
+		}
+	}
+	return GC_FORM_NOT_SERVED;
+}
+
+/* ---- mdb_dev_join_small.hip, mdb_dev_groupby.hip: the forms that answer before the staged driver.  0 = done, 1 = not served, < 0 = error */
+int tiny_group_count(mdb_dev_ctx *ctx, const gc_sides &s, bool has_r, bool null_group, const gc_out &out);
+int gc_unordered_try(mdb_dev_ctx *ctx, const gc_sides &s, const gc_out &out, const gc_table *x = NULL, int nextra = 0);
+int group_hashed_try(mdb_dev_ctx *ctx, const gc_table &t, bool null_group, const gc_out &out);
+int group_direct_try(mdb_dev_ctx *ctx, const gc_sides &s, bool null_group, const gc_out &out);
+
+/* ---- mdb_dev_join_leaf.hip: one workgroup per leaf */
+#define LD_MAX_REM 12u		/* direct-address leaves: tables of at most 2^LD_MAX_REM entries */
+#define GC_HEAVY (8u * GC_THREADS * LEAF_BATCH)	/* floor of the hot threshold (gc_args.heavy_l / heavy_r) */
+int leaf_hashed_launch(mdb_dev_ctx *ctx, const gc_args &a, bool has_r, bool build_r, bool narrow);
+int leaf_direct_launch(mdb_dev_ctx *ctx, const gc_args &a, uint32_t rem, uint32_t shift, bool has_r, int nextra);
+int leaf_bitmap_launch(mdb_dev_ctx *ctx, const uint32_t *hv_r, const uint32_t *cnt_r, uint32_t cap_r, uint32_t nleaves, uint32_t rem, uint32_t coarse, uint32_t shift,
+		       uint32_t *bits);
+int leaf_null_group_launch(mdb_dev_ctx *ctx, const gc_args &a, const uint64_t *null_l, uint64_t n_l);
+size_t leaf_hot_arena_bytes(void);
+int leaf_hot_launch(mdb_dev_ctx *ctx, const gc_args &a, bool has_r, bool build_r);
+int leaf_gather_i32_launch(mdb_dev_ctx *ctx, const int32_t *keys, const uint32_t *sel, uint64_t n, int64_t *out);
 /* mdb_dev_leaf_wide.hip: one workgroup per first-level digit */
 int leaf_wide_launch(mdb_dev_ctx *ctx, const gc_args &a, uint32_t nleaves, uint32_t rem, uint32_t shift, uint32_t nsub, bool has_r, bool r16);
 int leaf_wide4_launch(mdb_dev_ctx *ctx, const gc_args &a, uint32_t nleaves, uint32_t rem, uint32_t shift, uint32_t nsub);

@@ -1096,7 +1096,7 @@ __global__ __launch_bounds__(LW_THREADS, 8 /* waves per SIMD: two workgroups per
 	}
 }
 
-/* ------------------------------------------------------------------ launchers (mdb_dev_join.hip: gc_begin / gc_finish) */
+/* ------------------------------------------------------------------ launchers (mdb_dev_join.hip: gc_choose_bits, gc_launch_leaf, gc_leaf4_relaunch) */
 
 int leaf_wide_launch(mdb_dev_ctx *ctx, const gc_args &a, uint32_t nleaves, uint32_t rem, uint32_t shift, uint32_t nsub, bool has_r, bool r16)
 {

@@ -429,11 +429,6 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_pairs_emit(pj_args a)
 
 /* ------------------------------------------------------------------ what the host code of the pair and payload joins shares */
 
-/* the two tables of a call; the call with the sides swapped is pj_sides{ s.r, s.l } */
-struct pj_sides {
-	gc_table l, r;
-};
-
 /* the partition request of one table of a pair join: histogram-free layout unless the caller says otherwise */
 static mdb_part_request pj_request(const gc_table &t, int b1, int b2)
 {
@@ -560,7 +555,7 @@ static void pj_fill_rid_off(A *a, const mdb_part_result &pl, const mdb_part_resu
 
 /* 0 = done, 1 = not applicable (overflow: use the general path), 2 = a key outside the window met the narrow form (call
  * again with narrow = false), 3 = a right key occurs more than once (not a unique-key join this way round), < 0 = error */
-static int join_pairs_unique(mdb_dev_ctx *ctx, const pj_sides &s, bool narrow, int64_t base, pj_pairs *out)
+static int join_pairs_unique(mdb_dev_ctx *ctx, const gc_sides &s, bool narrow, int64_t base, pj_pairs *out)
 {
 	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	int b1, b2, sb1 = 0, sb2 = 0;
@@ -835,7 +830,7 @@ __global__ __launch_bounds__(MC_THREADS) void k_match_emit(const uint32_t *__res
 
 /* 0 = done, 1 = not applicable (a first-level region overflowed), 2 = a key outside the window, 3 = a right key occurs more
  * than once, < 0 = error */
-static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const pj_sides &s, uint32_t kbits, int64_t lo, pj_pairs *out)
+static int join_pairs_unique_wide(mdb_dev_ctx *ctx, const gc_sides &s, uint32_t kbits, int64_t lo, pj_pairs *out)
 {
 	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	const int b1 = 9;
@@ -1152,7 +1147,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_leaf_pairs_cell2(pl_args a, uint
 
 /* one call: the tables, the right table's carried columns and where the joined rows' cells go */
 struct pay_call {
-	pj_sides s;
+	gc_sides s;
 	const void *const *pay_in;
 	void *const *out;
 	int npay;
@@ -1353,7 +1348,7 @@ static int payload_one_level(mdb_dev_ctx *ctx, const pay_call &c, const gc_windo
  *   anything else (J short included)   not such a join: noted against the columns (VD_JP_BAD), not tried again for a while; not served */
 enum pay_verdict { PAY_SERVED, PAY_RETRY, PAY_NOT_SERVED };
 
-static pay_verdict payload_verdict(mdb_dev_ctx *ctx, const pj_sides &s, const pay_answer &ans, uint64_t expect_j, bool region_full_excused,
+static pay_verdict payload_verdict(mdb_dev_ctx *ctx, const gc_sides &s, const pay_answer &ans, uint64_t expect_j, bool region_full_excused,
 				   bool may_retry)
 {
 	if (ans.status == 0 && ans.J == expect_j)
@@ -1389,22 +1384,20 @@ extern "C" int mdb_dev_join_payload(mdb_dev_ctx *ctx, const int64_t *keys_l, con
 	if (ctx->vd[VD_JP_BAD].serve(keys_l, n_l, keys_r, n_r, MDB_HINT_SERVES))
 		return 1;	/* (these columns were not such a join last time: not tried again for a while) */
 	for (int attempt = 0; attempt < 2; attempt++) {
-		bool narrow = false;
-		int64_t base = 0;
-		gc_window win = { 0, 0, false, false, false, false };
-		int rc = gc_narrow_guess(ctx, keys_l, null_l, n_l, keys_r, null_r, n_r, &narrow, &base, &win);
+		gc_key_form kf;
+		int rc = gc_narrow_guess(ctx, call.s, &kf);
 		if (rc)
 			return rc;
 		const bool remembered = ctx->guess_remembered;
 		if (mdb_knob_set("MDB_DEBUG_PAYLOAD"))
-			fprintf(stderr, "join_payload: narrow %d window 2^%u at %lld (attempt %d, remembered %d)\n", (int)narrow, win.kbits, (long long)win.lo,
+			fprintf(stderr, "join_payload: narrow %d window 2^%u at %lld (attempt %d, remembered %d)\n", (int)kf.narrow, kf.win.kbits, (long long)kf.win.lo,
 				attempt, (int)remembered);
 		pay_form f;
-		if (!narrow || !win.kbits || !payload_applies(call, win, &f))
+		if (!kf.narrow || !kf.win.kbits || !payload_applies(call, kf.win, &f))
 			return 1;
 		pay_answer ans = { 0, 0, 0 };
-		rc = f.form == 3 ? payload_row_order(ctx, call, win, f, &ans) :
-		     f.form == 2 ? payload_two_levels(ctx, call, win, f, &ans) : payload_one_level(ctx, call, win, f, &ans);
+		rc = f.form == 3 ? payload_row_order(ctx, call, kf.win, f, &ans) :
+		     f.form == 2 ? payload_two_levels(ctx, call, kf.win, f, &ans) : payload_one_level(ctx, call, kf.win, f, &ans);
 		if (rc)
 			return rc;
 		if (ctx->explaining) {	/* (mdb_dev_explain_join_payload: nothing was launched) */
@@ -1583,7 +1576,7 @@ __global__ __launch_bounds__(GC_THREADS) void k_tiny_join_pairs(tinyp_args a)
 }
 
 /* 0 = done, 1 = not applicable (too many rows or pairs), < 0 = error */
-static int tiny_join_pairs(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+static int tiny_join_pairs(mdb_dev_ctx *ctx, const gc_sides &s, pj_pairs *out)
 {
 	if (s.l.n > TINY_ROWS || s.r.n > TINY_ROWS)
 		return 1;
@@ -1616,30 +1609,28 @@ static int tiny_join_pairs(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
 }
 
 /* the unique-key join with its narrow-form decision and retry; result codes of join_pairs_unique() except 2 */
-static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const gc_sides &s, pj_pairs *out)
 {
 	const uint64_t n_l = s.l.n, n_r = s.r.n;
-	bool narrow = false;
-	int64_t base = 0;
-	gc_window win = { 0, 0, false, false, false, false };
-	int urc = gc_narrow_guess(ctx, s.l.keys, s.l.nulls, n_l, s.r.keys, s.r.nulls, n_r, &narrow, &base, &win);
+	gc_key_form kf;
+	int urc = gc_narrow_guess(ctx, s, &kf);
 	if (urc)
 		return urc;
 	/* a compact window of at most 2^24 key values: one partition level, see join_pairs_unique_wide (MDB_ONE_LEVEL=0 switches
 	 * it off).  What it cannot do - a key outside the window after all, a first-level region overflow - goes the usual way */
-	if (narrow && win.kbits >= 9u + PW_MIN_REM && win.kbits <= 9u + PW_MAX_REM && n_l <= PW_MAX_LEFT && n_l + n_r >= (1ull << 20) &&
+	if (kf.narrow && kf.win.kbits >= 9u + PW_MIN_REM && kf.win.kbits <= 9u + PW_MAX_REM && n_l <= PW_MAX_LEFT && n_l + n_r >= (1ull << 20) &&
 	    !ctx->vd[VD_PW_BAD].holds(NULL, 0, s.r.keys, n_r) && !ld_disabled() &&
 	    !mdb_knob_off("MDB_ONE_LEVEL")) {
-		urc = join_pairs_unique_wide(ctx, s, win.kbits, win.lo, out);
+		urc = join_pairs_unique_wide(ctx, s, kf.win.kbits, kf.win.lo, out);
 		if (urc <= 0 || urc == 3)
 			return urc;
 		ctx->vd[VD_PW_BAD].note(NULL, 0, s.r.keys, n_r);
 	}
-	urc = join_pairs_unique(ctx, s, narrow, base, out);
+	urc = join_pairs_unique(ctx, s, kf.narrow, kf.base, out);
 	if (urc == 2) {	/* the sample (or what was remembered about these columns) missed a wide key */
 		if (ctx->narrow_mode == 1) {
 			ctx->nh_distrust = 8;
-			gc_narrow_note(ctx, s.l.keys, n_l, s.r.keys, n_r, false);
+			gc_narrow_note(ctx, s, false);
 		}
 		urc = join_pairs_unique(ctx, s, false, 0, out);
 	}
@@ -1650,13 +1641,13 @@ static int join_pairs_unique_auto(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs 
  * swapped - it delivers the pairs in right-row order - and a stable sort by left row id puts them into the reference's
  * left-major / right-minor order (for one left row the right rows are already ascending).  About half the time of the
  * general count / scan / emit path.  Same result codes as join_pairs_unique(). */
-static int join_pairs_unique_left(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+static int join_pairs_unique_left(mdb_dev_ctx *ctx, const gc_sides &s, pj_pairs *out)
 {
 	const uint64_t n_l = s.l.n, n_r = s.r.n;
 	if (n_l >= 0x7FFFFFFFull)
 		return 1;
 	pj_pairs swapped(ctx);	/* its "left" ids are right rows, its "right" ids are left rows */
-	int rc = join_pairs_unique_auto(ctx, pj_sides{ s.r, s.l }, &swapped);
+	int rc = join_pairs_unique_auto(ctx, gc_sides{ s.r, s.l }, &swapped);
 	if (rc)
 		return rc;
 	const uint64_t J = out->count = swapped.count;
@@ -1694,7 +1685,7 @@ static int join_pairs_unique_left(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs 
  * the sides swapped and a stable sort.  What a column turned out to be is remembered (by pointer and length), so that a repeated
  * query does not pay for failed attempts.  0 = answered, > 0 = duplicates on both sides, or a table / region overflowed: the general
  * path, < 0 = error */
-static int pairs_unique_side(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+static int pairs_unique_side(mdb_dev_ctx *ctx, const gc_sides &s, pj_pairs *out)
 {
 	int urc = 3;
 	bool right_dups = false, left_dups = false, right_unique = false;
@@ -1723,7 +1714,7 @@ static int pairs_unique_side(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
 /* One attempt of the general join up to the sizes of its output: both tables partitioned - fast: the histogram-free layout, the right
  * side in arbitrary order; else the exact layout, the right side stable -, the matches of every left row counted and scanned into
  * offsets.  *a: the leaf's arguments, for the emit; *status: the flags; *J, *total64: the 32-bit and the 64-bit sum of the counts */
-static int pairs_general_count(mdb_dev_ctx *ctx, const pj_sides &s, int b1, int b2, bool fast, pj_args *a, uint32_t *status, uint64_t *J,
+static int pairs_general_count(mdb_dev_ctx *ctx, const gc_sides &s, int b1, int b2, bool fast, pj_args *a, uint32_t *status, uint64_t *J,
 			       uint64_t *total64)
 {
 	const uint64_t n_l = s.l.n, n_r = s.r.n, mlen = n_l + 1;
@@ -1786,7 +1777,7 @@ static int pairs_general_count(mdb_dev_ctx *ctx, const pj_sides &s, int b1, int 
 }
 
 /* duplicates on both sides: count, scan, emit */
-static int pairs_general(mdb_dev_ctx *ctx, const pj_sides &s, pj_pairs *out)
+static int pairs_general(mdb_dev_ctx *ctx, const gc_sides &s, pj_pairs *out)
 {
 	int b1, b2;
 	mdb_choose_bits(s.r.n, PJ_TARGET, &b1, &b2);
@@ -1834,7 +1825,7 @@ extern "C" int mdb_dev_join_pairs(mdb_dev_ctx *ctx, const int64_t *keys_l, const
 	if (n_l == 0 || n_r == 0)
 		return MIDORIDB_OK;
 	mdb_memo_switch(ctx, keys_l, n_l, keys_r, n_r);
-	const pj_sides sides = { { keys_l, null_l, n_l }, { keys_r, null_r, n_r } };
+	const gc_sides sides = { { keys_l, null_l, n_l }, { keys_r, null_r, n_r } };
 	pj_pairs pairs(ctx);
 	int rc = tiny_join_pairs(ctx, sides, &pairs);
 	if (rc > 0)

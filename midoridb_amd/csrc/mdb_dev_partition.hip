@@ -6,7 +6,7 @@
  * src/engine/executor_select.c:1096-1141, O(nA*nB)) and groups by comparing every pair of
  * surviving rows (:1542-1583, O(n^2)).  Here both tables are split into 2^bits "leaves" whose
  * build side fits one CU's LDS; equal keys always land in the same leaf, so each leaf is joined /
- * grouped independently by one workgroup (mdb_dev_join.hip).
+ * grouped independently by one workgroup (mdb_dev_join_leaf.hip, mdb_dev_leaf_wide.hip).
  *
  * The default ("FAST") form has NO histogram pass: every child owns a fixed-capacity region and each (tile, digit)
  * run reserves its place with one global atomic on the region's cursor (first level: 8 sub-regions per digit, one
