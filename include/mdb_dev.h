@@ -855,18 +855,45 @@ uint64_t mdb_dev_count_distinct_bitmap_bits(void);
  * Scratch, taken from the context's allocator for the length of the call and beside what mdb_dev_sort_perm takes: 4 n bytes for the
  * permutation (with keys), n / 4 for the bitmaps, 4 n more when a COUNT(*) is among the functions, and 17 n bytes for EVERY SUM / MIN / MAX /
  * AVG of the call (a running (accumulator, cells) pair per sorted position and a NULL flag per row) - 1.7 GB per such function at 10^8 rows.
- * Memory that cannot be had fails the call with -MIDORIDB_NOMEM before anything is written; the context stays usable. */
-enum mdb_win_op { MDB_WIN_ROW_NUMBER = 1, MDB_WIN_RANK, MDB_WIN_DENSE_RANK, MDB_WIN_COUNT, MDB_WIN_SUM, MDB_WIN_MIN, MDB_WIN_MAX, MDB_WIN_AVG };
+ * Memory that cannot be had fails the call with -MIDORIDB_NOMEM before anything is written; the context stays usable.
+ *
+ * Navigation: the value of ANOTHER row of the window.  With the partition [b, pe) and "the cell at q" = the argument column's cell of the row
+ * at sorted position q (NULL when its NULL bit is set or its row id is MDB_NO_ROW):
+ *
+ *   MDB_WIN_LAG          the cell at p - arg when p - arg >= b, else the default
+ *   MDB_WIN_LEAD         the cell at p + arg when p + arg < pe, else the default
+ *   MDB_WIN_FIRST_VALUE  the cell at b
+ *   MDB_WIN_LAST_VALUE   the cell at e - 1: the row's last peer under SQL's default frame, the partition's last row without order keys
+ *   MDB_WIN_NTILE        the row's bucket of arg buckets: with s = pe - b, r = p - b, q = s / arg, m = s % arg the first m buckets hold q + 1
+ *                        rows, the others q: r < m (q + 1) ? r / (q + 1) + 1 : m + (r - m (q + 1)) / q + 1.  int64_t, never NULL, reads no column
+ *
+ * A cell is copied as its 8 bytes whatever its type (`type` is not looked at: dictionary ids, dates and doubles alike, -0.0 stays -0.0);
+ * nothing is ordered or added.  A NULL cell in range gives NULL (out = 0, its bit set), NOT the default; the default is `dflt` as 8 bytes, or
+ * NULL with dflt_null set.  arg == 0 is the row itself, an offset of any size is legal (it lies outside the partition); MDB_WIN_NTILE with
+ * arg == 0 fails the call before anything is written.  Ties in the order keys keep the stream order, so every function is deterministic.
+ * These share the sort, the bitmaps and the scans with the other functions of the call; their values are gathered by one more pass
+ * (k_win_nav).  Scratch: n bytes (a NULL flag per row) for every LAG / LEAD / FIRST_VALUE / LAST_VALUE, nothing for NTILE, and 4 n bytes
+ * once per call - b of every position, shared with COUNT(*) - when a LAG, FIRST_VALUE or NTILE is among the functions: 0.5 GB for
+ * LAG + LEAD + NTILE together at 10^8 rows.  The eight functions above ignore arg, dflt and dflt_null. */
+enum mdb_win_op {
+	MDB_WIN_ROW_NUMBER = 1, MDB_WIN_RANK, MDB_WIN_DENSE_RANK, MDB_WIN_COUNT, MDB_WIN_SUM, MDB_WIN_MIN, MDB_WIN_MAX, MDB_WIN_AVG,
+	MDB_WIN_LAG = 16, MDB_WIN_LEAD, MDB_WIN_FIRST_VALUE, MDB_WIN_LAST_VALUE, MDB_WIN_NTILE	/* (9 ... 15 are no functions) */
+};
 #define MDB_WIN_MAX_FNS 8
 struct mdb_window_fn {
 	int32_t op;			/* enum mdb_win_op */
 	int32_t type;			/* enum mdb_valtype of the cells (SUM / MIN / MAX / AVG) */
-	const void *values;		/* as struct mdb_agg; unused by the first four functions */
+	const void *values;		/* as struct mdb_agg; unused by the first four functions and by NTILE */
 	const uint64_t *nullbits;
 	const uint32_t *rid;
 	void *out;			/* n cells in STREAM order */
 	uint64_t *out_nullbits;		/* (n + 63) / 64 words, written in full */
+	uint64_t arg;			/* LAG / LEAD: the offset in rows; NTILE: the number of buckets */
+	uint64_t dflt;			/* LAG / LEAD: the 8 bytes of the default, for a row whose neighbour lies outside the partition */
+	int32_t dflt_null;		/* ... != 0: the default is NULL (dflt is not looked at) */
 };
+/* sizeof(struct mdb_window_fn) as the library was built: what a mirror of the struct in another language checks its array stride against */
+uint64_t mdb_dev_window_fn_size(void);
 int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part, int npart, const struct mdb_sort_key *order, int norder, uint64_t n,
 		   const struct mdb_window_fn *fns, int nfns, uint32_t *out_form);
 

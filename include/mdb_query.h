@@ -181,7 +181,9 @@ int mdb_database_aggregate_calls(struct database *db, unsigned long long *lds_fo
  * items of one statement share one operator call.  A GROUP BY answered by the identity counts in neither.  Either pointer may be NULL. */
 int mdb_database_count_distinct_calls(struct database *db, unsigned long long *bitmap_form, unsigned long long *sorted_form);
 /* Window functions, fn(...) OVER (PARTITION BY ... ORDER BY ...) (an extension too): mdb_dev_window (mdb_dev.h) calls of this database's
- * SELECT statements so far - one per distinct OVER clause of a statement: the items whose windows are equal field for field share a call. */
+ * SELECT statements so far - one per distinct OVER clause of a statement: the items whose windows are equal field for field share a call,
+ * ranking functions, running aggregates and the navigation functions (LAG, LEAD, FIRST_VALUE, LAST_VALUE, NTILE) alike.  A navigation
+ * function's result column has its argument column's type (query_column_type, query_column_text for VARCHAR); NTILE is INTEGER. */
 unsigned long long mdb_database_window_calls(struct database *db);
 /* Set operations, SELECT ... UNION [ALL] | INTERSECT | EXCEPT SELECT ... (an extension too): mdb_dev_rows_semi (mdb_dev.h) calls of this
  * database's compound statements so far - one per INTERSECT / EXCEPT step of a chain, none for UNION [ALL]. */

@@ -1,6 +1,6 @@
 /*
- * mdb_dev_window.hip - window functions (mdb_dev_window): ROW_NUMBER / RANK / DENSE_RANK / COUNT(*) / SUM / MIN / MAX / AVG ... OVER
- * (PARTITION BY ... ORDER BY ...).  An extension: the reference's grammar has no OVER clause (src/parser/midorisql.y) and its executor no
+ * mdb_dev_window.hip - window functions (mdb_dev_window): ROW_NUMBER / RANK / DENSE_RANK / COUNT(*) / SUM / MIN / MAX / AVG / LAG / LEAD /
+ * FIRST_VALUE / LAST_VALUE / NTILE ... OVER (PARTITION BY ... ORDER BY ...).  An extension: the reference's grammar has no OVER clause (src/parser/midorisql.y) and its executor no
  * per-row function of a row's neighbours.
  *
  * The stream is sorted once, stably, by the partition keys and then the order keys (mdb_dev_sort_perm): a partition is a run of equal
@@ -11,12 +11,18 @@
  *   k_win_scan<0>    chunks of WIN_CHUNK positions, one workgroup each, a strip of WIN_STRIP positions per thread: every thread folds its
  *                    strip, the strips are scanned by shuffles inside a wave and across the four waves through LDS, the workgroup's
  *                    total is the chunk's summary - the last partition head (b1), the last peer head (g1), the peer heads since the last
- *                    partition head (d), the chunk's first peer head (fh1), and per aggregate the open (accumulator, cell count) pair
- *   k_win_carry      ONE workgroup scans the summaries: carry[c] = what is open in front of chunk c, nexth[c] = the first peer head behind it
+ *                    partition head (d), the chunk's first peer head (fh1) and first partition head (fp1), and per aggregate the open
+ *                    (accumulator, cell count) pair
+ *   k_win_carry      ONE workgroup scans the summaries: carry[c] = what is open in front of chunk c, nexth[c] = the first peer head behind
+ *                    it, nextp[c] = the first partition head behind it
  *   k_win_scan<1>    the same chunks again, with their carry: ROW_NUMBER / RANK / DENSE_RANK are final here and written to out[stream
- *                    position]; every aggregate leaves its running pair T[q] = fold of the partition's cells up to q, COUNT(*) leaves b
+ *                    position]; every aggregate leaves its running pair T[q] = fold of the partition's cells up to q; COUNT(*), LAG,
+ *                    FIRST_VALUE and NTILE leave b
  *   k_win_ends       e = the position behind a row's peer group (from gh, or nexth): SQL's default frame ends at e - 1, so the value of an
  *                    aggregate is T[e - 1] and COUNT(*) is e - b
+ *   k_win_nav        LAG / LEAD / FIRST_VALUE / LAST_VALUE / NTILE: pe = the position behind a row's partition (from ph, or nextp) as e comes
+ *                    from gh; the value is the argument column's cell at p - k, p + k, b or e - 1 - one gather through the permutation -
+ *                    or the default outside [b, pe); NTILE is arithmetic on p, b and pe.  The cell's 8 bytes are copied, never interpreted
  *   k_win_pack       the NULL flags, written per stream position as bytes, become whole words of out_nullbits (one ballot per word)
  *
  * Carries between workgroups travel through these separate launches only.  Integer arithmetic and order images throughout (SUM / AVG over
@@ -37,7 +43,7 @@ static_assert(WIN_STRIP == 16u && WIN_CHUNK % 64u == 0, "a thread's strip is 16 
 struct win_fns {
 	mdb_stream_col c[WIN_MAX_FNS];
 	uint64_t *out[WIN_MAX_FNS];		/* n cells in stream order */
-	uint8_t *nf[WIN_MAX_FNS];		/* aggregates: n NULL flags in stream order */
+	uint8_t *nf[WIN_MAX_FNS];		/* aggregates, LAG ... LAST_VALUE: n NULL flags in stream order */
 	unsigned long long *T[WIN_MAX_FNS];	/* aggregates: n running (accumulator, cells) pairs in sorted order */
 	int nfns;
 };
@@ -47,13 +53,17 @@ struct win_st {
 	uint32_t b1, g1;	/* last partition head, last peer head */
 	uint32_t d;		/* peer heads since the last partition head (all of the range when it has none) */
 	uint32_t fh1;		/* first peer head of the range (summaries only) */
+	uint32_t fp1;		/* first partition head of the range (summaries only) */
 };
 
 struct win_ag {
 	uint64_t acc, cnt;
 };
 
-__host__ __device__ static inline bool win_is_agg(int op) { return op >= MDB_WIN_SUM; }
+__host__ __device__ static inline bool win_is_agg(int op) { return op >= MDB_WIN_SUM && op <= MDB_WIN_AVG; }
+__host__ __device__ static inline bool win_is_nav(int op) { return op >= MDB_WIN_LAG && op <= MDB_WIN_NTILE; }
+/* ... that copies a cell of its argument column (NTILE reads none) */
+__host__ __device__ static inline bool win_is_gather(int op) { return op >= MDB_WIN_LAG && op <= MDB_WIN_LAST_VALUE; }
 __host__ __device__ static inline bool win_is_minmax(int op) { return op == MDB_WIN_MIN || op == MDB_WIN_MAX; }
 
 /* left then right: right is folded INTO left, in that order; an empty side changes nothing */
@@ -81,6 +91,7 @@ __device__ static inline win_st win_join(win_st l, win_st r)
 	o.g1 = r.g1 ? r.g1 : l.g1;
 	o.d = r.b1 ? r.d : l.d + r.d;
 	o.fh1 = l.fh1 ? l.fh1 : r.fh1;
+	o.fp1 = l.fp1 ? l.fp1 : r.fp1;
 	return o;
 }
 
@@ -94,13 +105,14 @@ __device__ static inline win_st win_shfl_up_st(win_st v, uint32_t d)
 	o.g1 = (uint32_t)__shfl_up((int)v.g1, d, MDB_WAVE);
 	o.d = (uint32_t)__shfl_up((int)v.d, d, MDB_WAVE);
 	o.fh1 = (uint32_t)__shfl_up((int)v.fh1, d, MDB_WAVE);
+	o.fp1 = (uint32_t)__shfl_up((int)v.fp1, d, MDB_WAVE);
 	return o;
 }
 
 __device__ static inline win_st win_block_scan_st(win_st v, win_st *lds /* [WIN_WAVES] */, win_st *total)
 {
 	const uint32_t lane = mdb_lane(), wave = threadIdx.x >> 6;
-	const win_st none = {0, 0, 0, 0};
+	const win_st none = {0, 0, 0, 0, 0};
 	win_st incl = v;
 	for (uint32_t d = 1; d < MDB_WAVE; d <<= 1) {
 		const win_st o = win_shfl_up_st(incl, d);
@@ -206,7 +218,7 @@ struct win_scan_args {
 	uint32_t *hasp_sum;		/* [nchunks]: the chunk holds a partition head */
 	const win_st *st_carry;		/* APPLY: what is open in front of the chunk */
 	const win_ag *ag_carry;
-	uint32_t *B32;			/* APPLY, with COUNT(*): b of every sorted position */
+	uint32_t *B32;			/* APPLY, with COUNT(*), LAG, FIRST_VALUE or NTILE: b of every sorted position */
 	uint32_t *status;
 };
 
@@ -251,7 +263,7 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 	}
 
 	/* ---- the structure: b, g and the peer heads since b */
-	win_st mine = {0, 0, 0, 0};
+	win_st mine = {0, 0, 0, 0, 0};
 #pragma unroll
 	for (uint32_t j = 0; j < WIN_STRIP; j++) {
 		if (p0 + j >= n)
@@ -259,6 +271,8 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 		if ((pb >> j) & 1u) {
 			mine.b1 = (uint32_t)(p0 + j) + 1u;
 			mine.d = 0;
+			if (!mine.fp1)
+				mine.fp1 = (uint32_t)(p0 + j) + 1u;
 		}
 		if ((gb >> j) & 1u) {
 			mine.g1 = (uint32_t)(p0 + j) + 1u;
@@ -362,7 +376,7 @@ template <bool APPLY> __global__ __launch_bounds__(WIN_THREADS) void k_win_scan(
 
 /* ------------------------------------------------------------------ the chunk summaries, one workgroup: thread t takes a run of consecutive
  * chunks, folds it, the runs are scanned through LDS, and the thread walks its run again: carry[c] = everything in front of chunk c.
- * nexth[c] = the first peer head of a chunk behind c, n when there is none. */
+ * nexth[c] = the first peer head of a chunk behind c, n when there is none; nextp[c] = the first partition head there, likewise. */
 struct win_carry_args {
 	uint64_t n, nchunks;
 	int nslots;
@@ -372,20 +386,20 @@ struct win_carry_args {
 	const uint32_t *hasp_sum;
 	win_st *st_carry;
 	win_ag *ag_carry;
-	uint32_t *nexth;
+	uint32_t *nexth, *nextp;
 };
 
 __global__ __launch_bounds__(WIN_THREADS) void k_win_carry(win_carry_args A)
 {
 	__shared__ win_st s_st[WIN_WAVES];
 	__shared__ win_agf s_ag[WIN_WAVES];
-	__shared__ uint32_t s_first[WIN_THREADS];
+	__shared__ uint32_t s_first[WIN_THREADS], s_firstp[WIN_THREADS];
 	const uint32_t t = threadIdx.x;
 	const uint64_t per = (A.nchunks + WIN_THREADS - 1u) / WIN_THREADS;
 	const uint64_t c0 = (uint64_t)t * per < A.nchunks ? (uint64_t)t * per : A.nchunks;
 	const uint64_t c1 = c0 + per < A.nchunks ? c0 + per : A.nchunks;
 
-	win_st mine = {0, 0, 0, 0};
+	win_st mine = {0, 0, 0, 0, 0};
 	for (uint64_t c = c0; c < c1; c++)
 		mine = win_join(mine, A.st_sum[c]);
 	win_st total;
@@ -396,17 +410,26 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_carry(win_carry_args A)
 	}
 	/* the first peer head behind every chunk */
 	s_first[t] = mine.fh1;
+	s_firstp[t] = mine.fp1;
 	__syncthreads();
-	uint32_t nx = (uint32_t)A.n;
+	uint32_t nx = (uint32_t)A.n, np = (uint32_t)A.n;
 	for (uint32_t u = t + 1u; u < WIN_THREADS; u++)
 		if (s_first[u]) {
 			nx = s_first[u] - 1u;
 			break;
 		}
+	for (uint32_t u = t + 1u; u < WIN_THREADS; u++)
+		if (s_firstp[u]) {
+			np = s_firstp[u] - 1u;
+			break;
+		}
 	for (uint64_t c = c1; c > c0; c--) {
 		A.nexth[c - 1u] = nx;
+		A.nextp[c - 1u] = np;
 		if (A.st_sum[c - 1u].fh1)
 			nx = A.st_sum[c - 1u].fh1 - 1u;
+		if (A.st_sum[c - 1u].fp1)
+			np = A.st_sum[c - 1u].fp1 - 1u;
 	}
 	__syncthreads();
 
@@ -496,6 +519,97 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_ends(win_ends_args A)
 	}
 }
 
+/* ------------------------------------------------------------------ the navigation functions: the cell of another row of the partition.
+ * As k_win_ends, with the chunk's words of BOTH bitmaps in LDS: e from gh / nexth, pe = the position behind the row's partition from ph /
+ * nextp, b from B32.  One gather per function and row: perm[q], then the cell.  Plain stores; the NULL flags go through k_win_pack. */
+struct win_nav_args {
+	win_fns F;
+	uint64_t arg[WIN_MAX_FNS], dflt[WIN_MAX_FNS];
+	uint32_t dnull[WIN_MAX_FNS];
+	const uint32_t *perm;
+	uint64_t n;
+	const unsigned long long *ph, *gh;
+	const uint32_t *nexth, *nextp;
+	const uint32_t *B32;		/* NULL when no function of the call asks for b */
+};
+
+/* the first set bit of word w's bits above `bit` as a position, or nx[w] */
+__device__ static inline uint64_t win_next_head(const unsigned long long *s_w, const uint32_t *s_nx, uint64_t p, uint32_t w, uint32_t bit)
+{
+	const unsigned long long above = bit == 63u ? 0ull : s_w[w] >> (bit + 1u);
+	return above ? p + (uint64_t)__ffsll((long long)above) : (uint64_t)s_nx[w];
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void k_win_nav(win_nav_args A)
+{
+	__shared__ unsigned long long s_w[2][WIN_WORDS];	/* 0: gh, 1: ph */
+	__shared__ uint32_t s_nx[2][WIN_WORDS];			/* the first head in the chunk's words behind word w, or behind the chunk */
+	const uint64_t c = blockIdx.x, n = A.n, base = c * WIN_CHUNK;
+	const uint32_t t = threadIdx.x;
+	if (t < 2u * WIN_WORDS) {
+		const uint32_t which = t / WIN_WORDS, w = t % WIN_WORDS;
+		s_w[which][w] = base + (uint64_t)w * 64u < n ? (which ? A.ph : A.gh)[(base >> 6) + w] : 0ull;
+	}
+	__syncthreads();
+	if (t < 2u) {
+		uint32_t nx = t ? A.nextp[c] : A.nexth[c];
+		for (uint32_t w = WIN_WORDS; w > 0; w--) {
+			s_nx[t][w - 1u] = nx;
+			if (s_w[t][w - 1u])
+				nx = (uint32_t)(base + (uint64_t)(w - 1u) * 64u) + (uint32_t)__ffsll((long long)s_w[t][w - 1u]) - 1u;
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = 0; k < WIN_STRIP; k++) {
+		const uint64_t p = base + (uint64_t)k * WIN_THREADS + t;
+		if (p >= n)
+			break;
+		const uint32_t w = (uint32_t)(p - base) >> 6, bit = (uint32_t)p & 63u;
+		const uint64_t e = win_next_head(s_w[0], s_nx[0], p, w, bit);	/* (p < e <= pe <= n) */
+		const uint64_t pe = win_next_head(s_w[1], s_nx[1], p, w, bit);
+		const uint64_t sp = A.perm ? A.perm[p] : p;
+		if (sp >= n)
+			continue;	/* (k_win_scan has raised MDB_GROUPS_ST_PERM_RANGE) */
+		const uint64_t b = A.B32 ? (uint64_t)A.B32[p] : 0ull;	/* (b <= p) */
+		for (int f = 0; f < A.F.nfns; f++) {
+			const mdb_stream_col &col = A.F.c[f];
+			const uint64_t a = A.arg[f];
+			if (col.op == MDB_WIN_NTILE) {
+				const uint64_t s = pe - b, r = p - b, q = s / a, m = s % a;	/* (a != 0: checked by the host) */
+				const uint64_t big = m * (q + 1u);	/* (below s + a: no overflow) */
+				A.F.out[f][sp] = r < big ? r / (q + 1u) + 1u : (q ? m + (r - big) / q + 1u : m);
+				continue;
+			}
+			if (!win_is_gather(col.op))
+				continue;
+			uint64_t q = 0;
+			bool in = true;
+			if (col.op == MDB_WIN_LAG) {
+				in = a <= p - b;
+				q = p - (in ? a : 0u);
+			} else if (col.op == MDB_WIN_LEAD) {
+				in = a < pe - p;
+				q = p + (in ? a : 0u);
+			} else if (col.op == MDB_WIN_FIRST_VALUE) {
+				q = b;
+			} else {
+				q = e - 1u;
+			}
+			uint64_t bits = 0;
+			bool valid;
+			if (in) {	/* (b <= q < pe <= n) */
+				const uint64_t sq = A.perm ? A.perm[q] : q;
+				valid = sq < n && mdb_stream_cell(col, sq, &bits);
+			} else {
+				bits = A.dflt[f];
+				valid = !A.dnull[f];
+			}
+			A.F.out[f][sp] = valid ? bits : 0ull;
+			A.F.nf[f][sp] = valid ? 0u : 1u;
+		}
+	}
+}
+
 /* one thread per stream position, a wave per word of NULL bits: every word of out_nullbits is written whole */
 __global__ __launch_bounds__(WIN_THREADS) void k_win_pack(const uint8_t *__restrict__ nf, uint64_t n, unsigned long long *__restrict__ out_nullbits)
 {
@@ -532,17 +646,34 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 	win_fns F;
 	memset(&F, 0, sizeof(F));
 	F.nfns = nfns;
-	int nslots = 0;
-	bool has_count = false;
+	int nslots = 0, nnav = 0;
+	bool has_count = false, need_b = false;
+	win_nav_args N;
+	memset(&N, 0, sizeof(N));
 	for (int f = 0; f < nfns; f++) {
 		const struct mdb_window_fn *w = &fns[f];
-		if (w->op < MDB_WIN_ROW_NUMBER || w->op > MDB_WIN_AVG)
+		if (w->op < MDB_WIN_ROW_NUMBER || w->op > MDB_WIN_NTILE || (w->op > MDB_WIN_AVG && w->op < MDB_WIN_LAG))
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "window: function %d: unknown function %d", f, w->op);
 		if (!w->out || !w->out_nullbits)
 			return mdb_set_err(ctx, -MIDORIDB_ERROR, "window: function %d: no place for the result", f);
 		F.c[f].op = w->op;
 		F.out[f] = (uint64_t *)w->out;
 		has_count = has_count || w->op == MDB_WIN_COUNT;
+		need_b = need_b || w->op == MDB_WIN_COUNT || w->op == MDB_WIN_LAG || w->op == MDB_WIN_FIRST_VALUE || w->op == MDB_WIN_NTILE;
+		if (win_is_nav(w->op)) {
+			if (w->op == MDB_WIN_NTILE && !w->arg)
+				return mdb_set_err(ctx, -MIDORIDB_ERROR, "window: function %d: NTILE(0): the number of buckets must be at least 1", f);
+			nnav++;
+			N.arg[f] = w->arg;
+			N.dflt[f] = w->dflt;
+			N.dnull[f] = w->dflt_null ? 1u : 0u;
+			if (!win_is_gather(w->op))
+				continue;
+			if (n && !w->values)
+				return mdb_set_err(ctx, -MIDORIDB_ERROR, "window: function %d: no cells", f);
+			F.c[f] = mdb_stream_col_of(w->values, w->nullbits, w->rid, w->op, w->type);	/* (cells are copied: any type) */
+			continue;
+		}
 		if (!win_is_agg(w->op))
 			continue;
 		if ((w->type != MDB_T_INT64 && w->type != MDB_T_DOUBLE) || (n && !w->values))
@@ -573,16 +704,21 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 	unsigned long long *ph = (unsigned long long *)tmp.take(nchunks * WIN_WORDS * 8u * 2u);
 	win_st *st_sum = (win_st *)tmp.take(nchunks * sizeof(win_st) * 2u);
 	win_ag *ag_sum = (win_ag *)tmp.take((uint64_t)(nslots ? nslots : 1) * nchunks * sizeof(win_ag) * 2u);
-	uint32_t *hasp_sum = (uint32_t *)tmp.take(nchunks * 4u * 2u);
-	uint32_t *B32 = has_count ? (uint32_t *)tmp.take(n * 4u) : NULL;
+	uint32_t *hasp_sum = (uint32_t *)tmp.take(nchunks * 4u * 3u);
+	uint32_t *B32 = need_b ? (uint32_t *)tmp.take(n * 4u) : NULL;
 	uint32_t *status = (uint32_t *)tmp.take(256);
-	if (!ph || !st_sum || !ag_sum || !hasp_sum || (has_count && !B32) || !status)
+	if (!ph || !st_sum || !ag_sum || !hasp_sum || (need_b && !B32) || !status)
 		return mdb_set_err(ctx, -MIDORIDB_NOMEM, "window: no device memory for %llu chunks", (unsigned long long)nchunks);
 	unsigned long long *gh = ph + nchunks * WIN_WORDS;
 	win_st *st_carry = st_sum + nchunks;
 	win_ag *ag_carry = ag_sum + (uint64_t)(nslots ? nslots : 1) * nchunks;
-	uint32_t *nexth = hasp_sum + nchunks;
+	uint32_t *nexth = hasp_sum + nchunks, *nextp = nexth + nchunks;
 	for (int f = 0; f < nfns; f++) {
+		if (win_is_gather(F.c[f].op)) {
+			F.nf[f] = (uint8_t *)tmp.take(n);
+			if (!F.nf[f])
+				return mdb_set_err(ctx, -MIDORIDB_NOMEM, "window: no device memory for the NULL flags of %llu rows", (unsigned long long)n);
+		}
 		if (!win_is_agg(F.c[f].op))
 			continue;
 		F.T[f] = (unsigned long long *)tmp.take(n * 16u);
@@ -631,6 +767,7 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 	C.st_carry = st_carry;
 	C.ag_carry = ag_carry;
 	C.nexth = nexth;
+	C.nextp = nextp;
 	MDB_LAUNCH(ctx, "win_carry", k_win_carry, 1, WIN_THREADS, C);
 	MDB_LAUNCH(ctx, "win_scan_apply", k_win_scan<true>, (uint32_t)nchunks, WIN_THREADS, S);
 
@@ -645,11 +782,22 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 		E.B32 = B32;
 		MDB_LAUNCH(ctx, "win_ends", k_win_ends, (uint32_t)nchunks, WIN_THREADS, E);
 	}
+	if (nnav) {
+		N.F = F;
+		N.perm = perm;
+		N.n = n;
+		N.ph = ph;
+		N.gh = gh;
+		N.nexth = nexth;
+		N.nextp = nextp;
+		N.B32 = B32;
+		MDB_LAUNCH(ctx, "win_nav", k_win_nav, (uint32_t)nchunks, WIN_THREADS, N);
+	}
 	for (int f = 0; f < nfns; f++) {
-		if (win_is_agg(F.c[f].op))
+		if (win_is_agg(F.c[f].op) || win_is_gather(F.c[f].op))
 			MDB_LAUNCH(ctx, "win_pack", k_win_pack, (uint32_t)((n + WIN_THREADS - 1u) / WIN_THREADS), WIN_THREADS, (const uint8_t *)F.nf[f], n,
 				   (unsigned long long *)fns[f].out_nullbits);
-		else	/* (a rank or a count is never NULL) */
+		else	/* (a rank, a count or a bucket is never NULL) */
 			MDB_HIP(ctx, hipMemsetAsync(fns[f].out_nullbits, 0, words * 8u, ctx->stream));
 	}
 	{
@@ -663,3 +811,5 @@ extern "C" int mdb_dev_window(mdb_dev_ctx *ctx, const struct mdb_sort_key *part,
 		*out_form = form;
 	return MIDORIDB_OK;
 }
+
+extern "C" uint64_t mdb_dev_window_fn_size(void) { return sizeof(struct mdb_window_fn); }

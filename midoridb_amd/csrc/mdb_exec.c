@@ -506,7 +506,7 @@ int stream_windows(struct exec *x)
 		return MIDORIDB_OK;
 	for (int i = 0; i < x->nwin; i++) {
 		const struct mdb_expr *lead = x->win_item[i];
-		const int narg0 = lead->op >= MDB_WIN_SUM ? 1 : 0;
+		const int narg0 = mdb_win_narg(lead->op);
 		struct mdb_sort_key part[MDB_SORT_MAX_KEYS], order[MDB_SORT_MAX_KEYS];
 		struct mdb_window_fn fn[MDB_WIN_MAX_FNS];
 		uint32_t form = 0;
@@ -529,7 +529,13 @@ int stream_windows(struct exec *x)
 			done[j] = true;
 			memset(&fn[nfn], 0, sizeof(fn[nfn]));
 			fn[nfn].op = e->op;
-			if (e->op >= MDB_WIN_SUM) {
+			fn[nfn].arg = e->win_arg;	/* LAG / LEAD / NTILE; a default is an INTEGER's int64, a TINYINT's 0 / 1 or a DOUBLE's bits (resolve_window) */
+			fn[nfn].dflt_null = e->win_dflt == MDB_EX_NULL;
+			if (e->win_dflt == MDB_EX_FLOAT)
+				memcpy(&fn[nfn].dflt, &e->dval, 8);
+			else
+				fn[nfn].dflt = (uint64_t)e->ival;
+			if (mdb_win_narg(e->op)) {
 				struct mdb_sort_key arg;
 				window_key(x, e->kids[0], 0, &arg);
 				if (!arg.values && !(arg.values = no_cells ? no_cells : (no_cells = dalloc(x, 8))))

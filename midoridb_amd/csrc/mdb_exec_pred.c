@@ -244,6 +244,14 @@ static int pred_compile_in_subquery(struct pred_prog *p, const struct mdb_expr *
 	return pred_emit(p, in.op, in.cmp, in.type, in.a, in.b, in.imm);
 }
 
+/* a TINYINT column's cells: the column itself, or a window item that copies them (LAG / LEAD / FIRST_VALUE / LAST_VALUE of it) */
+static bool is_bool_column(const struct mdb_expr *f)
+{
+	if (f->type != MDB_CT_TINYINT)
+		return false;
+	return f->kind == MDB_EX_FIELD || (f->kind == MDB_EX_WINDOW && f->op >= MDB_WIN_LAG && f->op <= MDB_WIN_LAST_VALUE);
+}
+
 int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 {
 	int rc = 0, a, b;
@@ -258,7 +266,7 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 		const bool lcol = l->kind == MDB_EX_FIELD || l->kind == MDB_EX_COUNT || l->kind == MDB_EX_AGG || l->kind == MDB_EX_WINDOW;
 		const bool rcol = r->kind == MDB_EX_FIELD || r->kind == MDB_EX_COUNT || r->kind == MDB_EX_AGG || r->kind == MDB_EX_WINDOW;
 		if (lcol && rcol) {
-			if (l->kind == MDB_EX_FIELD && l->type == MDB_CT_TINYINT && e->op != MDB_CMP_EQ && e->op != MDB_CMP_NE)
+			if (is_bool_column(l) && e->op != MDB_CMP_EQ && e->op != MDB_CMP_NE)
 				return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
 			a = pred_slot(x, p, l);
 			b = pred_slot(x, p, r);
@@ -272,7 +280,7 @@ int pred_compile(struct exec *x, struct pred_prog *p, const struct mdb_expr *e)
 			if (v->kind == MDB_EX_NULL)	/* NULL operand: never true (executor_select.c:793-795) */
 				return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
 			/* TINYINT (bool) operands only know = and <> upstream (cmp_bool_value_to_value, executor_select.c:484-494): false */
-			if (f->kind == MDB_EX_FIELD && f->type == MDB_CT_TINYINT && e->op != MDB_CMP_EQ && e->op != MDB_CMP_NE)
+			if (is_bool_column(f) && e->op != MDB_CMP_EQ && e->op != MDB_CMP_NE)
 				return pred_emit(p, MDB_P_CONST, 0, 0, 0, 0, 0);
 			a = pred_slot(x, p, f);
 			if (a < 0)

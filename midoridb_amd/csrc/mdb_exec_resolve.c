@@ -79,7 +79,21 @@ static int resolve_agg(struct mdb_select *s, struct mdb_expr *e, char *err, size
 const char *mdb_win_name(int op)
 {
 	static const char *const names[] = { "?", "ROW_NUMBER", "RANK", "DENSE_RANK", "COUNT", "SUM", "MIN", "MAX", "AVG" };
+	static const char *const nav[] = { "LAG", "LEAD", "FIRST_VALUE", "LAST_VALUE", "NTILE" };
+	if (op >= MDB_WIN_LAG && op <= MDB_WIN_NTILE)
+		return nav[op - MDB_WIN_LAG];
 	return op >= MDB_WIN_ROW_NUMBER && op <= MDB_WIN_AVG ? names[op] : names[0];
+}
+
+/* how many columns a window function takes as its argument: one for the aggregates and for LAG / LEAD / FIRST_VALUE / LAST_VALUE */
+int mdb_win_narg(int op)
+{
+	return (op >= MDB_WIN_SUM && op <= MDB_WIN_AVG) || (op >= MDB_WIN_LAG && op <= MDB_WIN_LAST_VALUE) ? 1 : 0;
+}
+
+static bool win_is_nav_col(int op)
+{
+	return op >= MDB_WIN_LAG && op <= MDB_WIN_LAST_VALUE;
 }
 
 /* the aggregate function a window function folds with (enum mdb_agg_op), 0: a ranking function or COUNT(*) */
@@ -91,7 +105,11 @@ static int win_agg_op(int op)
 /* the result column's name of a resolved window item without an alias: the function's text as aggregates are named, then " OVER" */
 void mdb_win_result_name(const struct mdb_expr *e, char *out /* [MDB_NAME_LEN] */)
 {
-	if (e->op >= MDB_WIN_SUM)
+	if (e->op == MDB_WIN_NTILE)
+		snprintf(out, MDB_NAME_LEN, "NTILE(%llu) OVER", (unsigned long long)e->win_arg);
+	else if ((e->op == MDB_WIN_LAG || e->op == MDB_WIN_LEAD) && e->win_arg != 1)	/* (the offset where it is not 1; the default is not named) */
+		snprintf(out, MDB_NAME_LEN, "%s(%.50s.%.50s, %llu) OVER", mdb_win_name(e->op), e->tbl, e->col, (unsigned long long)e->win_arg);
+	else if (mdb_win_narg(e->op))
 		snprintf(out, MDB_NAME_LEN, "%s(%.56s.%.56s) OVER", mdb_win_name(e->op), e->tbl, e->col);
 	else
 		snprintf(out, MDB_NAME_LEN, "%s OVER", e->op == MDB_WIN_COUNT ? "COUNT(*)" : e->op == MDB_WIN_ROW_NUMBER ? "ROW_NUMBER()" :
@@ -113,7 +131,7 @@ bool expr_has_window(const struct mdb_expr *e)
 /* two resolved window items share one operator call when their OVER clauses are equal field for field */
 bool window_same_over(const struct mdb_expr *a, const struct mdb_expr *b)
 {
-	const int na = a->op >= MDB_WIN_SUM ? 1 : 0, nb = b->op >= MDB_WIN_SUM ? 1 : 0;
+	const int na = mdb_win_narg(a->op), nb = mdb_win_narg(b->op);
 	if (a->win_npart != b->win_npart || a->win_norder != b->win_norder || a->win_desc != b->win_desc)
 		return false;
 	for (int k = 0; k < a->win_npart + a->win_norder; k++)
@@ -127,10 +145,10 @@ bool window_same_over(const struct mdb_expr *a, const struct mdb_expr *b)
  * would) -; PARTITION BY takes a column of any type (cells compare as in GROUP BY), ORDER BY what the statement's ORDER BY takes */
 static int resolve_window(struct mdb_select *s, struct mdb_expr *e, char *err, size_t errlen)
 {
-	const int narg = e->op >= MDB_WIN_SUM ? 1 : 0;
+	const int narg = mdb_win_narg(e->op);
 	int rc;
 
-	if (e->op < MDB_WIN_ROW_NUMBER || e->op > MDB_WIN_AVG || e->win_npart < 0 || e->win_norder < 0 || e->nkids != narg + e->win_npart + e->win_norder) {
+	if (!strcmp(mdb_win_name(e->op), "?") || e->win_npart < 0 || e->win_norder < 0 || e->nkids != narg + e->win_npart + e->win_norder) {
 		ERR("error while running syntax analysis on query\n");
 		return -MIDORIDB_ERROR;
 	}
@@ -154,7 +172,32 @@ static int resolve_window(struct mdb_select *s, struct mdb_expr *e, char *err, s
 		}
 	}
 	e->type = MDB_CT_INTEGER;
-	if (narg) {
+	if (e->op == MDB_WIN_NTILE && !e->win_arg) {
+		ERR("NTILE(0) ... OVER: the number of buckets must be at least 1\n");
+		return -MIDORIDB_ERROR;
+	}
+	if (win_is_nav_col(e->op)) {	/* a cell of the column is copied: every type is served, the result has the column's type */
+		const struct mdb_expr *c = e->kids[0];
+		const char *want = c->type == MDB_CT_INTEGER ? "an integer" : c->type == MDB_CT_TINYINT ? "TRUE or FALSE" : "a number with a decimal point";
+		if (e->win_dflt != MDB_EX_NULL && (c->type == MDB_CT_VARCHAR || c->type == MDB_CT_DATE || c->type == MDB_CT_DATETIME)) {
+			ERR("%s ... OVER: a default for the %s column '%.100s.%.100s' is not supported: write NULL, or leave the default out\n", mdb_win_name(e->op),
+			    c->type == MDB_CT_VARCHAR ? "VARCHAR" : c->type == MDB_CT_DATE ? "DATE" : "DATETIME", c->tbl, c->col);
+			return -MIDORIDB_ERROR;
+		}
+		if (e->win_dflt == MDB_EX_BOOL && e->ival != 0 && e->ival != 1) {
+			ERR("%s ... OVER: UNKNOWN as a default is not supported: write NULL\n", mdb_win_name(e->op));
+			return -MIDORIDB_ERROR;
+		}
+		if (e->win_dflt != MDB_EX_NULL && e->win_dflt != (c->type == MDB_CT_INTEGER ? MDB_EX_INT : c->type == MDB_CT_TINYINT ? MDB_EX_BOOL : MDB_EX_FLOAT)) {
+			ERR("%s ... OVER: the default does not match the type of column '%.100s.%.100s': it takes %s, or NULL\n", mdb_win_name(e->op), c->tbl, c->col, want);
+			return -MIDORIDB_ERROR;
+		}
+		mdb_copy_name(e->tbl, c->tbl);
+		mdb_copy_name(e->col, c->col);
+		e->tbl_idx = c->tbl_idx;
+		e->col_idx = c->col_idx;
+		e->type = c->type;
+	} else if (narg) {
 		const struct mdb_expr *c = e->kids[0];
 		if (c->type == MDB_CT_VARCHAR) {
 			ERR("%s ... OVER over the VARCHAR column '%.100s.%.100s' is not supported: its cells are dictionary ids, which are not in string order\n",
@@ -392,7 +435,8 @@ int check_predicate_x(const struct mdb_expr *e, const char *clause, bool dml, ch
 		return MIDORIDB_OK;
 	}
 	case MDB_EX_ISNULL:
-		if (e->kids[0]->kind != MDB_EX_FIELD) {
+		/* (... and, in HAVING, a window item by its alias: LAG(v) OVER (...) AS prev ... HAVING prev IS NULL) */
+		if (e->kids[0]->kind != MDB_EX_FIELD && !(e->kids[0]->kind == MDB_EX_WINDOW && is_having_clause(clause))) {
 			ERR("only fields are allowed in IS NULL|IS NOT NULL\n");
 			return -MIDORIDB_ERROR;
 		}
@@ -784,8 +828,13 @@ int resolve_select(struct mdb_catalog *cat, struct mdb_select *s, char *err, siz
 		for (int i = 0; i < s->norder; i++) {
 			struct mdb_expr *o = s->order[i];
 			subst_alias(s, o, false, true);
-			if (o->kind == MDB_EX_WINDOW)	/* a window item by its alias: ordered by its result column */
+			if (o->kind == MDB_EX_WINDOW) {	/* a window item by its alias: ordered by its result column */
+				if (o->type == MDB_CT_VARCHAR) {	/* (LAG ... of a VARCHAR column: dictionary ids, as below) */
+					ERR("ORDER BY over the VARCHAR column '%s' is not supported on the MI355X path\n", o->col);
+					return -MIDORIDB_ERROR;
+				}
 				continue;
+			}
 			if (o->kind == MDB_EX_AGG) {	/* an aggregate of the select list, repeated or by its alias: ordered by its result column */
 				if ((rc = resolve_agg_refs(s, o, "ORDER BY", err, errlen)))
 					return rc;

@@ -237,6 +237,9 @@ static int locate_column(struct exec *x, const struct select_stmt *st, struct md
 	}
 	if (colsrc_win(tbl) >= 0) {	/* a window item: a typed column with its NULL bitmap, one row per row of the stream */
 		const int w = colsrc_win(tbl);
+		const struct mdb_expr *e = x->win_item[w];
+		if (e->type == MDB_CT_VARCHAR && e->tbl_idx >= 0 && e->col_idx >= 0)	/* (LAG ... of a VARCHAR column: its cells, its precision) */
+			res->colprec[c] = s->tabs[e->tbl_idx].t->cols[e->col_idx].precision;
 		if (pj->out_rows) {
 			if (!x->d_win[w]) {
 				snprintf(x->err, x->errlen, "execution phase: internal error (window function not computed)\n");

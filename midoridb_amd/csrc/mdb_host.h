@@ -173,6 +173,7 @@ int mdb_col_range(struct mdb_catalog *cat, struct mdb_table *t, struct mdb_colum
 int mdb_catalog_device(struct mdb_catalog *cat, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------ statement plans */
+int mdb_win_narg(int op);	/* the argument columns of a window function (enum mdb_win_op): 0 or 1 (mdb_exec_resolve.c) */
 enum mdb_expr_kind {
 	MDB_EX_NAME = 1,	/* bare column name (before resolution) */
 	MDB_EX_FIELD,		/* table.column */
@@ -191,8 +192,8 @@ enum mdb_expr_kind {
 	MDB_EX_ALIAS,		/* alias wrapper around kid[0] */
 	MDB_EX_AGG,		/* SUM / MIN / MAX / AVG (col): op = enum mdb_agg_op, kid[0] = the column; resolved: tbl_idx / col_idx / tbl / col are the
 				 * column's, type = the RESULT's column type (mdb_agg_result_type) */
-	MDB_EX_WINDOW,		/* fn(...) OVER (PARTITION BY ... ORDER BY ...): op = enum mdb_win_op; kids = the argument of SUM / MIN / MAX / AVG (none
-				 * for the other four), then win_npart partition fields, then win_norder order fields (bit i of win_desc: order field
+	MDB_EX_WINDOW,		/* fn(...) OVER (PARTITION BY ... ORDER BY ...): op = enum mdb_win_op; kids = the argument of SUM / MIN / MAX / AVG / LAG /
+				 * LEAD / FIRST_VALUE / LAST_VALUE (mdb_win_narg: none for the others), then win_npart partition fields, then win_norder order fields (bit i of win_desc: order field
 				 * i is DESC); resolved: tbl_idx / col_idx / tbl / col are the argument's, type = the RESULT's column type, win_idx =
 				 * which of the statement's window items it is.  A copy that stands for the item by its alias (HAVING, ORDER BY) has no kids */
 };
@@ -211,6 +212,8 @@ struct mdb_expr {
 	int tbl_idx, col_idx, type;
 	int win_npart, win_norder, win_idx;	/* MDB_EX_WINDOW */
 	uint32_t win_desc;
+	uint64_t win_arg;		/* ... LAG / LEAD: the offset (1 when not written), NTILE: the buckets */
+	int win_dflt;			/* ... LAG / LEAD: the default's literal kind (MDB_EX_INT / FLOAT / BOOL / STRING: in ival / dval) or MDB_EX_NULL */
 	/* MDB_EX_ISIN over a subquery: the nested statement, owned by the node (mdb_expr_free) and deliberately NOT among `kids` - the
 	 * outer statement's walkers never descend into it; it is resolved and run on its own.  The executor evaluates it once, before
 	 * the outer statement's plan is chosen (subqueries_eval, mdb_exec.c; subqueries_release ends it): sub_set = the device set of its one column, alive until the outer

@@ -16,7 +16,7 @@
 /* wrapper node kinds that only live on the builder stack */
 enum {
 	BX_TABLE = 100, BX_JOIN, BX_ONEXPR, BX_WHERE, BX_GROUPBY, BX_HAVING, BX_ORDERBYITEM, BX_ORDERBYLIST,
-	BX_LIMIT, BX_SELECTALL, BX_ASSIGN, BX_WINORDER,
+	BX_LIMIT, BX_SELECTALL, BX_ASSIGN, BX_WINORDER, BX_WINARG,
 	BX_SELECT,	/* a finished "SELECT d n": the plan in `sub` - the statement itself, or a subquery's once "SUBQUERY" has wrapped it */
 	BX_SUBQUERY,
 	BX_SETORDER,	/* an ORDER BY item of a compound: the result column's name in `col`, op = DESC */
@@ -480,34 +480,77 @@ int mdb_plan_build(const struct mdb_rpn *rpn, struct mdb_stmt *out, char *err, s
 				if (pop_n_into(&st, 1, e))
 					FAIL("error while running syntax analysis on query\n");
 			}
+		} else if (starts(t, "WINARG ")) {
+			/* "WINARG n" closes the n literal arguments behind the column of LAG / LEAD (offset, default) or of NTILE (buckets) */
+			x = atoi(t + 7);
+			if (x < 0 || x > 2 || st.n < x)
+				FAIL("error while running syntax analysis on query\n");
+			for (int k = 0; k < x; k++) {
+				const int kind = st.v[st.n - x + k]->kind;
+				if (kind != MDB_EX_INT && kind != MDB_EX_FLOAT && kind != MDB_EX_BOOL && kind != MDB_EX_STRING && kind != MDB_EX_NULL)
+					FAIL("error while running syntax analysis on query\n");
+			}
+			e = ex_new(BX_WINARG);
+			if (e && pop_n_into(&st, x, e))
+				FAIL("error while running syntax analysis on query\n");
 		} else if (starts(t, "WINDOW ")) {
-			/* "WINDOW fn npart norder" closes a window item: behind the argument of SUM / MIN / MAX / AVG (NAME / FIELDNAME; none for
-			 * the other functions), the npart partition fields and the norder "WINORDER" items.  op = enum mdb_win_op */
+			/* "WINDOW fn npart norder" closes a window item: behind the argument of SUM / MIN / MAX / AVG / LAG / LEAD / FIRST_VALUE /
+			 * LAST_VALUE (NAME / FIELDNAME; none for the other functions), the "WINARG" item of LAG / LEAD / NTILE, the npart partition
+			 * fields and the norder "WINORDER" items.  op = enum mdb_win_op */
 			static const char *const fns[] = { "", "ROW_NUMBER", "RANK", "DENSE_RANK", "COUNT", "SUM", "MIN", "MAX", "AVG" };
-			int fn = 0, narg;
+			static const char *const nav[] = { "LAG", "LEAD", "FIRST_VALUE", "LAST_VALUE", "NTILE" };
+			int fn = 0, narg, nlit;
 			if (sscanf(t + 7, "%15s %d %d", a, &x, &y) != 3 || x < 0 || y < 0 || x > 4096 || y > 4096)
 				FAIL("error while running syntax analysis on query\n");
 			for (int k = MDB_WIN_ROW_NUMBER; k <= MDB_WIN_AVG; k++)
 				if (!strcmp(a, fns[k]))
 					fn = k;
-			narg = fn >= MDB_WIN_SUM ? 1 : 0;
-			if (!fn || st.n < narg + x + y)
+			for (int k = MDB_WIN_LAG; k <= MDB_WIN_NTILE; k++)
+				if (!strcmp(a, nav[k - MDB_WIN_LAG]))
+					fn = k;
+			narg = mdb_win_narg(fn);
+			nlit = fn == MDB_WIN_LAG || fn == MDB_WIN_LEAD || fn == MDB_WIN_NTILE ? 1 : 0;
+			if (!fn || st.n < narg + nlit + x + y)
 				FAIL("error while running syntax analysis on query\n");
-			for (int k = 0; k < narg + x + y; k++) {
-				const int kind = st.v[st.n - (narg + x + y) + k]->kind;
-				if (k < narg + x ? kind != MDB_EX_NAME && kind != MDB_EX_FIELD : kind != BX_WINORDER)
+			for (int k = 0; k < narg + nlit + x + y; k++) {
+				const int kind = st.v[st.n - (narg + nlit + x + y) + k]->kind;
+				if (k < narg ? kind != MDB_EX_NAME && kind != MDB_EX_FIELD :
+				    k < narg + nlit ? kind != BX_WINARG :
+				    k < narg + nlit + x ? kind != MDB_EX_NAME && kind != MDB_EX_FIELD : kind != BX_WINORDER)
 					FAIL("error while running syntax analysis on query\n");
 			}
 			if (y > 32)
 				FAIL("too many ORDER BY fields in an OVER clause\n");
+			if (nlit) {	/* the literals: the offset (none: 1) and the default (none: NULL), or the bucket count */
+				const struct mdb_expr *w = st.v[st.n - (nlit + x + y)];
+				if (fn == MDB_WIN_NTILE ? w->nkids != 1 || w->kids[0]->kind != MDB_EX_INT || w->kids[0]->ival < 1 :
+				    w->nkids && (w->kids[0]->kind != MDB_EX_INT || w->kids[0]->ival < 0))
+					FAIL("error while running syntax analysis on query\n");
+			}
 			e = ex_new(MDB_EX_WINDOW);
 			if (e) {
 				e->op = fn;
 				e->win_npart = x;
 				e->win_norder = y;
 				e->win_idx = -1;
-				if (pop_n_into(&st, narg + x + y, e))
+				e->win_arg = 1;
+				e->win_dflt = MDB_EX_NULL;
+				if (pop_n_into(&st, narg + nlit + x + y, e))
 					FAIL("error while running syntax analysis on query\n");
+				if (nlit) {	/* unwrap the literals: they go into win_arg, win_dflt and ival / dval / sval; the item leaves the kids */
+					struct mdb_expr *w = e->kids[narg];
+					if (w->nkids > 0)
+						e->win_arg = (uint64_t)w->kids[0]->ival;
+					if (w->nkids > 1) {
+						e->win_dflt = w->kids[1]->kind;
+						e->ival = w->kids[1]->ival;
+						e->dval = w->kids[1]->dval;
+					}
+					for (int k = narg; k + 1 < e->nkids; k++)
+						e->kids[k] = e->kids[k + 1];
+					e->nkids--;
+					mdb_expr_free(w);
+				}
 				for (int k = 0; k < y; k++) {	/* unwrap the order items: the field stays, its direction goes into win_desc */
 					struct mdb_expr *w = e->kids[narg + x + k];
 					if (w->op)

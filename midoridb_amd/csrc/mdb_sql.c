@@ -28,6 +28,22 @@
  *   NAME | FIELDNAME, WINORDER d ...        every ORDER BY field, wrapped: d = 0 ASC, 1 DESC
  *   WINDOW fn npart norder                  closes the item: fn = ROW_NUMBER | RANK | DENSE_RANK | COUNT | SUM | MIN | MAX | AVG
  *
+ * and the navigation functions
+ *
+ *   LAG(col [, k [, default]]) | LEAD(col [, k [, default]]) | FIRST_VALUE(col) | LAST_VALUE(col) | NTILE(n)     OVER ( ... )
+ *       col: col | tbl.col; k: a non-negative integer literal (default 1); n: a positive integer literal; default: a literal or NULL
+ *
+ * emit the column as SUM's argument is emitted, then the literals as their own tokens and one word that closes them:
+ *
+ *   NAME col | FIELDNAME tbl.col            (not NTILE)
+ *   [NUMBER k [NUMBER | FLOAT | BOOL | STRING | NULL]], WINARG count      LAG / LEAD: count = 0 ... 2;  NTILE: NUMBER n, WINARG 1;
+ *                                           FIRST_VALUE / LAST_VALUE: nothing
+ *   ... the PARTITION BY fields, the ORDER BY items, WINDOW LAG | LEAD | FIRST_VALUE | LAST_VALUE | NTILE npart norder
+ *
+ * IGNORE NULLS / RESPECT NULLS, FROM FIRST / FROM LAST, an offset or default that is no literal, a negative offset, NTILE(0), NTILE of a
+ * column, LAG() without a column and DISTINCT inside are refused, each with a text of its own.  LAG / LEAD / FIRST_VALUE / LAST_VALUE /
+ * NTILE are functions only with the parenthesis right behind the name, as ROW_NUMBER is.
+ *
  * No word becomes reserved for it: ROW_NUMBER / RANK / DENSE_RANK are functions only with the parenthesis right behind the name (as
  * SUM( is), OVER is a window only behind the `)` of one of the eight functions and in front of `(`, PARTITION only inside that
  * parenthesis.  `SELECT SUM(v) over FROM A` still aliases the aggregate as `over`.
@@ -56,10 +72,11 @@
  */
 #include "mdb_host.h"
 #include <ctype.h>
+#include <limits.h>
 #include <strings.h>
 
 enum tk {
-	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_FAGG, T_FWIN, T_ANDOP, T_OROP, T_ERR
+	T_EOF, T_NAME, T_STRING, T_INT, T_FLOAT, T_BOOL, T_CMP, T_PUNCT, T_KW, T_FCOUNT, T_FAGG, T_FWIN, T_FNAV, T_ANDOP, T_OROP, T_ERR
 };
 
 static const char *const KEYWORDS[] = {
@@ -76,6 +93,7 @@ struct lexer {
 	enum tk type;
 	char text[256];		/* NAME / STRING (with quotes) / keyword upper-cased / punct */
 	long ival;
+	long long wval;		/* T_INT: the literal at full width (ival is what the reference's 32-bit lexer makes of it) */
 	double fval;
 	int sub;		/* comparison code */
 };
@@ -203,6 +221,7 @@ static void next(struct parser *p)
 			} else {
 				l->type = T_INT;
 				l->ival = atoi(tmp);	/* 32-bit, as the reference lexer (midorisql.l:85) */
+				l->wval = strtoll(tmp, NULL, 10);
 			}
 			l->pos = j;
 			return;
@@ -282,6 +301,12 @@ static void next(struct parser *p)
 		 * column, table or alias called `rank` stays a name (text keeps the spelling: CREATE TABLE rank(...) names a table) */
 		if (s[j] == '(' && (strcmp(up, "ROW_NUMBER") == 0 || strcmp(up, "RANK") == 0 || strcmp(up, "DENSE_RANK") == 0)) {
 			l->type = T_FWIN;
+			return;
+		}
+		/* LAG( LEAD( FIRST_VALUE( LAST_VALUE( NTILE( - the navigation window functions, by the same rule */
+		if (s[j] == '(' && (strcmp(up, "LAG") == 0 || strcmp(up, "LEAD") == 0 || strcmp(up, "FIRST_VALUE") == 0 || strcmp(up, "LAST_VALUE") == 0 ||
+				    strcmp(up, "NTILE") == 0)) {
+			l->type = T_FNAV;
 			return;
 		}
 		if (strcmp(up, "TRUE") == 0 || strcmp(up, "FALSE") == 0 || strcmp(up, "UNKNOWN") == 0) {
@@ -396,6 +421,7 @@ enum { P_OR = 1, P_XOR = 2, P_AND = 3, P_ISIN = 4, P_NOT = 5, P_CMP = 7, P_ADD =
 static void parse_expr(struct parser *p, int min_prec);
 static void parse_select(struct parser *p);
 static int setop_follows(struct parser *p);
+static const char *word_at(const char *q, char *up, size_t cap);
 
 /* IN ( SELECT ... ) - an extension (the reference's grammar knows value lists only, midorisql.y:283-284): the lexer stands on SELECT.
  * The inner statement's tokens are emitted in place and end in its own "SELECT d n"; "SUBQUERY" wraps it into one stack entry.  Inside
@@ -559,6 +585,158 @@ static void parse_over(struct parser *p, const char *fn)
 	}
 	expect_punct(p, ')');
 	emit(p, "WINDOW %s %d %d", fn, npart, norder);
+}
+
+/* LAG(col [, k [, default]]) | LEAD(...) | FIRST_VALUE(col) | LAST_VALUE(col) | NTILE(n): the lexer stands on the function's name.  The
+ * column is emitted as the argument of SUM is; k, the default and n travel as the literals' own tokens and "WINARG count" closes them
+ * (LAG / LEAD / NTILE; FIRST_VALUE / LAST_VALUE have none), then the OVER clause as for every window function. */
+static bool nav_literal(struct parser *p)
+{
+	struct lexer *l = &p->lx;
+
+	if (l->type == T_INT)
+		emit(p, "NUMBER %d", (int)l->ival);	/* (the caller has refused what does not fit: "NUMBER" is 32-bit, as the reference's) */
+	else if (l->type == T_FLOAT)
+		emit(p, "FLOAT %g", l->fval);
+	else if (l->type == T_BOOL)
+		emit(p, "BOOL %d", (int)l->ival);
+	else if (l->type == T_STRING)
+		emit(p, "STRING %s", l->text);
+	else if (is_kw(p, "NULL"))
+		emit(p, "NULL");
+	else
+		return false;
+	next(p);
+	return true;
+}
+
+/* do the words w1 (one of two spellings) and then w2 (one of three, NULL: any text) stand in the raw text behind the current token? */
+static bool words_behind(const struct lexer *l, const char *w1a, const char *w1b, const char *w2a, const char *w2b, const char *w2c)
+{
+	char up[16];
+	const char *q = skip_blank(word_at(skip_blank(l->s + l->pos), up, sizeof(up)));
+
+	if (strcmp(up, w1a) != 0 && (!w1b || strcmp(up, w1b) != 0))
+		return false;
+	if (!w2a)
+		return true;
+	(void)word_at(q, up, sizeof(up));
+	return !strcmp(up, w2a) || (w2b && !strcmp(up, w2b)) || (w2c && !strcmp(up, w2c));
+}
+
+static void parse_nav(struct parser *p)
+{
+	struct lexer *l = &p->lx;
+	char fn[16];
+	size_t k = 0;
+	int nextra = 0;
+	bool offs, ntile;
+
+	for (; l->text[k] && k < sizeof(fn) - 1; k++)
+		fn[k] = (char)toupper((unsigned char)l->text[k]);
+	fn[k] = 0;
+	offs = !strcmp(fn, "LAG") || !strcmp(fn, "LEAD");
+	ntile = !strcmp(fn, "NTILE");
+	if (p->dml) {
+		fail(p, "window function %s ... OVER can't be used in DELETE / UPDATE", fn);
+		return;
+	}
+	next(p);
+	expect_punct(p, '(');
+	if (p->failed)
+		return;
+	if (is_kw(p, "DISTINCT")) {
+		fail(p, "syntax error, DISTINCT inside a window function is not supported: %s(DISTINCT ...) OVER", fn);
+		return;
+	}
+	if (ntile) {
+		if (l->type == T_NAME) {
+			fail(p, "syntax error, NTILE takes the number of buckets as a positive integer literal, not a column: NTILE(n)");
+			return;
+		}
+		if (l->type != T_INT) {
+			fail(p, "syntax error, NTILE takes the number of buckets as a positive integer literal: NTILE(n)");
+			return;
+		}
+		if (l->wval < 1) {
+			fail(p, "syntax error, NTILE(%lld): the number of buckets must be at least 1", l->wval);
+			return;
+		}
+		if (l->wval > INT_MAX) {
+			fail(p, "syntax error, NTILE(%lld): more than %d buckets are not supported in a statement", l->wval, INT_MAX);
+			return;
+		}
+		nav_literal(p);
+		nextra = 1;
+	} else {
+		if (is_punct(p, ')')) {
+			fail(p, "syntax error, %s() needs a column: %s(col) or %s(tbl.col)", fn, fn, fn);
+			return;
+		}
+		if (l->type != T_NAME) {
+			fail(p, "syntax error, %s takes a column as its first argument: %s(col) or %s(tbl.col)", fn, fn, fn);
+			return;
+		}
+		if (!window_field(p))
+			return;
+		if (!offs && !is_punct(p, ')')) {
+			fail(p, "syntax error, %s takes one column: %s(col) or %s(tbl.col)", fn, fn, fn);
+			return;
+		}
+		if (offs && is_punct(p, ',')) {
+			next(p);
+			if (l->type == T_INT && l->wval < 0) {
+				fail(p, "syntax error, a negative offset in %s is not supported: %s(col, %lld) is %s(col, %lld)", fn, fn, l->wval,
+				     !strcmp(fn, "LAG") ? "LEAD" : "LAG", -l->wval);
+				return;
+			}
+			if (l->type == T_INT && l->wval > INT_MAX) {
+				fail(p, "syntax error, the offset %lld of %s is not supported in a statement: integer literals are 32-bit, at most %d", l->wval, fn, INT_MAX);
+				return;
+			}
+			if (l->type != T_INT || (nav_literal(p), !is_punct(p, ',') && !is_punct(p, ')'))) {
+				fail(p, "syntax error, the offset of %s must be a non-negative integer literal: %s(col, k [, default])", fn, fn);
+				return;
+			}
+			nextra = 1;
+			if (is_punct(p, ',')) {
+				next(p);
+				if (l->type == T_INT && (l->wval > INT_MAX || l->wval < INT_MIN)) {
+					fail(p, "syntax error, the default %lld of %s is not supported: integer literals are 32-bit, %d ... %d", l->wval, fn, INT_MIN, INT_MAX);
+					return;
+				}
+				if (!nav_literal(p) || !is_punct(p, ')')) {
+					fail(p, "syntax error, the default of %s must be a literal or NULL: %s(col, k, default)", fn, fn);
+					return;
+				}
+				nextra = 2;
+			}
+		}
+	}
+	if (offs || ntile)
+		emit(p, "WINARG %d", nextra);
+	expect_punct(p, ')');
+	if (p->failed)
+		return;
+	/* (the current token is what stands behind the call; the words behind IT are looked at in the raw text, as over_follows() does) */
+	if (is_kw(p, "FROM") && words_behind(l, "FIRST", "LAST", "OVER", "IGNORE", "RESPECT")) {
+		fail(p, "syntax error, FROM FIRST / FROM LAST behind %s is not supported: rows are counted from the partition's first row", fn);
+		return;
+	}
+	if ((name_is(l, "ignore") || name_is(l, "respect")) && words_behind(l, "NULLS", NULL, NULL, NULL, NULL)) {
+		fail(p, "syntax error, IGNORE NULLS / RESPECT NULLS behind %s is not supported: NULL cells are respected", fn);
+		return;
+	}
+	{
+		const int ov = over_follows(p);
+		if (ov < 0)
+			return;
+		if (!ov) {
+			fail(p, "syntax error, %s(...) needs its window: %s(...) OVER ( [PARTITION BY f, ...] [ORDER BY f [ASC|DESC], ...] )", fn, fn);
+			return;
+		}
+	}
+	parse_over(p, fn);
 }
 
 /* ------------------------------------------------------------------ set operations: UNION [ALL] / INTERSECT / EXCEPT
@@ -828,6 +1006,9 @@ static void parse_primary(struct parser *p)
 		parse_over(p, fn);
 		return;
 	}
+	case T_FNAV:
+		parse_nav(p);
+		return;
 	case T_KW:
 		if (strcmp(l->text, "NULL") == 0) {
 			emit(p, "NULL");
@@ -1168,7 +1349,7 @@ static void parse_create(struct parser *p)
 		expect_kw(p, "EXISTS");
 		ifne = 1;
 	}
-	if (p->lx.type == T_FWIN)	/* (a table called `rank`, its parenthesis right behind the name) */
+	if (p->lx.type == T_FWIN || p->lx.type == T_FNAV)	/* (a table called `rank` or `lag`, its parenthesis right behind the name) */
 		p->lx.type = T_NAME;
 	if (p->lx.type != T_NAME) {
 		fail(p, "syntax error, expecting table name");
@@ -1301,7 +1482,7 @@ static void parse_insert(struct parser *p)
 	int hascols = 0, ntuples = 0;
 
 	accept_kw(p, "INTO");
-	if (p->lx.type == T_FWIN)	/* (a table called `rank`, its parenthesis right behind the name) */
+	if (p->lx.type == T_FWIN || p->lx.type == T_FNAV)	/* (a table called `rank` or `lag`, its parenthesis right behind the name) */
 		p->lx.type = T_NAME;
 	if (p->lx.type != T_NAME) {
 		fail(p, "syntax error, expecting table name");

@@ -5,6 +5,7 @@ library launches on, and torch.distributed provides the RCCL all-to-all in bench
 operator below is one call through the C-ABI into hand-written HIP; nothing here computes.
 """
 import ctypes
+import struct
 from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import numpy as np
@@ -24,6 +25,7 @@ T_INT64, T_DOUBLE = 0, 1
 AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG = 1, 2, 3, 4     # enum mdb_agg_op
 AGG_IDENTITY = -1                                   # MDB_AGG_IDENTITY: group i is row i
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX, WIN_AVG = 1, 2, 3, 4, 5, 6, 7, 8     # enum mdb_win_op
+WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_NTILE = 16, 17, 18, 19, 20     # ... its navigation functions
 WIN_MAX_FNS = 8                                     # MDB_WIN_MAX_FNS
 
 
@@ -65,9 +67,13 @@ class CountDistinct(ctypes.Structure):     # struct mdb_count_distinct (include/
                 ("max", c_int64), ("out", c_void_p)]
 
 
-class WindowFn(ctypes.Structure):     # struct mdb_window_fn (include/mdb_dev.h)
+class WindowFn(ctypes.Structure):     # struct mdb_window_fn (include/mdb_dev.h): the fields every function reads ...
     _fields_ = [("op", c_int32), ("type", c_int32), ("values", c_void_p), ("nullbits", c_void_p), ("rid", c_void_p), ("out", c_void_p),
                 ("out_nullbits", c_void_p)]
+
+
+class WindowFnFull(WindowFn):         # ... and the whole struct: the navigation functions' fields are appended behind them.  The stride of
+    _fields_ = [("arg", c_uint64), ("dflt", c_uint64), ("dflt_null", c_int32)]     # mdb_dev_window's array (mdb_dev_window_fn_size)
 
 
 class RowsInfo(ctypes.Structure):     # struct mdb_dev_rows_info (include/mdb_dev.h)
@@ -301,7 +307,8 @@ def _bind(lib):
         "mdb_dev_group_count_distinct": ([P, POINTER(SortKey), c_int, c_uint64, P, c_uint64, POINTER(CountDistinct), c_int, POINTER(c_uint32)], c_int),
         "mdb_dev_group_count_distinct_lds_groups": ([], c_uint64),
         "mdb_dev_count_distinct_bitmap_bits": ([], c_uint64),
-        "mdb_dev_window": ([P, POINTER(SortKey), c_int, POINTER(SortKey), c_int, c_uint64, POINTER(WindowFn), c_int, POINTER(c_uint32)], c_int),
+        "mdb_dev_window_fn_size": ([], c_uint64),
+        "mdb_dev_window": ([P, POINTER(SortKey), c_int, POINTER(SortKey), c_int, c_uint64, POINTER(WindowFnFull), c_int, POINTER(c_uint32)], c_int),
         "mdb_dev_rows_semi": ([P, POINTER(SortKey), c_uint64, POINTER(SortKey), c_uint64, c_int, c_int, P, POINTER(c_uint64), POINTER(RowsInfo)], c_int),
         "mdb_dev_concat64": ([P, POINTER(ConcatPart), c_int, P, P], c_int),
     }
@@ -325,6 +332,7 @@ DEV_SYMBOLS = [
     "mdb_dev_group_aggregate", "mdb_dev_group_aggregate_lds_groups",
     "mdb_dev_group_count_distinct", "mdb_dev_group_count_distinct_lds_groups", "mdb_dev_count_distinct_bitmap_bits",
     "mdb_dev_window",
+    "mdb_dev_window_fn_size",
     "mdb_dev_rows_semi", "mdb_dev_concat64",
 ]
 
@@ -1102,15 +1110,27 @@ class DeviceCtx:
     def window(self, part, order, n, fns, outs=None, nulls=None):
         """Window functions over one window (mdb_dev_window).  part / order = the PARTITION BY / ORDER BY key columns as sort_perm takes
         them ([]: none), fns = [(WIN_ROW_NUMBER | WIN_RANK | WIN_DENSE_RANK | WIN_COUNT,), ... or (WIN_SUM | WIN_MIN | WIN_MAX | WIN_AVG,
-        T_INT64 | T_DOUBLE, values, nullbits or None, rid or None), ...].  outs / nulls: the callers' own result tensors (n cells of 8 bytes;
+        T_INT64 | T_DOUBLE, values, nullbits or None, rid or None), ... or (WIN_LAG | WIN_LEAD | WIN_FIRST_VALUE | WIN_LAST_VALUE, type, values,
+        nullbits or None, rid or None, offset = 1, default = None: NULL, else an int or a float whose 8 bytes are the default) or
+        (WIN_NTILE, buckets), ...]; a navigation function's result has the dtype of its cells.  outs / nulls: the callers' own result tensors (n cells of 8 bytes;
         (n + 63) // 64 int64 words) per function, allocated here when not given -> (result columns in stream order: int64 or float64
         tensors of n cells, their NULL words: int64 tensors, the form: 1 no keys, 2 sorted)."""
-        arr = (WindowFn * len(fns))()
+        arr = (WindowFnFull * len(fns))()
         res, words = [], []
         for i, fn in enumerate(fns):
             op = fn[0]
-            ty, v, nb, rid = (tuple(fn[1:]) + (None,) * 4)[:4] if len(fn) > 1 else (T_INT64, None, None, None)
-            as_double = op == WIN_AVG or (op in (WIN_MIN, WIN_MAX) and ty == T_DOUBLE)
+            if op == WIN_NTILE:
+                ty, v, nb, rid = T_INT64, None, None, None
+                arr[i].arg = int(fn[1])
+            else:
+                ty, v, nb, rid = (tuple(fn[1:]) + (None,) * 4)[:4] if len(fn) > 1 else (T_INT64, None, None, None)
+            if op in (WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE, WIN_LAST_VALUE):
+                dflt = fn[6] if len(fn) > 6 else None
+                arr[i].arg = int(fn[5]) if len(fn) > 5 else 1
+                arr[i].dflt_null = 1 if dflt is None else 0
+                if dflt is not None:
+                    arr[i].dflt = struct.unpack("<Q", struct.pack("<d", dflt) if isinstance(dflt, float) else struct.pack("<q", int(dflt)))[0]
+            as_double = op == WIN_AVG or (op in (WIN_MIN, WIN_MAX) and ty == T_DOUBLE) or (v is not None and v.dtype == torch.float64 and op >= WIN_LAG)
             out = outs[i] if outs is not None else torch.zeros(max(n, 1), dtype=torch.float64 if as_double else torch.int64, device=self.device)
             onb = nulls[i] if nulls is not None else torch.zeros((n + 63) // 64 or 1, dtype=torch.int64, device=self.device)
             arr[i].op, arr[i].type = op, ty
